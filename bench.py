@@ -14,6 +14,12 @@ CU.  Mode "adaptive": default_compress_ratio = 2.0 and the codec of every page i
 device by the reference's selector (RLE for this data; the CPU oracle agrees).  Nothing is in
 forbidden_compressions: every codec of the reference is a candidate, as with its default options.
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: it sets up the batch, runs W
+untimed and N timed steps and prints the one JSON line (`value`, `ms_per_step`, ...).  `--dump-outputs DIR` also writes
+a fixed, seeded sample of what the last timed step returned (see dump_outputs).  Everything below — the round-trip
+check, the per-kernel pass behind `roofline`, the CPU baseline, the other configurations, `bench_detail.json` — runs
+only with `--full` (`--no-cpu-baseline`, `--no-configs` and `--only` narrow it; `--only` implies `--full`).
+
 `configs` (same JSON line, N=1 only): every other BASELINE.json configuration and the reference's
 own bench shapes (benches/write_strawboat.rs:30-67), each with encode / decode GB/s of Arrow bytes,
 the fraction of the HBM roofline its algorithmic bytes reach per direction, the kernel that
@@ -1096,6 +1102,44 @@ def write_detail(detail):
     print("[bench-detail] " + txt, file=sys.stderr, flush=True)
 
 
+DUMP_SEED = 1234             # the sample of --dump-outputs: fixed, so two builds can be compared file for file
+DUMP_COLUMNS = 8             # sampled columns of the batch
+DUMP_ROWS = 262144           # sampled rows of each of them (the same rows in every column)
+DUMP_PAGE_BYTES = 1 << 19    # leading bytes of each sampled column's pages
+DUMP_LIMIT = 64 << 20        # bytes of .npy data in all
+
+
+def dump_outputs(out_dir, enc, dec):
+    """--dump-outputs DIR: what the timed path returned in its last step (every step computes the same), as .npy files:
+      page_metas.npy         float64 (pages, 3): column index, page bytes, rows of every page of every column (encode)
+      pages_sample.npy       float32: the first DUMP_PAGE_BYTES page bytes of each sampled column, one after another (encode)
+      values_sample.npy      float64 (columns, rows): decoded values at the sampled rows, 0.0 in null slots (undefined there) (decode)
+      validity_sample.npy    float32 (columns, rows): decoded validity bits at the sampled rows (decode)
+    Columns and rows are drawn with DUMP_SEED, so they depend on --columns only; 40 MiB at most besides page_metas."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    pick = np.sort(rng.choice(len(enc), min(len(enc), DUMP_COLUMNS), replace=False))
+    rows = np.sort(rng.choice(ROWS, min(ROWS, DUMP_ROWS), replace=False))
+    out = {}
+    metas = [np.column_stack([np.full(e.n_pages, i, np.float64), e.metas_array().astype(np.float64)]) for i, e in enumerate(enc)]
+    out["page_metas"] = np.concatenate(metas).reshape(-1, 3)
+    out["pages_sample"] = np.concatenate([enc[i].pages[:min(enc[i].length, DUMP_PAGE_BYTES)].cpu().numpy() for i in pick]).astype(np.float32)
+    idx = torch.from_numpy(rows).to(dec[0].values.device)
+    vals, valid = [], []
+    for i in pick:
+        v = dec[i].values[:ROWS * 8].view(torch.float64)[idx].cpu().numpy()
+        m = np.unpackbits(dec[i].validity_numpy(), bitorder="little")[:ROWS][rows].astype(bool)
+        vals.append(np.where(m, v, 0.0))
+        valid.append(m.astype(np.float32))
+    out["values_sample"] = np.stack(vals)
+    out["validity_sample"] = np.stack(valid)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT, "--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_LIMIT)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1110,11 +1154,23 @@ def main():
                     help="collective backend; nccl = RCCL over xGMI (the measured configuration).  gloo lets the N > 1 path be "
                          "exercised on a box with fewer GPUs than ranks (ranks then share devices): a functional check, not a number")
     ap.add_argument("--only", default=None, help="comma list of configs (c1,c3,c3_lz4,c4,c5,one_page,host_boundary,continuity): run ONLY these, "
-                                                 "without the headline (profiling runs)")
+                                                 "without the headline (profiling runs; implies --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: round-trip check, per-kernel pass (roofline), CPU baseline, the other "
+                         "configurations and bench_detail.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a seeded sample of the last step's outputs as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.only and args.dump_outputs:
+        raise SystemExit("--dump-outputs writes the headline's outputs; --only runs without the headline")
+    full = args.full or bool(args.only)
+    cpu_on = full and not args.no_cpu_baseline
+    configs_on = full and not args.no_configs
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args.gpus, args.backend)   # does not return
 
@@ -1183,18 +1239,19 @@ def main():
     U_col = ROWS * 8 + (ROWS + 7) // 8          # uncompressed Arrow bytes of one column
     U = U_col * B
 
-    # ---- one untimed pass to allocate outputs and to verify the round trip bit for bit
+    # ---- one untimed pass to allocate outputs (and, with --full, to verify the round trip bit for bit)
     enc = write.encode_columns(ctx, cols, opts)
     ctx.synchronize()
     pages = [read.ColumnPages(PhysicalType.FLOAT64, True, e.pages, e.metas_array()) for e in enc]
     dec = read.batch_read_columns(ctx, pages)
     ctx.synchronize()
     page_bytes = sum(e.length for e in enc)
-    valid_rows = torch.from_numpy(np.unpackbits(host0[1], bitorder="little")[:ROWS].astype(bool)).to(dev)
-    assert torch.equal(dec[0].validity[:(ROWS + 7) // 8], cols[0].validity), "validity round trip failed"
-    got = dec[0].values.view(torch.float64)
-    ref = cols[0].values.view(torch.float64)
-    assert torch.equal(got[valid_rows], ref[valid_rows]), "value round trip failed"
+    if full:
+        valid_rows = torch.from_numpy(np.unpackbits(host0[1], bitorder="little")[:ROWS].astype(bool)).to(dev)
+        assert torch.equal(dec[0].validity[:(ROWS + 7) // 8], cols[0].validity), "validity round trip failed"
+        got = dec[0].values.view(torch.float64)
+        ref = cols[0].values.view(torch.float64)
+        assert torch.equal(got[valid_rows], ref[valid_rows]), "value round trip failed"
 
     wbatch = write.WriteBatch(ctx, cols, opts, out=enc)   # descriptors built once, outside the loop
     rbatch = read.ReadBatch(ctx, pages, out=dec)
@@ -1224,15 +1281,19 @@ def main():
         assert len(shard.column_metas(all_metas)) == world * B
     barrier()
     t1 = time.perf_counter()
-    # ---- the same K steps once more with HIP events around every kernel launch (recorded by the
-    # library on the stream the kernels run on): per-kernel durations for the roofline figure.  Kept
-    # out of the timed region above because 2 event records per launch cost ~15 % of a 0.6 ms step.
-    ctx.profile(True)
-    for _ in range(args.steps):
-        step()
-    ctx.synchronize()
-    stats = ctx.profile_read()
-    ctx.profile(False)
+    if args.dump_outputs and rank == 0:   # (the buffers of the timed path hold what its last step returned)
+        dump_outputs(args.dump_outputs, enc, dec)
+    stats = {}
+    if full:
+        # ---- the same K steps once more with HIP events around every kernel launch (recorded by the
+        # library on the stream the kernels run on): per-kernel durations for the roofline figure.  Kept
+        # out of the timed region above because 2 event records per launch cost ~15 % of a 0.6 ms step.
+        ctx.profile(True)
+        for _ in range(args.steps):
+            step()
+        ctx.synchronize()
+        stats = ctx.profile_read()
+        ctx.profile(False)
 
     elapsed = t1 - t0
     if world > 1:
@@ -1240,7 +1301,7 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     c4s = c5s = None
-    if world > 1 and not args.no_configs:   # the configuration BASELINE names for 8 GPUs, sharded by page ranges
+    if world > 1 and configs_on:   # the configuration BASELINE names for 8 GPUs, sharded by page ranges
         del wbatch, rbatch
         try:   # (its own failures are caught inside, rank-collectively; this guards what is not: the headline line comes first)
             c4s = run_c4_sharded(harness, world, rank, dist, on_device=args.backend == "nccl")
@@ -1275,8 +1336,8 @@ def main():
         kernels = {k: {"launches": v[0], "avg_ms": round(v[1] / v[0], 4)} for k, v in stats.items()}
         # HBM traffic of the dominant kernel from the PMC counters (rocprofv3 --pmc FETCH_SIZE /
         # WRITE_SIZE, separate passes of this same command; summary committed under profiles/)
-        src_sha = kernel_source_sha()
-        for pf in ("r06_pmc_traffic.json", "r05_pmc_traffic.json"):
+        src_sha = kernel_source_sha() if full else None
+        for pf in ("r06_pmc_traffic.json", "r05_pmc_traffic.json") if roof else ():   # (no roofline without --full)
             try:
                 pmc = json.load(open(os.path.join(ROOT, "profiles", pf)))
                 pc = pmc["config"]
@@ -1295,7 +1356,7 @@ def main():
                 pass
 
         cpu = None
-        if not args.no_cpu_baseline and world == 1:   # (the CPU leg is a property of the box: timed at N = 1 only)
+        if cpu_on and world == 1:   # (the CPU leg is a property of the box: timed at N = 1 only)
             from oracle import sbo
             if codec < 0:
                 o = sbo.make_options(max_page_size=PAGE, ratio=2.0, forbidden=())
@@ -1305,9 +1366,9 @@ def main():
             cpu = cpu_baseline([c0], o, U_col, "1 column (1 M rows, 16 pages) of the same workload, encode+decode, best of 2; the all-cores "
                                                "leg runs replicas of it page-parallel over std::threads")
         configs = None
-        if world > 1 and not args.no_configs:
+        if world > 1 and configs_on:
             configs = {"c4_sharded": c4s, "c5_sharded": c5s}
-        if world == 1 and not args.no_configs:
+        if world == 1 and configs_on:
             del wbatch, rbatch, enc, dec, pages, cols
             torch.cuda.empty_cache()
             configs = run_configs(harness, None, not args.no_cpu_baseline, log)
@@ -1338,8 +1399,9 @@ def main():
             "data": "synthetic",
         }
         out = assemble_line(head, cfg, roof, north, cpu, configs)
-        write_detail(dict(head, config=cfg, roofline=roof, north_star_decode=north, cpu_baseline=cpu, kernels=kernels, configs=configs,
-                          kernel_source_sha16=src_sha))
+        if full:
+            write_detail(dict(head, config=cfg, roofline=roof, north_star_decode=north, cpu_baseline=cpu, kernels=kernels,
+                              configs=configs, kernel_source_sha16=src_sha))
         print(bench_line(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

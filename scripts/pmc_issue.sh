@@ -12,7 +12,7 @@ timeout 120 rocprofv3 -L > $OUT/avail.txt 2>&1 < /dev/null
 grep -o "SQ_[A-Z_0-9]*" $OUT/avail.txt | sort -u > $OUT/sq_names.txt
 for set in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS" "SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY" "SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA" "SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM" "GRBM_GUI_ACTIVE SQ_WAIT_ANY SQ_INSTS_SMEM"; do
     name=$(echo $set | tr ' ' '+')
-    timeout 400 rocprofv3 --pmc $set -d $OUT/$name -o b -- python $R/bench.py --no-configs --no-cpu-baseline --steps 10 > /dev/null 2> $OUT/$name.err < /dev/null
+    timeout 400 rocprofv3 --pmc $set -d $OUT/$name -o b -- python $R/bench.py --full --no-configs --no-cpu-baseline --steps 10 > /dev/null 2> $OUT/$name.err < /dev/null
 done
 python - <<PYEOF
 import glob, json, sqlite3, collections, os

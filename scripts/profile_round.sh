@@ -19,7 +19,7 @@ run() {  # name, pmc (0/1), bench args...
         done
     fi
 }
-run c2 1 --no-configs --no-cpu-baseline --steps 10
+run c2 1 --full --no-configs --no-cpu-baseline --steps 10
 run c1 1 --only c1 --no-cpu-baseline
 run c3 1 --only c3,c3_lz4 --no-cpu-baseline
 run c4 1 --only c4 --no-cpu-baseline

@@ -170,3 +170,43 @@ def test_kernel_source_sha_covers_every_kernel_source():
     assert {"sb_decode.hip", "sb_encode.hip", "sb_zstd_blocks.h", "sb_lz4_big.h", "sb_nested.hip"} <= set(srcs)
     a = bench.kernel_source_sha()
     assert len(a) == 16 and a == bench.kernel_source_sha()
+
+
+def test_bench_dump_outputs_is_seeded_and_bounded(tmp_path):
+    """bench.py --dump-outputs on host stand-ins of the batch's outputs: float32 / float64 files within the 64 MB budget,
+    the same sample on every call, null slots written as 0.0"""
+    import torch
+    import bench
+
+    class Enc:
+        def __init__(self, i):
+            self.pages = torch.from_numpy(np.random.default_rng(i).integers(0, 256, 700_000).astype(np.uint8))
+            self.length, self.n_pages = 600_000 + i, 16
+
+        def metas_array(self):
+            return np.tile(np.array([[37_500, 65_536]], np.uint64), (16, 1))
+
+    class Dec:
+        def __init__(self, i):
+            rng = np.random.default_rng(1000 + i)
+            self.values = torch.from_numpy(rng.random(bench.ROWS).view(np.uint8).copy())
+            self.validity = torch.from_numpy(np.packbits(rng.random(bench.ROWS) < 0.9, bitorder="little"))
+
+        def validity_numpy(self):
+            return self.validity.numpy()
+
+    enc, dec = [Enc(i) for i in range(16)], [Dec(i) for i in range(16)]
+    bench.dump_outputs(str(tmp_path / "a"), enc, dec)
+    bench.dump_outputs(str(tmp_path / "b"), enc, dec)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["page_metas.npy", "pages_sample.npy", "validity_sample.npy", "values_sample.npy"]
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "a" / "page_metas.npy").shape == (16 * 16, 3)
+    vals, valid = np.load(tmp_path / "a" / "values_sample.npy"), np.load(tmp_path / "a" / "validity_sample.npy")
+    assert vals.shape == valid.shape == (bench.DUMP_COLUMNS, bench.DUMP_ROWS)
+    assert np.all(vals[valid == 0] == 0.0) and 0.85 < valid.mean() < 0.95
