@@ -444,8 +444,6 @@ __global__ void __launch_bounds__(BP_WG) k_enc_bin_page(EncodeArgs a) {
     uint32_t bm_c = 0, bm_n = 0;
     unsigned long long my_tus = 0, slow_rows = 0;   // (bit k: row k * BP_WG + t)
     constexpr int U = 4;
-    const uint8_t* dummy = (const uint8_t*)aux;   // 64 readable bytes for the loads of lanes that have nothing to load
-    const uint8_t* vsafe = vlen >= 32 ? values : dummy;   // (uniform) base of the 32-byte loads: idle lanes read its first bytes
     using Off = typename std::conditional<sizeof(O) == 4, uint32_t, uint64_t>::type;   // (Arrow offsets are not negative)
     // The table is 8192 BUCKETS of four slots (one ds_read_b128 per probe): a key takes the first free slot of its bucket —
     // slots fill in order and are never freed, so a string's copies find it there — and moves on to the next bucket only

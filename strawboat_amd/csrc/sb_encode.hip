@@ -106,7 +106,7 @@ struct EncodeArgs {
     const EncCol* vcols;  // virtual columns / pages of Freq exceptions: entries n_cols.. / n_pages.. (device-written)
     const EncPage* vpages;
     uint32_t* freq_count;  // pages that chose Freq in this call (the Freq kernels return at once when 0)
-    uint32_t* codec_counts;  // [32] adaptive mode: pages per chosen codec ([31]: left to the row-level selector); an emit
+    uint32_t* codec_counts;  // [32] adaptive mode: pages per chosen codec, and the HINT_* slots above the codec ids; an emit
                              // kernel whose codec nobody chose returns before it looks at a page
     uint32_t use_counts;     // this launch may trust codec_counts (adaptive wave over real pages)
     uint32_t null_cols;      // the batch holds Null columns (their empty pages are recorded by k_enc_emit_tiles)
@@ -129,6 +129,11 @@ struct EncodeArgs {
                                     // that needs one after all is left unwritten, and k_enc_layout asks for the replay (KIND_REPLAY)
 };
 constexpr uint32_t SKIP_DICT_BIG = 1u, SKIP_FREQ_BIG = 2u, SKIP_EMIT = 4u;
+// codec_counts slots above the codec ids: counts of the call that tell the next call with the same plan which kernels it needs
+constexpr int HINT_FREQ = 28;            // pages that went through the Freq kernels (k_enc_freq_finish)
+constexpr int HINT_RLE_EMIT = 29;        // 4- / 8-byte RLE pages the fused selectors left to the page kernel
+constexpr int HINT_BIN_DICT_EMIT = 30;   // binary Dict pages k_enc_bin_page left to the page kernel
+constexpr int HINT_ROW_SELECT = 31;      // pages k_enc_select_runs left to the row-level k_enc_select_rle
 constexpr uint32_t ZPAR_CH = 32768;      // a Zstd frame's blocks when they are compressed by waves of their own (measured on C5, write / read GB/s: 16 KiB 129 / 171, 32 KiB 147 / 201, 64 KiB 90 / 175)
 constexpr uint32_t ZPAR_CH_SMALL = 16384; // ... in calls with fewer pieces than chunk waves
 constexpr uint32_t ZPAR_WAVES = 2048;     // 8 per CU: what 20 KB of LDS per wave (and 221 VGPRs) keep resident; a larger pool runs a second, thin round
@@ -3359,7 +3364,7 @@ constexpr uint32_t BIN_LDS_SLOTS = 16384;
 // page kernels it was a serial chain of ~20 staged tiles per page (0.37 ms of a page's 0.93 ms in the selector even alone on
 // a CU).  One workgroup per (page, BH_ROWS rows): the tile's bytes are staged in LDS with coalesced 16-byte loads and hashed
 // from there; the selector and the dictionary builder then start from h64.
-constexpr uint32_t BH_ROWS = 2048, BH_LDS_WORDS = 10240;   // 40 KiB of staging: 4 workgroups per CU
+constexpr uint32_t BH_ROWS = 2048;
 #ifndef BV_ROWS_
 #define BV_ROWS_ 4096
 #endif
@@ -3627,7 +3632,7 @@ __global__ void __launch_bounds__(WG, 4) k_enc_select_rle(EncodeArgs a) {
     __shared__ uint32_t s_misc[2 * WG + 16];
     __shared__ __attribute__((aligned(16))) uint8_t sample_mem[SAMPLE_CAP * (KIND + 1) + 16];
     __shared__ uint32_t s_cnt2[2];
-    if (a.codec_counts[31] == 0) return;  // k_enc_select_runs (launched before) took every page
+    if (a.codec_counts[HINT_ROW_SELECT] == 0) return;  // k_enc_select_runs (launched before) took every page
     const uint32_t page = blockIdx.x;
     const EncPage p = a.pages[page];
     if (p.codec != CODEC_ON_DEVICE) return;
@@ -3684,7 +3689,7 @@ __global__ void __launch_bounds__(WG, SB_RUNS_OCC) k_enc_select_runs(EncodeArgs 
     if (N >= SEL_BIG_ROWS) {   // long pages: section-parallel selection and RLE (sb_select_big.h), not one workgroup's walk
         if (threadIdx.x == 0) {
             a.codecs[page] = CODEC_PENDING;
-            atomicAdd(&a.codec_counts[31], 1u);
+            atomicAdd(&a.codec_counts[HINT_ROW_SELECT], 1u);
         }
         return;
     }
@@ -3701,7 +3706,7 @@ __global__ void __launch_bounds__(WG, SB_RUNS_OCC) k_enc_select_runs(EncodeArgs 
     if (threadIdx.x == 0) {
         if (fallback) {
             a.codecs[page] = CODEC_PENDING;
-            atomicAdd(&a.codec_counts[31], 1u);
+            atomicAdd(&a.codec_counts[HINT_ROW_SELECT], 1u);
             return;
         }
         a.codecs[page] = (int32_t)codec;
@@ -3776,14 +3781,14 @@ __global__ void __launch_bounds__(WG, (emit_pages_occupancy<KIND, CODEC>()))
         if (a.outs[page].pad == 1 && a.outs[page].length != 0) return;
     }
     if constexpr (CODEC == SB_CODEC_RLE) {
-        if (threadIdx.x == 0 && a.use_counts) atomicAdd(&a.codec_counts[29], 1u);   // (RLE pages the fused selectors did not write: the hint for the next call)
+        if (threadIdx.x == 0 && a.use_counts) atomicAdd(&a.codec_counts[HINT_RLE_EMIT], 1u);   // (RLE pages the fused selectors did not write: the hint for the next call)
     }
     if constexpr (CODEC == SB_CODEC_DICT) {
         // a long page whose section-parallel writers were skipped on a hint: not one workgroup's walk over millions of rows —
         // the page stays unwritten and the call is replayed (k_enc_layout)
         if ((a.skips & SKIP_DICT_BIG) && p.bigx_off && page < a.n_pages) return;
         // (binary Dict pages k_enc_bin_page did not finish itself: the hint for the next call)
-        if (KIND < 0 && threadIdx.x == 0 && a.use_counts) atomicAdd(&a.codec_counts[30], 1u);
+        if (KIND < 0 && threadIdx.x == 0 && a.use_counts) atomicAdd(&a.codec_counts[HINT_BIN_DICT_EMIT], 1u);
     }
     const EncCol c = get_col(a, p.col);
     if (c.ptype == SB_TYPE_NULL) return;
@@ -5291,7 +5296,7 @@ __global__ void __launch_bounds__(64) k_enc_layout(EncodeArgs a, const uint64_t*
         off += __shfl(incl, 63, 64);
     }
     const bool any_bad = __ballot(bad) != 0;
-    if (lane == 0 && blockIdx.x == 0) a.codec_counts[28] = *a.freq_count;   // (pages that went through the Freq kernels, for the next call's hint)
+    if (lane == 0 && blockIdx.x == 0) a.codec_counts[HINT_FREQ] = *a.freq_count;   // (pages that went through the Freq kernels, for the next call's hint)
     if (lane == 0) {
         res[2 * c.n_pages] = off;
         if (any_bad && a.skips) {   // a page whose kernel was skipped on a hint: the interval is issued again in full
@@ -5370,6 +5375,8 @@ static uint64_t slot_fixed_bytes(int32_t ptype, int32_t nullable, uint64_t N) {
     return b + 9 + 9 + N * (w + 8) + 4 + 64;
 }
 
+static int32_t write_columns_impl(sb_ctx* ctx, sb_column_write* cols, uint64_t n, const sb_write_options* opts, int32_t mem);
+
 extern "C" {
 
 uint64_t sb_write_bound(int32_t physical_type, int32_t is_nullable, uint64_t rows, uint64_t values_len,
@@ -5387,7 +5394,6 @@ uint64_t sb_write_bound(int32_t physical_type, int32_t is_nullable, uint64_t row
     return total;
 }
 
-static int32_t write_columns_impl(sb_ctx* ctx, sb_column_write* cols, uint64_t n, const sb_write_options* opts, int32_t mem);
 // SB_MEM_HOST calls of many columns in groups (see sb_read_columns): the pages of group g travel back while group g + 1's
 // Arrow buffers travel in.  How many bytes a column's pages are is known when its results are back, so the host waits for
 // group g's results (its inputs and kernels run behind group g + 1's copies, which are already queued) and sends exactly
@@ -5434,84 +5440,99 @@ int32_t sb_write_columns(sb_ctx* ctx, sb_column_write* cols, uint64_t n, const s
     if (rc == SB_OK && ctx && n && !ctx->in_replay) ctx->calls.push_back(sb_ctx::Call{1, cols, n, *opts, mem});   // (for a replay: sb_host.h)
     return rc;
 }
-static int32_t write_columns_impl(sb_ctx* ctx, sb_column_write* cols, uint64_t n, const sb_write_options* opts, int32_t mem) {
-    if (!ctx || (!cols && n) || !opts) return SB_ERR_INVALID;
-    if (n == 0) return SB_OK;
-    (void)hipSetDevice(ctx->device);
-    hipStream_t s = ctx->stream;
-    // codec known on the host? (forced, or default_compress_ratio == None => Basic(default))
-    int32_t host_codec = -1;
-    if (opts->force_codec >= 0 && !((opts->forbidden_compressions >> opts->force_codec) & 1))
-        host_codec = opts->force_codec;
-    else if (!opts->has_default_compress_ratio)
-        host_codec = opts->default_compression;
-    const bool adaptive = host_codec < 0;  // codec chosen per page on the device (k_enc_select)
-    const uint32_t forb = opts->forbidden_compressions;
-    if (host_codec == SB_CODEC_FREQ)
-        for (uint64_t i = 0; i < n; i++) {
-            const int32_t t = cols[i].physical_type;
-            if (t == SB_TYPE_BOOLEAN || t == SB_TYPE_NULL)
-                return ctx->fail(SB_ERR_OUT_OF_SPEC, "Unknown compression codec Freq for boolean");
-        }
-    // Freq pages (chosen or forced) send their exceptions through a second wave of the same kernels
-    bool freq_possible = false;
-    const bool dict_freq = host_codec == SB_CODEC_DICT &&  // a forced Dict page whose u32 indices may become a Freq block
-                           (opts->force_index_codec == SB_CODEC_FREQ ||
-                            (opts->force_index_codec < 0 && opts->has_default_compress_ratio && !((forb >> SB_CODEC_FREQ) & 1)));
-    if (host_codec == SB_CODEC_FREQ || dict_freq || (adaptive && !((forb >> SB_CODEC_FREQ) & 1)))
-        for (uint64_t i = 0; i < n; i++) {
-            const int32_t t = cols[i].physical_type;
-            freq_possible |= t != SB_TYPE_BOOLEAN && t != SB_TYPE_NULL;
-        }
 
-    // ---- plan cache: everything below that depends only on the shape of the call (sb_ctx::EncPlan)
-    uint64_t plan_key = 0xcbf29ce484222325ull;
-    std::vector<uint64_t>& key_words = ctx->enc_plan_probe;   // every word that goes into the hash: a hit compares them all
-    key_words.clear();
-    {
-        auto mixk = [&](uint64_t v) {
-            plan_key = (plan_key ^ v) * 0x100000001b3ull;
-            plan_key ^= plan_key >> 29;
-            key_words.push_back(v);
-        };
-        mixk(n); mixk((uint64_t)mem);
-        mixk((uint64_t)opts->default_compression); mixk((uint64_t)opts->has_default_compress_ratio); mixk(opts->max_page_size);
-        mixk(opts->forbidden_compressions); mixk((uint64_t)(int64_t)opts->force_codec); mixk((uint64_t)(int64_t)opts->force_index_codec);
-        mixk(opts->flags); mixk(opts->rng_seed);
-        for (uint64_t i = 0; i < n; i++) {
-            const sb_column_write& c = cols[i];
-            mixk((uint64_t)(int64_t)c.physical_type); mixk((uint64_t)c.is_nullable); mixk(c.rows); mixk(c.values_len); mixk(c.out_capacity);
-            mixk(c.first_page_index); mixk(c.n_pages_capacity); mixk(c.page_rows ? c.n_pages_in + 1 : 0);
-            if (c.page_rows)
-                for (uint64_t q = 0; q < c.n_pages_in; q++) {
-                    mixk(c.page_rows[q]);
-                    mixk(c.page_head_bytes ? c.page_head_bytes[q] : 0);
-                }
-        }
-    }
-    sb_ctx::EncPlan& plan = ctx->enc_plan;
-    // (a 64-bit hash is not proof of an identical shape: a collision would reuse page offsets and row counts of another
-    // call and write outside the scratch and output areas)
-    bool hit = plan.valid && plan.key == plan_key && plan.n == n && plan.key_words == key_words;
-    if (hit) {   // (a second, independent look at the shape: the page count per column)
-        for (uint64_t i = 0; i < n && hit; i++) {
-            const uint64_t ps = page_size_of(cols[i].rows, opts);
-            const uint64_t np = cols[i].page_rows ? cols[i].n_pages_in : (cols[i].rows ? (cols[i].rows + ps - 1) / ps : 0);
-            hit = np == plan.col_pages[i];
-        }
-    }
-    uint64_t P = 0, max_tiles = 1, max_chunks = 1;
-    bool big_possible = false;
+}  // extern "C"
+
+// ---- write_columns_impl, step by step: call shape -> plan lookup -> checks -> (plan miss) the plan -> host staging ->
+// tables -> launches -> readbacks
+
+// What the options and the column types decide for the whole call
+struct CallShape {
+    int32_t host_codec;   // the codec when the host knows it (forced, or default_compress_ratio == None => Basic(default)); -1: adaptive
+    bool adaptive;        // codec chosen per page on the device (k_enc_select)
+    uint32_t forb;        // forbidden_compressions
+    bool dict_freq;       // a forced Dict page whose u32 indices may become a Freq block
+    bool freq_possible;   // Freq pages (chosen or forced) send their exceptions through a second pass of the same kernels
+    bool big_possible;    // long pages that may become Dict pages run their index arrays as virtual pages (sb_dict_big.h)
     // LZ4 blocks of more than LZC_CH bytes are compressed chunk by chunk (flat pages, the matcher that is free to choose)
-    const bool zs_possible = host_codec == SB_CODEC_ZSTD || (adaptive && opts->default_compression == SB_CODEC_ZSTD);
-    const bool sn_possible = host_codec == SB_CODEC_SNAPPY || (adaptive && opts->default_compression == SB_CODEC_SNAPPY);
-    const bool lz_possible = zs_possible || sn_possible || (!(opts->flags & SB_WRITE_LZ4_EXACT) &&
-                             (host_codec == SB_CODEC_LZ4 || (adaptive && opts->default_compression == SB_CODEC_LZ4)));
-    uint64_t lz_chunk = zs_possible ? ZPAR_CH : LZC_CH;
-    uint64_t lz_cap = 0, lz_cap_small = 0;   // (_small: with Zstd pieces of ZPAR_CH_SMALL bytes, see below)
-    bool lz_any = false, lz_any_small = false;
+    bool zs_possible, sn_possible, lz_possible;
+    bool forbids(int32_t codec) const { return (forb >> codec) & 1; }
+};
+
+static int32_t call_shape(sb_ctx* ctx, const sb_column_write* cols, uint64_t n, const sb_write_options* opts, CallShape& sh) {
+    sh.host_codec = -1;
+    if (opts->force_codec >= 0 && !((opts->forbidden_compressions >> opts->force_codec) & 1))
+        sh.host_codec = opts->force_codec;
+    else if (!opts->has_default_compress_ratio)
+        sh.host_codec = opts->default_compression;
+    sh.adaptive = sh.host_codec < 0;
+    sh.forb = opts->forbidden_compressions;
+    bool any_bool = false, any_other = false, any_long = false;
     for (uint64_t i = 0; i < n; i++) {
-        sb_column_write& c = cols[i];
+        const int32_t t = cols[i].physical_type;
+        any_bool |= t == SB_TYPE_BOOLEAN || t == SB_TYPE_NULL;
+        any_other |= t != SB_TYPE_BOOLEAN && t != SB_TYPE_NULL;
+        any_long |= cols[i].rows >= std::min<uint64_t>(SEL_BIG_ROWS, BIN_BIG_ROWS);
+    }
+    if (sh.host_codec == SB_CODEC_FREQ && any_bool) return ctx->fail(SB_ERR_OUT_OF_SPEC, "Unknown compression codec Freq for boolean");
+    sh.dict_freq = sh.host_codec == SB_CODEC_DICT &&
+                   (opts->force_index_codec == SB_CODEC_FREQ ||
+                    (opts->force_index_codec < 0 && opts->has_default_compress_ratio && !sh.forbids(SB_CODEC_FREQ)));
+    sh.freq_possible = any_other && (sh.host_codec == SB_CODEC_FREQ || sh.dict_freq || (sh.adaptive && !sh.forbids(SB_CODEC_FREQ)));
+    sh.big_possible = sh.adaptive && any_long;
+    const int32_t dc = opts->default_compression;
+    sh.zs_possible = sh.host_codec == SB_CODEC_ZSTD || (sh.adaptive && dc == SB_CODEC_ZSTD);
+    sh.sn_possible = sh.host_codec == SB_CODEC_SNAPPY || (sh.adaptive && dc == SB_CODEC_SNAPPY);
+    sh.lz_possible = sh.zs_possible || sh.sn_possible ||
+                     (!(opts->flags & SB_WRITE_LZ4_EXACT) && (sh.host_codec == SB_CODEC_LZ4 || (sh.adaptive && dc == SB_CODEC_LZ4)));
+    return SB_OK;
+}
+
+static uint64_t pages_of(const sb_column_write& c, const sb_write_options* opts) {
+    if (c.page_rows) return c.n_pages_in;
+    const uint64_t ps = page_size_of(c.rows, opts);
+    return c.rows ? (c.rows + ps - 1) / ps : 0;
+}
+
+// ---- plan cache: everything that depends only on the shape of the call (sb_ctx::EncPlan).  `key` is an FNV hash over
+// ctx->enc_plan_probe, every word that went into it; a hit compares them all, and the page count per column once more.
+// (A 64-bit hash is not proof of an identical shape: a collision would reuse page offsets and row counts of another call
+// and write outside the scratch and output areas.)
+static bool plan_lookup(sb_ctx* ctx, const sb_column_write* cols, uint64_t n, const sb_write_options* opts, int32_t mem, uint64_t& key) {
+    key = 0xcbf29ce484222325ull;
+    std::vector<uint64_t>& key_words = ctx->enc_plan_probe;
+    key_words.clear();
+    auto mixk = [&](uint64_t v) {
+        key = (key ^ v) * 0x100000001b3ull;
+        key ^= key >> 29;
+        key_words.push_back(v);
+    };
+    mixk(n); mixk((uint64_t)mem);
+    mixk((uint64_t)opts->default_compression); mixk((uint64_t)opts->has_default_compress_ratio); mixk(opts->max_page_size);
+    mixk(opts->forbidden_compressions); mixk((uint64_t)(int64_t)opts->force_codec); mixk((uint64_t)(int64_t)opts->force_index_codec);
+    mixk(opts->flags); mixk(opts->rng_seed);
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_column_write& c = cols[i];
+        mixk((uint64_t)(int64_t)c.physical_type); mixk((uint64_t)c.is_nullable); mixk(c.rows); mixk(c.values_len); mixk(c.out_capacity);
+        mixk(c.first_page_index); mixk(c.n_pages_capacity); mixk(c.page_rows ? c.n_pages_in + 1 : 0);
+        if (c.page_rows)
+            for (uint64_t q = 0; q < c.n_pages_in; q++) {
+                mixk(c.page_rows[q]);
+                mixk(c.page_head_bytes ? c.page_head_bytes[q] : 0);
+            }
+    }
+    const sb_ctx::EncPlan& plan = ctx->enc_plan;
+    if (!(plan.valid && plan.key == key && plan.n == n && plan.key_words == key_words)) return false;
+    for (uint64_t i = 0; i < n; i++)
+        if (pages_of(cols[i], opts) != plan.col_pages[i]) return false;
+    return true;
+}
+
+// The checks of every call (those the plan key covers are made when the plan is built); P: the pages of the call
+static int32_t validate_cols(sb_ctx* ctx, const sb_column_write* cols, uint64_t n, const sb_write_options* opts, uint64_t& P) {
+    P = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_column_write& c = cols[i];
         if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return ctx->fail(SB_ERR_INVALID, "bad physical_type");
         // a flat column of zero rows: encode_chunk panics upstream (common.rs:54-58 divides by the page size).  A
         // nested leaf with explicit paging may hold zero leaf slots (every list empty or null): write_nested
@@ -5521,190 +5542,100 @@ static int32_t write_columns_impl(sb_ctx* ctx, sb_column_write* cols, uint64_t n
         if (c.rows && c.physical_type != SB_TYPE_NULL && !c.values && !(enc_is_binary(c.physical_type) && c.values_len == 0))
             return ctx->fail(SB_ERR_INVALID, "values is null");  // (a binary column of empty strings has no value bytes)
         if (enc_is_binary(c.physical_type) && !c.offsets) return ctx->fail(SB_ERR_INVALID, "offsets is null");
-        const uint64_t ps = page_size_of(c.rows, opts);
-        const uint64_t np = c.page_rows ? c.n_pages_in : (c.rows + ps - 1) / ps;
+        const uint64_t np = pages_of(c, opts);
         if (np > c.n_pages_capacity || !c.out_metas) return ctx->fail(SB_ERR_INVALID, "out_metas too small");
-        // (long pages that may become Dict pages run their index arrays as virtual pages: sb_dict_big.h)
-        big_possible |= adaptive && c.rows >= std::min<uint64_t>(SEL_BIG_ROWS, BIN_BIG_ROWS);
         if (!c.out_pages && c.physical_type != SB_TYPE_NULL) return ctx->fail(SB_ERR_INVALID, "out_pages is null");
         P += np;
-        if (hit) continue;   // (the per-page arithmetic of this shape is in the plan)
+    }
+    if (P >= 0x7FFFFFFFull) return ctx->fail(SB_ERR_INVALID, "too many pages in one call");
+    return SB_OK;
+}
+
+// The Dict hash area of a page of N rows (2N slots or more, a power of two) and its N-entry arrays
+static uint64_t dict_aux_bytes(uint64_t N) {
+    uint64_t M = 64;
+    while (M < 2 * N) M <<= 1;
+    return (M + 3 * N) * 4;
+}
+
+// A plan miss: the page table (written into the staging slot `hp`, uploaded from there to the plan's own buffer), the
+// scratch layout and the launch sizes of this shape.  Everything after it reads them from ctx->enc_plan.
+static int32_t build_plan(sb_ctx* ctx, hipStream_t s, const sb_column_write* cols, uint64_t n, const sb_write_options* opts,
+                          const CallShape& sh, uint64_t P, uint64_t key, EncPage* hp) {
+    // launch sizes: tiles per page, and an upper bound of the LZ4 chunks the columns can ask for
+    uint64_t max_tiles = 1, lz_chunk = sh.zs_possible ? ZPAR_CH : LZC_CH;
+    uint64_t lz_cap = 0, lz_cap_small = 0;   // (_small: with Zstd pieces of ZPAR_CH_SMALL bytes, see below)
+    bool lz_any = false, lz_any_small = false;
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_column_write& c = cols[i];
+        const uint64_t ps = page_size_of(c.rows, opts), np = pages_of(c, opts);
         if (c.page_rows) {
             uint64_t sum = 0;
             for (uint64_t q = 0; q < np; q++) sum += c.page_rows[q];
             if (sum != c.rows) return ctx->fail(SB_ERR_INVALID, "page_rows do not add up to rows");
         }
-        {
-            uint64_t mx = ps;
-            if (c.page_rows)
-                for (uint64_t q = 0; q < np; q++) mx = std::max<uint64_t>(mx, c.page_rows[q]);
-            max_tiles = std::max<uint64_t>(max_tiles, (mx + TILE_ROWS - 1) / TILE_ROWS);
+        uint64_t mx = ps;
+        if (c.page_rows)
+            for (uint64_t q = 0; q < np; q++) mx = std::max<uint64_t>(mx, c.page_rows[q]);
+        max_tiles = std::max<uint64_t>(max_tiles, (mx + TILE_ROWS - 1) / TILE_ROWS);
+        if (!sh.lz_possible || c.physical_type == SB_TYPE_NULL) continue;
+        const bool bin = enc_is_binary(c.physical_type);
+        const uint64_t w = enc_type_width(c.physical_type);
+        for (uint64_t q = 0, r = 0; q < np; q++) {
+            const uint64_t N = c.page_rows ? c.page_rows[q] : std::min<uint64_t>(ps, c.rows - r);
+            r += N;
+            const uint64_t fb = c.physical_type == SB_TYPE_BOOLEAN ? (N + 7) / 8 : bin ? (N + 1) * w : N * w;   // the first block
+            const uint64_t ch = sh.zs_possible ? lz_chunk : lz4_chunk_bytes(fb);
+            lz_cap += (fb + ch - 1) / ch;
+            lz_any |= fb > lz_chunk;
+            lz_cap_small += (fb + ZPAR_CH_SMALL - 1) / ZPAR_CH_SMALL;
+            lz_any_small |= fb > ZPAR_CH_SMALL;
         }
-        if (lz_possible && c.physical_type != SB_TYPE_NULL) {   // upper bound of the LZ4 chunks this column can ask for
-            const bool bin = enc_is_binary(c.physical_type);
-            const uint64_t w = enc_type_width(c.physical_type);
-            auto first_block = [&](uint64_t N) {
-                return c.physical_type == SB_TYPE_BOOLEAN ? (N + 7) / 8 : bin ? (N + 1) * w : N * w;
-            };
-            for (uint64_t q = 0, r = 0; q < np; q++) {
-                const uint64_t N = c.page_rows ? c.page_rows[q] : std::min<uint64_t>(ps, c.rows - r);
-                r += N;
-                const uint64_t fb = first_block(N);
-                const uint64_t ch = zs_possible ? lz_chunk : lz4_chunk_bytes(fb);
-                lz_cap += (fb + ch - 1) / ch;
-                lz_any |= fb > lz_chunk;
-                lz_cap_small += (fb + ZPAR_CH_SMALL - 1) / ZPAR_CH_SMALL;
-                lz_any_small |= fb > ZPAR_CH_SMALL;
-            }
-            if (bin) {   // (a page's value bytes are not known here: LZC_LONG of them in one page need that many in the column)
-                lz_cap += c.values_len / (zs_possible ? lz_chunk : lz4_chunk_bytes(c.values_len)) + np + 1;
-                lz_any |= c.values_len > lz_chunk;
-                lz_cap_small += c.values_len / ZPAR_CH_SMALL + np + 1;
-                lz_any_small |= c.values_len > ZPAR_CH_SMALL;
-            }
+        if (bin) {   // (a page's value bytes are not known here: LZC_LONG of them in one page need that many in the column)
+            lz_cap += c.values_len / (sh.zs_possible ? lz_chunk : lz4_chunk_bytes(c.values_len)) + np + 1;
+            lz_any |= c.values_len > lz_chunk;
+            lz_cap_small += c.values_len / ZPAR_CH_SMALL + np + 1;
+            lz_any_small |= c.values_len > ZPAR_CH_SMALL;
         }
     }
     // a call with fewer Zstd pieces than chunk waves (one nested array, a short column): smaller pieces, more waves — the
     // call's time is the latency of one piece there, not the chip's throughput
-    if (zs_possible && !hit && lz_cap < ZPAR_WAVES) {
+    if (sh.zs_possible && lz_cap < ZPAR_WAVES) {
         lz_chunk = ZPAR_CH_SMALL;
         lz_cap = lz_cap_small;
         lz_any = lz_any_small;
     }
     if (!lz_any) lz_cap = 0;
-    if (hit) {
-        max_tiles = plan.max_tiles;
-        lz_cap = plan.lz_cap;
-        lz_chunk = plan.lz_chunk;
-    }
     if (lz_cap >= 0x7FFFFFFFull) return ctx->fail(SB_ERR_INVALID, "too many LZ4 chunks in one call");
-    if (P >= 0x7FFFFFFFull) return ctx->fail(SB_ERR_INVALID, "too many pages in one call");
 
-    // SB_MEM_HOST: the caller holds host Arrow buffers (the reference's shape); stage them over PCIe
-    std::vector<const uint8_t*> dv(n, nullptr), dval(n, nullptr), doff(n, nullptr), dheads(n, nullptr);
-    std::vector<uint8_t*> dout(n, nullptr);
-    if (mem == SB_MEM_HOST) {
-        auto stage_in = [&](const void* host, size_t bytes, const uint8_t** out) -> bool {
-            *out = nullptr;
-            if (!host || !bytes) return true;
-            uint8_t* d = ctx->stage_alloc(bytes);
-            if (!d) return false;
-            *out = d;
-            return hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, s) == hipSuccess;
-        };
-        for (uint64_t i = 0; i < n; i++) {
-            const sb_column_write& c = cols[i];
-            const uint32_t w = enc_type_width(c.physical_type);
-            size_t vbytes = c.physical_type == SB_TYPE_BOOLEAN ? (size_t)((c.values_bit_offset + c.rows + 7) / 8)
-                            : enc_is_binary(c.physical_type) ? (size_t)c.values_len : (size_t)(c.rows * w);
-            if (!stage_in(c.values, vbytes, &dv[i]) ||
-                !stage_in(c.validity, (size_t)((c.validity_bit_offset + c.rows + 7) / 8), &dval[i]) ||
-                !stage_in(enc_is_binary(c.physical_type) ? c.offsets : nullptr, (size_t)((c.rows + 1) * w), &doff[i]))
-                return ctx->fail(SB_ERR_EXTERNAL, "staging of host buffers failed");
-            if (c.page_heads && c.page_head_bytes) {  // nested level sections travel like every other DEVICE buffer
-                size_t hb = 0;
-                for (uint64_t q = 0; q < c.n_pages_in; q++) hb += (size_t)c.page_head_bytes[q];
-                if (!stage_in(c.page_heads, hb, &dheads[i])) return ctx->fail(SB_ERR_EXTERNAL, "staging of host buffers failed");
-            }
-            if (c.out_capacity) {
-                if (!(dout[i] = ctx->stage_alloc(c.out_capacity)))
-                    return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(out_pages) failed");
-                ctx->copybacks.push_back({c.out_pages, dout[i], (size_t)c.out_capacity, &cols[i].out_len});
-            }
-        }
+    sb_ctx::EncPlan& plan = ctx->enc_plan;
+    plan.valid = false;
+    plan.counts_valid = false;
+    memset(plan.prev_counts, 0, sizeof plan.prev_counts);
+    plan.bin_pages = plan.bin_unfused = false;
+    if (!ensure(ctx, plan.pages, P * sizeof(EncPage) + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(page table) failed");
+    plan.col_first.assign(n, 0);
+    plan.col_pages.assign(n, 0);
+    plan.hro.assign(n, 0);
+    for (int k = 0; k < 5; k++) {
+        plan.bigw[k].clear();
+        plan.big_secs[k] = 0;
     }
-
-
-    size_t off = 0;
-    const size_t o_cols = off;
-    off = align_up(off + n * sizeof(EncCol), 64);
-    const size_t o_resoff = off;
-    off = align_up(off + n * sizeof(uint64_t), 64);
-    const size_t upload_bytes = off;
-    const size_t o_outs = off;
-    off = align_up(off + 2 * P * sizeof(EncOut), 64);
-    const size_t o_results = off;
-    const size_t results_words = 2 * P + n;
-    off = align_up(off + results_words * sizeof(uint64_t), 64);
-    const size_t o_codecs = off;
-    off = align_up(off + 2 * P * sizeof(int32_t), 64);
-    const size_t o_freqcnt = off;
-    off = align_up(off + 64 + 32 * sizeof(uint32_t), 64);  // freq_count | codec_counts[32]
-    const size_t o_lzplan = off;                             // (inside the region zeroed per call: count | per-page plans)
-    off = align_up(off + (lz_cap ? 64 + P * sizeof(LzChunkPlan) : 0), 64);
-    const size_t o_vcols = off;
-    off = align_up(off + (freq_possible || big_possible ? P : 0) * sizeof(EncCol), 64);
-    const size_t o_vpages = off;
-    off = align_up(off + (freq_possible || big_possible ? P : 0) * sizeof(EncPage), 64);
-    const size_t o_lzlist = off;
-    off = align_up(off + lz_cap * sizeof(LzChunkDesc), 64);
-    if (!ensure(ctx, ctx->tables, off)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(tables) failed");
-
-    // staging: [cols | result offsets | readback of the results | (plan miss) the page table]
-    const size_t o_hres = upload_bytes;
-    const size_t o_hcounts = align_up(o_hres + results_words * sizeof(uint64_t), 64);   // codec counts of the call (ENC_HINT)
-    const size_t o_hpages = o_hcounts + 128;
-    StageSlot* slot = acquire_slot(ctx, o_hpages + (hit ? 0 : P * sizeof(EncPage)) + 64);
-    if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
-    EncCol* hc = (EncCol*)(slot->host + o_cols);
-    EncPage* hp = hit ? nullptr : (EncPage*)(slot->host + o_hpages);
-    uint64_t* hro = (uint64_t*)(slot->host + o_resoff);
-    if (!hit) {
-        plan.valid = false;
-        plan.counts_valid = false;
-        memset(plan.prev_counts, 0, sizeof plan.prev_counts);
-        plan.bin_pages = plan.bin_unfused = false;
-        if (!ensure(ctx, plan.pages, P * sizeof(EncPage) + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(page table) failed");
-        plan.col_first.assign(n, 0);
-        plan.col_pages.assign(n, 0);
-        plan.hro.assign(n, 0);
-        for (int k = 0; k < 5; k++) {
-            plan.bigw[k].clear();
-            plan.big_secs[k] = 0;
-        }
-    }
-
+    const int32_t codec = sh.host_codec, dc = opts->default_compression;
+    const bool adaptive = sh.adaptive, no_dict = sh.forbids(SB_CODEC_DICT);
     size_t scratch_off = 0;
     uint64_t pi = 0, res_off = 0;
     bool any_tiles = false, any_pages = false, any_compact = false, any_lz4 = false;
     for (uint64_t i = 0; i < n; i++) {
         const sb_column_write& c = cols[i];
-        EncCol& d = hc[i];
-        memset(&d, 0, sizeof d);
-        d.values = mem == SB_MEM_HOST ? dv[i] : (const uint8_t*)c.values;
-        d.validity = mem == SB_MEM_HOST ? dval[i] : c.validity;
-        d.offsets = mem == SB_MEM_HOST ? doff[i] : (const uint8_t*)c.offsets;
-        d.out = mem == SB_MEM_HOST ? dout[i] : c.out_pages;
-        d.heads = mem == SB_MEM_HOST ? dheads[i] : c.page_heads;
-        d.values_bit_offset = c.values_bit_offset;
-        d.values_len = c.values_len;
-        d.values_len_total = c.column_values_len ? c.column_values_len : c.values_len;
-        d.validity_bit_offset = c.validity_bit_offset;
-        d.out_cap = c.out_capacity;
-        d.rows = c.rows;
-        d.ptype = c.physical_type;
-        d.nullable = c.is_nullable;
-        d.width = enc_type_width(c.physical_type);
-        d.first_page = (uint32_t)pi;
-        d.fkind = c.physical_type == SB_TYPE_FLOAT32 ? 1 : c.physical_type == SB_TYPE_FLOAT64 ? 2 : 0;
-        d.nk = c.physical_type == SB_TYPE_FLOAT32 ? NK_F32 : c.physical_type == SB_TYPE_FLOAT64 ? NK_F64
-               : (c.physical_type >= SB_TYPE_UINT8 && c.physical_type <= SB_TYPE_UINT64) ? NK_UNSIGNED : NK_SIGNED;
-        const uint64_t ps = page_size_of(c.rows, opts);
+        const uint64_t ps = page_size_of(c.rows, opts), width = enc_type_width(c.physical_type);
         const bool bin = enc_is_binary(c.physical_type);
-        int32_t codec = host_codec;
         // sizes known up front => write straight to the final position
         const bool direct = !adaptive && !bin && (codec == SB_CODEC_NONE || codec == SB_CODEC_ONEVALUE) &&
                             c.physical_type != SB_TYPE_NULL;
-        uint64_t direct_off = 0, k = 0;
-        if (hit) {
-            d.first_page = plan.col_first[i];
-            d.n_pages = plan.col_pages[i];
-            hro[i] = plan.hro[i];
-            continue;
-        }
+        uint64_t direct_off = 0, k = 0, head_off = 0;
+        plan.col_first[i] = (uint32_t)pi;
         if (bin) scratch_off = align_up(scratch_off, 16);
-        const size_t col_slot_base = scratch_off;
-        uint64_t head_off = 0;
         for (uint64_t r = 0; r < c.rows || (c.page_rows && k < c.n_pages_in); k++, pi++) {
             EncPage& p = hp[pi];
             memset(&p, 0, sizeof p);
@@ -5719,14 +5650,14 @@ static int32_t write_columns_impl(sb_ctx* ctx, sb_column_write* cols, uint64_t n
             p.icodec = opts->force_index_codec;
             p.seed = page_seed_of(opts->rng_seed, c.first_page_index + k);
             p.direct = direct ? 1 : 0;
-            if (adaptive && !bin && N >= SEL_BIG_ROWS && d.width <= 8 && c.physical_type != SB_TYPE_BOOLEAN &&
+            if (adaptive && !bin && N >= SEL_BIG_ROWS && width <= 8 && c.physical_type != SB_TYPE_BOOLEAN &&
                 c.physical_type != SB_TYPE_NULL) {
                 const uint32_t secs = (uint32_t)((N + big_sec_rows(N) - 1) / big_sec_rows(N));
-                const int k = d.width == 1 ? 0 : d.width == 2 ? 1 : d.width == 4 ? 2 : 3;
-                plan.bigw[k].push_back((uint32_t)pi);
-                plan.big_secs[k] = std::max(plan.big_secs[k], secs);
-                if (!((forb >> SB_CODEC_DICT) & 1) || freq_possible) p.bigx_off = 1;   // (placed with the aux areas below)
-            } else if (adaptive && bin && N >= BIN_BIG_ROWS && !((forb >> SB_CODEC_DICT) & 1)) {   // (row hashes exist: Dict is a candidate)
+                const int b = width == 1 ? 0 : width == 2 ? 1 : width == 4 ? 2 : 3;
+                plan.bigw[b].push_back((uint32_t)pi);
+                plan.big_secs[b] = std::max(plan.big_secs[b], secs);
+                if (!no_dict || sh.freq_possible) p.bigx_off = 1;   // (placed with the aux areas below)
+            } else if (adaptive && bin && N >= BIN_BIG_ROWS && !no_dict) {   // (row hashes exist: Dict is a candidate)
                 const uint32_t secs = (uint32_t)((N + big_sec_rows(N) - 1) / big_sec_rows(N));
                 plan.bigw[4].push_back((uint32_t)pi);
                 plan.big_secs[4] = std::max(plan.big_secs[4], secs);
@@ -5736,21 +5667,21 @@ static int32_t write_columns_impl(sb_ctx* ctx, sb_column_write* cols, uint64_t n
                 p.direct_off = direct_off;
                 const uint64_t body = c.physical_type == SB_TYPE_BOOLEAN
                                           ? (codec == SB_CODEC_NONE ? (N + 7) / 8 : 1)
-                                          : (codec == SB_CODEC_NONE ? N * d.width : d.width);
+                                          : (codec == SB_CODEC_NONE ? N * width : width);
                 direct_off += p.head_bytes + (c.is_nullable ? def_section_bytes(N) : 0) + 9 + body;
             } else if (c.physical_type != SB_TYPE_NULL) {
                 p.slot_off = scratch_off;
                 scratch_off += align_up(slot_fixed_bytes(c.physical_type, c.is_nullable, N), 16);
                 any_compact = true;
-                if (freq_possible && !bin && c.physical_type != SB_TYPE_BOOLEAN) {
+                if (sh.freq_possible && !bin && c.physical_type != SB_TYPE_BOOLEAN) {
                     // a Freq page also holds the Roaring bitmap (<= 8 KiB + 8 B per 64 Ki rows, + header)
                     scratch_off += align_up(N / 8 + 16 * (N / 65536 + 1) + 8192 + 64, 16);
                     p.slot_cap = scratch_off - p.slot_off;
                     p.ex_off = scratch_off;  // exception values
-                    scratch_off += align_up(N * d.width + 64, 16);
+                    scratch_off += align_up(N * width + 64, 16);
                     p.vslot_off = scratch_off;  // slot of the exceptions block (a non-nullable page of <= N rows)
                     scratch_off += align_up(slot_fixed_bytes(c.physical_type, 0, N), 16);
-                } else if (freq_possible && bin && !((forb >> SB_CODEC_DICT) & 1) && (adaptive || codec == SB_CODEC_DICT)) {
+                } else if (sh.freq_possible && bin && !no_dict && (adaptive || codec == SB_CODEC_DICT)) {
                     // a binary Dict page with Freq-coded indices: < N/2 + 1 exception indices and their block
                     // (placed after all slots, below: a binary column's slots share one region with its value bytes)
                     p.ex_off = ~0ull;
@@ -5758,12 +5689,8 @@ static int32_t write_columns_impl(sb_ctx* ctx, sb_column_write* cols, uint64_t n
                 }
             }
             if (codec == SB_CODEC_DICT || codec == SB_CODEC_FREQ ||  // (forced Freq: exact counts when no value has a majority)
-                (adaptive && !((forb >> SB_CODEC_DICT) & 1) && c.physical_type != SB_TYPE_BOOLEAN &&
-                                           c.physical_type != SB_TYPE_NULL)) {
-                uint64_t M = 64;
-                while (M < 2 * N) M <<= 1;
-                p.aux_bytes = (M + 3 * N) * 4;
-            }
+                (adaptive && !no_dict && c.physical_type != SB_TYPE_BOOLEAN && c.physical_type != SB_TYPE_NULL))
+                p.aux_bytes = dict_aux_bytes(N);
             // (a long page counts its distinct keys exactly in a table of 8-byte keys at the start of the aux area: sb_select_big.h)
             if (p.aux_bytes && p.bigx_off && N >= std::min<uint64_t>(SEL_BIG_ROWS, BIN_BIG_ROWS))
                 p.aux_bytes = std::max<uint64_t>(p.aux_bytes, big_tab_slots(N) * 8);
@@ -5772,26 +5699,20 @@ static int32_t write_columns_impl(sb_ctx* ctx, sb_column_write* cols, uint64_t n
             if (bin && adaptive) {
                 plan.bin_pages = true;
                 if (!(p.h64_off == 0 && opts->has_default_compress_ratio && bp_fits(N, p.aux_bytes) && !(N >= BP_BIG_ROWS && p.bigx_off) &&
-                      !((forb >> SB_CODEC_DICT) & 1)))
+                      !no_dict))
                     plan.bin_unfused = true;
             }
             p.zst_off = ~0ull;
-            if (c.physical_type != SB_TYPE_NULL &&
-                (codec == SB_CODEC_ZSTD || (adaptive && opts->default_compression == SB_CODEC_ZSTD)))
+            if (c.physical_type != SB_TYPE_NULL && (codec == SB_CODEC_ZSTD || (adaptive && dc == SB_CODEC_ZSTD)))
                 p.zst_off = 0;
-            if (p.vslot_off && !((forb >> SB_CODEC_DICT) & 1)) {  // the exceptions block may be a Dict block
-                uint64_t M = 64;
-                while (M < 2 * N) M <<= 1;
-                p.vaux_bytes = (M + 3 * N) * 4;
-            }
+            if (p.vslot_off && !no_dict) p.vaux_bytes = dict_aux_bytes(N);   // the exceptions block may be a Dict block
             if (codec == SB_CODEC_LZ4 || codec == SB_CODEC_ZSTD || codec == SB_CODEC_SNAPPY ||
-                (adaptive && (opts->default_compression == SB_CODEC_LZ4 || opts->default_compression == SB_CODEC_ZSTD ||
-                              opts->default_compression == SB_CODEC_SNAPPY))) {
+                (adaptive && (dc == SB_CODEC_LZ4 || dc == SB_CODEC_ZSTD || dc == SB_CODEC_SNAPPY))) {
                 any_lz4 = true;  // staging for re-based offsets / re-packed bitmaps
-                const uint64_t st = bin ? (N + 1) * d.width + 16 : (c.physical_type == SB_TYPE_BOOLEAN ? (N + 7) / 8 + 16 : 0);
+                const uint64_t st = bin ? (N + 1) * width + 16 : (c.physical_type == SB_TYPE_BOOLEAN ? (N + 7) / 8 + 16 : 0);
                 if (st > p.aux_bytes) p.aux_bytes = st;
             }
-            if (codec == SB_CODEC_NONE || (adaptive && opts->default_compression == SB_CODEC_NONE))
+            if (codec == SB_CODEC_NONE || (adaptive && dc == SB_CODEC_NONE))
                 any_tiles = true;
             if (codec != SB_CODEC_NONE && codec != SB_CODEC_LZ4 && codec != SB_CODEC_ZSTD && codec != SB_CODEC_SNAPPY) any_pages = true;
             if (p.head_bytes) any_compact = true;  // k_enc_compact also places the heads
@@ -5799,629 +5720,702 @@ static int32_t write_columns_impl(sb_ctx* ctx, sb_column_write* cols, uint64_t n
             if (N == 0 && !c.page_rows) break;
         }
         if (bin) scratch_off += align_up(c.values_len + c.values_len / 64 + 64 * k + 64, 16);
-        (void)col_slot_base;
-        d.n_pages = (uint32_t)k;
-        hro[i] = res_off;
-        plan.col_first[i] = d.first_page;
-        plan.col_pages[i] = d.n_pages;
+        plan.col_pages[i] = (uint32_t)k;
         plan.hro[i] = res_off;
         res_off += 2 * k + 1;
         if (direct && direct_off > c.out_capacity) return ctx->fail(SB_ERR_INVALID, "out_capacity too small");
     }
     // Dict aux areas after the slots
-    for (uint64_t q = 0; q < P && !hit; q++) {
-        if (hp[q].aux_bytes) {
+    uint64_t max_chunks = 1;
+    for (uint64_t q = 0; q < P; q++) {
+        EncPage& p = hp[q];
+        const sb_column_write& c = cols[p.col];
+        if (p.aux_bytes) {
             scratch_off = align_up(scratch_off, 16);
-            hp[q].aux_off = scratch_off;
-            scratch_off += hp[q].aux_bytes;
+            p.aux_off = scratch_off;
+            scratch_off += p.aux_bytes;
         }
-        if (hp[q].h64_off == 0) {
+        if (p.h64_off == 0) {
             scratch_off = align_up(scratch_off, 16);
-            hp[q].h64_off = scratch_off;
-            scratch_off += hp[q].rows * 8;
+            p.h64_off = scratch_off;
+            scratch_off += p.rows * 8;
         }
-        if (hp[q].bigx_off == 1) {
+        if (p.bigx_off == 1) {
             scratch_off = align_up(scratch_off, 64);
-            hp[q].bigx_off = scratch_off;
-            scratch_off += ((forb >> SB_CODEC_DICT) & 1) ? BIGX_HEAD : dbig_layout(hp[q].rows, enc_is_binary(hc[hp[q].col].ptype)).total;
+            p.bigx_off = scratch_off;
+            scratch_off += no_dict ? BIGX_HEAD : dbig_layout(p.rows, enc_is_binary(c.physical_type)).total;
         }
-        if (hp[q].zst_off == 0) {   // (one block is at most 128 KiB whatever the page holds)
+        if (p.zst_off == 0) {   // (one block is at most 128 KiB whatever the page holds)
             scratch_off = align_up(scratch_off, 16);
-            hp[q].zst_off = scratch_off;
+            p.zst_off = scratch_off;
             scratch_off += zstd_scratch_bytes(ZE_BLOCK);
         }
-        if (hp[q].vaux_bytes) {
+        if (p.vaux_bytes) {
             scratch_off = align_up(scratch_off, 16);
-            hp[q].vaux_off = scratch_off;
-            scratch_off += hp[q].vaux_bytes;
+            p.vaux_off = scratch_off;
+            scratch_off += p.vaux_bytes;
         }
-        if (hp[q].ex_off == ~0ull) {  // binary Dict page with Freq-coded indices: exception indices and their block
-            const uint64_t nh = hp[q].rows / 2 + 1;
+        if (p.ex_off == ~0ull) {  // binary Dict page with Freq-coded indices: exception indices and their block
+            const uint64_t nh = p.rows / 2 + 1;
             scratch_off = align_up(scratch_off, 16);
-            hp[q].ex_off = scratch_off;
+            p.ex_off = scratch_off;
             scratch_off += align_up(nh * 4 + 64, 16);
-            hp[q].vslot_off = scratch_off;
+            p.vslot_off = scratch_off;
             scratch_off += align_up(slot_fixed_bytes(SB_TYPE_UINT32, 0, nh), 16);
         }
-        if (!hp[q].direct) {
-            const EncCol& d = hc[hp[q].col];
-            uint64_t cap = std::max<uint64_t>(slot_fixed_bytes(d.ptype, d.nullable, hp[q].rows), hp[q].slot_cap);
-            if (enc_is_binary(d.ptype)) cap += d.values_len;
+        if (!p.direct) {
+            uint64_t cap = std::max<uint64_t>(slot_fixed_bytes(c.physical_type, c.is_nullable, p.rows), p.slot_cap);
+            if (enc_is_binary(c.physical_type)) cap += c.values_len;
             max_chunks = std::max<uint64_t>(max_chunks, (cap + COMPACT_CHUNK - 1) / COMPACT_CHUNK);
         }
     }
     scratch_off = align_up(scratch_off, 16);
-    size_t lz_pool_off = scratch_off;
+    plan.lz_pool_off = scratch_off;
     scratch_off += (size_t)lz_cap * LZC_SLOT;
-    size_t zpar_off = scratch_off;
-    const uint32_t zpar_waves = (uint32_t)std::min<uint64_t>(lz_cap, ZPAR_WAVES);
-    if (lz_cap && zs_possible) scratch_off += (size_t)zpar_waves * zstd_scratch_bytes(ZPAR_CH);
-    if (hit) {
-        scratch_off = plan.scratch_total;
-        lz_pool_off = plan.lz_pool_off;
-        zpar_off = plan.zpar_off;
-        max_chunks = plan.max_chunks;
-        any_tiles = plan.any_tiles;
-        any_pages = plan.any_pages;
-        any_compact = plan.any_compact;
-        any_lz4 = plan.any_lz4;
-    }
-    if (!ensure(ctx, ctx->scratch, scratch_off + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(scratch) failed");
+    plan.zpar_off = scratch_off;
+    if (lz_cap && sh.zs_possible) scratch_off += (size_t)std::min<uint64_t>(lz_cap, ZPAR_WAVES) * zstd_scratch_bytes(ZPAR_CH);
 
-    uint8_t* tb = ctx->tables.p;
-    hipError_t e = hipMemcpyAsync(tb, slot->host, upload_bytes, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return check_hip(ctx, e, "table upload");
-    if (!hit) {   // the page table goes to the plan's own device buffer and stays there
-        e = hipMemcpyAsync(plan.pages.p, hp, P * sizeof(EncPage), hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) return check_hip(ctx, e, "page table upload");
-        if (const size_t nb = plan.bigw[0].size() + plan.bigw[1].size() + plan.bigw[2].size() + plan.bigw[3].size() + plan.bigw[4].size()) {   // (pageable source: the copy is staged before the call returns)
-            if (!ensure(ctx, plan.big, nb * sizeof(uint32_t) + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(long-page list) failed");
-            std::vector<uint32_t> both;
-            for (int k = 0; k < 5; k++) both.insert(both.end(), plan.bigw[k].begin(), plan.bigw[k].end());
-            e = hipMemcpyAsync(plan.big.p, both.data(), nb * sizeof(uint32_t), hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);   // (`both` goes out of scope; plan misses are rare)
-            if (e != hipSuccess) return check_hip(ctx, e, "long-page list upload");
-        }
-        plan.key = plan_key;
-        plan.key_words = key_words;
-        plan.n = n;
-        plan.P = P;
-        plan.max_tiles = max_tiles;
-        plan.max_chunks = max_chunks;
-        plan.lz_cap = lz_cap;
-        plan.lz_chunk = lz_chunk;
-        plan.any_tiles = any_tiles;
-        plan.any_pages = any_pages;
-        plan.any_compact = any_compact;
-        plan.any_lz4 = any_lz4;
-        plan.scratch_total = scratch_off;
-        plan.lz_pool_off = lz_pool_off;
-        plan.zpar_off = zpar_off;
-        plan.valid = true;
+    // the page table goes to the plan's own device buffer and stays there
+    hipError_t e = hipMemcpyAsync(plan.pages.p, hp, P * sizeof(EncPage), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return check_hip(ctx, e, "page table upload");
+    if (const size_t nb = plan.bigw[0].size() + plan.bigw[1].size() + plan.bigw[2].size() + plan.bigw[3].size() + plan.bigw[4].size()) {   // (pageable source: the copy is staged before the call returns)
+        if (!ensure(ctx, plan.big, nb * sizeof(uint32_t) + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(long-page list) failed");
+        std::vector<uint32_t> both;
+        for (int k = 0; k < 5; k++) both.insert(both.end(), plan.bigw[k].begin(), plan.bigw[k].end());
+        e = hipMemcpyAsync(plan.big.p, both.data(), nb * sizeof(uint32_t), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);   // (`both` goes out of scope; plan misses are rare)
+        if (e != hipSuccess) return check_hip(ctx, e, "long-page list upload");
     }
+    plan.key = key;
+    plan.key_words = ctx->enc_plan_probe;
+    plan.n = n;
+    plan.P = P;
+    plan.max_tiles = max_tiles;
+    plan.max_chunks = max_chunks;
+    plan.lz_cap = lz_cap;
+    plan.lz_chunk = lz_chunk;
+    plan.any_tiles = any_tiles;
+    plan.any_pages = any_pages;
+    plan.any_compact = any_compact;
+    plan.any_lz4 = any_lz4;
+    plan.scratch_total = scratch_off;
+    plan.valid = true;
+    return SB_OK;
+}
 
-    EncodeArgs a;
-    a.cols = (const EncCol*)(tb + o_cols);
-    a.pages = (const EncPage*)plan.pages.p;
-    a.outs = (EncOut*)(tb + o_outs);
-    a.scratch = ctx->scratch.p;
-    a.status = ctx->d_status;
-    a.results = (uint64_t*)(tb + o_results);
-    a.codecs = (int32_t*)(tb + o_codecs);
-    a.ratio = opts->default_compress_ratio;
-    a.has_ratio = opts->has_default_compress_ratio ? 1u : 0u;
-    a.forbidden = forb;
-    a.n_pages = (uint32_t)P;
-    a.n_cols = (uint32_t)n;
-    a.default_compression = (uint32_t)opts->default_compression;
-    a.vcols = (const EncCol*)(tb + o_vcols);
-    a.vpages = (const EncPage*)(tb + o_vpages);
-    a.page_base = 0;
-    a.nested_force = opts->force_index_codec;
-    a.flags = opts->flags;
-    a.lzc_plan = lz_cap ? (LzChunkPlan*)(tb + o_lzplan + 64) : nullptr;
-    a.lzc_count = (uint32_t*)(tb + o_lzplan);
-    a.lzc_list = (LzChunkDesc*)(tb + o_lzlist);
-    a.lzc_pool = ctx->scratch.p + lz_pool_off;
-    a.lzc_cap = (uint32_t)lz_cap;
-    a.lzc_chunk = (uint32_t)lz_chunk;
-    a.lzc_codec = zs_possible ? SB_CODEC_ZSTD : sn_possible ? SB_CODEC_SNAPPY : SB_CODEC_LZ4;
-    a.zpar_scratch = lz_cap && zs_possible ? ctx->scratch.p + zpar_off : nullptr;
-    a.freq_count = (uint32_t*)(tb + o_freqcnt);
-    a.codec_counts = (uint32_t*)(tb + o_freqcnt + 64);
-    a.use_counts = 0;
-    a.pre_hashed = 0;
-    a.redo = 0;
-    a.null_cols = 0;
-    for (uint64_t i = 0; i < n; i++) a.null_cols |= cols[i].physical_type == SB_TYPE_NULL ? 1u : 0u;
-    // one memset: page outputs (length 0 = not emitted), results, device-chosen codecs, the Freq page counter
-    (void)hipMemsetAsync(tb + o_outs, 0, o_vcols - o_outs, s);
-    if (host_codec == SB_CODEC_FREQ) (void)hipMemsetAsync(a.freq_count, 1, 4, s);  // forced: every page is a Freq page (non-zero)
-    auto kind_of = [](const EncCol& d) {
-        return d.ptype == SB_TYPE_BOOLEAN ? 0 : d.ptype == SB_TYPE_BINARY ? -4 : d.ptype == SB_TYPE_LARGE_BINARY ? -8 : (int)d.width;
+// The device buffers of each column: the caller's own (SB_MEM_DEVICE), or, for SB_MEM_HOST (the caller holds host Arrow
+// buffers: the reference's shape), staged copies of them over PCIe and an output area whose pages are copied back
+struct ColBufs {
+    const uint8_t *values, *validity, *offsets, *heads;
+    uint8_t* out;
+};
+static int32_t stage_cols(sb_ctx* ctx, hipStream_t s, sb_column_write* cols, uint64_t n, int32_t mem, std::vector<ColBufs>& bufs) {
+    bufs.assign(n, ColBufs{});
+    if (mem != SB_MEM_HOST) {
+        for (uint64_t i = 0; i < n; i++)
+            bufs[i] = {(const uint8_t*)cols[i].values, cols[i].validity, (const uint8_t*)cols[i].offsets, cols[i].page_heads, cols[i].out_pages};
+        return SB_OK;
+    }
+    auto stage_in = [&](const void* host, size_t bytes, const uint8_t** out) -> bool {
+        *out = nullptr;
+        if (!host || !bytes) return true;
+        uint8_t* d = ctx->stage_alloc(bytes);
+        if (!d) return false;
+        *out = d;
+        return hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, s) == hipSuccess;
     };
-    std::vector<int> kinds;
     for (uint64_t i = 0; i < n; i++) {
-        if (hc[i].ptype == SB_TYPE_NULL) continue;
-        const int kd = kind_of(hc[i]);
-        bool seen = false;
-        for (int q : kinds) seen |= q == kd;
-        if (!seen) kinds.push_back(kd);
+        const sb_column_write& c = cols[i];
+        ColBufs& b = bufs[i];
+        const uint32_t w = enc_type_width(c.physical_type);
+        size_t vbytes = c.physical_type == SB_TYPE_BOOLEAN ? (size_t)((c.values_bit_offset + c.rows + 7) / 8)
+                        : enc_is_binary(c.physical_type) ? (size_t)c.values_len : (size_t)(c.rows * w);
+        if (!stage_in(c.values, vbytes, &b.values) ||
+            !stage_in(c.validity, (size_t)((c.validity_bit_offset + c.rows + 7) / 8), &b.validity) ||
+            !stage_in(enc_is_binary(c.physical_type) ? c.offsets : nullptr, (size_t)((c.rows + 1) * w), &b.offsets))
+            return ctx->fail(SB_ERR_EXTERNAL, "staging of host buffers failed");
+        if (c.page_heads && c.page_head_bytes) {  // nested level sections travel like every other DEVICE buffer
+            size_t hb = 0;
+            for (uint64_t q = 0; q < c.n_pages_in; q++) hb += (size_t)c.page_head_bytes[q];
+            if (!stage_in(c.page_heads, hb, &b.heads)) return ctx->fail(SB_ERR_EXTERNAL, "staging of host buffers failed");
+        }
+        if (c.out_capacity) {
+            if (!(b.out = ctx->stage_alloc(c.out_capacity)))
+                return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(out_pages) failed");
+            ctx->copybacks.push_back({c.out_pages, b.out, (size_t)c.out_capacity, &cols[i].out_len});
+        }
     }
-    // One wave of select + emit kernels over the table entries [aa.page_base, aa.page_base + P).
-    // wave_adaptive: codecs are chosen on the device; wave_codec: the one codec otherwise (-1: several possible).
-    // (what the last call with this plan chose: see EncPlan.last_counts)
-    const bool big_hint = hit && plan.counts_valid && adaptive && !ctx->no_hints;
-    {
-        size_t nbig_prim = plan.bigw[0].size() + plan.bigw[1].size() + plan.bigw[2].size() + plan.bigw[3].size(), nbig = nbig_prim + plan.bigw[4].size();
-        a.skips = 0;
-        if (big_hint && nbig && !((forb >> SB_CODEC_DICT) & 1) && !plan.last_counts[SB_CODEC_DICT]) a.skips |= SKIP_DICT_BIG;
-        if (big_hint && nbig_prim && freq_possible && !plan.last_counts[SB_CODEC_FREQ]) a.skips |= SKIP_FREQ_BIG;
+    return SB_OK;
+}
+
+// The call's column table (its page ranges from the plan)
+static void fill_cols(EncCol* hc, const sb_column_write* cols, uint64_t n, const std::vector<ColBufs>& bufs, const sb_ctx::EncPlan& plan) {
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_column_write& c = cols[i];
+        EncCol& d = hc[i];
+        memset(&d, 0, sizeof d);
+        d.values = bufs[i].values;
+        d.validity = bufs[i].validity;
+        d.offsets = bufs[i].offsets;
+        d.out = bufs[i].out;
+        d.heads = bufs[i].heads;
+        d.values_bit_offset = c.values_bit_offset;
+        d.values_len = c.values_len;
+        d.values_len_total = c.column_values_len ? c.column_values_len : c.values_len;
+        d.validity_bit_offset = c.validity_bit_offset;
+        d.out_cap = c.out_capacity;
+        d.rows = c.rows;
+        d.ptype = c.physical_type;
+        d.nullable = c.is_nullable;
+        d.width = enc_type_width(c.physical_type);
+        d.first_page = plan.col_first[i];
+        d.n_pages = plan.col_pages[i];
+        d.fkind = c.physical_type == SB_TYPE_FLOAT32 ? 1 : c.physical_type == SB_TYPE_FLOAT64 ? 2 : 0;
+        d.nk = c.physical_type == SB_TYPE_FLOAT32 ? NK_F32 : c.physical_type == SB_TYPE_FLOAT64 ? NK_F64
+               : (c.physical_type >= SB_TYPE_UINT8 && c.physical_type <= SB_TYPE_UINT64) ? NK_UNSIGNED : NK_SIGNED;
     }
-    // launches that the last call with this plan would not have needed (its pages per codec, read back with its results):
-    // skipped; a page that needs one after all stays unwritten and the interval is replayed with everything (k_enc_layout)
-    uint32_t emit_skips = 0;
-    auto unused_peek = [&](int slot) { return big_hint && !plan.last_counts[slot]; };
-    auto unused = [&](int slot) {
-        if (!big_hint || plan.last_counts[slot]) return false;
+}
+
+// Where the call's tables sit.  On the device (ctx->tables): [cols | result offsets] (uploaded from the slot) | page outputs |
+// results | device-chosen codecs | freq_count + codec_counts[32] | LZ4 chunk plans | virtual cols | virtual pages | LZ4
+// chunk list.  In the staging slot: [cols | result offsets] | readback of the results | codec counts (ENC_HINT) | (plan miss)
+// the page table; the slot's offsets do not depend on lz_cap.
+struct EncLayout {
+    size_t cols, resoff, upload, outs, results, results_words, codecs, freqcnt, lzplan, vcols, vpages, lzlist, total;
+    size_t hres, hcounts, hpages;
+};
+static EncLayout enc_layout(uint64_t n, uint64_t P, uint64_t lz_cap, bool vtables) {
+    EncLayout L;
+    size_t off = 0;
+    L.cols = off;
+    off = align_up(off + n * sizeof(EncCol), 64);
+    L.resoff = off;
+    off = align_up(off + n * sizeof(uint64_t), 64);
+    L.upload = off;
+    L.outs = off;
+    off = align_up(off + 2 * P * sizeof(EncOut), 64);
+    L.results = off;
+    L.results_words = 2 * P + n;
+    off = align_up(off + L.results_words * sizeof(uint64_t), 64);
+    L.codecs = off;
+    off = align_up(off + 2 * P * sizeof(int32_t), 64);
+    L.freqcnt = off;
+    off = align_up(off + 64 + 32 * sizeof(uint32_t), 64);  // freq_count | codec_counts[32]
+    L.lzplan = off;                                          // (inside the region zeroed per call: count | per-page plans)
+    off = align_up(off + (lz_cap ? 64 + P * sizeof(LzChunkPlan) : 0), 64);
+    L.vcols = off;
+    off = align_up(off + (vtables ? P : 0) * sizeof(EncCol), 64);
+    L.vpages = off;
+    off = align_up(off + (vtables ? P : 0) * sizeof(EncPage), 64);
+    L.lzlist = off;
+    off = align_up(off + lz_cap * sizeof(LzChunkDesc), 64);
+    L.total = off;
+    L.hres = L.upload;
+    L.hcounts = align_up(L.hres + L.results_words * sizeof(uint64_t), 64);
+    L.hpages = L.hcounts + 128;
+    return L;
+}
+
+// Calls f(std::integral_constant<int, W>()) for the W among Ws that equals w (none: no call).  Only the listed widths are
+// instantiated.
+template <int... Ws, class F>
+static void by_width(int w, F&& f) {
+    (void)((w == Ws ? (f(std::integral_constant<int, Ws>()), true) : false) || ...);
+}
+
+// The launches of one call and what they share
+struct EncLaunch {
+    sb_ctx* ctx;
+    hipStream_t s;                    // the call's stream
+    const sb_write_options* opts;
+    const CallShape& sh;
+    const sb_ctx::EncPlan& plan;
+    const EncCol* hc;                 // the call's columns (host copy)
+    uint64_t n, P;
+    EncodeArgs a;                     // the call's arguments: the Freq passes, k_enc_layout and k_enc_compact launch with these
+    EncodeArgs wa;                    // ... and the selectors and page kernels with these (codec counts, fused binary pages)
+    bool old_chain;                   // binary pages go through the hash -> select -> verify chain
+    std::vector<int> kinds;           // column kinds, in order of first appearance: the width, 0 Boolean, -4 / -8 binary
+    // launches that the last calls with this plan would not have needed (their pages per codec, read back with their
+    // results) are skipped; a page that needs one after all stays unwritten and the interval is replayed (k_enc_layout)
+    bool big_hint;
+    uint32_t emit_skips = 0;          // SKIP_EMIT once one was
+    bool unused_peek(int slot) const { return big_hint && !plan.last_counts[slot]; }
+    bool unused(int slot) {
+        if (!unused_peek(slot)) return false;
         emit_skips |= SKIP_EMIT;
         return true;
-    };
-    auto run_wave = [&](const EncodeArgs& aa_in, bool wave_adaptive, int32_t wave_codec, bool nested) -> int32_t {
-        EncodeArgs aa = aa_in;
-        aa.use_counts = wave_adaptive && !nested ? 1u : 0u;
-        aa.pre_hashed = 0;
-        aa.redo = 0;
-        // binary pages of BP_MIN_ROWS .. 65 536 rows: codec and dictionary in one pass (sb_bin_page.h); the chain below only for the rest
-        // (the flag also switches on k_enc_prim_dict for integer Dict pages: binary pages or not)
-        aa.bin_fused = wave_adaptive && !nested && ctx->bin_fused && !(opts->flags & SB_WRITE_DEBUG_VERIFY_FAIL_BIT) ? 1u : 0u;
-        const bool old_chain = !aa.bin_fused || plan.bin_unfused;
-        int n_bin_kinds = 0;
-        for (int kd : kinds) n_bin_kinds += kd < 0 ? 1 : 0;
-        const bool any_bin = n_bin_kinds > 0;
-        const uint64_t max_rows = max_tiles * TILE_ROWS;
-        const dim3 tile_grid((uint32_t)P, (uint32_t)((max_rows + BH_ROWS - 1) / BH_ROWS));
-        // Column kinds work on disjoint pages: in an adaptive wave over several kinds (a mixed schema: C4) every kind's chain
-        // selector -> [string check, re-selection] -> page kernels runs on a stream of its own between a fork and a join, so
-        // that a few hundred pages per kind share the chip instead of taking turns.  Not while profiling.
-        const bool multi = wave_adaptive && !nested && kinds.size() >= 2 && n_bin_kinds < (int)kinds.size() && !ctx->profile && side_streams(ctx);
+    }
+    uint32_t max_tiles() const { return (uint32_t)plan.max_tiles; }
+    const uint32_t* big_list(int k) const {   // the long pages of plan.bigw[k] on the device
+        size_t skip = 0;
+        for (int q = 0; q < k; q++) skip += plan.bigw[q].size();
+        return (const uint32_t*)plan.big.p + skip;
+    }
+};
+
+// row hashes of the binary pages, tile-parallel, before their selector
+static void launch_hash(EncLaunch& L, hipStream_t st) {
+    if (L.wa.bin_fused && L.plan.bin_pages) {
+        KScope k(L.ctx, "k_enc_bin_page");
+        for (int kd : L.kinds)
+            by_width<-4, -8>(kd, [&](auto w) {
+                k_enc_bin_page<typename std::conditional<w == -4, int32_t, int64_t>::type><<<(uint32_t)L.P, BP_WG, 0, st>>>(L.wa);
+            });
+    }
+    if (!L.old_chain) return;
+    KScope k(L.ctx, "k_enc_bin_hash");
+    const uint64_t max_rows = L.plan.max_tiles * TILE_ROWS;
+    k_enc_bin_hash<<<dim3((uint32_t)L.P, (uint32_t)((max_rows + BH_ROWS - 1) / BH_ROWS)), WG, 0, st>>>(L.wa);
+}
+
+// A virtual page of each long page in `list` (its u32 Dict indices, or its Freq exceptions block of W-byte values),
+// selected and written section-parallel (sb_select_big.h, sb_dict_big.h)
+static void launch_virtual_pages(EncLaunch& L, const EncodeArgs& a, hipStream_t st, int w, const uint32_t* list, uint32_t nbig,
+                                 uint32_t secs, bool exceptions) {
+    const uint32_t vo = (uint32_t)L.P;
+    const dim3 sg(secs, nbig), pg(1, nbig);
+    {
+        KScope kk(L.ctx, exceptions ? "k_sel_big(exceptions)" : "k_sel_big(indices)");
+        k_sel_big_init<<<dim3(4, nbig), WG, 0, st>>>(a, list, vo);
+        by_width<1, 2, 4, 8>(w, [&](auto W) {
+            k_sel_big_sec<W><<<dim3(sg.x * BIG_SEC_SPLIT, nbig), WG, 0, st>>>(a, list, vo);
+            k_sel_big_merge<W><<<pg, WG, 0, st>>>(a, list, vo);
+            if (exceptions) k_sel_big_clear<<<sg, WG, 0, st>>>(a, list, vo);
+            k_sel_big_count<W><<<dim3(sg.x * BIG_COUNT_SPLIT, nbig), WG, 0, st>>>(a, list, vo);   // (BIG_COUNT_SPLIT workgroups per section)
+            k_sel_big_decide<W><<<pg, WG, 0, st>>>(a, list, vo);
+        });
+    }
+    KScope kk(L.ctx, "k_nested_big");
+    if (!L.sh.forbids(SB_CODEC_RLE))
+        by_width<1, 2, 4, 8>(w, [&](auto W) {
+            k_rle_big_count<W><<<sg, WG, 0, st>>>(a, list, vo);
+            k_rle_big_plan<W><<<pg, WG, 0, st>>>(a, list, vo);
+            k_rle_big_emit<W><<<sg, WG, 0, st>>>(a, list, vo);
+            k_rle_big_done<W><<<pg, 64, 0, st>>>(a, list, vo);
+        });
+    if (w == 4) {
+        const dim3 tg(std::min<uint32_t>(L.max_tiles(), 4096), nbig);
+        k_bp_big<0><<<tg, WG, 0, st>>>(a, list);
+        k_bp_big<1><<<pg, WG, 0, st>>>(a, list);
+        k_bp_big<2><<<tg, WG, 0, st>>>(a, list);
+    }
+    k_plain_big<<<dim3(1024, nbig), WG, 0, st>>>(a, list);
+}
+
+// long pages (>= 2^18 rows) of 1- / 2- / 4- / 8-byte values: section-parallel statistics, the same decision, and the
+// RLE pages among them written section-parallel too (sb_select_big.h); they were left CODEC_PENDING by the page selectors
+static void launch_big(EncLaunch& L, int kd, hipStream_t st) {
+    const int k = kd == 1 ? 0 : kd == 2 ? 1 : kd == 4 ? 2 : kd == 8 ? 3 : kd < 0 ? 4 : -1;   // (binary pages: a list of their own)
+    if (k < 0) return;
+    const uint32_t nbig = (uint32_t)L.plan.bigw[k].size();
+    if (!nbig) return;
+    const EncodeArgs& aa = L.wa;
+    const uint32_t* list = L.big_list(k);
+    const dim3 sg(L.plan.big_secs[k], nbig), pg(1, nbig);
+    // 8-byte values, and binary pages as their u64 row hashes
+    by_width<1, 2, 4, 8>(kd > 0 ? kd : 8, [&](auto W) {
+        {
+            KScope kk(L.ctx, "k_sel_big_sec");
+            k_sel_big_init<<<dim3(4, nbig), WG, 0, st>>>(aa, list, 0u);
+            k_sel_big_sec<W><<<dim3(sg.x * BIG_SEC_SPLIT, nbig), WG, 0, st>>>(aa, list, 0u);
+        }
+        {
+            KScope kk(L.ctx, "k_sel_big_merge");
+            k_sel_big_merge<W><<<pg, WG, 0, st>>>(aa, list, 0u);
+        }
+        {
+            KScope kk(L.ctx, "k_sel_big_clear");
+            k_sel_big_clear<<<sg, WG, 0, st>>>(aa, list, 0u);
+        }
+        {
+            KScope kk(L.ctx, "k_sel_big_count");
+            k_sel_big_count<W><<<dim3(sg.x * BIG_COUNT_SPLIT, nbig), WG, 0, st>>>(aa, list, 0u);
+        }
+        {
+            KScope kk(L.ctx, "k_sel_big_decide");
+            k_sel_big_decide<W><<<pg, WG, 0, st>>>(aa, list, 0u);
+        }
+        if (!L.sh.forbids(SB_CODEC_RLE) && kd > 0) {
+            KScope kk(L.ctx, "k_rle_big");
+            k_rle_big_count<W><<<sg, WG, 0, st>>>(aa, list, 0u);
+            k_rle_big_plan<W><<<pg, WG, 0, st>>>(aa, list, 0u);
+            k_rle_big_emit<W><<<sg, WG, 0, st>>>(aa, list, 0u);
+            k_rle_big_done<W><<<pg, 64, 0, st>>>(aa, list, 0u);
+        }
+    });
+    if (L.sh.forbids(SB_CODEC_DICT) || L.unused_peek(SB_CODEC_DICT)) return;
+    // long Dict pages: sb_dict_big.h
+    const dim3 gg(256, nbig), sg4(sg.x * DBIG_SPLIT, nbig);
+    by_width<1, 2, 4, 8, -4, -8>(kd, [&](auto K) {
+        {
+            KScope kk(L.ctx, "k_dict_big_insert");
+            k_dict_big_clear<K><<<gg, WG, 0, st>>>(aa, list);
+            k_dict_big_insert<K><<<sg4, WG, 0, st>>>(aa, list);
+        }
+        {
+            KScope kk(L.ctx, "k_dict_big_ids");
+            k_dict_big_mark<K><<<gg, WG, 0, st>>>(aa, list);
+            k_dict_big_rank<K><<<sg, WG, 0, st>>>(aa, list);
+            k_dict_big_ids<K><<<gg, WG, 0, st>>>(aa, list);
+        }
+        {
+            KScope kk(L.ctx, "k_dict_big_idx");
+            k_dict_big_idx<K><<<sg4, WG, 0, st>>>(aa, list);
+            by_width<-4, -8>(kd, [&](auto B) { k_dict_big_verify<B><<<sg4, WG, 0, st>>>(aa, list); });
+        }
+    });
+    // the index arrays as virtual pages of u32: selected and written
+    launch_virtual_pages(L, aa, st, 4, list, nbig, sg.x, false);
+    by_width<1, 2, 4, 8, -4, -8>(kd, [&](auto K) {
+        KScope kk(L.ctx, "k_dict_big_finish");
+        k_dict_big_finish<K><<<pg, WG, 0, st>>>(aa, list);
+        k_dict_big_values<K><<<gg, WG, 0, st>>>(aa, list);
+    });
+}
+
+static void launch_selectors(EncLaunch& L, int kd, hipStream_t st) {
+    char nm[48];
+    if (kd == 4 || kd == 8) {  // statistics + speculative RLE in one pass
+        bool any_f = false, any_i = false;
+        for (uint64_t i = 0; i < L.n; i++)
+            if ((int)L.hc[i].width == kd && L.hc[i].ptype != SB_TYPE_BOOLEAN && !enc_is_binary(L.hc[i].ptype)) {
+                any_f |= L.hc[i].fkind != 0;
+                any_i |= L.hc[i].fkind == 0;
+            }
+        // lane = raw run first; pages with runs too short for that go through the lane = row kernel (slot HINT_ROW_SELECT)
+        by_width<4, 8>(kd, [&](auto W) {
+            auto run = [&](auto FK) {
+                snprintf(nm, sizeof nm, "k_enc_select_runs<%d, %d>", (int)W, (int)FK);
+                {
+                    KScope k(L.ctx, nm);
+                    k_enc_select_runs<W, FK><<<(uint32_t)L.P, WG, 0, st>>>(L.wa);
+                }
+                if (L.unused(HINT_ROW_SELECT)) return;
+                snprintf(nm, sizeof nm, "k_enc_select_rle<%d, %d>", (int)W, (int)FK);
+                KScope k(L.ctx, nm);
+                k_enc_select_rle<W, FK><<<(uint32_t)L.P, WG, 0, st>>>(L.wa);
+            };
+            if (any_f) run(std::integral_constant<int, W == 4 ? 1 : 2>());
+            if (any_i) run(std::integral_constant<int, 0>());
+        });
+        launch_big(L, kd, st);
+        return;
+    }
+    if (kd >= 0 || L.old_chain) {
+        snprintf(nm, sizeof nm, "k_enc_select<%d>", kd);
+        KScope k(L.ctx, nm);
+        enc_select_kernel(kd)<<<(uint32_t)L.P, WG, 0, st>>>(L.wa);
+    }
+    if (kd == 1 || kd == 2 || kd < 0) launch_big(L, kd, st);
+}
+
+// the dictionaries the binary selectors handed over: strings checked tile-parallel, pages that failed selected again
+// exactly (workgroups of all other pages return at once)
+static void launch_verify(EncLaunch& L, hipStream_t st) {
+    if (!L.old_chain) return;
+    {
+        KScope k(L.ctx, "k_enc_bin_verify");
+        const uint64_t max_rows = L.plan.max_tiles * TILE_ROWS;
+        const uint32_t tpp = (uint32_t)((max_rows + BV_ROWS - 1) / BV_ROWS);
+        k_enc_bin_verify<<<(uint32_t)(((L.P + 7) / 8) * 8 * tpp), WG, 0, st>>>(L.wa, tpp);
+    }
+    L.wa.redo = 1;
+    for (int kd : L.kinds)
+        if (kd < 0) enc_select_kernel(kd)<<<(uint32_t)L.P, WG, 0, st>>>(L.wa);
+    L.wa.redo = 0;
+}
+
+// one kernel instance per (kind, codec) that can occur in the call
+static int32_t launch_emit(EncLaunch& L, int kd, hipStream_t st) {
+    static const int32_t CAND[6] = {SB_CODEC_ONEVALUE, SB_CODEC_DICT, SB_CODEC_RLE, SB_CODEC_BITPACKING,
+                                    SB_CODEC_DELTA_BITPACKING, SB_CODEC_PATAS};
+    const bool adaptive = L.sh.adaptive;
+    for (int32_t cd : CAND) {
+        if (!adaptive && cd != L.sh.host_codec) continue;
+        if (adaptive) {
+            if (L.sh.forbids(cd)) continue;
+            if ((cd == SB_CODEC_BITPACKING || cd == SB_CODEC_DELTA_BITPACKING) && kd != 4) continue;
+            if (kd == 0 && cd == SB_CODEC_DICT) continue;
+            if (kd < 0 && cd == SB_CODEC_RLE) continue;
+            if (cd == SB_CODEC_PATAS) {  // candidates of float columns only (double/mod.rs:271-277)
+                bool any_float = false;
+                for (uint64_t i = 0; i < L.n; i++) any_float |= L.hc[i].fkind != 0 && (int)L.hc[i].width == kd;
+                if (!any_float) continue;
+            }
+        }
+        EncPageKernel kf = enc_page_kernel(kd, cd);
+        if (!kf) continue;
+        if (cd == SB_CODEC_DICT && L.wa.bin_fused && !L.unused_peek(SB_CODEC_DICT))
+            by_width<1, 2, 4>(kd, [&](auto W) {
+                KScope k(L.ctx, "k_enc_prim_dict");   // integer Dict pages of up to 65 536 rows: sb_bin_page.h
+                k_enc_prim_dict<W><<<(uint32_t)L.P, BP_WG, 0, st>>>(L.wa);
+            });
+        // (4- / 8-byte RLE pages come out of the fused selectors, binary Dict pages out of k_enc_bin_page whole when their
+        // index block is bit-packed: their slots count the pages the page kernel had to write)
+        if (L.unused(cd == SB_CODEC_RLE && (kd == 4 || kd == 8)                   ? HINT_RLE_EMIT
+                     : cd == SB_CODEC_DICT && kd < 0 && L.wa.bin_fused && !L.old_chain ? HINT_BIN_DICT_EMIT
+                                                                                        : (int)cd))
+            continue;
+        char nm[48];
+        snprintf(nm, sizeof nm, "k_enc_emit_pages<%d, %d>", kd, (int)cd);
+        KScope k(L.ctx, nm);
+        kf<<<(uint32_t)L.P, WG, 0, st>>>(L.wa);
+    }
+    const int32_t hc = L.sh.host_codec;
+    if (!adaptive && hc > 3 && hc != SB_CODEC_FREQ && !enc_page_kernel(kd, hc))
+        return L.ctx->fail(SB_ERR_NYI, "no device encoder for this codec and column type");
+    return SB_OK;
+}
+
+// The selectors and the page kernels of every column kind, the plain tiles and the LZ4 / Zstd / Snappy blocks
+static int32_t launch_pages(EncLaunch& L) {
+    sb_ctx* ctx = L.ctx;
+    const sb_ctx::EncPlan& plan = L.plan;
+    const bool adaptive = L.sh.adaptive;
+    const hipStream_t s = L.s;
+    EncodeArgs& aa = L.wa;
+    int n_bin_kinds = 0;
+    for (int kd : L.kinds) n_bin_kinds += kd < 0 ? 1 : 0;
+    const bool any_bin = n_bin_kinds > 0;
+    // Column kinds work on disjoint pages: in an adaptive call over several kinds (a mixed schema: C4) every kind's chain
+    // selector -> [string check, re-selection] -> page kernels runs on a stream of its own between a fork and a join, so
+    // that a few hundred pages per kind share the chip instead of taking turns.  Not while profiling.
+    const bool multi = adaptive && L.kinds.size() >= 2 && n_bin_kinds < (int)L.kinds.size() && !ctx->profile && side_streams(ctx);
+    if (multi) {
         // binary kinds (the longest chain: hash, selector, string check, dictionary pages) on the high-priority side stream,
         // the other kinds one after the other on the call's stream; without binary columns the kinds alternate between the
         // call's stream and a side stream.  (More streams than that only made every kernel slower: the page kernels are
         // latency chains, and four of them sharing the CUs doubled the binary selector's time.)
-        auto stream_of = [&](size_t ki) -> hipStream_t {
-            if (!multi) return s;
-            if (n_bin_kinds) return kinds[ki] < 0 ? ctx->side[0] : s;
-            return (ki & 1) ? ctx->side[1] : s;
-        };
-        uint32_t side_mask = 0;
-        if (multi) side_mask = n_bin_kinds ? 1u : 2u;
-        if (multi && n_bin_kinds == (int)kinds.size()) side_mask = 0;   // (only binary kinds: nothing to overlap with)
-        auto launch_hash = [&](hipStream_t st) {   // row hashes of the binary pages, tile-parallel, before their selector
-            if (aa.bin_fused && plan.bin_pages) {
-                KScope k(ctx, "k_enc_bin_page");
-                for (int kd : kinds) {
-                    if (kd == -4) k_enc_bin_page<int32_t><<<(uint32_t)P, BP_WG, 0, st>>>(aa);
-                    if (kd == -8) k_enc_bin_page<int64_t><<<(uint32_t)P, BP_WG, 0, st>>>(aa);
-                }
-            }
-            if (!old_chain) return;
-            KScope k(ctx, "k_enc_bin_hash");
-            k_enc_bin_hash<<<tile_grid, WG, 0, st>>>(aa);
-        };
-        // long pages (>= 2^18 rows) of 1- / 2- / 4- / 8-byte values: section-parallel statistics, the same decision, and the
-        // RLE pages among them written section-parallel too (sb_select_big.h); they were left CODEC_PENDING by the page selectors
-        auto launch_big = [&](int kd, hipStream_t st) {
-            const int k = kd == 1 ? 0 : kd == 2 ? 1 : kd == 4 ? 2 : kd == 8 ? 3 : kd < 0 ? 4 : -1;   // (binary pages: a list of their own)
-            if (k < 0 || aa.page_base != 0) return;
-            const uint32_t nbig = (uint32_t)plan.bigw[k].size();
-            if (!nbig) return;
-            size_t skip = 0;
-            for (int q = 0; q < k; q++) skip += plan.bigw[q].size();
-            const uint32_t* list = (const uint32_t*)plan.big.p + skip;
-            const dim3 sg(plan.big_secs[k], nbig), pg(1, nbig);
-#define SB_BIG_W(KERNEL, GRID, THREADS)                                    \
-    do {                                                                   \
-        if (kd == 1) KERNEL<1><<<GRID, THREADS, 0, st>>>(aa, list, 0u);        \
-        else if (kd == 2) KERNEL<2><<<GRID, THREADS, 0, st>>>(aa, list, 0u);   \
-        else if (kd == 4) KERNEL<4><<<GRID, THREADS, 0, st>>>(aa, list, 0u);   \
-        else KERNEL<8><<<GRID, THREADS, 0, st>>>(aa, list, 0u);   /* 8-byte values, and binary pages as their u64 row hashes */ \
-    } while (0)
-            {
-                KScope kk(ctx, "k_sel_big_sec");
-                k_sel_big_init<<<dim3(4, nbig), WG, 0, st>>>(aa, list, 0u);
-                const dim3 sgp(sg.x * BIG_SEC_SPLIT, nbig);
-                SB_BIG_W(k_sel_big_sec, sgp, WG);
-            }
-            {
-                KScope kk(ctx, "k_sel_big_merge");
-                SB_BIG_W(k_sel_big_merge, pg, WG);
-            }
-            {
-                KScope kk(ctx, "k_sel_big_clear");
-                k_sel_big_clear<<<sg, WG, 0, st>>>(aa, list, 0u);
-            }
-            {
-                KScope kk(ctx, "k_sel_big_count");
-                const dim3 cg(sg.x * BIG_COUNT_SPLIT, nbig);
-                SB_BIG_W(k_sel_big_count, cg, WG);
-            }
-            {
-                KScope kk(ctx, "k_sel_big_decide");
-                SB_BIG_W(k_sel_big_decide, pg, WG);
-            }
-            if (!((forb >> SB_CODEC_RLE) & 1) && kd > 0) {
-                KScope kk(ctx, "k_rle_big");
-                SB_BIG_W(k_rle_big_count, sg, WG);
-                SB_BIG_W(k_rle_big_plan, pg, WG);
-                SB_BIG_W(k_rle_big_emit, sg, WG);
-                SB_BIG_W(k_rle_big_done, pg, 64);
-            }
-#undef SB_BIG_W
-            if (!((forb >> SB_CODEC_DICT) & 1) && (!big_hint || plan.last_counts[SB_CODEC_DICT])) {   // long Dict pages: sb_dict_big.h
-                const dim3 gg(256, nbig), sg4(sg.x * DBIG_SPLIT, nbig);
-                const uint32_t vo = (uint32_t)P;
-#define SB_DBIG_W(KERNEL, GRID, THREADS)                                   \
-    do {                                                                   \
-        if (kd == 1) KERNEL<1><<<GRID, THREADS, 0, st>>>(aa, list);        \
-        else if (kd == 2) KERNEL<2><<<GRID, THREADS, 0, st>>>(aa, list);   \
-        else if (kd == 4) KERNEL<4><<<GRID, THREADS, 0, st>>>(aa, list);   \
-        else if (kd == 8) KERNEL<8><<<GRID, THREADS, 0, st>>>(aa, list);   \
-        else if (kd == -4) KERNEL<-4><<<GRID, THREADS, 0, st>>>(aa, list); \
-        else KERNEL<-8><<<GRID, THREADS, 0, st>>>(aa, list);               \
-    } while (0)
-                {
-                    KScope kk(ctx, "k_dict_big_insert");
-                    SB_DBIG_W(k_dict_big_clear, gg, WG);
-                    SB_DBIG_W(k_dict_big_insert, sg4, WG);
-                }
-                {
-                    KScope kk(ctx, "k_dict_big_ids");
-                    SB_DBIG_W(k_dict_big_mark, gg, WG);
-                    SB_DBIG_W(k_dict_big_rank, sg, WG);
-                    SB_DBIG_W(k_dict_big_ids, gg, WG);
-                }
-                {
-                    KScope kk(ctx, "k_dict_big_idx");
-                    SB_DBIG_W(k_dict_big_idx, sg4, WG);
-                    if (kd == -4) k_dict_big_verify<-4><<<sg4, WG, 0, st>>>(aa, list);
-                    else if (kd == -8) k_dict_big_verify<-8><<<sg4, WG, 0, st>>>(aa, list);
-                }
-                {   // the index arrays as virtual pages of u32: selected ...
-                    KScope kk(ctx, "k_sel_big(indices)");
-                    k_sel_big_init<<<dim3(4, nbig), WG, 0, st>>>(aa, list, vo);
-                    k_sel_big_sec<4><<<dim3(sg.x * BIG_SEC_SPLIT, nbig), WG, 0, st>>>(aa, list, vo);
-                    k_sel_big_merge<4><<<pg, WG, 0, st>>>(aa, list, vo);
-                    k_sel_big_count<4><<<dim3(sg.x * BIG_COUNT_SPLIT, nbig), WG, 0, st>>>(aa, list, vo);   // (BIG_COUNT_SPLIT workgroups per section)
-                    k_sel_big_decide<4><<<pg, WG, 0, st>>>(aa, list, vo);
-                }
-                {   // ... and written
-                    KScope kk(ctx, "k_nested_big");
-                    if (!((forb >> SB_CODEC_RLE) & 1)) {
-                        k_rle_big_count<4><<<sg, WG, 0, st>>>(aa, list, vo);
-                        k_rle_big_plan<4><<<pg, WG, 0, st>>>(aa, list, vo);
-                        k_rle_big_emit<4><<<sg, WG, 0, st>>>(aa, list, vo);
-                        k_rle_big_done<4><<<pg, 64, 0, st>>>(aa, list, vo);
-                    }
-                    const dim3 tg((uint32_t)std::min<uint64_t>(max_tiles, 4096), nbig);
-                    k_bp_big<0><<<tg, WG, 0, st>>>(aa, list);
-                    k_bp_big<1><<<pg, WG, 0, st>>>(aa, list);
-                    k_bp_big<2><<<tg, WG, 0, st>>>(aa, list);
-                    k_plain_big<<<dim3(1024, nbig), WG, 0, st>>>(aa, list);
-                }
-                {
-                    KScope kk(ctx, "k_dict_big_finish");
-                    SB_DBIG_W(k_dict_big_finish, pg, WG);
-                    SB_DBIG_W(k_dict_big_values, gg, WG);
-                }
-#undef SB_DBIG_W
-            }
-        };
-        auto launch_selectors = [&](int kd, hipStream_t st) {
-            if (nested && (kd <= 0 || kd > 8)) return;
-            if (!nested && (kd == 4 || kd == 8)) {  // statistics + speculative RLE in one pass
-                bool any_f = false, any_i = false;
-                for (uint64_t i = 0; i < n; i++)
-                    if ((int)hc[i].width == kd && hc[i].ptype != SB_TYPE_BOOLEAN && !enc_is_binary(hc[i].ptype)) {
-                        any_f |= hc[i].fkind != 0;
-                        any_i |= hc[i].fkind == 0;
-                    }
-                // lane = raw run first; pages with runs too short for that go through the lane = row kernel
-                if (any_f) {
-                    {
-                        KScope k(ctx, kd == 4 ? "k_enc_select_runs<4, 1>" : "k_enc_select_runs<8, 2>");
-                        if (kd == 4)
-                            k_enc_select_runs<4, 1><<<(uint32_t)P, WG, 0, st>>>(aa);
-                        else
-                            k_enc_select_runs<8, 2><<<(uint32_t)P, WG, 0, st>>>(aa);
-                    }
-                    if (!unused(31)) {   // (pages the run-level kernel left to the row-level one)
-                        KScope k(ctx, kd == 4 ? "k_enc_select_rle<4, 1>" : "k_enc_select_rle<8, 2>");
-                        if (kd == 4)
-                            k_enc_select_rle<4, 1><<<(uint32_t)P, WG, 0, st>>>(aa);
-                        else
-                            k_enc_select_rle<8, 2><<<(uint32_t)P, WG, 0, st>>>(aa);
-                    }
-                }
-                if (any_i) {
-                    {
-                        KScope k(ctx, kd == 4 ? "k_enc_select_runs<4, 0>" : "k_enc_select_runs<8, 0>");
-                        if (kd == 4)
-                            k_enc_select_runs<4, 0><<<(uint32_t)P, WG, 0, st>>>(aa);
-                        else
-                            k_enc_select_runs<8, 0><<<(uint32_t)P, WG, 0, st>>>(aa);
-                    }
-                    if (!unused(31)) {
-                        KScope k(ctx, kd == 4 ? "k_enc_select_rle<4, 0>" : "k_enc_select_rle<8, 0>");
-                        if (kd == 4)
-                            k_enc_select_rle<4, 0><<<(uint32_t)P, WG, 0, st>>>(aa);
-                        else
-                            k_enc_select_rle<8, 0><<<(uint32_t)P, WG, 0, st>>>(aa);
-                    }
-                }
-                launch_big(kd, st);
-                return;
-            }
-            char nm[48];
-            snprintf(nm, sizeof nm, "k_enc_select<%d>", kd);
-            if (kd > 0 || kd == 0 || old_chain) {
-                KScope k(ctx, nm);
-                enc_select_kernel(kd)<<<(uint32_t)P, WG, 0, st>>>(aa);
-            }
-            if (!nested && (kd == 1 || kd == 2 || kd < 0)) launch_big(kd, st);
-        };
-        // the dictionaries the binary selectors handed over: strings checked tile-parallel, pages that failed selected again
-        // exactly (workgroups of all other pages return at once); kd_only: the one binary kind of this stream, or 0 = both
-        auto launch_verify = [&](int kd_only, hipStream_t st) {
-            if (!old_chain) return;
-            {
-                KScope k(ctx, "k_enc_bin_verify");
-                const uint32_t tpp = (uint32_t)((max_rows + BV_ROWS - 1) / BV_ROWS);
-            k_enc_bin_verify<<<(uint32_t)(((P + 7) / 8) * 8 * tpp), WG, 0, st>>>(aa, tpp);
-            }
-            aa.redo = 1;
-            for (int kd : kinds)
-                if (kd < 0 && (!kd_only || kd == kd_only)) enc_select_kernel(kd)<<<(uint32_t)P, WG, 0, st>>>(aa);
-            aa.redo = 0;
-        };
-        auto launch_emit = [&](int kd, hipStream_t st) -> int32_t {
-            // one kernel instance per (kind, codec) that can occur in the batch
-            static const int32_t CAND[6] = {SB_CODEC_ONEVALUE, SB_CODEC_DICT, SB_CODEC_RLE, SB_CODEC_BITPACKING,
-                                            SB_CODEC_DELTA_BITPACKING, SB_CODEC_PATAS};
-            if (nested && (kd <= 0 || kd > 8)) return SB_OK;
-            for (int32_t cd : CAND) {
-                if (!wave_adaptive && cd != wave_codec) continue;
-                if (wave_adaptive) {
-                    if ((forb >> cd) & 1) continue;
-                    if ((cd == SB_CODEC_BITPACKING || cd == SB_CODEC_DELTA_BITPACKING) && kd != 4) continue;
-                    if (kd == 0 && cd == SB_CODEC_DICT) continue;
-                    if (kd < 0 && cd == SB_CODEC_RLE) continue;
-                    if (cd == SB_CODEC_PATAS) {  // candidates of float columns only (double/mod.rs:271-277)
-                        bool any_float = false;
-                        for (uint64_t i = 0; i < n; i++) any_float |= hc[i].fkind != 0 && (int)hc[i].width == kd;
-                        if (!any_float) continue;
-                    }
-                }
-                EncPageKernel kf = enc_page_kernel(kd, cd);
-                if (!kf) continue;
-                if (cd == SB_CODEC_DICT && aa.bin_fused && (kd == 1 || kd == 2 || kd == 4) && !unused_peek(SB_CODEC_DICT)) {
-                    KScope k(ctx, "k_enc_prim_dict");   // integer Dict pages of up to 65 536 rows: sb_bin_page.h
-                    if (kd == 4) k_enc_prim_dict<4><<<(uint32_t)P, BP_WG, 0, st>>>(aa);
-                    else if (kd == 2) k_enc_prim_dict<2><<<(uint32_t)P, BP_WG, 0, st>>>(aa);
-                    else k_enc_prim_dict<1><<<(uint32_t)P, BP_WG, 0, st>>>(aa);
-                }
-                // (4- / 8-byte RLE pages come out of the fused selectors: slot 29 counts the ones the page kernel had to write)
-                // (binary Dict pages come out of k_enc_bin_page whole when their index block is bit-packed: slot 30 likewise)
-                if (wave_adaptive && !nested &&
-                    unused(cd == SB_CODEC_RLE && (kd == 4 || kd == 8) ? 29 : cd == SB_CODEC_DICT && kd < 0 && aa.bin_fused && !old_chain ? 30 : (int)cd))
-                    continue;
-                char nm[48];
-                snprintf(nm, sizeof nm, "k_enc_emit_pages<%d, %d>", kd, (int)cd);
-                KScope k(ctx, nm);
-                kf<<<(uint32_t)P, WG, 0, st>>>(aa);
-            }
-            if (!nested && !wave_adaptive && wave_codec != SB_CODEC_NONE && wave_codec != SB_CODEC_FREQ && wave_codec > 3 &&
-                !enc_page_kernel(kd, wave_codec))
-                return ctx->fail(SB_ERR_NYI, "no device encoder for this codec and column type");
-            return SB_OK;
-        };
-        const bool emit_pages_wanted = nested || any_pages;
-
-        if (multi) {
-            if (any_bin) aa.pre_hashed = 1;
-            side_fork(ctx, side_mask);
-            int32_t rc = SB_OK;
-            if (any_bin) {   // the binary chain, in order, on the high-priority side stream
-                hipStream_t st = ctx->side[0];
-                launch_hash(st);
-                for (int kd : kinds)
-                    if (kd < 0) launch_selectors(kd, st);
-                launch_verify(0, st);
-                for (int kd : kinds)
-                    if (kd < 0 && emit_pages_wanted && rc == SB_OK) rc = launch_emit(kd, st);
-            }
-            for (size_t ki = 0; ki < kinds.size() && rc == SB_OK; ki++) {
-                const int kd = kinds[ki];
-                if (kd < 0) continue;
-                hipStream_t st = stream_of(ki);
-                launch_selectors(kd, st);
-                if (emit_pages_wanted) rc = launch_emit(kd, st);
-            }
-            side_join(ctx, side_mask);
-            if (rc != SB_OK) return rc;
-        } else {
-            if (wave_adaptive && !nested && any_bin) {
-                launch_hash(s);
-                aa.pre_hashed = 1;
-            }
-            if (wave_adaptive)
-                for (int kd : kinds) launch_selectors(kd, s);
-            if (aa.pre_hashed) launch_verify(0, s);
+        const uint32_t side_mask = n_bin_kinds ? 1u : 2u;
+        if (any_bin) aa.pre_hashed = 1;
+        side_fork(ctx, side_mask);
+        int32_t rc = SB_OK;
+        if (any_bin) {   // the binary chain, in order, on the high-priority side stream
+            hipStream_t st = ctx->side[0];
+            launch_hash(L, st);
+            for (int kd : L.kinds)
+                if (kd < 0) launch_selectors(L, kd, st);
+            launch_verify(L, st);
+            for (int kd : L.kinds)
+                if (kd < 0 && plan.any_pages && rc == SB_OK) rc = launch_emit(L, kd, st);
         }
-        const int32_t dc = opts->default_compression;
-        const bool basic_comp = dc == SB_CODEC_LZ4 || dc == SB_CODEC_ZSTD || dc == SB_CODEC_SNAPPY;
-        if (!nested && wave_adaptive && any_tiles && !aa.null_cols && unused(SB_CODEC_NONE)) {
-            // (no plain page last time; Null columns' empty pages are recorded by this kernel: never skipped then)
-        } else if (nested ? (wave_adaptive ? dc == SB_CODEC_NONE : wave_codec == SB_CODEC_NONE) : any_tiles) {
-            KScope k(ctx, K_ENC_TILES);
-            // (adaptive: few pages stay plain, so one workgroup per page looks — unless the pages are few and long)
-            const uint32_t ty = wave_adaptive ? (uint32_t)std::min<uint64_t>(max_tiles, std::max<uint64_t>(1, 2048 / P)) : (uint32_t)max_tiles;
-            k_enc_emit_tiles<<<dim3((uint32_t)P, ty), WG, 0, s>>>(aa, (uint32_t)max_tiles);
+        for (size_t ki = 0; ki < L.kinds.size() && rc == SB_OK; ki++) {
+            const int kd = L.kinds[ki];
+            if (kd < 0) continue;
+            hipStream_t st = n_bin_kinds || !(ki & 1) ? s : ctx->side[1];
+            launch_selectors(L, kd, st);
+            if (plan.any_pages) rc = launch_emit(L, kd, st);
         }
-        const bool basic_unused = !nested && wave_adaptive && any_lz4 && big_hint && !plan.last_counts[SB_CODEC_LZ4] && !plan.last_counts[SB_CODEC_ZSTD] &&
-                                  !plan.last_counts[SB_CODEC_SNAPPY];
-        if (basic_unused) {
-            emit_skips |= SKIP_EMIT;
-        } else if (nested ? (wave_adaptive ? basic_comp : (wave_codec >= 1 && wave_codec <= 3)) : any_lz4) {
-            if (!nested && aa.lzc_plan) {   // blocks of more than one chunk: one wave per chunk, then joined
-                {
-                    KScope k(ctx, "k_enc_lz4_plan");
-                    k_enc_lz4_plan<<<dim3((uint32_t)P, (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, max_tiles / 8), std::max<uint64_t>(1, 1024 / P))), WG, 0, s>>>(aa);
-                }
-                if (aa.zpar_scratch) {
-                    KScope k(ctx, "k_enc_zstd_chunks");
-                    k_enc_zstd_chunks<<<zpar_waves, 64, 0, s>>>(aa);
-                } else {
-                    KScope k(ctx, "k_enc_lz4_chunks");
-                    k_enc_lz4_chunks<<<(uint32_t)std::min<uint64_t>(aa.lzc_cap, 1u << 20), 64, 0, s>>>(aa);
-                }
-                KScope k(ctx, "k_enc_lz4_stitch");
-                k_enc_lz4_stitch<<<dim3((uint32_t)P, (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, max_chunks / 4), std::max<uint64_t>(1, 2048 / P))), WG, 0, s>>>(aa);
-            }
-            KScope k(ctx, K_ENC_LZ4);
-            k_enc_emit_lz4<false><<<(uint32_t)P, WG, 0, s>>>(aa);
-            if (dc == SB_CODEC_ZSTD || wave_codec == SB_CODEC_ZSTD) {   // (virtual pages inherit their page's encoder scratch)
-                KScope kz(ctx, "k_enc_emit_lz4<true>");
-                k_enc_emit_lz4<true><<<(uint32_t)P, WG, 0, s>>>(aa);
-            }
-        }
-        if (emit_pages_wanted && !multi) {
-            for (int kd : kinds) {
-                const int32_t rc = launch_emit(kd, s);
-                if (rc != SB_OK) return rc;
-            }
-        }
-        return SB_OK;
-    };
-    {
-        const int32_t rc = run_wave(a, adaptive, host_codec, false);
+        side_join(ctx, side_mask);
         if (rc != SB_OK) return rc;
+    } else if (adaptive) {
+        if (any_bin) {
+            launch_hash(L, s);
+            aa.pre_hashed = 1;
+        }
+        for (int kd : L.kinds) launch_selectors(L, kd, s);
+        if (aa.pre_hashed) launch_verify(L, s);
     }
-    if (freq_possible && adaptive && (!big_hint || plan.last_counts[SB_CODEC_FREQ])) {
-        // long pages that chose Freq: prepared container-parallel, their exceptions block (a virtual page) selected and
-        // written section-parallel when it has VBIG_ROWS rows or more (sb_freq_big.h, sb_dict_big.h)
-        const uint32_t vo = (uint32_t)P;
-        EncCol* vcols_rw = (EncCol*)(tb + o_vcols);
-        EncPage* vpages_rw = (EncPage*)(tb + o_vpages);
-        for (int k = 0; k < 4; k++) {
-            const uint32_t nbig = (uint32_t)plan.bigw[k].size();
-            if (!nbig) continue;
-            size_t skip = 0;
-            for (int q = 0; q < k; q++) skip += plan.bigw[q].size();
-            const uint32_t* list = (const uint32_t*)plan.big.p + skip;
-            const dim3 sg(plan.big_secs[k], nbig), pg(1, nbig);
-            const dim3 cg((uint32_t)((max_tiles * TILE_ROWS + 65535) / 65536), nbig);
-#define SB_FBIG_W(KERNEL, GRID, THREADS, ...)                                             \
-    do {                                                                                  \
-        if (k == 0) KERNEL<1><<<GRID, THREADS, 0, s>>>(a, list, ##__VA_ARGS__);           \
-        else if (k == 1) KERNEL<2><<<GRID, THREADS, 0, s>>>(a, list, ##__VA_ARGS__);      \
-        else if (k == 2) KERNEL<4><<<GRID, THREADS, 0, s>>>(a, list, ##__VA_ARGS__);      \
-        else KERNEL<8><<<GRID, THREADS, 0, s>>>(a, list, ##__VA_ARGS__);                  \
-    } while (0)
+    // (no plain page last time: not launched, unless Null columns' empty pages are to be recorded by this kernel)
+    if (plan.any_tiles && (aa.null_cols || !L.unused(SB_CODEC_NONE))) {
+        KScope k(ctx, K_ENC_TILES);
+        // (adaptive: few pages stay plain, so one workgroup per page looks — unless the pages are few and long)
+        const uint32_t ty = adaptive ? (uint32_t)std::min<uint64_t>(plan.max_tiles, std::max<uint64_t>(1, 2048 / L.P)) : L.max_tiles();
+        k_enc_emit_tiles<<<dim3((uint32_t)L.P, ty), WG, 0, s>>>(aa, L.max_tiles());
+    }
+    if (plan.any_lz4 && L.unused_peek(SB_CODEC_LZ4) && L.unused_peek(SB_CODEC_ZSTD) && L.unused_peek(SB_CODEC_SNAPPY)) {
+        L.emit_skips |= SKIP_EMIT;
+    } else if (plan.any_lz4) {
+        if (aa.lzc_plan) {   // blocks of more than one chunk: one wave per chunk, then joined
             {
-                KScope kk(ctx, "k_freq_big");
-                SB_FBIG_W(k_freq_big_count, dim3(cg.x * 4, nbig), WG);
-                SB_FBIG_W(k_freq_big_plan, pg, WG, vcols_rw, vpages_rw);
-                SB_FBIG_W(k_freq_big_emit, cg, WG);
-                SB_FBIG_W(k_freq_big_done, pg, 64);
+                KScope k(ctx, "k_enc_lz4_plan");
+                k_enc_lz4_plan<<<dim3((uint32_t)L.P, (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, plan.max_tiles / 8), std::max<uint64_t>(1, 1024 / L.P))), WG, 0, s>>>(aa);
             }
-            {
-                KScope kk(ctx, "k_sel_big(exceptions)");
-                k_sel_big_init<<<dim3(4, nbig), WG, 0, s>>>(a, list, vo);
-                SB_FBIG_W(k_sel_big_sec, dim3(sg.x * BIG_SEC_SPLIT, nbig), WG, vo);
-                SB_FBIG_W(k_sel_big_merge, pg, WG, vo);
-                k_sel_big_clear<<<sg, WG, 0, s>>>(a, list, vo);
-                SB_FBIG_W(k_sel_big_count, dim3(sg.x * BIG_COUNT_SPLIT, nbig), WG, vo);
-                SB_FBIG_W(k_sel_big_decide, pg, WG, vo);
+            if (aa.zpar_scratch) {
+                KScope k(ctx, "k_enc_zstd_chunks");
+                k_enc_zstd_chunks<<<(uint32_t)std::min<uint64_t>(plan.lz_cap, ZPAR_WAVES), 64, 0, s>>>(aa);
+            } else {
+                KScope k(ctx, "k_enc_lz4_chunks");
+                k_enc_lz4_chunks<<<(uint32_t)std::min<uint64_t>(aa.lzc_cap, 1u << 20), 64, 0, s>>>(aa);
             }
-            {
-                KScope kk(ctx, "k_nested_big");
-                if (!((forb >> SB_CODEC_RLE) & 1)) {
-                    SB_FBIG_W(k_rle_big_count, sg, WG, vo);
-                    SB_FBIG_W(k_rle_big_plan, pg, WG, vo);
-                    SB_FBIG_W(k_rle_big_emit, sg, WG, vo);
-                    SB_FBIG_W(k_rle_big_done, pg, 64, vo);
-                }
-                if (k == 2) {
-                    const dim3 tg((uint32_t)std::min<uint64_t>(max_tiles, 4096), nbig);
-                    k_bp_big<0><<<tg, WG, 0, s>>>(a, list);
-                    k_bp_big<1><<<pg, WG, 0, s>>>(a, list);
-                    k_bp_big<2><<<tg, WG, 0, s>>>(a, list);
-                }
-                k_plain_big<<<dim3(1024, nbig), WG, 0, s>>>(a, list);
-            }
-#undef SB_FBIG_W
+            KScope k(ctx, "k_enc_lz4_stitch");
+            k_enc_lz4_stitch<<<dim3((uint32_t)L.P, (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, plan.max_chunks / 4), std::max<uint64_t>(1, 2048 / L.P))), WG, 0, s>>>(aa);
+        }
+        KScope k(ctx, K_ENC_LZ4);
+        k_enc_emit_lz4<false><<<(uint32_t)L.P, WG, 0, s>>>(aa);
+        if (L.opts->default_compression == SB_CODEC_ZSTD || L.sh.host_codec == SB_CODEC_ZSTD) {   // (virtual pages inherit their page's encoder scratch)
+            KScope kz(ctx, "k_enc_emit_lz4<true>");
+            k_enc_emit_lz4<true><<<(uint32_t)L.P, WG, 0, s>>>(aa);
         }
     }
-    if (freq_possible && adaptive && unused(28) ) {
-        // (no page went through the Freq kernels last time: not launched)
-    } else if (freq_possible) {  // Freq pages: bitmap + exceptions, then the exceptions block like any other block
-        {
-            KScope k(ctx, K_ENC_FREQ);
-            k_enc_freq_prep<<<(uint32_t)std::min<uint64_t>(P, 1024), WG, 0, s>>>(a, (EncCol*)(tb + o_vcols), (EncPage*)(tb + o_vpages));
+    if (plan.any_pages && !multi)
+        for (int kd : L.kinds) {
+            const int32_t rc = launch_emit(L, kd, s);
+            if (rc != SB_OK) return rc;
         }
-        bool has4 = false, wide = false;
-        for (int kd : kinds) has4 |= kd == 4;
-        for (uint64_t i = 0; i < n; i++)  // only integers get there: a mostly-one-value float column takes Freq itself
-            wide |= (hc[i].fkind == 0 || dict_freq) && hc[i].ptype != SB_TYPE_BOOLEAN && hc[i].ptype != SB_TYPE_NULL && !enc_is_binary(hc[i].ptype) &&
-                    (hc[i].width <= 2 || hc[i].width >= 8);
-        for (uint64_t i = 0; i < n; i++) wide |= enc_is_binary(hc[i].ptype);
-        if (!has4 && wide && (adaptive || dict_freq) && !((forb >> SB_CODEC_DICT) & 1)) {  // Freq-coded u32 indices of Dict pages
-            KScope k(ctx, K_ENC_FREQ);
-            k_enc_nested<4><<<(uint32_t)std::min<uint64_t>(P, 512), WG, 0, s>>>(a);
-        }
-        for (int kd : kinds) {
-            if (kd != 1 && kd != 2 && kd != 4 && kd != 8 && kd != 16 && kd != 32) continue;
-            KScope k(ctx, K_ENC_FREQ);
-            if (kd == 16)
-                k_enc_nested<16><<<(uint32_t)std::min<uint64_t>(P, 512), WG, 0, s>>>(a);
-            else if (kd == 32)
-                k_enc_nested<32><<<(uint32_t)std::min<uint64_t>(P, 512), WG, 0, s>>>(a);
-            else if (kd == 1)
-                k_enc_nested<1><<<(uint32_t)std::min<uint64_t>(P, 512), WG, 0, s>>>(a);
-            else if (kd == 2)
-                k_enc_nested<2><<<(uint32_t)std::min<uint64_t>(P, 512), WG, 0, s>>>(a);
-            else if (kd == 4)
-                k_enc_nested<4><<<(uint32_t)std::min<uint64_t>(P, 512), WG, 0, s>>>(a);
-            else
-                k_enc_nested<8><<<(uint32_t)std::min<uint64_t>(P, 512), WG, 0, s>>>(a);
-        }
-        KScope k(ctx, K_ENC_FREQ);
-        k_enc_freq_finish<<<(uint32_t)P, WG, 0, s>>>(a);
+    return SB_OK;
+}
+
+// long pages that chose Freq: prepared container-parallel, their exceptions block (a virtual page) selected and written
+// section-parallel when it has VBIG_ROWS rows or more (sb_freq_big.h, sb_dict_big.h)
+static void launch_freq_big(EncLaunch& L) {
+    const EncodeArgs& a = L.a;
+    const hipStream_t s = L.s;
+    for (int k = 0; k < 4; k++) {
+        const uint32_t nbig = (uint32_t)L.plan.bigw[k].size();
+        if (!nbig) continue;
+        const uint32_t* list = L.big_list(k);
+        const dim3 pg(1, nbig), cg((uint32_t)((L.plan.max_tiles * TILE_ROWS + 65535) / 65536), nbig);
+        by_width<1, 2, 4, 8>(1 << k, [&](auto W) {
+            KScope kk(L.ctx, "k_freq_big");
+            k_freq_big_count<W><<<dim3(cg.x * 4, nbig), WG, 0, s>>>(a, list);
+            k_freq_big_plan<W><<<pg, WG, 0, s>>>(a, list, (EncCol*)a.vcols, (EncPage*)a.vpages);
+            k_freq_big_emit<W><<<cg, WG, 0, s>>>(a, list);
+            k_freq_big_done<W><<<pg, 64, 0, s>>>(a, list);
+        });
+        launch_virtual_pages(L, a, s, 1 << k, list, nbig, L.plan.big_secs[k], true);
     }
-    a.skips |= emit_skips;
+}
+
+// Freq pages: bitmap + exceptions, then the exceptions block like any other block
+static void launch_freq(EncLaunch& L) {
+    const EncodeArgs& a = L.a;
+    const hipStream_t s = L.s;
+    const uint32_t P = (uint32_t)L.P;
+    {
+        KScope k(L.ctx, K_ENC_FREQ);
+        k_enc_freq_prep<<<std::min<uint32_t>(P, 1024), WG, 0, s>>>(a, (EncCol*)a.vcols, (EncPage*)a.vpages);
+    }
+    bool has4 = false, wide = false;
+    for (int kd : L.kinds) has4 |= kd == 4;
+    for (uint64_t i = 0; i < L.n; i++) {  // only integers get there: a mostly-one-value float column takes Freq itself
+        const EncCol& d = L.hc[i];
+        wide |= (d.fkind == 0 || L.sh.dict_freq) && d.ptype != SB_TYPE_BOOLEAN && d.ptype != SB_TYPE_NULL && !enc_is_binary(d.ptype) &&
+                (d.width <= 2 || d.width >= 8);
+        wide |= enc_is_binary(d.ptype);
+    }
+    if (!has4 && wide && (L.sh.adaptive || L.sh.dict_freq) && !L.sh.forbids(SB_CODEC_DICT)) {  // Freq-coded u32 indices of Dict pages
+        KScope k(L.ctx, K_ENC_FREQ);
+        k_enc_nested<4><<<std::min<uint32_t>(P, 512), WG, 0, s>>>(a);
+    }
+    for (int kd : L.kinds)
+        by_width<1, 2, 4, 8, 16, 32>(kd, [&](auto W) {
+            KScope k(L.ctx, K_ENC_FREQ);
+            k_enc_nested<W><<<std::min<uint32_t>(P, 512), WG, 0, s>>>(a);
+        });
+    KScope k(L.ctx, K_ENC_FREQ);
+    k_enc_freq_finish<<<P, WG, 0, s>>>(a);
+}
+
+static int32_t write_columns_impl(sb_ctx* ctx, sb_column_write* cols, uint64_t n, const sb_write_options* opts, int32_t mem) {
+    if (!ctx || (!cols && n) || !opts) return SB_ERR_INVALID;
+    if (n == 0) return SB_OK;
+    (void)hipSetDevice(ctx->device);
+    const hipStream_t s = ctx->stream;
+    CallShape sh;
+    int32_t rc = call_shape(ctx, cols, n, opts, sh);
+    if (rc != SB_OK) return rc;
+    uint64_t key = 0, P = 0;
+    const bool hit = plan_lookup(ctx, cols, n, opts, mem, key);
+    if ((rc = validate_cols(ctx, cols, n, opts, P)) != SB_OK) return rc;
+    const size_t hpages = enc_layout(n, P, 0, false).hpages;
+    StageSlot* slot = acquire_slot(ctx, hpages + (hit ? 0 : P * sizeof(EncPage)) + 64);
+    if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
+    if (!hit && (rc = build_plan(ctx, s, cols, n, opts, sh, P, key, (EncPage*)(slot->host + hpages))) != SB_OK) return rc;
+    const sb_ctx::EncPlan& plan = ctx->enc_plan;
+    std::vector<ColBufs> bufs;
+    if ((rc = stage_cols(ctx, s, cols, n, mem, bufs)) != SB_OK) return rc;
+    const EncLayout T = enc_layout(n, P, plan.lz_cap, sh.freq_possible || sh.big_possible);
+    if (!ensure(ctx, ctx->tables, T.total)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(tables) failed");
+    if (!ensure(ctx, ctx->scratch, plan.scratch_total + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(scratch) failed");
+    EncCol* hc = (EncCol*)(slot->host + T.cols);
+    fill_cols(hc, cols, n, bufs, plan);
+    memcpy(slot->host + T.resoff, plan.hro.data(), n * sizeof(uint64_t));
+    uint8_t* tb = ctx->tables.p;
+    hipError_t e = hipMemcpyAsync(tb, slot->host, T.upload, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return check_hip(ctx, e, "table upload");
+
+    EncodeArgs a{};
+    a.cols = (const EncCol*)(tb + T.cols);
+    a.pages = (const EncPage*)plan.pages.p;
+    a.outs = (EncOut*)(tb + T.outs);
+    a.scratch = ctx->scratch.p;
+    a.status = ctx->d_status;
+    a.results = (uint64_t*)(tb + T.results);
+    a.codecs = (int32_t*)(tb + T.codecs);
+    a.ratio = opts->default_compress_ratio;
+    a.has_ratio = opts->has_default_compress_ratio ? 1u : 0u;
+    a.forbidden = sh.forb;
+    a.n_pages = (uint32_t)P;
+    a.n_cols = (uint32_t)n;
+    a.default_compression = (uint32_t)opts->default_compression;
+    a.vcols = (const EncCol*)(tb + T.vcols);
+    a.vpages = (const EncPage*)(tb + T.vpages);
+    a.page_base = 0;
+    a.nested_force = opts->force_index_codec;
+    a.flags = opts->flags;
+    a.lzc_plan = plan.lz_cap ? (LzChunkPlan*)(tb + T.lzplan + 64) : nullptr;
+    a.lzc_count = (uint32_t*)(tb + T.lzplan);
+    a.lzc_list = (LzChunkDesc*)(tb + T.lzlist);
+    a.lzc_pool = ctx->scratch.p + plan.lz_pool_off;
+    a.lzc_cap = (uint32_t)plan.lz_cap;
+    a.lzc_chunk = (uint32_t)plan.lz_chunk;
+    a.lzc_codec = sh.zs_possible ? SB_CODEC_ZSTD : sh.sn_possible ? SB_CODEC_SNAPPY : SB_CODEC_LZ4;
+    a.zpar_scratch = plan.lz_cap && sh.zs_possible ? ctx->scratch.p + plan.zpar_off : nullptr;
+    a.freq_count = (uint32_t*)(tb + T.freqcnt);
+    a.codec_counts = (uint32_t*)(tb + T.freqcnt + 64);
+    for (uint64_t i = 0; i < n; i++) a.null_cols |= cols[i].physical_type == SB_TYPE_NULL ? 1u : 0u;
+    // one memset: page outputs (length 0 = not emitted), results, device-chosen codecs, the Freq page counter
+    (void)hipMemsetAsync(tb + T.outs, 0, T.vcols - T.outs, s);
+    if (sh.host_codec == SB_CODEC_FREQ) (void)hipMemsetAsync(a.freq_count, 1, 4, s);  // forced: every page is a Freq page (non-zero)
+
+    EncLaunch L{ctx, s, opts, sh, plan, hc, n, P};
+    // (what the last calls with this plan chose: see EncPlan.last_counts)
+    L.big_hint = hit && plan.counts_valid && sh.adaptive && !ctx->no_hints;
+    for (uint64_t i = 0; i < n; i++) {
+        const EncCol& d = hc[i];
+        if (d.ptype == SB_TYPE_NULL) continue;
+        const int kd = d.ptype == SB_TYPE_BOOLEAN ? 0 : d.ptype == SB_TYPE_BINARY ? -4 : d.ptype == SB_TYPE_LARGE_BINARY ? -8 : (int)d.width;
+        if (std::find(L.kinds.begin(), L.kinds.end(), kd) == L.kinds.end()) L.kinds.push_back(kd);
+    }
+    const size_t nbig_prim = plan.bigw[0].size() + plan.bigw[1].size() + plan.bigw[2].size() + plan.bigw[3].size();
+    if (nbig_prim + plan.bigw[4].size() && !sh.forbids(SB_CODEC_DICT) && L.unused_peek(SB_CODEC_DICT)) a.skips |= SKIP_DICT_BIG;
+    if (nbig_prim && sh.freq_possible && L.unused_peek(SB_CODEC_FREQ)) a.skips |= SKIP_FREQ_BIG;
+    L.a = a;
+    L.wa = a;
+    L.wa.use_counts = sh.adaptive ? 1u : 0u;
+    // binary pages of BP_MIN_ROWS .. 65 536 rows: codec and dictionary in one pass (sb_bin_page.h); the hash -> select ->
+    // verify chain only for the rest.  (The flag also switches on k_enc_prim_dict for integer Dict pages.)
+    L.wa.bin_fused = sh.adaptive && ctx->bin_fused && !(opts->flags & SB_WRITE_DEBUG_VERIFY_FAIL_BIT) ? 1u : 0u;
+    L.old_chain = !L.wa.bin_fused || plan.bin_unfused;
+
+    if ((rc = launch_pages(L)) != SB_OK) return rc;
+    if (sh.freq_possible && sh.adaptive && !L.unused_peek(SB_CODEC_FREQ)) launch_freq_big(L);
+    if (sh.freq_possible && !L.unused(HINT_FREQ)) launch_freq(L);
+    a.skips |= L.emit_skips;
     {
         KScope k(ctx, K_ENC_LAYOUT);
-        k_enc_layout<<<(uint32_t)n, 64, 0, s>>>(a, (const uint64_t*)(tb + o_resoff));
+        k_enc_layout<<<(uint32_t)n, 64, 0, s>>>(a, (const uint64_t*)(tb + T.resoff));
     }
-    if (any_compact) {
+    if (plan.any_compact) {
         KScope k(ctx, K_ENC_COMPACT);
-        k_enc_compact<<<dim3((uint32_t)P, (uint32_t)std::min<uint64_t>(max_chunks, std::max<uint64_t>(1, 8192 / P))), WG, 0, s>>>(a);
+        k_enc_compact<<<dim3((uint32_t)P, (uint32_t)std::min<uint64_t>(plan.max_chunks, std::max<uint64_t>(1, 8192 / P))), WG, 0, s>>>(a);
     }
     e = hipGetLastError();
     if (e != hipSuccess) return check_hip(ctx, e, "encode launch");
 
-    uint8_t* hres = slot->host + o_hres;
-    e = hipMemcpyAsync(hres, a.results, results_words * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+    uint8_t* hres = slot->host + T.hres;
+    e = hipMemcpyAsync(hres, a.results, T.results_words * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
     if (e != hipSuccess) return check_hip(ctx, e, "metas readback");
-    if (adaptive) {   // the pages per codec, for the next call with this plan
-        e = hipMemcpyAsync(slot->host + o_hcounts, a.codec_counts, 128, hipMemcpyDeviceToHost, s);
+    if (sh.adaptive) {   // the pages per codec, for the next call with this plan
+        e = hipMemcpyAsync(slot->host + T.hcounts, a.codec_counts, 128, hipMemcpyDeviceToHost, s);
         if (e != hipSuccess) return check_hip(ctx, e, "codec counts readback");
         Pending pd;
         pd.kind = Pending::ENC_HINT;
         pd.user = nullptr;
-        pd.host = slot->host + o_hcounts;
-        pd.n = plan_key;
+        pd.host = slot->host + T.hcounts;
+        pd.n = plan.key;
         ctx->pending.push_back(pd);
     }
     (void)hipEventRecord(slot->done, s);
@@ -6431,11 +6425,9 @@ static int32_t write_columns_impl(sb_ctx* ctx, sb_column_write* cols, uint64_t n
         Pending pd;
         pd.kind = Pending::WRITE_COL;
         pd.user = &cols[i];
-        pd.host = hres + hro[i] * sizeof(uint64_t);
+        pd.host = hres + plan.hro[i] * sizeof(uint64_t);
         pd.n = hc[i].n_pages;
         ctx->pending.push_back(pd);
     }
     return SB_OK;
 }
-
-}  // extern "C"
