@@ -155,6 +155,58 @@ int32_t sb_read_columns(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t m
 /* Parses only the page headers on the device and fills rows / values_len (synchronous). */
 int32_t sb_read_columns_sizes(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem);
 
+/* ------------------------------------------------------------------ filter
+ * What a query engine does first with the filter columns of a block (databend: read the columns of a
+ * WHERE clause, evaluate it, then decide which rows of the other columns it needs): the pages of a
+ * primitive column go in, one bit per row comes out.  The values are compared where the decoder
+ * would have stored them (one compare per run of an RLE page, per entry of a Dict page, per OneValue
+ * page), so `rows / 8` bytes are written instead of `rows * width`.
+ *
+ * Comparisons (EQ .. GE): INT8..INT64, UINT8..UINT64 (signedness from the physical type), FLOAT32,
+ * FLOAT64.  A null row never satisfies a comparison.  Floats compare as IEEE 754: NaN satisfies only
+ * NE, -0.0 == 0.0.  IS_NULL / IS_NOT_NULL: every physical type (only the def-level section of a page
+ * is looked at; a non-nullable column has no null row, every row of a SB_TYPE_NULL column is null).
+ * A comparison on any other type: SB_ERR_NYI at the call, the selection is not touched. */
+#define SB_PRED_EQ 0
+#define SB_PRED_NE 1
+#define SB_PRED_LT 2
+#define SB_PRED_LE 3
+#define SB_PRED_GT 4
+#define SB_PRED_GE 5
+#define SB_PRED_IS_NULL 6
+#define SB_PRED_IS_NOT_NULL 7
+
+#define SB_SEL_SET 0 /* selection  = result; bits at positions >= rows of the last word are written as 0 */
+#define SB_SEL_AND 1 /* selection &= result; bits at positions >= rows stay as they are */
+#define SB_SEL_OR 2  /* selection |= result; bits at positions >= rows stay as they are */
+
+typedef struct sb_column_filter {
+    int32_t physical_type;   /* SB_TYPE_* */
+    int32_t is_nullable;
+    const uint8_t* pages;    /* DEVICE: as in sb_column_read */
+    uint64_t pages_len;
+    const sb_page_meta* metas; /* HOST */
+    uint64_t n_pages;
+    const uint64_t* page_offsets; /* optional (HOST), as in sb_column_read */
+    int32_t op;              /* SB_PRED_* */
+    int32_t combine;         /* SB_SEL_* */
+    uint8_t literal[8];      /* a value of the column's own type, little endian; ignored by IS_[NOT_]NULL */
+    uint8_t* selection;      /* DEVICE: LSB-first bitmap, 4-byte aligned */
+    uint64_t selection_capacity; /* >= 4*ceil(rows/32) bytes */
+    /* results (HOST, valid after sb_ctx_synchronize) */
+    uint64_t rows;           /* sum of num_values */
+    uint64_t selected;       /* bits set in `selection` below `rows`, after combining */
+} sb_column_filter;
+
+/* Enqueue the filter of `n` columns, like sb_read_columns: results and errors (the codes the decoder raises for the
+ * same corrupt page) at sb_ctx_synchronize.  With SB_SEL_AND / SB_SEL_OR the buffer's contents are an input: chain
+ * predicates with one call after the other on the context's stream; two columns of ONE call whose selection buffers
+ * overlap are refused (SB_ERR_INVALID).  The call is part of its synchronize interval like a read call: when the
+ * interval is issued again (sb_ctx_replays) it is issued again in its place, which gives the same bits for all three
+ * modes.  Its own kernels are launched without consulting the launch hints of the read path.
+ * `mem`: SB_MEM_DEVICE.  SB_MEM_HOST is not implemented (SB_ERR_NYI): stage the pages and the bitmap yourself. */
+int32_t sb_filter_columns(sb_ctx* ctx, sb_column_filter* cols, uint64_t n, int32_t mem);
+
 /* ------------------------------------------------------------------ encode
  * Replaces, per leaf column, the page loop of NativeWriter::encode_chunk
  * (src/write/common.rs:54-109): page slicing, then per page write::write -> write_simple

@@ -22,7 +22,10 @@ EXPORTS = ("sb_version", "sb_ctx_create", "sb_ctx_destroy", "sb_ctx_synchronize"
            "sb_file_writer_write_column", "sb_file_writer_finish", "sb_file_writer_close", "sb_file_reader_open",
            "sb_file_reader_n_columns", "sb_file_reader_column", "sb_file_reader_schema", "sb_file_reader_read_pages",
            "sb_file_reader_close", "sb_stat_page", "sb_schema_last_error", "sb_schema_to_bytes", "sb_schema_from_bytes",
-           "sb_schema_metadata_from_bytes")
+           "sb_schema_metadata_from_bytes", "sb_filter_columns")
+
+SB_PRED_EQ, SB_PRED_NE, SB_PRED_LT, SB_PRED_LE, SB_PRED_GT, SB_PRED_GE, SB_PRED_IS_NULL, SB_PRED_IS_NOT_NULL = range(8)
+SB_SEL_SET, SB_SEL_AND, SB_SEL_OR = range(3)
 
 
 class PageMetaC(C.Structure):
@@ -42,6 +45,14 @@ class ColumnReadC(C.Structure):
                 ("values", C.c_void_p), ("values_capacity", C.c_uint64), ("validity", C.c_void_p),
                 ("validity_capacity", C.c_uint64), ("offsets", C.c_void_p), ("offsets_capacity", C.c_uint64),
                 ("rows", C.c_uint64), ("values_len", C.c_uint64), ("page_offsets", C.c_void_p)]
+
+
+class ColumnFilterC(C.Structure):
+    _fields_ = [("physical_type", C.c_int32), ("is_nullable", C.c_int32), ("pages", C.c_void_p),
+                ("pages_len", C.c_uint64), ("metas", C.POINTER(PageMetaC)), ("n_pages", C.c_uint64),
+                ("page_offsets", C.c_void_p), ("op", C.c_int32), ("combine", C.c_int32),
+                ("literal", C.c_uint8 * 8), ("selection", C.c_void_p), ("selection_capacity", C.c_uint64),
+                ("rows", C.c_uint64), ("selected", C.c_uint64)]
 
 
 class ColumnWriteC(C.Structure):
@@ -131,6 +142,8 @@ def load():
     L.sb_ctx_stream.argtypes = [C.c_void_p]
     L.sb_read_columns.restype = C.c_int32
     L.sb_read_columns.argtypes = [C.c_void_p, C.POINTER(ColumnReadC), C.c_uint64, C.c_int32]
+    L.sb_filter_columns.restype = C.c_int32
+    L.sb_filter_columns.argtypes = [C.c_void_p, C.POINTER(ColumnFilterC), C.c_uint64, C.c_int32]
     L.sb_read_columns_sizes.restype = C.c_int32
     L.sb_read_columns_sizes.argtypes = [C.c_void_p, C.POINTER(ColumnReadC), C.c_uint64, C.c_int32]
     L.sb_write_bound.restype = C.c_uint64

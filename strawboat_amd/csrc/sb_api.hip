@@ -8,7 +8,8 @@
 
 namespace sb {
 
-void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, uint64_t* col_values_len);
+void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, uint64_t* col_values_len, const FilterLaunch* flt);
+void launch_filter_plain(sb_ctx* ctx, const FilterCol& f, const uint8_t* values, const uint8_t* validity, uint64_t rows, uint32_t w, uint64_t* count);
 void launch_parse_sizes(sb_ctx* ctx, const DecodeArgs& a, uint64_t* col_values_len);
 void launch_freq_scatter(sb_ctx* ctx, const FreqEntry* entries, uint32_t n, const uint64_t* ex_off, const uint8_t* ex_base);
 
@@ -83,7 +84,7 @@ StageSlot* acquire_slot(sb_ctx* ctx, size_t need) {
     if (s.host)
         for (auto& p : ctx->pending) {
             if (p.host < s.host || p.host >= s.host + s.cap) continue;
-            const size_t nb = p.kind == Pending::READ_COL ? 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R) ? (size_t)p.bytes
+            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL) ? 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R) ? (size_t)p.bytes
                                                                                                    : (size_t)(2 * p.n + 1) * 8;
             ctx->rescued.emplace_back(p.host, p.host + nb);
             p.host = ctx->rescued.back().data();
@@ -214,6 +215,7 @@ void sb_ctx_destroy(sb_ctx* ctx) {
     if (ctx->tables.p) (void)hipFree(ctx->tables.p);
     if (ctx->scratch.p) (void)hipFree(ctx->scratch.p);
     if (ctx->staging.p) (void)hipFree(ctx->staging.p);
+    if (ctx->filter_stage.p) (void)hipFree(ctx->filter_stage.p);
     if (ctx->zlit.p) (void)hipFree(ctx->zlit.p);
     if (ctx->zrec.p) (void)hipFree(ctx->zrec.p);
     if (ctx->zb_stats) (void)hipFree(ctx->zb_stats);
@@ -238,7 +240,9 @@ void sb_ctx_destroy(sb_ctx* ctx) {
 const char* sb_ctx_last_error(sb_ctx* ctx) { return ctx ? ctx->last_error.c_str() : "null context"; }
 void* sb_ctx_stream(sb_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 
-static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, bool sizes_only);
+// (filt / users: the call is a filter call — sb_filter_columns — whose columns end in the filter kernels)
+static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, bool sizes_only, const FilterCol* filt = nullptr,
+                                 sb_column_filter* const* users = nullptr);
 
 // Freq pages (integer/freq.rs:90-127) found by the decode calls of this synchronize interval: their
 // exception blocks are ordinary BLOCK<T>s, so they go through the decoder once more as one-page
@@ -390,10 +394,12 @@ int32_t sb_ctx_synchronize(sb_ctx* ctx) {
         for (void* p : ctx->temp_dev) (void)hipFree(p);
         ctx->temp_dev.clear();
         ctx->stage_rewind();
+        ctx->filter_tmp.clear();
         for (auto& log : ctx->freq_logs) {
             log.reserved = 0;
             (void)hipMemsetAsync(log.dev, 0, 16, ctx->stream);
         }
+        ctx->filter_freq = (ctx->h_status->kinds & KIND_FILTER_FREQ) != 0;
         std::vector<sb_ctx::Call> calls;
         calls.swap(ctx->calls);
         const bool saved = ctx->no_hints;
@@ -402,10 +408,13 @@ int32_t sb_ctx_synchronize(sb_ctx* ctx) {
         ctx->replays++;
         if (ctx->h_status->kinds & KIND_REPLAY_LZG) ctx->lzg_state = 1;
         for (auto& cl : calls) {
-            rc = cl.kind ? sb_write_columns(ctx, (sb_column_write*)cl.cols, cl.n, &cl.opts, cl.mem) : sb_read_columns(ctx, (sb_column_read*)cl.cols, cl.n, cl.mem);
+            rc = cl.kind == 2 ? sb_filter_columns(ctx, (sb_column_filter*)cl.cols, cl.n, cl.mem)
+                 : cl.kind  ? sb_write_columns(ctx, (sb_column_write*)cl.cols, cl.n, &cl.opts, cl.mem)
+                            : sb_read_columns(ctx, (sb_column_read*)cl.cols, cl.n, cl.mem);
             if (rc != SB_OK) break;
         }
         ctx->no_hints = saved;
+        ctx->filter_freq = false;
         if (rc != SB_OK) ctx->sticky = rc;
         rc = sb_ctx_synchronize(ctx);
         ctx->in_replay = false;
@@ -448,6 +457,8 @@ int32_t sb_ctx_synchronize(sb_ctx* ctx) {
             uint64_t v;
             memcpy(&v, p.host, 8);
             c->values_len = v;
+        } else if (p.kind == Pending::FILTER_COL) {
+            memcpy(&((sb_column_filter*)p.user)->selected, p.host, 8);
         } else if (p.kind == Pending::ENC_HINT) {
             if (ctx->enc_plan.valid && ctx->enc_plan.key == p.n && rc == SB_OK) {
                 uint32_t now[32];
@@ -472,6 +483,7 @@ int32_t sb_ctx_synchronize(sb_ctx* ctx) {
         }
     }
     ctx->pending.clear();
+    ctx->filter_tmp.clear();
     ctx->rescued.clear();
     for (void* p : ctx->stale_host) (void)hipHostFree(p);   // (the stream is drained: nothing reads them any more)
     ctx->stale_host.clear();
@@ -552,7 +564,7 @@ uint32_t sb_ctx_profile_read(sb_ctx* ctx, sb_kernel_stat* out, uint32_t cap) {
 }
 
 // ------------------------------------------------------------------------------------ decode
-static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, bool sizes_only) {
+static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, bool sizes_only, const FilterCol* filt, sb_column_filter* const* users) {
     if (!ctx || (!cols && n)) return SB_ERR_INVALID;
     if (n == 0) return SB_OK;
     (void)hipSetDevice(ctx->device);
@@ -582,7 +594,7 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
         if (!sizes_only && c.physical_type != SB_TYPE_NULL && rows) {
             const uint32_t w = type_width(c.physical_type);
             if (!c.values) return ctx->fail(SB_ERR_INVALID, "values is null");
-            if (c.is_nullable && (!c.validity || c.validity_capacity < (rows + 31) / 32 * 4))
+            if (c.is_nullable && !filt && (!c.validity || c.validity_capacity < (rows + 31) / 32 * 4))
                 return ctx->fail(SB_ERR_INVALID, "validity buffer missing or smaller than 4*ceil(rows/32) bytes");
             if (is_binary_t(c.physical_type)) {
                 if (!c.offsets || c.offsets_capacity < (rows + 1) * w)
@@ -606,6 +618,8 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
     off = align_up(off + n * sizeof(ColDesc), 64);
     const size_t o_tasks = off;
     off = align_up(off + P * sizeof(PageTask), 64);
+    const size_t o_fcols = off;
+    if (filt) off = align_up(off + n * sizeof(FilterCol), 64);
     const size_t upload_bytes = off;
     const size_t o_descs = off;
     off = align_up(off + P * sizeof(PageDesc), 64);
@@ -626,8 +640,9 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
     const size_t o_vlen = off;
     off = align_up(off + n * sizeof(uint64_t), 64);
     // the block-parallel Zstd pipeline: frames + counters here, blocks / literals / records in pools of their own
-    const bool zb_on = ctx->zb_mode == 1 || (ctx->zb_mode == 2 && (ctx->zstd_recent || ctx->no_hints));
-    if (!ctx->in_freq_pass) ctx->read_calls++;   // (the Freq second pass runs inside a synchronize: not a call of the next interval)
+    // (a filter call consults no launch hint and leaves the read calls' hint state alone)
+    const bool zb_on = ctx->zb_mode == 1 || (ctx->zb_mode == 2 && (ctx->zstd_recent || ctx->no_hints || filt));
+    if (!ctx->in_freq_pass && !filt) ctx->read_calls++;   // (the Freq second pass runs inside a synchronize: not a call of the next interval)
     const size_t o_zb_counts = off;
     if (zb_on) off = align_up(off + 64, 64);
     const size_t o_zb_frames = off;
@@ -716,6 +731,7 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
         }
         if (in_off > c.pages_len) return ctx->fail(SB_ERR_IO, "sum of PageMeta.length exceeds pages_len");
     }
+    if (filt) memcpy(slot->host + o_fcols, filt, n * sizeof(FilterCol));
     if (!ensure(ctx, ctx->scratch, scratch_off + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(scratch) failed");
     // the inflate pool's per-wave areas: a literal buffer of one block, and (calls with at least 4 queue entries per pool
     // wave: batches) the arena of pre-decoded Zstd sequences
@@ -786,12 +802,12 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
     // the inflate kernels of queue A / the tile kernel of primitives are left out when the last read interval queued nothing
     // for them (C2: four launches that found nothing to do, ~30 us of a 0.9 ms read); k_plan asks for the replay otherwise
     a.read_skips = 0;
-    if (!ctx->no_hints && !ctx->in_freq_pass && !sizes_only) {
+    if (!ctx->no_hints && !ctx->in_freq_pass && !sizes_only && !filt) {
         if (ctx->qa_idle >= 2) a.read_skips |= RSKIP_QUEUE_A;
         if (ctx->tiles_idle >= 2) a.read_skips |= RSKIP_TILES;
     }
     a.zb_skipped = (!zb_on && ctx->zb_mode == 2 && !sizes_only && max_page_len >= (1u << 20)) ? 1u : 0u;
-    if (!sizes_only && max_page_len >= LZG_MIN && ctx->lzg_state == 2 && !ctx->no_hints) {
+    if (!sizes_only && max_page_len >= LZG_MIN && ctx->lzg_state == 2 && !ctx->no_hints && !filt) {
         // the context's last intervals met no LZ4 block of megabytes: no pool, no launches; k_inflate_lz4_big leaves such
         // a block alone and asks for the replay (it used to walk it with one workgroup: 0.8 s for 68 MB)
         a.lzg_skipped = 1;
@@ -824,7 +840,7 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
             a.lzg.st = ctx->d_status;
             a.lzg_chunks = (uint32_t)((max_page_len + LZG_CH - 1) / LZG_CH);
             a.lzg_jobs = (uint32_t)std::min<uint64_t>(lzg_pages, LZG_JOBS);
-            ctx->lzg_long_pages = true;
+            if (!filt) ctx->lzg_long_pages = true;
             a.lzg_wins = (uint32_t)std::min<uint64_t>((out_max + LZG_WIN - 1) / LZG_WIN, 0x7FFFFFFFu);
             uint32_t bits = 1;
             while ((1ull << bits) < out_max + 1 && bits < 32) bits++;
@@ -886,6 +902,13 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
     a.job_cap_a = a.job_cap_b = (uint32_t)job_cap;
     if (sizes_only) {
         if (P) launch_parse_sizes(ctx, a, d_vlen);
+    } else if (filt) {
+        FilterLaunch fl{(const FilterCol*)(tb + o_fcols), d_vlen, false, false, false};
+        for (uint64_t i = 0; i < n; i++) {
+            (filt[i].op >= SB_PRED_IS_NULL ? fl.any_null : fl.any_cmp) = true;
+            if (filt[i].combine == SB_SEL_SET) fl.any_set = true;
+        }
+        if (P) launch_decode(ctx, a, false, any_prim, d_vlen, &fl);
     } else {
         // bitmaps are assembled with OR at page seams: start from zero
         for (uint64_t i = 0; i < n; i++) {
@@ -894,14 +917,14 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
             if (d.nullable && d.validity && d.rows) (void)hipMemsetAsync(d.validity, 0, (d.rows + 31) / 32 * 4, s);
             if (d.ptype == SB_TYPE_BOOLEAN && d.values && d.rows) (void)hipMemsetAsync(d.values, 0, (d.rows + 31) / 32 * 4, s);
         }
-        if (P) launch_decode(ctx, a, any_binary, any_prim, d_vlen);
+        if (P) launch_decode(ctx, a, any_binary, any_prim, d_vlen, nullptr);
     }
     e = hipGetLastError();
     if (e != hipSuccess) return check_hip(ctx, e, "decode launch");
 
     // results: values_len per column
     uint8_t* hv = slot->host + upload_bytes;
-    if (P && (any_binary || sizes_only)) {
+    if (P && (any_binary || sizes_only || filt)) {   // (a filter call: the bits set per column)
         e = hipMemcpyAsync(hv, d_vlen, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
         if (e != hipSuccess) return check_hip(ctx, e, "values_len readback");
     } else {
@@ -914,8 +937,8 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
     slot->in_flight = true;
     for (uint64_t i = 0; i < n; i++) {
         Pending pd;
-        pd.kind = Pending::READ_COL;
-        pd.user = &cols[i];
+        pd.kind = filt ? Pending::FILTER_COL : Pending::READ_COL;
+        pd.user = filt ? (void*)users[i] : (void*)&cols[i];
         pd.host = hv + i * sizeof(uint64_t);
         pd.n = 0;
         ctx->pending.push_back(pd);
@@ -971,6 +994,183 @@ int32_t sb_read_columns(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t m
         }
     }
     if (rc == SB_OK && ctx && n && !ctx->in_replay) ctx->calls.push_back(sb_ctx::Call{0, cols, n, sb_write_options{}, mem});
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------ filter
+static bool filter_comparable(int32_t t) {
+    return (t >= SB_TYPE_INT8 && t <= SB_TYPE_UINT64) || t == SB_TYPE_FLOAT32 || t == SB_TYPE_FLOAT64;
+}
+
+// The replay of an interval in which a filter call met a Freq page (KIND_FILTER_FREQ): the comparison columns are decoded
+// like a read — values and validity into the staging area, the exceptions of Freq pages by the second pass, which needs
+// the host and so cannot run inside the enqueue-only call — and compared from there.
+static int32_t filter_columns_decoded(sb_ctx* ctx, sb_column_filter* const* users, const FilterCol* hf, uint64_t m) {
+    hipStream_t s = ctx->stream;
+    ctx->filter_tmp.emplace_back(m);
+    std::vector<sb_column_read>& rr = ctx->filter_tmp.back();
+    size_t total = 0;
+    std::vector<size_t> o_val(m), o_bits(m);
+    for (uint64_t i = 0; i < m; i++) {
+        o_val[i] = total;
+        total += align_up(users[i]->rows * type_width(users[i]->physical_type), 64);
+        o_bits[i] = total;
+        total += align_up((users[i]->rows + 31) / 32 * 4, 64);
+    }
+    if (!ensure(ctx, ctx->filter_stage, total + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
+    for (uint64_t i = 0; i < m; i++) {
+        const sb_column_filter& u = *users[i];
+        sb_column_read& r = rr[i];
+        memset(&r, 0, sizeof r);
+        r.physical_type = u.physical_type;
+        r.is_nullable = u.is_nullable;
+        r.pages = u.pages;
+        r.pages_len = u.pages_len;
+        r.metas = u.metas;
+        r.n_pages = u.n_pages;
+        r.page_offsets = u.page_offsets;
+        r.values = ctx->filter_stage.p + o_val[i];
+        r.values_capacity = u.rows * type_width(u.physical_type);
+        r.validity = ctx->filter_stage.p + o_bits[i];
+        r.validity_capacity = (u.rows + 31) / 32 * 4;
+    }
+    int32_t rc = read_columns_impl(ctx, rr.data(), m, SB_MEM_DEVICE, false);
+    if (rc != SB_OK) return rc;
+    if (hipStreamSynchronize(s) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "filter replay: synchronize failed");
+    rc = freq_second_pass(ctx);
+    if (rc != SB_OK) return rc;
+    uint64_t* d_counts = nullptr;
+    if (hipMalloc((void**)&d_counts, m * sizeof(uint64_t)) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter counts) failed");
+    ctx->temp_dev.push_back(d_counts);
+    StageSlot* slot = acquire_slot(ctx, m * sizeof(uint64_t));
+    if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
+    for (uint64_t i = 0; i < m; i++) {
+        const uint64_t rows = users[i]->rows;
+        if (hf[i].combine == SB_SEL_SET && rows) (void)hipMemsetAsync(hf[i].sel, 0, (rows + 31) / 32 * 4, s);
+        launch_filter_plain(ctx, hf[i], (const uint8_t*)rr[i].values, users[i]->is_nullable ? rr[i].validity : nullptr, rows,
+                            type_width(users[i]->physical_type), d_counts + i);
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(slot->host, d_counts, m * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return check_hip(ctx, e, "filter replay");
+    (void)hipEventRecord(slot->done, s);
+    slot->in_flight = true;
+    for (uint64_t i = 0; i < m; i++) {
+        Pending pd;
+        pd.kind = Pending::FILTER_COL;
+        pd.user = users[i];
+        pd.host = slot->host + i * sizeof(uint64_t);
+        pd.n = 0;
+        ctx->pending.push_back(pd);
+    }
+    return SB_OK;
+}
+
+int32_t sb_filter_columns(sb_ctx* ctx, sb_column_filter* cols, uint64_t n, int32_t mem) {
+    if (!ctx || (!cols && n)) return SB_ERR_INVALID;
+    if (n == 0) return SB_OK;
+    // what is refused here is refused before anything is enqueued, and does not show again at the synchronize
+    auto refuse = [&](int32_t code, const char* msg) {
+        ctx->last_error = msg;
+        return code;
+    };
+    if (mem != SB_MEM_DEVICE) return refuse(SB_ERR_NYI, "sb_filter_columns: SB_MEM_HOST is not implemented");
+    std::vector<FilterCol> hf(n);
+    std::vector<sb_column_read> rc_cols(n);
+    std::vector<sb_column_filter*> users(n);
+    size_t stage = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        sb_column_filter& c = cols[i];
+        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(SB_ERR_INVALID, "bad physical_type");
+        if (c.op < SB_PRED_EQ || c.op > SB_PRED_IS_NOT_NULL) return refuse(SB_ERR_INVALID, "bad op");
+        if (c.combine < SB_SEL_SET || c.combine > SB_SEL_OR) return refuse(SB_ERR_INVALID, "bad combine");
+        const bool null_op = c.op >= SB_PRED_IS_NULL;
+        if (!null_op && !filter_comparable(c.physical_type))
+            return refuse(SB_ERR_NYI, "comparison predicates are implemented for 8- to 64-bit integers and floats");
+        if (c.n_pages && !c.metas) return refuse(SB_ERR_INVALID, "metas is null");
+        uint64_t rows = 0;
+        for (uint64_t p = 0; p < c.n_pages; p++) rows += c.metas[p].num_values;
+        const uint64_t sel_bytes = (rows + 31) / 32 * 4;
+        if (rows && (!c.selection || ((uintptr_t)c.selection & 3) || c.selection_capacity < sel_bytes))
+            return refuse(SB_ERR_INVALID, "selection missing, not 4-byte aligned or smaller than 4*ceil(rows/32) bytes");
+        for (uint64_t j = 0; j < i && rows; j++)
+            if (cols[j].rows && c.selection < cols[j].selection + (cols[j].rows + 31) / 32 * 4 && cols[j].selection < c.selection + sel_bytes)
+                return refuse(SB_ERR_INVALID, "two columns of one call share a selection buffer: chain them with two calls");
+        c.rows = rows;
+        c.selected = 0;
+        users[i] = &c;
+        FilterCol& f = hf[i];
+        memset(&f, 0, sizeof f);
+        f.sel = (uint32_t*)c.selection;
+        f.op = (uint32_t)c.op;
+        f.combine = (uint32_t)c.combine;
+        f.ptype = c.physical_type;
+        if (!null_op) {
+            static const uint32_t MASKS[6] = {2u, 13u, 1u, 3u, 4u, 6u};   // EQ NE LT LE GT GE over (less, equal, greater, unordered)
+            f.mask = MASKS[c.op];
+            const uint32_t w = type_width(c.physical_type);
+            uint64_t raw = 0;
+            memcpy(&raw, c.literal, w);
+            if (c.physical_type == SB_TYPE_FLOAT32) {
+                float v;
+                memcpy(&v, c.literal, 4);
+                const double dv = (double)v;
+                memcpy(&f.lit, &dv, 8);
+                f.kind = FK_F32;
+            } else if (c.physical_type == SB_TYPE_FLOAT64) {
+                f.lit = raw;
+                f.kind = FK_F64;
+            } else if (c.physical_type <= SB_TYPE_INT64) {
+                const uint32_t sh = 64 - 8 * w;
+                f.lit = (uint64_t)((int64_t)(raw << sh) >> sh);
+                f.kind = FK_SIGNED;
+            } else {
+                f.lit = raw;
+                f.kind = FK_UNSIGNED;
+            }
+            stage += align_up(rows * w, 64);
+        }
+    }
+    (void)hipSetDevice(ctx->device);
+    int32_t rc = SB_OK;
+    if (ctx->in_replay && ctx->filter_freq) {
+        // IS_[NOT_]NULL columns as ever; the comparison columns through a full decode
+        std::vector<sb_column_filter*> u_cmp, u_null;
+        std::vector<FilterCol> f_cmp, f_null;
+        for (uint64_t i = 0; i < n; i++) {
+            const bool null_op = cols[i].op >= SB_PRED_IS_NULL;
+            (null_op ? u_null : u_cmp).push_back(users[i]);
+            (null_op ? f_null : f_cmp).push_back(hf[i]);
+        }
+        if (!u_cmp.empty()) rc = filter_columns_decoded(ctx, u_cmp.data(), f_cmp.data(), u_cmp.size());
+        if (rc != SB_OK || u_null.empty()) return rc;
+        users.swap(u_null);
+        hf.swap(f_null);
+        n = users.size();
+        stage = 0;
+    }
+    if (!ensure(ctx, ctx->filter_stage, stage + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
+    size_t so = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_column_filter& c = *users[i];
+        const bool null_op = c.op >= SB_PRED_IS_NULL;
+        sb_column_read& r = rc_cols[i];
+        memset(&r, 0, sizeof r);
+        r.physical_type = null_op ? SB_TYPE_NULL : c.physical_type;   // (no page body is parsed, queued or planned for a null test)
+        r.is_nullable = c.is_nullable;
+        r.pages = c.pages;
+        r.pages_len = c.pages_len;
+        r.metas = c.metas;
+        r.n_pages = c.n_pages;
+        r.page_offsets = c.page_offsets;
+        if (!null_op) {
+            r.values = ctx->filter_stage.p + so;
+            r.values_capacity = c.rows * type_width(c.physical_type);
+            so += align_up(r.values_capacity, 64);
+        }
+    }
+    rc = read_columns_impl(ctx, rc_cols.data(), n, SB_MEM_DEVICE, false, hf.data(), users.data());
+    if (rc == SB_OK && !ctx->in_replay) ctx->calls.push_back(sb_ctx::Call{2, cols, n, sb_write_options{}, mem});
     return rc;
 }
 

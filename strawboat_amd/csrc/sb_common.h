@@ -116,6 +116,7 @@ constexpr uint32_t KIND_REPLAY = 8u;      // a page was left undone because a ke
 constexpr uint32_t KIND_REPLAY_LZG = 16u; // ... and it was an LZ4 block of megabytes that asked (the context turns the block-parallel chain on again)
 constexpr uint32_t KIND_QUEUE_A = 32u;    // a read call queued inflate jobs for queue A (Basic blocks of primitive pages, index / offset blocks)
 constexpr uint32_t KIND_TILES = 64u;      // a read call had tile tasks (k_expand / k_expand_binary)
+constexpr uint32_t KIND_FILTER_FREQ = 128u; // a filter call met a primitive Freq page (with KIND_REPLAY): the replay decodes that call's columns into the staging area (sb_filter.h)
 constexpr uint32_t KIND_ZSEQ_LONG = 2u;   // a Zstd block of >= 8192 sequences was met (zb_hdr): the sequence chains are the long pole
 
 // one general-purpose block (LZ4 / Zstd / Snappy) to inflate: src -> dst
@@ -271,6 +272,23 @@ struct DecodeArgs {
     uint32_t read_skips;    // RSKIP_* bits: kernels left out because the context's last read interval had no work for them (k_plan asks for the replay when this call has)
     uint32_t lzg_skipped;   // the call has pages long enough but the context's last intervals met no such block: the chain is not launched, a block that shows up after all asks for a replay (KIND_REPLAY)
 };
+// one column of a filter call (sb_filter_columns, sb_filter.h), next to its ColDesc
+struct FilterCol {
+    uint32_t* sel;     // the selection bitmap, in 32-bit words
+    uint64_t lit;      // the literal: zero- / sign-extended to 64 bits, floats as the bits of a double
+    uint32_t kind;     // how values compare: FK_*
+    uint32_t mask;     // bit r set: relation r (0 less, 1 equal, 2 greater, 3 unordered) satisfies the predicate
+    uint32_t op;       // SB_PRED_*
+    uint32_t combine;  // SB_SEL_*
+    int32_t ptype;     // the column's physical type (an IS_[NOT_]NULL column is parsed as SB_TYPE_NULL: no page body is looked at)
+    uint32_t pad;
+};
+struct FilterLaunch {   // what launch_decode needs to end a call with the filter kernels instead of the expand kernels
+    const FilterCol* fcols;
+    uint64_t* counts;      // [n_cols]: bits set per column
+    bool any_cmp, any_null, any_set;
+};
+constexpr uint32_t FK_UNSIGNED = 0, FK_SIGNED = 1, FK_F32 = 2, FK_F64 = 3;
 constexpr uint32_t LZ4_BIG_MIN = 64u << 10;
 constexpr uint32_t RSKIP_QUEUE_A = 1u, RSKIP_TILES = 2u;   // k_zstd_split + k_inflate + k_inflate_lz4 of queue A / k_expand
 

@@ -3070,7 +3070,11 @@ static void launch_lzg(sb_ctx* ctx, const DecodeArgs& a, InflateJob* q, const ui
     k_lzg_pack<<<dim3(std::min<uint32_t>(a.lzg_wins * 2 + 1, 4096u), NJ), 256, 0, s>>>(g);
 }
 
-void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, uint64_t* col_values_len) {
+}  // namespace sb
+#include "sb_filter.h"
+namespace sb {
+
+void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, uint64_t* col_values_len, const FilterLaunch* flt) {
     hipStream_t s = ctx->stream;
     (void)hipMemsetAsync(a.job_counts, 0, 16 * sizeof(uint32_t), s);
     const bool qa = !(a.read_skips & RSKIP_QUEUE_A);
@@ -3127,6 +3131,10 @@ void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_p
     if (any_binary && a.lz4_big_min != 0xFFFFFFFFu) {
         KScope k(ctx, "k_inflate_lz4_big(values)");
         k_inflate_lz4_big<<<min(a.zs_segs ? a.job_cap_a : 2 * a.n_pages, LZ4_BIG_POOL), LB_T, 0, s>>>(a.jobs_b, a.job_counts + 1, a.status, a.lz4_big_min, a.job_cap_a, a.lzg_skipped);
+    }
+    if (flt) {   // sb_filter_columns: the same pages, compared instead of stored
+        launch_filter(ctx, a, flt->fcols, flt->any_cmp, flt->any_null, flt->any_set, flt->counts);
+        return;
     }
     // the three expand kernels work on disjoint pages (page-level RLE, tiles of primitives, tiles of binary columns): side
     // by side on streams of their own when the call has both kinds of columns (a mixed schema), joined before the call ends

@@ -1,0 +1,454 @@
+// strawboat-hip: sb_filter_columns — the value sink of a filter call and its kernels (included by sb_decode.hip behind
+// the expand kernels, whose page walk they share).
+//
+// A filter call runs k_parse, the inflate queues and k_plan exactly as a read call does; where the read call launches
+// k_expand_rle / k_expand, it launches k_filter_rle / k_filter: the same walk over runs, indices and tiles, but every
+// value is compared with the column's literal and the outcome of 32 rows goes into a word of the selection bitmap.
+//   None                     one load per row, compared in registers
+//   OneValue                 one compare per tile
+//   RLE                      one compare per run: the chunk's runs become predicate BYTES in LDS, rows gather those
+//   Dict                     one compare per entry into an LDS bit table (<= FILTER_DICT_BITS entries), rows look bits up;
+//                            longer dictionaries: the row's entry is gathered and compared, as the decoder gathers it
+//   Bitpacking / Delta       unpacked into LDS by u32_tile_to_lds as for a read, compared from there
+//   LZ4 / Zstd / Snappy / Patas   inflated by the queues into the call's staging area (ColDesc.values), compared from there
+//   Freq                     the exceptions are a block of their own that a second decode pass expands at the synchronize:
+//                            the page is left alone here and the interval is issued again (KIND_REPLAY | KIND_FILTER_FREQ)
+//                            with this call decoded into the staging area and compared by k_filter_plain
+// k_filter_null serves IS_NULL / IS_NOT_NULL from the def-level section alone; k_filter_count counts the bits at the end.
+#pragma once
+
+namespace sb {
+
+constexpr uint32_t FILTER_DICT_BITS = 8192;   // entries of the LDS bit table (1 KiB): at most two compares per row of a full
+                                              // tile, read coalesced; beyond that a gather per row is less work
+
+struct FilterCmp {
+    uint64_t lit;
+    uint32_t kind, mask, w;
+};
+__device__ __forceinline__ FilterCmp filter_cmp(const FilterCol& f, uint32_t w) { return FilterCmp{f.lit, f.kind, f.mask, w}; }
+__device__ __forceinline__ uint64_t flt_load(const uint8_t* p, uint32_t w) {
+    switch (w) {
+        case 1:
+            return ldu8(p);
+        case 2:
+            return ldu16(p);
+        case 4:
+            return ldu32(p);
+        default:
+            return ldu64(p);
+    }
+}
+// the relation of the value to the literal (0 less, 1 equal, 2 greater, 3 unordered) picks a bit of the predicate's mask
+__device__ __forceinline__ bool flt_eval(const FilterCmp& k, uint64_t raw) {
+    uint32_t rel;
+    if (k.kind == FK_UNSIGNED) {
+        rel = raw < k.lit ? 0u : raw == k.lit ? 1u : 2u;
+    } else if (k.kind == FK_SIGNED) {
+        const uint32_t sh = 64 - 8 * k.w;
+        const int64_t v = (int64_t)(raw << sh) >> sh, l = (int64_t)k.lit;
+        rel = v < l ? 0u : v == l ? 1u : 2u;
+    } else {
+        const double v = k.kind == FK_F32 ? (double)__uint_as_float((uint32_t)raw) : __longlong_as_double((long long)raw);
+        const double l = __longlong_as_double((long long)k.lit);
+        rel = v < l ? 0u : v == l ? 1u : v > l ? 2u : 3u;
+    }
+    return (k.mask >> rel) & 1u;
+}
+
+// `b` are the result bits of the positions `m` of one selection word.  A word whose 32 positions come from one put is
+// owned by the lane that puts it: plain accesses.  A word shared by puts (page seams, chunk seams of an RLE page, the
+// column's last word) is touched with atomics only: OR into the word the call cleared (SET) or that holds the earlier
+// selection (OR), AND with the positions outside `m` set (AND).
+__device__ __forceinline__ void sel_word(uint32_t* w, uint32_t m, uint32_t b, uint32_t combine) {
+    if (m == 0xFFFFFFFFu) {
+        if (combine == SB_SEL_SET) gst32(w, b);
+        else if (combine == SB_SEL_AND) gst32(w, gld32(w) & b);
+        else gst32(w, gld32(w) | b);
+    } else if (combine == SB_SEL_AND) {
+        if (~b & m) atomicAnd(w, b | ~m);
+    } else if (b) {
+        atomicOr(w, b);
+    }
+}
+// the result of rows [pos, pos + nbits) of the column, nbits <= 32
+__device__ __forceinline__ void sel_put(uint32_t* sel, uint64_t pos, uint32_t bits, uint32_t nbits, uint32_t combine) {
+    const uint32_t m = nbits < 32 ? (1u << nbits) - 1 : 0xFFFFFFFFu;
+    bits &= m;
+    uint32_t* w = sel + (pos >> 5);
+    const uint32_t sh = (uint32_t)(pos & 31);
+    sel_word(w, m << sh, bits << sh, combine);
+    if (sh && (m >> (32 - sh))) sel_word(w + 1, m >> (32 - sh), bits >> (32 - sh), combine);
+}
+
+struct FilterSink {
+    uint32_t* sel;
+    const uint8_t* def_bits;   // the page's validity bits (bit 0 = row 0 of the page) or null
+    uint64_t out_row;          // the page's first row in the column
+    uint64_t N;                // rows of the page
+    uint32_t combine;
+};
+// Rows [lo, hi) of a page, pred(row) per row, by the whole workgroup: a lane per row, a ballot per wave, and the two
+// 32-row halves of the ballot — ANDed with the rows' validity: a null row satisfies nothing — put by lanes 0 and 32.
+// The halves start at multiples of 32 rows OF THE PAGE, so that the validity bits are a byte-aligned load.
+template <class P>
+__device__ __forceinline__ void filter_span(const FilterSink& k, uint64_t lo, uint64_t hi, P pred) {
+    constexpr int U = 4;   // rows per lane whose loads are issued before the first ballot
+    const uint32_t tid = threadIdx.x;
+    for (uint64_t g0 = lo & ~31ull; g0 < hi; g0 += (uint64_t)U * WG) {
+        bool bit[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t row = g0 + (uint64_t)u * WG + tid;
+            bit[u] = row >= lo && row < hi && pred(row);
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t row = g0 + (uint64_t)u * WG + tid;
+            const uint64_t m = __ballot(bit[u]);
+            if ((tid & 31) == 0 && row < hi && row + 32 > lo) {
+                uint32_t half = (tid & 32) ? (uint32_t)(m >> 32) : (uint32_t)m;
+                if (k.def_bits) half &= tile_bits_load(k.def_bits, row, k.N);
+                const uint64_t glo = max(row, lo), ghi = min(row + 32, hi);
+                sel_put(k.sel, k.out_row + glo, half >> (uint32_t)(glo - row), (uint32_t)(ghi - glo), k.combine);
+            }
+        }
+    }
+}
+
+// ---- tiles of None / OneValue / Dict / bit-packed / inflated pages (the pages k_expand has tiles for)
+__device__ void filter_tile(const DecodeArgs& a, const FilterCol* fcols, uint32_t ti, uint32_t* s_a, uint32_t* s_w, uint32_t* s_tab) {
+    const TileTask tt = a.tiles[ti];
+    const PageDesc d = a.descs[tt.page];
+    const PageTask t = a.tasks[tt.page];
+    const ColDesc c = a.cols[tt.col];
+    if (!d.ok) return;
+    const FilterCol f = fcols[tt.col];
+    if (f.op >= SB_PRED_IS_NULL) return;   // (k_filter_null)
+    const uint32_t w = c.width;
+    const uint64_t lo = (uint64_t)tt.tile * TILE_ROWS;
+    const uint32_t rows = (uint32_t)min((uint64_t)TILE_ROWS, t.num_values - lo);
+    const uint64_t hi = lo + rows;
+    const FilterSink k{f.sel, d.def_bits, t.out_row, t.num_values, f.combine};
+    const FilterCmp cmp = filter_cmp(f, w);
+    switch (d.codec) {
+        case SB_CODEC_NONE: {
+            const uint8_t* src = d.src;
+            filter_span(k, lo, hi, [&](uint64_t r) { return flt_eval(cmp, flt_load(src + r * w, w)); });
+            break;
+        }
+        case SB_CODEC_LZ4:
+        case SB_CODEC_ZSTD:
+        case SB_CODEC_SNAPPY:
+        case SB_CODEC_PATAS: {   // inflated into the staging area, where a read call has the column's values
+            const uint8_t* src = c.values + t.out_row * w;
+            filter_span(k, lo, hi, [&](uint64_t r) { return flt_eval(cmp, flt_load(src + r * w, w)); });
+            break;
+        }
+        case SB_CODEC_FREQ:   // SET: the rows stay cleared; AND / OR: untouched.  The replay puts them (see the head of the file)
+            if (threadIdx.x == 0 && tt.tile == 0) atomicOr(&a.status->kinds, KIND_REPLAY | KIND_FILTER_FREQ);
+            break;
+        case SB_CODEC_ONEVALUE: {
+            const bool v = flt_eval(cmp, flt_load(d.body, w));
+            filter_span(k, lo, hi, [&](uint64_t) { return v; });
+            break;
+        }
+        case SB_CODEC_DICT: {
+            U32Stream is{d.isrc, (const uint32_t*)(a.scratch + t.aux_off), d.icodec, d.n_runs, t.num_values};
+            u32_tile_to_lds(is, tt.tile, rows, s_a, s_w);
+            const uint8_t* dict = d.dict;
+            const uint32_t D = d.dict_n;
+            bool bad = false;
+            if (D <= FILTER_DICT_BITS) {
+                for (uint32_t e0 = 0; e0 < D; e0 += WG) {
+                    const uint32_t e = e0 + threadIdx.x;
+                    const uint64_t m = __ballot(e < D && flt_eval(cmp, flt_load(dict + (uint64_t)e * w, w)));
+                    if ((threadIdx.x & 31) == 0 && e < D) s_tab[e >> 5] = (threadIdx.x & 32) ? (uint32_t)(m >> 32) : (uint32_t)m;
+                }
+                __syncthreads();
+                filter_span(k, lo, hi, [&](uint64_t r) {
+                    const uint32_t e = s_a[sidx((int)(r - lo))];
+                    if (e >= D) {
+                        bad = true;
+                        return false;
+                    }
+                    return ((s_tab[e >> 5] >> (e & 31)) & 1u) != 0;
+                });
+            } else {
+                filter_span(k, lo, hi, [&](uint64_t r) {
+                    const uint32_t e = s_a[sidx((int)(r - lo))];
+                    if (e >= D) {
+                        bad = true;
+                        return false;
+                    }
+                    return flt_eval(cmp, flt_load(dict + (uint64_t)e * w, w));
+                });
+            }
+            if (bad) raise(a.status, SB_ERR_OUT_OF_SPEC, tt.page, 400);
+            break;
+        }
+        case SB_CODEC_BITPACKING:
+        case SB_CODEC_DELTA_BITPACKING: {
+            if (w != 4) break;
+            U32Stream vs{d.body, (const uint32_t*)(a.scratch + t.aux_off), d.codec, 0, t.num_values};
+            u32_tile_to_lds(vs, tt.tile, rows, s_a, s_w);
+            filter_span(k, lo, hi, [&](uint64_t r) { return flt_eval(cmp, s_a[sidx((int)(r - lo))]); });
+            break;
+        }
+        default:   // (RLE pages of <= 8-byte values have no tiles: k_filter_rle)
+            break;
+    }
+}
+
+// 18 KB of LDS (k_expand's 17 KB and the Dict bit table): 8 workgroups per CU like k_expand
+__global__ void __launch_bounds__(WG) k_filter(DecodeArgs a, const FilterCol* fcols) {
+    __shared__ uint32_t s_a[SIDX_WORDS];
+    __shared__ uint32_t s_w[4];
+    __shared__ uint32_t s_tab[FILTER_DICT_BITS / 32];
+    const uint32_t count = a.job_counts[2];
+    for (uint32_t ti = blockIdx.x; ti < count; ti += gridDim.x) {
+        filter_tile(a, fcols, ti, s_a, s_w, s_tab);
+        __syncthreads();
+    }
+}
+
+// ---- RLE pages, one workgroup per page (or per part of a long page): expand_rle_page's walk with the values of a chunk's
+// runs replaced by their predicate bytes; the rows of a chunk start and end anywhere in a selection word, which filter_span
+// and sel_put allow for
+__device__ void filter_rle_page(const ColDesc& c, const PageTask& t, const PageDesc& d, const FilterSink& k, const FilterCmp& cmp,
+                                uint32_t* s_flag, uint8_t* s_pred, uint32_t* s_w, uint64_t* s_w64, Status* st, uint32_t page,
+                                uint32_t part, uint32_t parts, const uint64_t* sums) {
+    const uint32_t w = c.width, REC = 4 + w;
+    const int tid = threadIdx.x;
+    const uint64_t N = t.num_values;
+    const uint8_t* body = d.body;
+    const uint8_t* page_end = c.pages + t.in_off + t.length;
+    const uint32_t max_runs = (uint32_t)((uint64_t)(page_end - body) / REC);
+    uint32_t ncnt[RLE_RPT];
+    bool nbit[RLE_RPT];
+    auto fetch = [&](uint32_t base) {
+#pragma unroll
+        for (int j = 0; j < RLE_RPT; j++) {
+            const uint32_t r = base + (uint32_t)tid * RLE_RPT + j;
+            const bool in = r < max_runs;
+            const uint8_t* rec = body + (uint64_t)(in ? r : 0) * REC;
+            ncnt[j] = in ? ldu32(rec) : 0;
+            nbit[j] = in && flt_eval(cmp, flt_load(rec + 4, w));
+        }
+    };
+    const uint32_t nchunks = (max_runs + RLE_CHUNK - 1) / RLE_CHUNK, cpp = (nchunks + parts - 1) / parts;
+    const uint32_t b0 = part * cpp * RLE_CHUNK;
+    const bool owns_end = (uint64_t)(part + 1) * cpp >= nchunks;
+    const uint64_t b1 = owns_end ? ~0ull : (uint64_t)(part + 1) * cpp * RLE_CHUNK;
+    if (part && b0 >= max_runs) return;
+    uint64_t carry = 0;
+    for (uint32_t q = 0; q < part; q++) carry += sums[q];
+    if (max_runs) fetch(b0);
+    for (uint64_t base64 = b0; carry < N && base64 < b1; base64 += RLE_CHUNK) {
+        const uint32_t base = (uint32_t)base64;
+        if (base64 >= max_runs) {
+            if (tid == 0) raise(st, SB_ERR_IO, page, 200);
+            return;
+        }
+        uint32_t cnt[RLE_RPT];
+        bool bit[RLE_RPT];
+#pragma unroll
+        for (int j = 0; j < RLE_RPT; j++) {
+            cnt[j] = ncnt[j];
+            bit[j] = nbit[j];
+        }
+        if (base + RLE_CHUNK < max_runs) fetch(base + RLE_CHUNK);
+        uint64_t loc[RLE_RPT], run = 0;
+#pragma unroll
+        for (int j = 0; j < RLE_RPT; j++) {
+            run += cnt[j];
+            loc[j] = run;
+        }
+        const uint64_t incl = wave_incl_scan64(run);
+        __syncthreads();  // the previous chunk's readers of s_w64 / s_pred are done
+#pragma unroll
+        for (int j = 0; j < RLE_RPT; j++) s_pred[tid * RLE_RPT + j] = bit[j] ? 1 : 0;
+        if ((tid & 63) == 63) s_w64[tid >> 6] = incl;
+        __syncthreads();
+        uint64_t pre = carry + incl - run;
+        const int wv = tid >> 6;
+        if (wv > 0) pre += s_w64[0];
+        if (wv > 1) pre += s_w64[1];
+        if (wv > 2) pre += s_w64[2];
+        const uint64_t chunk_total = s_w64[0] + s_w64[1] + s_w64[2] + s_w64[3];
+        uint64_t start[RLE_RPT];
+#pragma unroll
+        for (int j = 0; j < RLE_RPT; j++) start[j] = pre + (j ? loc[j - 1] : 0);
+        const uint64_t S0 = carry, S1 = min(N, carry + chunk_total);
+#pragma unroll
+        for (int j = 0; j < RLE_RPT; j++)
+            if (start[j] < N && start[j] + cnt[j] > N) raise(st, SB_ERR_OUT_OF_SPEC, page, 202);
+        for (uint64_t tile_lo = S0 / TILE_ROWS * TILE_ROWS; tile_lo < S1; tile_lo += TILE_ROWS) {
+            const uint64_t lo = max(S0, tile_lo), hi = min(S1, tile_lo + TILE_ROWS);
+            for (int i = tid; i < SIDX_WORDS / 4; i += WG) ((u32x4*)s_flag)[i] = u32x4{0, 0, 0, 0};
+            uint32_t le = 0;
+#pragma unroll
+            for (int j = 0; j < RLE_RPT; j++) le += (base + (uint32_t)tid * RLE_RPT + j < max_runs && start[j] <= lo) ? 1u : 0u;
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < RLE_RPT; j++)
+                if (base + (uint32_t)tid * RLE_RPT + j < max_runs && start[j] > lo && start[j] < hi)
+                    atomicAdd(&s_flag[sidx((int)(start[j] - tile_lo))], 1u);
+            uint32_t v = le;
+#pragma unroll
+            for (int dlt = 32; dlt > 0; dlt >>= 1) v += __shfl_down(v, dlt, 64);
+            if ((tid & 63) == 0) s_w[tid >> 6] = v;
+            __syncthreads();
+            const uint32_t A = s_w[0] + s_w[1] + s_w[2] + s_w[3] - 1;
+            __syncthreads();
+            tile_incl_scan(s_flag, s_w);
+            filter_span(k, lo, hi, [&](uint64_t r) { return s_pred[A + s_flag[sidx((int)(r - tile_lo))]] != 0; });
+            __syncthreads();  // s_flag / s_w are reused by the next tile
+        }
+        carry += chunk_total;
+        if (chunk_total == 0 && base + RLE_CHUNK >= max_runs && carry < N) {
+            if (tid == 0) raise(st, SB_ERR_IO, page, 200);
+            return;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(WG) k_filter_rle(DecodeArgs a, const FilterCol* fcols) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_flag[SIDX_WORDS];
+    __shared__ uint8_t s_pred[RLE_CHUNK];
+    __shared__ uint32_t s_w[4];
+    __shared__ uint64_t s_w64[4];
+    if (a.job_counts[4] == 0) return;  // no RLE page in this call
+    const uint32_t p = blockIdx.x;
+    const PageDesc d = a.descs[p];
+    const PageTask t = a.tasks[p];
+    const ColDesc c = a.cols[t.col];
+    if (!rle_by_page(c, d)) return;
+    const FilterCol f = fcols[t.col];
+    if (f.op >= SB_PRED_IS_NULL) return;
+    const uint32_t part = blockIdx.y, parts = gridDim.y;
+    const uint64_t* sums = parts > 1 ? a.rle_sums + (uint64_t)p * parts : nullptr;
+    const FilterSink k{f.sel, d.def_bits, t.out_row, t.num_values, f.combine};
+    filter_rle_page(c, t, d, k, filter_cmp(f, c.width), s_flag, s_pred, s_w, s_w64, a.status, p, part, parts, sums);
+}
+
+// ---- IS_NULL / IS_NOT_NULL: the def-level section of every page of such a column (u32 def_len | ULEB128 | bits,
+// read_basic.rs:36-63; the checks and their sites are k_parse's), one workgroup per page
+__global__ void __launch_bounds__(WG) k_filter_null(DecodeArgs a, const FilterCol* fcols) {
+    const uint32_t p = blockIdx.x;
+    const PageTask t = a.tasks[p];
+    const FilterCol f = fcols[t.col];
+    if (f.op < SB_PRED_IS_NULL) return;
+    const ColDesc c = a.cols[t.col];
+    const uint64_t N = t.num_values;
+    if (!N) return;
+    const uint8_t* def = nullptr;
+#define NFAIL(code, tag)                                           \
+    do {                                                           \
+        if (threadIdx.x == 0) raise(a.status, (code), p, (tag));   \
+        return;                                                    \
+    } while (0)
+    if (f.ptype != SB_TYPE_NULL && c.nullable) {
+        if (t.in_off + t.length > c.pages_len) NFAIL(SB_ERR_IO, 1);
+        const uint8_t* cur = c.pages + t.in_off;
+        const uint8_t* end = cur + t.length;
+        if (end - cur < 4) NFAIL(SB_ERR_IO, 2);
+        const uint32_t def_len = ldu32(cur);
+        cur += 4;
+        if ((uint64_t)(end - cur) < def_len) NFAIL(SB_ERR_IO, 3);
+        if (def_len == 0) NFAIL(SB_ERR_OUT_OF_SPEC, 4);
+        uint64_t ind = 0;
+        uint32_t sh = 0, n = 0;
+        for (;;) {
+            if (n >= def_len || n >= 10) NFAIL(SB_ERR_OUT_OF_SPEC, 5);
+            const uint8_t b = cur[n++];
+            ind |= (uint64_t)(b & 0x7F) << sh;
+            sh += 7;
+            if (!(b & 0x80)) break;
+        }
+        if (!(ind & 1)) NFAIL(SB_ERR_OUT_OF_SPEC, 6);
+        uint64_t nbytes = ind >> 1;
+        if (nbytes > def_len - n) nbytes = def_len - n;
+        if (nbytes * 8 < N) NFAIL(SB_ERR_OUT_OF_SPEC, 7);
+        def = cur + n;
+    }
+#undef NFAIL
+    const uint32_t none = f.ptype == SB_TYPE_NULL ? 0u : 0xFFFFFFFFu;   // validity of a page without a def-level section
+    const uint64_t nwords = (N + 31) / 32;
+    for (uint64_t g = threadIdx.x; g < nwords; g += WG) {
+        uint32_t v = def ? tile_bits_load(def, g * 32, N) : none;
+        if (f.op == SB_PRED_IS_NULL) v = ~v;
+        sel_put(f.sel, t.out_row + g * 32, v, (uint32_t)min((uint64_t)32, N - g * 32), f.combine);
+    }
+}
+
+// ---- bits set below `rows`, one workgroup per column
+__device__ void filter_count(const uint32_t* sel, uint64_t rows, uint64_t* out, uint64_t* s_w64) {
+    const uint64_t nwords = (rows + 31) / 32;
+    uint64_t n = 0;
+    for (uint64_t g = threadIdx.x; g < nwords; g += WG) {
+        uint32_t v = gld32(sel + g);
+        if (g == nwords - 1 && (rows & 31)) v &= (1u << (rows & 31)) - 1;
+        n += (uint64_t)__popc(v);
+    }
+    n = wg_sum64(n, s_w64);
+    if (threadIdx.x == 0) *out = n;
+}
+__global__ void __launch_bounds__(WG) k_filter_count(const ColDesc* cols, const FilterCol* fcols, uint64_t* counts) {
+    __shared__ uint64_t s_w64[4];
+    filter_count(fcols[blockIdx.x].sel, cols[blockIdx.x].rows, counts + blockIdx.x, s_w64);
+}
+
+// ---- the replay of a call that met a Freq page: the column was decoded like a read (values and validity in the staging
+// area, exceptions scattered by the second pass); one launch per column, a workgroup per TILE_ROWS rows, then the count
+__global__ void __launch_bounds__(WG) k_filter_plain(FilterCol f, const uint8_t* values, const uint8_t* validity, uint64_t rows, uint32_t w) {
+    const uint64_t lo = (uint64_t)blockIdx.x * TILE_ROWS, hi = min(rows, lo + TILE_ROWS);
+    const FilterSink k{f.sel, validity, 0, rows, f.combine};
+    const FilterCmp cmp = filter_cmp(f, w);
+    filter_span(k, lo, hi, [&](uint64_t r) { return flt_eval(cmp, flt_load(values + r * w, w)); });
+}
+__global__ void __launch_bounds__(WG) k_filter_count_one(const uint32_t* sel, uint64_t rows, uint64_t* out) {
+    __shared__ uint64_t s_w64[4];
+    filter_count(sel, rows, out, s_w64);
+}
+
+// SET columns start from zero: shared words are assembled with OR, and the bits behind the last row are written as 0
+// (one launch for the call's columns: a memset per column costs a 64-column call more than its kernels)
+__global__ void __launch_bounds__(WG) k_filter_clear(const ColDesc* cols, const FilterCol* fcols) {
+    const FilterCol f = fcols[blockIdx.x];
+    if (f.combine != SB_SEL_SET) return;
+    const uint64_t nwords = (cols[blockIdx.x].rows + 31) / 32;
+    for (uint64_t g = (uint64_t)blockIdx.y * WG + threadIdx.x; g < nwords; g += (uint64_t)gridDim.y * WG) gst32(f.sel + g, 0u);
+}
+
+void launch_filter(sb_ctx* ctx, const DecodeArgs& a, const FilterCol* fcols, bool any_cmp, bool any_null, bool any_set, uint64_t* counts) {
+    hipStream_t s = ctx->stream;
+    if (any_set) {
+        KScope k(ctx, "k_filter_clear");
+        k_filter_clear<<<dim3(a.n_cols, 16), WG, 0, s>>>(a.cols, fcols);
+    }
+    if (any_null) {
+        KScope k(ctx, "k_filter_null");
+        k_filter_null<<<a.n_pages, WG, 0, s>>>(a, fcols);
+    }
+    if (any_cmp) {
+        KScope k(ctx, "k_filter_rle");
+        if (a.rle_parts > 1) k_rle_sums<<<dim3(a.n_pages, a.rle_parts), WG, 0, s>>>(a);
+        k_filter_rle<<<dim3(a.n_pages, std::max<uint32_t>(1u, a.rle_parts)), WG, 0, s>>>(a, fcols);
+    }
+    if (any_cmp && a.n_tiles) {
+        KScope k(ctx, "k_filter");
+        k_filter<<<min(a.n_tiles, TILE_GRID), WG, 0, s>>>(a, fcols);
+    }
+    KScope k(ctx, "k_filter_count");
+    k_filter_count<<<a.n_cols, WG, 0, s>>>(a.cols, fcols, counts);
+}
+
+void launch_filter_plain(sb_ctx* ctx, const FilterCol& f, const uint8_t* values, const uint8_t* validity, uint64_t rows, uint32_t w,
+                         uint64_t* count) {
+    hipStream_t s = ctx->stream;
+    if (rows) k_filter_plain<<<(uint32_t)((rows + TILE_ROWS - 1) / TILE_ROWS), WG, 0, s>>>(f, values, validity, rows, w);
+    k_filter_count_one<<<1, WG, 0, s>>>(f.sel, rows, count);
+}
+
+}  // namespace sb

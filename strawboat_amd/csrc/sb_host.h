@@ -23,9 +23,9 @@ struct StageSlot {
 };
 
 struct Pending {  // results to hand back to the caller's structs at synchronize
-    enum Kind { READ_COL, WRITE_COL, ENC_HINT, NESTED_W, NESTED_R } kind;   // ENC_HINT: the codec counts of a write call (n = the plan's key), 32 words
+    enum Kind { READ_COL, WRITE_COL, ENC_HINT, NESTED_W, NESTED_R, FILTER_COL } kind;   // ENC_HINT: the codec counts of a write call (n = the plan's key), 32 words
                                                                            // NESTED_W / _R: the page records of an enqueued level call (user = its items, n = how many)
-    void* user;            // sb_column_read* / sb_column_write*
+    void* user;            // sb_column_read* / sb_column_write* / sb_column_filter* (FILTER_COL: 8 bytes, the bits set)
     const uint8_t* host;   // where the readback lands (pinned)
     uint64_t n;            // WRITE_COL: number of pages
     uint64_t bytes = 0;    // NESTED_*: bytes of the readback at `host`
@@ -57,6 +57,9 @@ struct sb_ctx {
     sb::DevBuf tables;   // ColDesc / PageTask / PageDesc / TileTask / jobs / counters
     sb::DevBuf scratch;  // per-page aux + inflate areas, encode slots
     sb::DevBuf staging;  // device staging for SB_MEM_HOST callers
+    sb::DevBuf filter_stage;   // sb_filter_columns: where the inflate queues put the values of LZ4 / Zstd / Snappy / Patas pages (no caller's buffer to inflate into)
+    bool filter_freq = false;  // replay of an interval in which a filter call met a Freq page: filter calls decode into filter_stage first
+    std::deque<std::vector<sb_column_read>> filter_tmp;   // the read columns of those decodes (alive until the synchronize returns)
     sb::DevBuf zlit;     // Zstd literal buffers (fixed pool of inflate waves)
     sb::DevBuf zrec;     // Zstd sequence records (one arena per inflate wave; allocated by the first batch-sized read)
     sb::Status* d_status = nullptr;
@@ -203,7 +206,7 @@ struct sb_ctx {
     // never a one-workgroup walk over a million-row page.  (The callers' column arrays and buffers live until the
     // synchronize anyway: the results are written into them there.)
     struct Call {
-        int kind;   // 0 read, 1 write
+        int kind;   // 0 read, 1 write, 2 filter
         void* cols;
         uint64_t n;
         sb_write_options opts;

@@ -1,0 +1,158 @@
+"""filter:: — evaluate a predicate on the pages of primitive columns, on the GPU.
+
+What a query engine does first with the filter columns of a block: `WHERE x < 5` over the
+pages of `x` gives one bit per row (LSB-first, like an Arrow validity bitmap) and the number of
+bits set, without the decoded values ever being written to memory (sb_filter_columns in
+include/strawboat_hip.h).  Null rows satisfy no comparison; floats compare as IEEE 754.
+"""
+import ctypes as C
+import math
+import struct
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+from . import _native as N
+from .read import ColumnPages, _dev_ptr
+from .types import PhysicalType
+
+OPS = {"eq": N.SB_PRED_EQ, "ne": N.SB_PRED_NE, "lt": N.SB_PRED_LT, "le": N.SB_PRED_LE, "gt": N.SB_PRED_GT,
+       "ge": N.SB_PRED_GE, "is_null": N.SB_PRED_IS_NULL, "is_not_null": N.SB_PRED_IS_NOT_NULL}
+COMBINE = {"set": N.SB_SEL_SET, "and": N.SB_SEL_AND, "or": N.SB_SEL_OR}
+
+_P = PhysicalType
+_INT_FORMATS = {_P.INT8: "<b", _P.INT16: "<h", _P.INT32: "<i", _P.INT64: "<q",
+                _P.UINT8: "<B", _P.UINT16: "<H", _P.UINT32: "<I", _P.UINT64: "<Q"}
+
+
+def pack_literal(physical_type, value) -> bytes:
+    """The 8 literal bytes of sb_column_filter for a value of the column's own physical type.
+    No implicit widening: an integer that does not fit the type, or a float that is not integral
+    for an integer column, raises ValueError (the engine above folds `int8_col < 1000` itself)."""
+    if isinstance(value, (bool, np.bool_)):
+        raise ValueError("a boolean is not a literal of a numeric column")
+    if physical_type in _INT_FORMATS:
+        if isinstance(value, (float, np.floating)):
+            if not math.isfinite(value) or value != math.floor(value):
+                raise ValueError("literal %r is not integral, the column is an integer column" % (value,))
+            value = int(value)
+        elif isinstance(value, (int, np.integer)):
+            value = int(value)
+        else:
+            raise ValueError("literal %r is not a number" % (value,))
+        try:
+            raw = struct.pack(_INT_FORMATS[physical_type], value)
+        except struct.error:
+            raise ValueError("literal %d does not fit physical type %d" % (value, physical_type))
+    elif physical_type in (_P.FLOAT32, _P.FLOAT64):
+        if not isinstance(value, (int, float, np.integer, np.floating)):
+            raise ValueError("literal %r is not a number" % (value,))
+        value = float(value)
+        if physical_type == _P.FLOAT32:
+            with np.errstate(over="ignore"):
+                f = np.float32(value)
+            if math.isfinite(value) and not np.isfinite(f):
+                raise ValueError("literal %r does not fit a 32-bit float" % (value,))
+            raw = f.tobytes()
+        else:
+            raw = struct.pack("<d", value)
+    else:
+        raise ValueError("comparison predicates are implemented for 8- to 64-bit integers and floats, "
+                         "not physical type %d" % physical_type)
+    return raw + b"\0" * (8 - len(raw))
+
+
+class Predicate:
+    """op: "eq" "ne" "lt" "le" "gt" "ge" (with a literal) or "is_null" "is_not_null" (without)."""
+
+    def __init__(self, op, literal=None):
+        if op not in OPS:
+            raise ValueError("unknown predicate %r" % (op,))
+        if op in ("is_null", "is_not_null"):
+            if literal is not None:
+                raise ValueError("%s takes no literal" % op)
+        elif literal is None:
+            raise ValueError("%s needs a literal" % op)
+        self.op = op
+        self.literal = literal
+
+    def __repr__(self):
+        return "Predicate(%r, %r)" % (self.op, self.literal)
+
+
+class Selection:
+    """The selection bitmap of one column in HBM; `selected` is valid after Context.synchronize()."""
+
+    def __init__(self, bitmap, rows, cstruct):
+        self.bitmap = bitmap   # torch.uint8, 4*ceil(rows/32) bytes
+        self.rows = rows
+        self._c = cstruct
+
+    @property
+    def selected(self):
+        return int(self._c.selected)
+
+    def numpy(self):
+        """bool array of `rows` entries"""
+        b = self.bitmap[:(self.rows + 7) // 8].cpu().numpy()
+        return np.unpackbits(b, bitorder="little")[:self.rows].astype(bool)
+
+
+class FilterBatch:
+    """A prepared filter call: the C descriptors and the selection buffers are built once;
+    enqueue() then costs one C call (steady-state callers, scripts/filter_probe.py)."""
+
+    def __init__(self, ctx, columns: List[ColumnPages], predicates: Sequence[Predicate], combine="set",
+                 out: Optional[List[Selection]] = None):
+        import torch
+        from .read import _prepare
+        if len(columns) != len(predicates):
+            raise ValueError("one predicate per column")
+        if combine not in COMBINE:
+            raise ValueError("unknown combine mode %r" % (combine,))
+        if combine != "set" and out is None:
+            raise ValueError("combine=%r needs the selections to combine with (out=)" % combine)
+        if out is not None and len(out) != len(columns):
+            raise ValueError("one selection per column")
+        n = len(columns)
+        literals = []
+        for col, pr in zip(columns, predicates):   # every literal is checked before anything is enqueued
+            literals.append(b"\0" * 8 if pr.literal is None else pack_literal(col.physical_type, pr.literal))
+        rarr, keep = _prepare(ctx, columns)   # (validates the page tensors; the descriptors' common head)
+        arr = (N.ColumnFilterC * n)()
+        res = []
+        with torch.cuda.stream(ctx.torch_stream):
+            for i, (col, pr) in enumerate(zip(columns, predicates)):
+                c, r = arr[i], rarr[i]
+                c.physical_type, c.is_nullable = r.physical_type, r.is_nullable
+                c.pages, c.pages_len, c.metas, c.n_pages = r.pages, r.pages_len, r.metas, r.n_pages
+                c.op = OPS[pr.op]
+                c.combine = COMBINE[combine]
+                c.literal = (C.c_uint8 * 8)(*literals[i])
+                rows = int(col.metas_array()[:, 1].sum()) if c.n_pages else 0
+                if out is not None:
+                    if out[i].rows != rows:
+                        raise ValueError("selection %d has %d rows, the column %d" % (i, out[i].rows, rows))
+                    bitmap = out[i].bitmap
+                else:
+                    bitmap = torch.empty(((rows + 31) // 32) * 4, dtype=torch.uint8, device=ctx.torch_device)
+                keep.append(bitmap)
+                c.selection = _dev_ptr(bitmap)
+                c.selection_capacity = bitmap.numel()
+                res.append(Selection(bitmap, rows, c))
+        self.ctx, self._arr, self._keep, self._n = ctx, arr, keep, n
+        self.selections = res
+
+    def enqueue(self):
+        ctx = self.ctx
+        ctx._keep.append(self)
+        ctx._check(ctx._lib.sb_filter_columns(ctx._h, self._arr, self._n, N.SB_MEM_DEVICE))
+        return self.selections
+
+
+def filter_columns(ctx, columns: List[ColumnPages], predicates: Sequence[Predicate], combine="set",
+                   out: Optional[List[Selection]] = None) -> List[Selection]:
+    """Enqueue predicates[i] over columns[i] on ctx's stream.  combine: "set" writes the result,
+    "and" / "or" combine it with what `out[i].bitmap` holds (chain predicates with one call after
+    the other).  `out` re-uses earlier selections' buffers; required for "and" / "or"."""
+    return FilterBatch(ctx, columns, predicates, combine, out).enqueue()
