@@ -166,7 +166,8 @@ int32_t sb_read_columns_sizes(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int
  * FLOAT64.  A null row never satisfies a comparison.  Floats compare as IEEE 754: NaN satisfies only
  * NE, -0.0 == 0.0.  IS_NULL / IS_NOT_NULL: every physical type (only the def-level section of a page
  * is looked at; a non-nullable column has no null row, every row of a SB_TYPE_NULL column is null).
- * A comparison on any other type: SB_ERR_NYI at the call, the selection is not touched. */
+ * A comparison on any other type: SB_ERR_NYI at the call, the selection is not touched (Binary / LargeBinary columns:
+ * sb_filter_columns_var below, whose literal is a pointer and a length). */
 #define SB_PRED_EQ 0
 #define SB_PRED_NE 1
 #define SB_PRED_LT 2
@@ -206,6 +207,48 @@ typedef struct sb_column_filter {
  * modes.  Its own kernels are launched without consulting the launch hints of the read path.
  * `mem`: SB_MEM_DEVICE.  SB_MEM_HOST is not implemented (SB_ERR_NYI): stage the pages and the bitmap yourself. */
 int32_t sb_filter_columns(sb_ctx* ctx, sb_column_filter* cols, uint64_t n, int32_t mem);
+
+/* The same call with a literal of any length: what a predicate on a Binary / LargeBinary column (Utf8 / LargeUtf8 are
+ * stored as these) needs.  Numeric columns, IS_[NOT_]NULL, SET / AND / OR, `rows` / `selected`, errors and replays are
+ * those of sb_filter_columns bit for bit, and numeric and binary columns may share one call.
+ *
+ * Binary columns, EQ .. GE: values compare as byte strings — bytes unsigned, lexicographic, a proper prefix is less
+ * than the longer string (Rust's `<[u8] as Ord>`, what arrow2 compares Binary and Utf8 with).  The empty string is a
+ * value like any other.  STARTS_WITH: the value has at least literal_len bytes and its first literal_len bytes equal
+ * the literal; an empty literal selects every non-null row.  A null row satisfies nothing.
+ * The predicate is evaluated once per entry of a Dict page (and of a Freq page, which is read as one), once per
+ * OneValue page and once per row of a plain page; no offsets and no value bytes are written.  The value blocks of
+ * LZ4 / Zstd / Snappy pages are inflated into a staging area of the context first: `stage_capacity` bounds the bytes
+ * this column may take there (the sum of the uncompressed sizes of those blocks; 0 = 4 * pages_len, the reference's
+ * guess for a binary read, src/read/array/binary.rs:241).  A column that needs more raises SB_ERR_INVALID at the
+ * synchronize, as sb_read_columns does for a `values` buffer that is too small.
+ *
+ * Refused at the call (nothing enqueued, no selection touched): STARTS_WITH on a type that is not binary, a numeric
+ * literal_len that is not the type's width, a binary literal of more than 2^30 bytes, a null literal with
+ * literal_len > 0 (SB_ERR_INVALID); comparisons on Boolean / Int128 / Int256 / Null, SB_MEM_HOST (SB_ERR_NYI). */
+#define SB_PRED_STARTS_WITH 8
+
+typedef struct sb_column_filter_var {
+    int32_t physical_type;   /* SB_TYPE_* */
+    int32_t is_nullable;
+    const uint8_t* pages;    /* DEVICE */
+    uint64_t pages_len;
+    const sb_page_meta* metas; /* HOST */
+    uint64_t n_pages;
+    const uint64_t* page_offsets; /* optional (HOST) */
+    int32_t op;              /* SB_PRED_* */
+    int32_t combine;         /* SB_SEL_* */
+    const uint8_t* literal;  /* HOST, literal_len bytes; must stay valid until sb_ctx_synchronize (a replay reads it again) */
+    uint64_t literal_len;    /* numbers: exactly the type's width; binary: any length, 0 included; ignored by IS_[NOT_]NULL */
+    uint8_t* selection;      /* DEVICE: LSB-first bitmap, 4-byte aligned */
+    uint64_t selection_capacity; /* >= 4*ceil(rows/32) bytes */
+    uint64_t stage_capacity; /* binary comparison columns: see above; 0 = 4 * pages_len */
+    /* results (HOST, valid after sb_ctx_synchronize) */
+    uint64_t rows;
+    uint64_t selected;
+} sb_column_filter_var;      /* 112 bytes */
+
+int32_t sb_filter_columns_var(sb_ctx* ctx, sb_column_filter_var* cols, uint64_t n, int32_t mem);
 
 /* ------------------------------------------------------------------ encode
  * Replaces, per leaf column, the page loop of NativeWriter::encode_chunk

@@ -240,9 +240,10 @@ void sb_ctx_destroy(sb_ctx* ctx) {
 const char* sb_ctx_last_error(sb_ctx* ctx) { return ctx ? ctx->last_error.c_str() : "null context"; }
 void* sb_ctx_stream(sb_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 
-// (filt / users: the call is a filter call — sb_filter_columns — whose columns end in the filter kernels)
+// (filt / sel_out / lits: the call is a filter call — sb_filter_columns[_var] — whose columns end in the filter kernels; sel_out[i]:
+// the caller's `selected`; lits: the literals of the FK_BYTES columns, FilterCol.lit being the offset of each)
 static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, bool sizes_only, const FilterCol* filt = nullptr,
-                                 sb_column_filter* const* users = nullptr);
+                                 uint64_t* const* sel_out = nullptr, const std::vector<uint8_t>* lits = nullptr);
 
 // Freq pages (integer/freq.rs:90-127) found by the decode calls of this synchronize interval: their
 // exception blocks are ordinary BLOCK<T>s, so they go through the decoder once more as one-page
@@ -408,7 +409,8 @@ int32_t sb_ctx_synchronize(sb_ctx* ctx) {
         ctx->replays++;
         if (ctx->h_status->kinds & KIND_REPLAY_LZG) ctx->lzg_state = 1;
         for (auto& cl : calls) {
-            rc = cl.kind == 2 ? sb_filter_columns(ctx, (sb_column_filter*)cl.cols, cl.n, cl.mem)
+            rc = cl.kind == 3 ? sb_filter_columns_var(ctx, (sb_column_filter_var*)cl.cols, cl.n, cl.mem)
+                 : cl.kind == 2 ? sb_filter_columns(ctx, (sb_column_filter*)cl.cols, cl.n, cl.mem)
                  : cl.kind  ? sb_write_columns(ctx, (sb_column_write*)cl.cols, cl.n, &cl.opts, cl.mem)
                             : sb_read_columns(ctx, (sb_column_read*)cl.cols, cl.n, cl.mem);
             if (rc != SB_OK) break;
@@ -458,7 +460,7 @@ int32_t sb_ctx_synchronize(sb_ctx* ctx) {
             memcpy(&v, p.host, 8);
             c->values_len = v;
         } else if (p.kind == Pending::FILTER_COL) {
-            memcpy(&((sb_column_filter*)p.user)->selected, p.host, 8);
+            memcpy(p.user, p.host, 8);
         } else if (p.kind == Pending::ENC_HINT) {
             if (ctx->enc_plan.valid && ctx->enc_plan.key == p.n && rc == SB_OK) {
                 uint32_t now[32];
@@ -564,7 +566,8 @@ uint32_t sb_ctx_profile_read(sb_ctx* ctx, sb_kernel_stat* out, uint32_t cap) {
 }
 
 // ------------------------------------------------------------------------------------ decode
-static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, bool sizes_only, const FilterCol* filt, sb_column_filter* const* users) {
+static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, bool sizes_only, const FilterCol* filt, uint64_t* const* sel_out,
+                                 const std::vector<uint8_t>* lits) {
     if (!ctx || (!cols && n)) return SB_ERR_INVALID;
     if (n == 0) return SB_OK;
     (void)hipSetDevice(ctx->device);
@@ -596,7 +599,9 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
             if (!c.values) return ctx->fail(SB_ERR_INVALID, "values is null");
             if (c.is_nullable && !filt && (!c.validity || c.validity_capacity < (rows + 31) / 32 * 4))
                 return ctx->fail(SB_ERR_INVALID, "validity buffer missing or smaller than 4*ceil(rows/32) bytes");
-            if (is_binary_t(c.physical_type)) {
+            if (is_binary_t(c.physical_type) && filt) {
+                // (a filter call writes no offsets; `values` is the column's share of the staging area)
+            } else if (is_binary_t(c.physical_type)) {
                 if (!c.offsets || c.offsets_capacity < (rows + 1) * w)
                     return ctx->fail(SB_ERR_INVALID, "offsets buffer missing or too small");
             } else if (c.physical_type == SB_TYPE_BOOLEAN) {
@@ -620,6 +625,8 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
     off = align_up(off + P * sizeof(PageTask), 64);
     const size_t o_fcols = off;
     if (filt) off = align_up(off + n * sizeof(FilterCol), 64);
+    const size_t o_lits = off;
+    if (lits) off = align_up(off + lits->size(), 64);
     const size_t upload_bytes = off;
     const size_t o_descs = off;
     off = align_up(off + P * sizeof(PageDesc), 64);
@@ -723,6 +730,7 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
             t.first_tile = (uint32_t)tile_i;
             t.aux_off = scratch_off;
             scratch_off += align_up((L / 4 + N / 128 + 4 * ntiles + 16) * 4, 16);   // (4 * ntiles: tile_k0 / tile_base + tile_bytes, and the u64 tile totals of a long binary Dict page)
+            if (filt && is_binary_t(c.physical_type)) scratch_off += filter_bin_table_words(L) * 4;   // (a bit per dictionary entry: sb_filter_bin.h)
             t.infl_off = scratch_off;
             scratch_off += align_up((N + 1) * 8 + 16, 16);
             in_off += L;
@@ -731,7 +739,13 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
         }
         if (in_off > c.pages_len) return ctx->fail(SB_ERR_IO, "sum of PageMeta.length exceeds pages_len");
     }
-    if (filt) memcpy(slot->host + o_fcols, filt, n * sizeof(FilterCol));
+    if (filt) {
+        FilterCol* hfc = (FilterCol*)(slot->host + o_fcols);
+        memcpy(hfc, filt, n * sizeof(FilterCol));
+        if (lits && !lits->empty()) memcpy(slot->host + o_lits, lits->data(), lits->size());
+        for (uint64_t i = 0; i < n; i++)
+            if (hfc[i].kind == FK_BYTES) hfc[i].lit += (uint64_t)(uintptr_t)(ctx->tables.p + o_lits);
+    }
     if (!ensure(ctx, ctx->scratch, scratch_off + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(scratch) failed");
     // the inflate pool's per-wave areas: a literal buffer of one block, and (calls with at least 4 queue entries per pool
     // wave: batches) the arena of pre-decoded Zstd sequences
@@ -903,12 +917,13 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
     if (sizes_only) {
         if (P) launch_parse_sizes(ctx, a, d_vlen);
     } else if (filt) {
-        FilterLaunch fl{(const FilterCol*)(tb + o_fcols), d_vlen, false, false, false};
+        FilterLaunch fl{(const FilterCol*)(tb + o_fcols), d_vlen, false, false, false, false};
         for (uint64_t i = 0; i < n; i++) {
-            (filt[i].op >= SB_PRED_IS_NULL ? fl.any_null : fl.any_cmp) = true;
+            const bool null_op = filt[i].op >= SB_PRED_IS_NULL;
+            (null_op ? fl.any_null : filt[i].kind == FK_BYTES ? fl.any_bin : fl.any_cmp) = true;
             if (filt[i].combine == SB_SEL_SET) fl.any_set = true;
         }
-        if (P) launch_decode(ctx, a, false, any_prim, d_vlen, &fl);
+        if (P) launch_decode(ctx, a, any_binary, any_prim, d_vlen, &fl);
     } else {
         // bitmaps are assembled with OR at page seams: start from zero
         for (uint64_t i = 0; i < n; i++) {
@@ -938,7 +953,7 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
     for (uint64_t i = 0; i < n; i++) {
         Pending pd;
         pd.kind = filt ? Pending::FILTER_COL : Pending::READ_COL;
-        pd.user = filt ? (void*)users[i] : (void*)&cols[i];
+        pd.user = filt ? (void*)sel_out[i] : (void*)&cols[i];
         pd.host = hv + i * sizeof(uint64_t);
         pd.n = 0;
         ctx->pending.push_back(pd);
@@ -1002,10 +1017,10 @@ static bool filter_comparable(int32_t t) {
     return (t >= SB_TYPE_INT8 && t <= SB_TYPE_UINT64) || t == SB_TYPE_FLOAT32 || t == SB_TYPE_FLOAT64;
 }
 
-// The replay of an interval in which a filter call met a Freq page (KIND_FILTER_FREQ): the comparison columns are decoded
-// like a read — values and validity into the staging area, the exceptions of Freq pages by the second pass, which needs
-// the host and so cannot run inside the enqueue-only call — and compared from there.
-static int32_t filter_columns_decoded(sb_ctx* ctx, sb_column_filter* const* users, const FilterCol* hf, uint64_t m) {
+// The replay of an interval in which a filter call met a primitive Freq page (KIND_FILTER_FREQ): the numeric comparison
+// columns are decoded like a read — values and validity into the staging area, the exceptions of Freq pages by the second
+// pass, which needs the host and so cannot run inside the enqueue-only call — and compared from there.
+static int32_t filter_columns_decoded(sb_ctx* ctx, sb_column_filter_var* const* users, const FilterCol* hf, uint64_t* const* sel_out, uint64_t m) {
     hipStream_t s = ctx->stream;
     ctx->filter_tmp.emplace_back(m);
     std::vector<sb_column_read>& rr = ctx->filter_tmp.back();
@@ -1019,7 +1034,7 @@ static int32_t filter_columns_decoded(sb_ctx* ctx, sb_column_filter* const* user
     }
     if (!ensure(ctx, ctx->filter_stage, total + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
     for (uint64_t i = 0; i < m; i++) {
-        const sb_column_filter& u = *users[i];
+        const sb_column_filter_var& u = *users[i];
         sb_column_read& r = rr[i];
         memset(&r, 0, sizeof r);
         r.physical_type = u.physical_type;
@@ -1058,7 +1073,7 @@ static int32_t filter_columns_decoded(sb_ctx* ctx, sb_column_filter* const* user
     for (uint64_t i = 0; i < m; i++) {
         Pending pd;
         pd.kind = Pending::FILTER_COL;
-        pd.user = users[i];
+        pd.user = sel_out[i];
         pd.host = slot->host + i * sizeof(uint64_t);
         pd.n = 0;
         ctx->pending.push_back(pd);
@@ -1066,27 +1081,34 @@ static int32_t filter_columns_decoded(sb_ctx* ctx, sb_column_filter* const* user
     return SB_OK;
 }
 
-int32_t sb_filter_columns(sb_ctx* ctx, sb_column_filter* cols, uint64_t n, int32_t mem) {
-    if (!ctx || (!cols && n)) return SB_ERR_INVALID;
-    if (n == 0) return SB_OK;
+// Both entry points end here.  `cols` is the call in the var layout (sb_filter_columns copies its columns into one that
+// lives for the call); results[i] are the caller's own { rows, selected } words, which outlive the call.
+static int32_t filter_impl(sb_ctx* ctx, const sb_column_filter_var* cols, uint64_t* const* results, uint64_t n) {
     // what is refused here is refused before anything is enqueued, and does not show again at the synchronize
     auto refuse = [&](int32_t code, const char* msg) {
         ctx->last_error = msg;
         return code;
     };
-    if (mem != SB_MEM_DEVICE) return refuse(SB_ERR_NYI, "sb_filter_columns: SB_MEM_HOST is not implemented");
     std::vector<FilterCol> hf(n);
     std::vector<sb_column_read> rc_cols(n);
-    std::vector<sb_column_filter*> users(n);
-    size_t stage = 0;
+    std::vector<sb_column_filter_var> work(cols, cols + n);   // (with rows and the default stage_capacity filled in)
+    std::vector<sb_column_filter_var*> users(n);
+    std::vector<uint8_t> lits;   // the binary literals, each at a multiple of 8 and followed by 8 zero bytes
     for (uint64_t i = 0; i < n; i++) {
-        sb_column_filter& c = cols[i];
+        sb_column_filter_var& c = work[i];
         if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(SB_ERR_INVALID, "bad physical_type");
-        if (c.op < SB_PRED_EQ || c.op > SB_PRED_IS_NOT_NULL) return refuse(SB_ERR_INVALID, "bad op");
+        if (c.op < SB_PRED_EQ || c.op > SB_PRED_STARTS_WITH) return refuse(SB_ERR_INVALID, "bad op");
         if (c.combine < SB_SEL_SET || c.combine > SB_SEL_OR) return refuse(SB_ERR_INVALID, "bad combine");
-        const bool null_op = c.op >= SB_PRED_IS_NULL;
-        if (!null_op && !filter_comparable(c.physical_type))
-            return refuse(SB_ERR_NYI, "comparison predicates are implemented for 8- to 64-bit integers and floats");
+        const bool null_op = c.op == SB_PRED_IS_NULL || c.op == SB_PRED_IS_NOT_NULL;
+        const bool bin = is_binary_t(c.physical_type);
+        if (c.op == SB_PRED_STARTS_WITH && !bin) return refuse(SB_ERR_INVALID, "STARTS_WITH needs a Binary / LargeBinary column");
+        if (!null_op && !bin && !filter_comparable(c.physical_type))
+            return refuse(SB_ERR_NYI, "comparison predicates are implemented for 8- to 64-bit integers, floats and binary types");
+        if (!null_op) {
+            if (!bin && c.literal_len != type_width(c.physical_type)) return refuse(SB_ERR_INVALID, "literal_len is not the width of the column's type");
+            if (bin && c.literal_len > (1ull << 30)) return refuse(SB_ERR_INVALID, "a binary literal has at most 2^30 bytes");
+            if (c.literal_len && !c.literal) return refuse(SB_ERR_INVALID, "literal is null");
+        }
         if (c.n_pages && !c.metas) return refuse(SB_ERR_INVALID, "metas is null");
         uint64_t rows = 0;
         for (uint64_t p = 0; p < c.n_pages; p++) rows += c.metas[p].num_values;
@@ -1094,66 +1116,89 @@ int32_t sb_filter_columns(sb_ctx* ctx, sb_column_filter* cols, uint64_t n, int32
         if (rows && (!c.selection || ((uintptr_t)c.selection & 3) || c.selection_capacity < sel_bytes))
             return refuse(SB_ERR_INVALID, "selection missing, not 4-byte aligned or smaller than 4*ceil(rows/32) bytes");
         for (uint64_t j = 0; j < i && rows; j++)
-            if (cols[j].rows && c.selection < cols[j].selection + (cols[j].rows + 31) / 32 * 4 && cols[j].selection < c.selection + sel_bytes)
+            if (work[j].rows && c.selection < work[j].selection + (work[j].rows + 31) / 32 * 4 && work[j].selection < c.selection + sel_bytes)
                 return refuse(SB_ERR_INVALID, "two columns of one call share a selection buffer: chain them with two calls");
         c.rows = rows;
-        c.selected = 0;
+    }
+    size_t stage = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        sb_column_filter_var& c = work[i];
+        const bool null_op = c.op == SB_PRED_IS_NULL || c.op == SB_PRED_IS_NOT_NULL;
+        results[i][0] = c.rows;
+        results[i][1] = 0;
         users[i] = &c;
         FilterCol& f = hf[i];
         memset(&f, 0, sizeof f);
         f.sel = (uint32_t*)c.selection;
-        f.op = (uint32_t)c.op;
+        f.op = c.op == SB_PRED_STARTS_WITH ? (uint32_t)SB_PRED_EQ : (uint32_t)c.op;   // (the kernels tell null tests by op >= IS_NULL; a prefix test by its mask)
         f.combine = (uint32_t)c.combine;
         f.ptype = c.physical_type;
-        if (!null_op) {
-            static const uint32_t MASKS[6] = {2u, 13u, 1u, 3u, 4u, 6u};   // EQ NE LT LE GT GE over (less, equal, greater, unordered)
-            f.mask = MASKS[c.op];
-            const uint32_t w = type_width(c.physical_type);
-            uint64_t raw = 0;
-            memcpy(&raw, c.literal, w);
-            if (c.physical_type == SB_TYPE_FLOAT32) {
-                float v;
-                memcpy(&v, c.literal, 4);
-                const double dv = (double)v;
-                memcpy(&f.lit, &dv, 8);
-                f.kind = FK_F32;
-            } else if (c.physical_type == SB_TYPE_FLOAT64) {
-                f.lit = raw;
-                f.kind = FK_F64;
-            } else if (c.physical_type <= SB_TYPE_INT64) {
-                const uint32_t sh = 64 - 8 * w;
-                f.lit = (uint64_t)((int64_t)(raw << sh) >> sh);
-                f.kind = FK_SIGNED;
-            } else {
-                f.lit = raw;
-                f.kind = FK_UNSIGNED;
-            }
-            stage += align_up(rows * w, 64);
+        if (null_op) continue;
+        static const uint32_t MASKS[6] = {2u, 13u, 1u, 3u, 4u, 6u};   // EQ NE LT LE GT GE over (less, equal, greater, unordered)
+        f.mask = c.op == SB_PRED_STARTS_WITH ? FILTER_MASK_PREFIX : MASKS[c.op];
+        if (is_binary_t(c.physical_type)) {
+            f.kind = FK_BYTES;
+            f.lit_len = (uint32_t)c.literal_len;
+            lits.resize(align_up(lits.size(), 8));
+            f.lit = lits.size();   // (offset in `lits`; read_columns_impl makes it the device address)
+            if (c.literal_len) lits.insert(lits.end(), c.literal, c.literal + c.literal_len);
+            lits.insert(lits.end(), 8, (uint8_t)0);
+            if (!c.stage_capacity) c.stage_capacity = 4 * c.pages_len;
+            stage += align_up(c.stage_capacity, 64);
+            continue;
         }
+        const uint32_t w = type_width(c.physical_type);
+        uint64_t raw = 0;
+        memcpy(&raw, c.literal, w);
+        if (c.physical_type == SB_TYPE_FLOAT32) {
+            float v;
+            memcpy(&v, c.literal, 4);
+            const double dv = (double)v;
+            memcpy(&f.lit, &dv, 8);
+            f.kind = FK_F32;
+        } else if (c.physical_type == SB_TYPE_FLOAT64) {
+            f.lit = raw;
+            f.kind = FK_F64;
+        } else if (c.physical_type <= SB_TYPE_INT64) {
+            const uint32_t sh = 64 - 8 * w;
+            f.lit = (uint64_t)((int64_t)(raw << sh) >> sh);
+            f.kind = FK_SIGNED;
+        } else {
+            f.lit = raw;
+            f.kind = FK_UNSIGNED;
+        }
+        stage += align_up(c.rows * w, 64);
     }
     (void)hipSetDevice(ctx->device);
     int32_t rc = SB_OK;
+    std::vector<uint64_t*> sel_out(n);
+    for (uint64_t i = 0; i < n; i++) sel_out[i] = results[i] + 1;
     if (ctx->in_replay && ctx->filter_freq) {
-        // IS_[NOT_]NULL columns as ever; the comparison columns through a full decode
-        std::vector<sb_column_filter*> u_cmp, u_null;
-        std::vector<FilterCol> f_cmp, f_null;
+        // IS_[NOT_]NULL and binary columns as ever; the numeric comparison columns through a full decode
+        std::vector<sb_column_filter_var*> u_cmp, u_rest;
+        std::vector<FilterCol> f_cmp, f_rest;
+        std::vector<uint64_t*> s_cmp, s_rest;
         for (uint64_t i = 0; i < n; i++) {
-            const bool null_op = cols[i].op >= SB_PRED_IS_NULL;
-            (null_op ? u_null : u_cmp).push_back(users[i]);
-            (null_op ? f_null : f_cmp).push_back(hf[i]);
+            const bool dec = hf[i].op < SB_PRED_IS_NULL && hf[i].kind != FK_BYTES;
+            (dec ? u_cmp : u_rest).push_back(users[i]);
+            (dec ? f_cmp : f_rest).push_back(hf[i]);
+            (dec ? s_cmp : s_rest).push_back(sel_out[i]);
         }
-        if (!u_cmp.empty()) rc = filter_columns_decoded(ctx, u_cmp.data(), f_cmp.data(), u_cmp.size());
-        if (rc != SB_OK || u_null.empty()) return rc;
-        users.swap(u_null);
-        hf.swap(f_null);
+        if (!u_cmp.empty()) rc = filter_columns_decoded(ctx, u_cmp.data(), f_cmp.data(), s_cmp.data(), u_cmp.size());
+        if (rc != SB_OK || u_rest.empty()) return rc;
+        users.swap(u_rest);
+        hf.swap(f_rest);
+        sel_out.swap(s_rest);
         n = users.size();
         stage = 0;
+        for (uint64_t i = 0; i < n; i++)
+            if (hf[i].kind == FK_BYTES) stage += align_up(users[i]->stage_capacity, 64);
     }
     if (!ensure(ctx, ctx->filter_stage, stage + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
     size_t so = 0;
     for (uint64_t i = 0; i < n; i++) {
-        const sb_column_filter& c = *users[i];
-        const bool null_op = c.op >= SB_PRED_IS_NULL;
+        const sb_column_filter_var& c = *users[i];
+        const bool null_op = c.op == SB_PRED_IS_NULL || c.op == SB_PRED_IS_NOT_NULL;
         sb_column_read& r = rc_cols[i];
         memset(&r, 0, sizeof r);
         r.physical_type = null_op ? SB_TYPE_NULL : c.physical_type;   // (no page body is parsed, queued or planned for a null test)
@@ -1165,11 +1210,63 @@ int32_t sb_filter_columns(sb_ctx* ctx, sb_column_filter* cols, uint64_t n, int32
         r.page_offsets = c.page_offsets;
         if (!null_op) {
             r.values = ctx->filter_stage.p + so;
-            r.values_capacity = c.rows * type_width(c.physical_type);
+            r.values_capacity = is_binary_t(c.physical_type) ? c.stage_capacity : c.rows * type_width(c.physical_type);
             so += align_up(r.values_capacity, 64);
         }
     }
-    rc = read_columns_impl(ctx, rc_cols.data(), n, SB_MEM_DEVICE, false, hf.data(), users.data());
+    return read_columns_impl(ctx, rc_cols.data(), n, SB_MEM_DEVICE, false, hf.data(), sel_out.data(), &lits);
+}
+
+int32_t sb_filter_columns_var(sb_ctx* ctx, sb_column_filter_var* cols, uint64_t n, int32_t mem) {
+    if (!ctx || (!cols && n)) return SB_ERR_INVALID;
+    if (n == 0) return SB_OK;
+    if (mem != SB_MEM_DEVICE) {
+        ctx->last_error = "sb_filter_columns_var: SB_MEM_HOST is not implemented";
+        return SB_ERR_NYI;
+    }
+    std::vector<uint64_t*> results(n);
+    for (uint64_t i = 0; i < n; i++) results[i] = &cols[i].rows;   // { rows, selected }
+    const int32_t rc = filter_impl(ctx, cols, results.data(), n);
+    if (rc == SB_OK && !ctx->in_replay) ctx->calls.push_back(sb_ctx::Call{3, cols, n, sb_write_options{}, mem});
+    return rc;
+}
+
+int32_t sb_filter_columns(sb_ctx* ctx, sb_column_filter* cols, uint64_t n, int32_t mem) {
+    if (!ctx || (!cols && n)) return SB_ERR_INVALID;
+    if (n == 0) return SB_OK;
+    auto refuse = [&](int32_t code, const char* msg) {
+        ctx->last_error = msg;
+        return code;
+    };
+    if (mem != SB_MEM_DEVICE) return refuse(SB_ERR_NYI, "sb_filter_columns: SB_MEM_HOST is not implemented");
+    // the eight inline literal bytes hold numbers only: everything else this entry point refused before stays refused
+    std::vector<sb_column_filter_var> v(n);
+    std::vector<uint64_t*> results(n);
+    for (uint64_t i = 0; i < n; i++) {
+        sb_column_filter& c = cols[i];
+        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(SB_ERR_INVALID, "bad physical_type");
+        if (c.op < SB_PRED_EQ || c.op > SB_PRED_IS_NOT_NULL) return refuse(SB_ERR_INVALID, "bad op");
+        if (c.op < SB_PRED_IS_NULL && !filter_comparable(c.physical_type))
+            return refuse(SB_ERR_NYI, "comparison predicates are implemented for 8- to 64-bit integers and floats");
+        sb_column_filter_var& d = v[i];
+        memset(&d, 0, sizeof d);
+        d.physical_type = c.physical_type;
+        d.is_nullable = c.is_nullable;
+        d.pages = c.pages;
+        d.pages_len = c.pages_len;
+        d.metas = c.metas;
+        d.n_pages = c.n_pages;
+        d.page_offsets = c.page_offsets;
+        d.op = c.op;
+        d.combine = c.combine;
+        d.literal = c.literal;
+        d.literal_len = c.op < SB_PRED_IS_NULL ? type_width(c.physical_type) : 0;
+        d.selection = c.selection;
+        d.selection_capacity = c.selection_capacity;
+        static_assert(offsetof(sb_column_filter, selected) == offsetof(sb_column_filter, rows) + 8, "{ rows, selected }");
+        results[i] = &c.rows;
+    }
+    const int32_t rc = filter_impl(ctx, v.data(), results.data(), n);
     if (rc == SB_OK && !ctx->in_replay) ctx->calls.push_back(sb_ctx::Call{2, cols, n, sb_write_options{}, mem});
     return rc;
 }

@@ -275,20 +275,26 @@ struct DecodeArgs {
 // one column of a filter call (sb_filter_columns, sb_filter.h), next to its ColDesc
 struct FilterCol {
     uint32_t* sel;     // the selection bitmap, in 32-bit words
-    uint64_t lit;      // the literal: zero- / sign-extended to 64 bits, floats as the bits of a double
+    uint64_t lit;      // the literal: zero- / sign-extended to 64 bits, floats as the bits of a double; FK_BYTES: the DEVICE
+                       // address of its lit_len bytes, followed by at least 8 zero bytes (sb_filter_bin.h)
     uint32_t kind;     // how values compare: FK_*
     uint32_t mask;     // bit r set: relation r (0 less, 1 equal, 2 greater, 3 unordered) satisfies the predicate
     uint32_t op;       // SB_PRED_*
     uint32_t combine;  // SB_SEL_*
     int32_t ptype;     // the column's physical type (an IS_[NOT_]NULL column is parsed as SB_TYPE_NULL: no page body is looked at)
-    uint32_t pad;
+    uint32_t lit_len;  // FK_BYTES: bytes of the literal
 };
 struct FilterLaunch {   // what launch_decode needs to end a call with the filter kernels instead of the expand kernels
     const FilterCol* fcols;
     uint64_t* counts;      // [n_cols]: bits set per column
     bool any_cmp, any_null, any_set;
+    bool any_bin;          // comparison columns of a binary type: k_filter_bin_base / _entries / k_filter_bin (sb_filter_bin.h)
 };
-constexpr uint32_t FK_UNSIGNED = 0, FK_SIGNED = 1, FK_F32 = 2, FK_F64 = 3;
+constexpr uint32_t FK_UNSIGNED = 0, FK_SIGNED = 1, FK_F32 = 2, FK_F64 = 3, FK_BYTES = 4;
+constexpr uint32_t FILTER_MASK_PREFIX = 16u;   // FilterCol.mask of SB_PRED_STARTS_WITH (the four relation bits are clear)
+// words of the bit table (a bit per dictionary entry) that a filter call reserves at the END of the aux area of every page
+// of a binary comparison column: an entry is a u64 length and its bytes, so a page of L bytes has at most L / 8 of them
+__host__ __device__ inline uint64_t filter_bin_table_words(uint64_t page_len) { return (page_len / 256 + 4) & ~3ull; }
 constexpr uint32_t LZ4_BIG_MIN = 64u << 10;
 constexpr uint32_t RSKIP_QUEUE_A = 1u, RSKIP_TILES = 2u;   // k_zstd_split + k_inflate + k_inflate_lz4 of queue A / k_expand
 

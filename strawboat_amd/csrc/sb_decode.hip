@@ -3072,6 +3072,7 @@ static void launch_lzg(sb_ctx* ctx, const DecodeArgs& a, InflateJob* q, const ui
 
 }  // namespace sb
 #include "sb_filter.h"
+#include "sb_filter_bin.h"
 namespace sb {
 
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, uint64_t* col_values_len, const FilterLaunch* flt) {
@@ -3106,12 +3107,16 @@ void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_p
         }
         k_plan<<<a.n_pages, WG, 0, s>>>(a);
     }
-    if (any_binary && a.n_tiles >= BIN_DEFER_TILES) {   // long binary Dict pages: the tiles' value bytes by a workgroup per tile
+    if (any_binary && flt) {   // no tile totals, no bases but those of the value blocks to inflate (sb_filter_bin.h)
+        launch_filter_bin_base(ctx, a, flt->fcols);
+        launch_zstd_split(a, a.jobs_b, a.job_counts + 1, a.job_counts + 9, a.job_cap_b, s);
+    }
+    if (any_binary && !flt && a.n_tiles >= BIN_DEFER_TILES) {   // long binary Dict pages: the tiles' value bytes by a workgroup per tile
         KScope k(ctx, "k_bin_tile_sums");
         k_bin_tile_sums<<<min(a.n_tiles, TILE_GRID), WG, 0, s>>>(a);
         k_bin_tile_scan<<<min((a.n_pages + WG / 64 - 1) / (WG / 64), 1024u), WG, 0, s>>>(a);
     }
-    if (any_binary) {  // (without binary columns the host knows every values_len itself)
+    if (any_binary && !flt) {  // (without binary columns the host knows every values_len itself)
         KScope k(ctx, K_COLSCAN);
         k_colscan<<<a.n_cols, 64, 0, s>>>(a, col_values_len);
         launch_zstd_split(a, a.jobs_b, a.job_counts + 1, a.job_counts + 9, a.job_cap_b, s);
@@ -3133,7 +3138,7 @@ void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_p
         k_inflate_lz4_big<<<min(a.zs_segs ? a.job_cap_a : 2 * a.n_pages, LZ4_BIG_POOL), LB_T, 0, s>>>(a.jobs_b, a.job_counts + 1, a.status, a.lz4_big_min, a.job_cap_a, a.lzg_skipped);
     }
     if (flt) {   // sb_filter_columns: the same pages, compared instead of stored
-        launch_filter(ctx, a, flt->fcols, flt->any_cmp, flt->any_null, flt->any_set, flt->counts);
+        launch_filter(ctx, a, *flt);
         return;
     }
     // the three expand kernels work on disjoint pages (page-level RLE, tiles of primitives, tiles of binary columns): side

@@ -15,6 +15,7 @@
 //                            the page is left alone here and the interval is issued again (KIND_REPLAY | KIND_FILTER_FREQ)
 //                            with this call decoded into the staging area and compared by k_filter_plain
 // k_filter_null serves IS_NULL / IS_NOT_NULL from the def-level section alone; k_filter_count counts the bits at the end.
+// Comparison columns of a binary type (sb_filter_columns_var) share the sink and have kernels of their own: sb_filter_bin.h.
 #pragma once
 
 namespace sb {
@@ -123,6 +124,7 @@ __device__ void filter_tile(const DecodeArgs& a, const FilterCol* fcols, uint32_
     const PageTask t = a.tasks[tt.page];
     const ColDesc c = a.cols[tt.col];
     if (!d.ok) return;
+    if (is_binary(c.ptype)) return;   // (k_filter_bin)
     const FilterCol f = fcols[tt.col];
     if (f.op >= SB_PRED_IS_NULL) return;   // (k_filter_null)
     const uint32_t w = c.width;
@@ -421,8 +423,12 @@ __global__ void __launch_bounds__(WG) k_filter_clear(const ColDesc* cols, const 
     for (uint64_t g = (uint64_t)blockIdx.y * WG + threadIdx.x; g < nwords; g += (uint64_t)gridDim.y * WG) gst32(f.sel + g, 0u);
 }
 
-void launch_filter(sb_ctx* ctx, const DecodeArgs& a, const FilterCol* fcols, bool any_cmp, bool any_null, bool any_set, uint64_t* counts) {
+void launch_filter_bin(sb_ctx* ctx, const DecodeArgs& a, const FilterCol* fcols);   // sb_filter_bin.h
+void launch_filter(sb_ctx* ctx, const DecodeArgs& a, const FilterLaunch& fl) {
     hipStream_t s = ctx->stream;
+    const FilterCol* fcols = fl.fcols;
+    const bool any_cmp = fl.any_cmp, any_null = fl.any_null, any_set = fl.any_set;
+    uint64_t* counts = fl.counts;
     if (any_set) {
         KScope k(ctx, "k_filter_clear");
         k_filter_clear<<<dim3(a.n_cols, 16), WG, 0, s>>>(a.cols, fcols);
@@ -440,6 +446,7 @@ void launch_filter(sb_ctx* ctx, const DecodeArgs& a, const FilterCol* fcols, boo
         KScope k(ctx, "k_filter");
         k_filter<<<min(a.n_tiles, TILE_GRID), WG, 0, s>>>(a, fcols);
     }
+    if (fl.any_bin) launch_filter_bin(ctx, a, fcols);
     KScope k(ctx, "k_filter_count");
     k_filter_count<<<a.n_cols, WG, 0, s>>>(a.cols, fcols, counts);
 }

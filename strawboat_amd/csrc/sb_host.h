@@ -25,7 +25,7 @@ struct StageSlot {
 struct Pending {  // results to hand back to the caller's structs at synchronize
     enum Kind { READ_COL, WRITE_COL, ENC_HINT, NESTED_W, NESTED_R, FILTER_COL } kind;   // ENC_HINT: the codec counts of a write call (n = the plan's key), 32 words
                                                                            // NESTED_W / _R: the page records of an enqueued level call (user = its items, n = how many)
-    void* user;            // sb_column_read* / sb_column_write* / sb_column_filter* (FILTER_COL: 8 bytes, the bits set)
+    void* user;            // sb_column_read* / sb_column_write* / FILTER_COL: the caller's `selected` (8 bytes, the bits set)
     const uint8_t* host;   // where the readback lands (pinned)
     uint64_t n;            // WRITE_COL: number of pages
     uint64_t bytes = 0;    // NESTED_*: bytes of the readback at `host`
@@ -206,7 +206,7 @@ struct sb_ctx {
     // never a one-workgroup walk over a million-row page.  (The callers' column arrays and buffers live until the
     // synchronize anyway: the results are written into them there.)
     struct Call {
-        int kind;   // 0 read, 1 write, 2 filter
+        int kind;   // 0 read, 1 write, 2 filter (sb_filter_columns), 3 filter (sb_filter_columns_var)
         void* cols;
         uint64_t n;
         sb_write_options opts;

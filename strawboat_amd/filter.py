@@ -1,9 +1,11 @@
-"""filter:: — evaluate a predicate on the pages of primitive columns, on the GPU.
+"""filter:: — evaluate a predicate on the pages of primitive and binary columns, on the GPU.
 
-What a query engine does first with the filter columns of a block: `WHERE x < 5` over the
-pages of `x` gives one bit per row (LSB-first, like an Arrow validity bitmap) and the number of
-bits set, without the decoded values ever being written to memory (sb_filter_columns in
-include/strawboat_hip.h).  Null rows satisfy no comparison; floats compare as IEEE 754.
+What a query engine does first with the filter columns of a block: `WHERE x < 5 AND s = 'a'` over
+the pages of `x` and `s` gives one bit per row (LSB-first, like an Arrow validity bitmap) and the
+number of bits set, without the decoded values ever being written to memory
+(sb_filter_columns_var in include/strawboat_hip.h).  Null rows satisfy no comparison; floats
+compare as IEEE 754; Binary / Utf8 values compare as byte strings (bytes unsigned, a proper
+prefix is less), and have "starts_with" beside the six orderings.
 """
 import ctypes as C
 import math
@@ -17,7 +19,8 @@ from .read import ColumnPages, _dev_ptr
 from .types import PhysicalType
 
 OPS = {"eq": N.SB_PRED_EQ, "ne": N.SB_PRED_NE, "lt": N.SB_PRED_LT, "le": N.SB_PRED_LE, "gt": N.SB_PRED_GT,
-       "ge": N.SB_PRED_GE, "is_null": N.SB_PRED_IS_NULL, "is_not_null": N.SB_PRED_IS_NOT_NULL}
+       "ge": N.SB_PRED_GE, "is_null": N.SB_PRED_IS_NULL, "is_not_null": N.SB_PRED_IS_NOT_NULL,
+       "starts_with": N.SB_PRED_STARTS_WITH}
 COMBINE = {"set": N.SB_SEL_SET, "and": N.SB_SEL_AND, "or": N.SB_SEL_OR}
 
 _P = PhysicalType
@@ -62,8 +65,34 @@ def pack_literal(physical_type, value) -> bytes:
     return raw + b"\0" * (8 - len(raw))
 
 
+_BINARY = (_P.BINARY, _P.LARGE_BINARY)
+_WIDTH = {_P.INT8: 1, _P.UINT8: 1, _P.INT16: 2, _P.UINT16: 2, _P.INT32: 4, _P.UINT32: 4, _P.FLOAT32: 4,
+          _P.INT64: 8, _P.UINT64: 8, _P.FLOAT64: 8}
+
+
+def literal_bytes(physical_type, op, value) -> bytes:
+    """The literal of sb_column_filter_var: exactly the type's width for a number (pack_literal's
+    rules), the bytes themselves for a Binary / LargeBinary column (`str` is encoded as UTF-8).
+    A bytes / str literal on a numeric column, a number on a binary column and "starts_with" on
+    a numeric column raise ValueError."""
+    if op in ("is_null", "is_not_null"):
+        return b""
+    if physical_type in _BINARY:
+        if isinstance(value, str):
+            return value.encode("utf-8")
+        if isinstance(value, (bytes, bytearray, memoryview)):
+            return bytes(value)
+        raise ValueError("literal %r is not bytes or str, the column is a binary column" % (value,))
+    if op == "starts_with":
+        raise ValueError("starts_with needs a Binary / LargeBinary column, not physical type %d" % physical_type)
+    if isinstance(value, (str, bytes, bytearray, memoryview)):
+        raise ValueError("literal %r is not a number" % (value,))
+    return pack_literal(physical_type, value)[:_WIDTH[physical_type]]
+
+
 class Predicate:
-    """op: "eq" "ne" "lt" "le" "gt" "ge" (with a literal) or "is_null" "is_not_null" (without)."""
+    """op: "eq" "ne" "lt" "le" "gt" "ge" (with a literal), "starts_with" (binary columns, with a
+    bytes / str literal) or "is_null" "is_not_null" (without)."""
 
     def __init__(self, op, literal=None):
         if op not in OPS:
@@ -103,7 +132,7 @@ class FilterBatch:
     enqueue() then costs one C call (steady-state callers, scripts/filter_probe.py)."""
 
     def __init__(self, ctx, columns: List[ColumnPages], predicates: Sequence[Predicate], combine="set",
-                 out: Optional[List[Selection]] = None):
+                 out: Optional[List[Selection]] = None, stage_capacity: Optional[Sequence[int]] = None):
         import torch
         from .read import _prepare
         if len(columns) != len(predicates):
@@ -114,12 +143,14 @@ class FilterBatch:
             raise ValueError("combine=%r needs the selections to combine with (out=)" % combine)
         if out is not None and len(out) != len(columns):
             raise ValueError("one selection per column")
+        if stage_capacity is not None and len(stage_capacity) != len(columns):
+            raise ValueError("one stage_capacity per column")
         n = len(columns)
         literals = []
         for col, pr in zip(columns, predicates):   # every literal is checked before anything is enqueued
-            literals.append(b"\0" * 8 if pr.literal is None else pack_literal(col.physical_type, pr.literal))
+            literals.append(literal_bytes(col.physical_type, pr.op, pr.literal))
         rarr, keep = _prepare(ctx, columns)   # (validates the page tensors; the descriptors' common head)
-        arr = (N.ColumnFilterC * n)()
+        arr = (N.ColumnFilterVarC * n)()
         res = []
         with torch.cuda.stream(ctx.torch_stream):
             for i, (col, pr) in enumerate(zip(columns, predicates)):
@@ -128,7 +159,11 @@ class FilterBatch:
                 c.pages, c.pages_len, c.metas, c.n_pages = r.pages, r.pages_len, r.metas, r.n_pages
                 c.op = OPS[pr.op]
                 c.combine = COMBINE[combine]
-                c.literal = (C.c_uint8 * 8)(*literals[i])
+                buf = C.create_string_buffer(literals[i], max(1, len(literals[i])))   # (read again by a replay: kept with the batch)
+                keep.append(buf)
+                c.literal = C.addressof(buf)
+                c.literal_len = len(literals[i])
+                c.stage_capacity = int(stage_capacity[i]) if stage_capacity is not None else 0
                 rows = int(col.metas_array()[:, 1].sum()) if c.n_pages else 0
                 if out is not None:
                     if out[i].rows != rows:
@@ -146,13 +181,15 @@ class FilterBatch:
     def enqueue(self):
         ctx = self.ctx
         ctx._keep.append(self)
-        ctx._check(ctx._lib.sb_filter_columns(ctx._h, self._arr, self._n, N.SB_MEM_DEVICE))
+        ctx._check(ctx._lib.sb_filter_columns_var(ctx._h, self._arr, self._n, N.SB_MEM_DEVICE))
         return self.selections
 
 
 def filter_columns(ctx, columns: List[ColumnPages], predicates: Sequence[Predicate], combine="set",
-                   out: Optional[List[Selection]] = None) -> List[Selection]:
-    """Enqueue predicates[i] over columns[i] on ctx's stream.  combine: "set" writes the result,
-    "and" / "or" combine it with what `out[i].bitmap` holds (chain predicates with one call after
-    the other).  `out` re-uses earlier selections' buffers; required for "and" / "or"."""
-    return FilterBatch(ctx, columns, predicates, combine, out).enqueue()
+                   out: Optional[List[Selection]] = None, stage_capacity: Optional[Sequence[int]] = None) -> List[Selection]:
+    """Enqueue predicates[i] over columns[i] on ctx's stream; numeric and binary columns may share
+    a call.  combine: "set" writes the result, "and" / "or" combine it with what `out[i].bitmap`
+    holds (chain predicates with one call after the other).  `out` re-uses earlier selections'
+    buffers; required for "and" / "or".  stage_capacity[i]: the bytes the value blocks of a binary
+    column's LZ4 / Zstd / Snappy pages may inflate to (0 / None: 4 x the column's page bytes)."""
+    return FilterBatch(ctx, columns, predicates, combine, out, stage_capacity).enqueue()
