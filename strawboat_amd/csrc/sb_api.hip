@@ -8,7 +8,7 @@
 
 namespace sb {
 
-void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, uint64_t* col_values_len, const FilterLaunch* flt);
+void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt);
 void launch_filter_plain(sb_ctx* ctx, const FilterCol& f, const uint8_t* values, const uint8_t* validity, uint64_t rows, uint32_t w, uint64_t* count);
 void launch_parse_sizes(sb_ctx* ctx, const DecodeArgs& a, uint64_t* col_values_len);
 void launch_freq_scatter(sb_ctx* ctx, const FreqEntry* entries, uint32_t n, const uint64_t* ex_off, const uint8_t* ex_base);
@@ -105,35 +105,6 @@ StageSlot* acquire_slot(sb_ctx* ctx, size_t need) {
     if (!s.done) (void)hipEventCreateWithFlags(&s.done, hipEventDisableTiming);
     return &s;
 }
-
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-static uint32_t type_width(int32_t t) {
-    switch (t) {
-        case SB_TYPE_INT8:
-        case SB_TYPE_UINT8:
-            return 1;
-        case SB_TYPE_INT16:
-        case SB_TYPE_UINT16:
-            return 2;
-        case SB_TYPE_INT32:
-        case SB_TYPE_UINT32:
-        case SB_TYPE_FLOAT32:
-        case SB_TYPE_BINARY:
-            return 4;
-        case SB_TYPE_INT64:
-        case SB_TYPE_UINT64:
-        case SB_TYPE_FLOAT64:
-        case SB_TYPE_LARGE_BINARY:
-            return 8;
-        case SB_TYPE_INT128:
-            return 16;
-        case SB_TYPE_INT256:
-            return 32;
-    }
-    return 0;
-}
-static bool is_binary_t(int32_t t) { return t == SB_TYPE_BINARY || t == SB_TYPE_LARGE_BINARY; }
 
 static const char* status_text(const Status& s, char* buf, size_t n) {
     const char* kind = s.code == SB_ERR_OUT_OF_SPEC ? "OutOfSpec"
@@ -240,10 +211,20 @@ void sb_ctx_destroy(sb_ctx* ctx) {
 const char* sb_ctx_last_error(sb_ctx* ctx) { return ctx ? ctx->last_error.c_str() : "null context"; }
 void* sb_ctx_stream(sb_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 
-// (filt / sel_out / lits: the call is a filter call — sb_filter_columns[_var] — whose columns end in the filter kernels; sel_out[i]:
-// the caller's `selected`; lits: the literals of the FK_BYTES columns, FilterCol.lit being the offset of each)
-static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, bool sizes_only, const FilterCol* filt = nullptr,
-                                 uint64_t* const* sel_out = nullptr, const std::vector<uint8_t>* lits = nullptr);
+// What kind of call read_columns_impl serves: built at the entry points, read by every step of the call
+struct ReadMode {
+    // sb_read_columns (and the decode of a filter replay) / sb_read_columns_sizes / the Freq second pass, from inside a
+    // synchronize / sb_filter_columns[_var], whose columns end in the filter kernels
+    enum Kind { READ, SIZES, FREQ_PASS, FILTER } kind;
+    const FilterCol* filt = nullptr;             // FILTER: one per column
+    uint64_t* const* sel_out = nullptr;          // ... sel_out[i]: the caller's `selected`
+    const std::vector<uint8_t>* lits = nullptr;  // ... the literals of the FK_BYTES columns, FilterCol.lit being the offset of each
+    bool sizes() const { return kind == SIZES; }
+    bool freq_pass() const { return kind == FREQ_PASS; }
+    bool filter() const { return kind == FILTER; }
+};
+static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, const ReadMode& mode);
+static void update_read_hints(sb_ctx* ctx, uint32_t kinds);   // (next to read_hints, its reader)
 
 // Freq pages (integer/freq.rs:90-127) found by the decode calls of this synchronize interval: their
 // exception blocks are ordinary BLOCK<T>s, so they go through the decoder once more as one-page
@@ -306,9 +287,7 @@ static int32_t freq_second_pass(sb_ctx* ctx) {
     if (batches.empty()) return SB_OK;
     ctx->freq_pass_ran = true;
     for (size_t i = 0; i < ctx->freq_cols.size(); i++) ctx->freq_cols[i].metas = &ctx->freq_metas[i];
-    ctx->in_freq_pass = true;
-    int32_t rc = read_columns_impl(ctx, ctx->freq_cols.data(), ctx->freq_cols.size(), SB_MEM_DEVICE, false);
-    ctx->in_freq_pass = false;
+    int32_t rc = read_columns_impl(ctx, ctx->freq_cols.data(), ctx->freq_cols.size(), SB_MEM_DEVICE, ReadMode{ReadMode::FREQ_PASS});
     if (rc != SB_OK) return rc;
     for (const Batch& b : batches) launch_freq_scatter(ctx, b.d_entries, b.n, b.d_off, b.ex_base);
     hipError_t e = hipMemcpyAsync(ctx->h_status, ctx->d_status, sizeof(Status), hipMemcpyDeviceToHost, ctx->stream);
@@ -325,6 +304,27 @@ static int32_t freq_second_pass(sb_ctx* ctx) {
     return rc;
 }
 
+// the Freq records of the interval point into buffers the caller may reuse: drop them all
+static void clear_freq_logs(sb_ctx* ctx) {
+    for (auto& log : ctx->freq_logs) {
+        log.reserved = 0;
+        (void)hipMemsetAsync(log.dev, 0, 16, ctx->stream);
+    }
+}
+// What the end of an interval and the start of its replay share, once the stream (and the copy stream) is drained and
+// nothing reads the interval's buffers any more
+static void release_interval(sb_ctx* ctx) {
+    for (auto& s : ctx->slots) s.in_flight = false;
+    for (void* p : ctx->stale_host) (void)hipHostFree(p);
+    ctx->stale_host.clear();
+    ctx->copybacks.clear();
+    ctx->pipe_ev_used = 0;
+    for (void* p : ctx->temp_dev) (void)hipFree(p);
+    ctx->temp_dev.clear();
+    ctx->stage_rewind();
+    ctx->filter_tmp.clear();
+}
+
 int32_t sb_ctx_synchronize(sb_ctx* ctx) {
     if (!ctx) return SB_ERR_INVALID;
     (void)hipSetDevice(ctx->device);
@@ -333,34 +333,7 @@ int32_t sb_ctx_synchronize(sb_ctx* ctx) {
     hipError_t e = hipMemcpyAsync(ctx->h_status, ctx->d_status, sizeof(Status), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess) {
-        ctx->kinds_seen |= ctx->h_status->kinds & KIND_ZSTD;
-        // what the LAST interval's read calls met decides what the next ones launch: a context that read Zstd pages once and
-        // LZ4 / plain pages ever since stops paying for the block pipeline's launches (7 kernels, ~40 us of a 0.6 ms call)
-        // (two read intervals in a row without one: a nested reader alternates level calls — no Zstd — and leaf calls)
-        if (ctx->h_status->kinds & KIND_ZSTD) {
-            ctx->zstd_recent = true;
-            ctx->zstd_idle = 0;
-        } else if (ctx->read_calls && ++ctx->zstd_idle >= 2) {
-            ctx->zstd_recent = false;
-        }
-        if (ctx->read_calls) {
-            ctx->qa_idle = (ctx->h_status->kinds & KIND_QUEUE_A) ? 0 : ctx->qa_idle + 1;
-            ctx->tiles_idle = (ctx->h_status->kinds & KIND_TILES) ? 0 : ctx->tiles_idle + 1;
-        }
-        ctx->read_calls = 0;
-        // (three intervals with long pages and no such block before the chain is dropped: a reader that alternates giant-LZ4
-        // columns with long plain ones keeps it; a wrong 2 costs a replay, not a one-workgroup walk)
-        if (ctx->h_status->kinds & KIND_LZ4_GIANT) {
-            ctx->lzg_state = 1;
-            ctx->lzg_idle = 0;
-        } else if (ctx->lzg_long_pages && ctx->lzg_state == 0) {
-            ctx->lzg_state = 2;
-        } else if (ctx->lzg_long_pages && ctx->lzg_state == 1 && ++ctx->lzg_idle >= 3) {
-            ctx->lzg_state = 2;
-        }
-        ctx->lzg_long_pages = false;
-        // (not sticky: what the calls since the last synchronize looked like decides the order of the next call's entropy kernels)
-        if (ctx->h_status->kinds & KIND_ZSTD) ctx->zb_seq_long = (ctx->h_status->kinds & KIND_ZSEQ_LONG) != 0;
+        update_read_hints(ctx, ctx->h_status->kinds);
         // the device only ever sets bits: the word is cleared here so that it describes the calls of ONE interval (the host's
         // kinds_seen keeps what must stay)
         if (ctx->h_status->kinds) (void)hipMemsetAsync(&ctx->d_status->kinds, 0, sizeof ctx->d_status->kinds, ctx->stream);
@@ -371,8 +344,7 @@ int32_t sb_ctx_synchronize(sb_ctx* ctx) {
     // a real error shows again in the replay)
     if (e == hipSuccess && (ctx->h_status->kinds & KIND_REPLAY) && rc == SB_OK && !ctx->in_replay && !ctx->calls.empty()) {
         if (ctx->h_status->code != 0) (void)hipMemsetAsync(ctx->d_status, 0, sizeof(Status), ctx->stream);
-        for (auto& s : ctx->slots) s.in_flight = false;
-        for (auto& sp : ctx->spans) {
+        for (auto& sp : ctx->spans) {   // (recycled, not timed)
             ctx->free_events.push_back(sp.a);
             ctx->free_events.push_back(sp.b);
         }
@@ -387,19 +359,9 @@ int32_t sb_ctx_synchronize(sb_ctx* ctx) {
                 }
             ctx->pending.swap(keep);
         }
-        for (void* p : ctx->stale_host) (void)hipHostFree(p);
-        ctx->stale_host.clear();
         if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);   // (copies of groups that ran: overwritten by the replay's)
-        ctx->copybacks.clear();
-        ctx->pipe_ev_used = 0;
-        for (void* p : ctx->temp_dev) (void)hipFree(p);
-        ctx->temp_dev.clear();
-        ctx->stage_rewind();
-        ctx->filter_tmp.clear();
-        for (auto& log : ctx->freq_logs) {
-            log.reserved = 0;
-            (void)hipMemsetAsync(log.dev, 0, 16, ctx->stream);
-        }
+        release_interval(ctx);
+        clear_freq_logs(ctx);
         ctx->filter_freq = (ctx->h_status->kinds & KIND_FILTER_FREQ) != 0;
         std::vector<sb_ctx::Call> calls;
         calls.swap(ctx->calls);
@@ -409,10 +371,12 @@ int32_t sb_ctx_synchronize(sb_ctx* ctx) {
         ctx->replays++;
         if (ctx->h_status->kinds & KIND_REPLAY_LZG) ctx->lzg_state = 1;
         for (auto& cl : calls) {
-            rc = cl.kind == 3 ? sb_filter_columns_var(ctx, (sb_column_filter_var*)cl.cols, cl.n, cl.mem)
-                 : cl.kind == 2 ? sb_filter_columns(ctx, (sb_column_filter*)cl.cols, cl.n, cl.mem)
-                 : cl.kind  ? sb_write_columns(ctx, (sb_column_write*)cl.cols, cl.n, &cl.opts, cl.mem)
-                            : sb_read_columns(ctx, (sb_column_read*)cl.cols, cl.n, cl.mem);
+            switch (cl.kind) {
+                case sb_ctx::Call::READ: rc = sb_read_columns(ctx, (sb_column_read*)cl.cols, cl.n, cl.mem); break;
+                case sb_ctx::Call::WRITE: rc = sb_write_columns(ctx, (sb_column_write*)cl.cols, cl.n, &cl.opts, cl.mem); break;
+                case sb_ctx::Call::FILTER: rc = sb_filter_columns(ctx, (sb_column_filter*)cl.cols, cl.n, cl.mem); break;
+                case sb_ctx::Call::FILTER_VAR: rc = sb_filter_columns_var(ctx, (sb_column_filter_var*)cl.cols, cl.n, cl.mem); break;
+            }
             if (rc != SB_OK) break;
         }
         ctx->no_hints = saved;
@@ -434,15 +398,10 @@ int32_t sb_ctx_synchronize(sb_ctx* ctx) {
         (void)hipMemsetAsync(ctx->d_status, 0, sizeof(Status), ctx->stream);
     }
     if (rc == SB_OK) rc = freq_second_pass(ctx);
-    if (rc != SB_OK) {
-        // a failed interval: its Freq records point into buffers the caller may reuse — drop them all
-        for (auto& log : ctx->freq_logs) {
-            log.reserved = 0;
-            (void)hipMemsetAsync(log.dev, 0, 16, ctx->stream);
-        }
+    if (rc != SB_OK) {   // a failed interval
+        clear_freq_logs(ctx);
         (void)hipStreamSynchronize(ctx->stream);
     }
-    for (auto& s : ctx->slots) s.in_flight = false;
     for (auto& sp : ctx->spans) {
         float ms = 0;
         if (hipEventElapsedTime(&ms, sp.a, sp.b) == hipSuccess) {
@@ -485,10 +444,7 @@ int32_t sb_ctx_synchronize(sb_ctx* ctx) {
         }
     }
     ctx->pending.clear();
-    ctx->filter_tmp.clear();
     ctx->rescued.clear();
-    for (void* p : ctx->stale_host) (void)hipHostFree(p);   // (the stream is drained: nothing reads them any more)
-    ctx->stale_host.clear();
     {   // SB_MEM_HOST: what was not sent back while the interval ran (all copies on the copy stream, one wait)
         // (the stream exists only in contexts that serve host-memory calls: one more stream in the process changes how the
         // runtime maps streams to hardware queues — C4's side streams lost their overlap, 1.03 -> 1.55 ms per read)
@@ -511,12 +467,8 @@ int32_t sb_ctx_synchronize(sb_ctx* ctx) {
             if (ce != hipSuccess && rc == SB_OK) rc = check_hip(ctx, ce, "copy back");
         }
     }
-    ctx->copybacks.clear();
+    release_interval(ctx);
     ctx->freq_pass_ran = false;
-    ctx->pipe_ev_used = 0;
-    for (void* p : ctx->temp_dev) (void)hipFree(p);
-    ctx->temp_dev.clear();
-    ctx->stage_rewind();
     ctx->sticky = 0;
     return rc;
 }
@@ -566,14 +518,20 @@ uint32_t sb_ctx_profile_read(sb_ctx* ctx, sb_kernel_stat* out, uint32_t cap) {
 }
 
 // ------------------------------------------------------------------------------------ decode
-static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, bool sizes_only, const FilterCol* filt, uint64_t* const* sel_out,
-                                 const std::vector<uint8_t>* lits) {
-    if (!ctx || (!cols && n)) return SB_ERR_INVALID;
-    if (n == 0) return SB_OK;
-    (void)hipSetDevice(ctx->device);
-    hipStream_t s = ctx->stream;
-    uint64_t P = 0, T = 0, max_page_len = 0, max_page_rows = 0, lzg_pages = 0;
+// ---- read_columns_impl, step by step: checks and call shape -> launch hints -> table layout -> host staging -> tables ->
+// pools -> upload -> arguments -> launches -> readbacks.  Every step reads the call's ReadMode.
+
+// What the columns and their page lists decide for the whole call
+struct ReadShape {
+    uint64_t P = 0, T = 0;   // pages, tiles
+    uint64_t max_page_len = 0, max_page_rows = 0, pages_bytes = 0;
+    uint64_t lzg_pages = 0;  // blocks that may go block-parallel: sb_lz4_giant.h
     bool any_binary = false, any_prim = false;
+};
+
+// The checks of every call; fills in cols[i].rows and clears cols[i].values_len
+static int32_t read_shape(sb_ctx* ctx, sb_column_read* cols, uint64_t n, const ReadMode& mode, ReadShape& sh) {
+    ReadShape a;   // (a local: the page loop's sums stay in registers)
     for (uint64_t i = 0; i < n; i++) {
         sb_column_read& c = cols[i];
         if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return ctx->fail(SB_ERR_INVALID, "bad physical_type");
@@ -582,24 +540,25 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
         uint64_t rows = 0;
         for (uint64_t p = 0; p < c.n_pages; p++) {
             rows += c.metas[p].num_values;
-            T += (c.metas[p].num_values + TILE_ROWS - 1) / TILE_ROWS;
-            max_page_len = std::max<uint64_t>(max_page_len, c.metas[p].length);
-            if (c.metas[p].length >= LZG_MIN) lzg_pages += is_binary_t(c.physical_type) ? 2 : 1;   // (blocks that may go block-parallel: sb_lz4_giant.h)
-            max_page_rows = std::max<uint64_t>(max_page_rows, c.metas[p].num_values);
+            a.T += (c.metas[p].num_values + TILE_ROWS - 1) / TILE_ROWS;
+            a.max_page_len = std::max<uint64_t>(a.max_page_len, c.metas[p].length);
+            if (c.metas[p].length >= LZG_MIN) a.lzg_pages += is_binary_t(c.physical_type) ? 2 : 1;
+            a.max_page_rows = std::max<uint64_t>(a.max_page_rows, c.metas[p].num_values);
         }
         c.rows = rows;
         c.values_len = 0;
-        P += c.n_pages;
+        a.P += c.n_pages;
+        a.pages_bytes += c.pages_len;
         if (is_binary_t(c.physical_type))
-            any_binary = true;
+            a.any_binary = true;
         else if (c.physical_type != SB_TYPE_NULL)
-            any_prim = true;
-        if (!sizes_only && c.physical_type != SB_TYPE_NULL && rows) {
+            a.any_prim = true;
+        if (!mode.sizes() && c.physical_type != SB_TYPE_NULL && rows) {
             const uint32_t w = type_width(c.physical_type);
             if (!c.values) return ctx->fail(SB_ERR_INVALID, "values is null");
-            if (c.is_nullable && !filt && (!c.validity || c.validity_capacity < (rows + 31) / 32 * 4))
+            if (c.is_nullable && !mode.filter() && (!c.validity || c.validity_capacity < (rows + 31) / 32 * 4))
                 return ctx->fail(SB_ERR_INVALID, "validity buffer missing or smaller than 4*ceil(rows/32) bytes");
-            if (is_binary_t(c.physical_type) && filt) {
+            if (is_binary_t(c.physical_type) && mode.filter()) {
                 // (a filter call writes no offsets; `values` is the column's share of the staging area)
             } else if (is_binary_t(c.physical_type)) {
                 if (!c.offsets || c.offsets_capacity < (rows + 1) * w)
@@ -612,100 +571,218 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
             }
         }
     }
-    if (P >= 0x7FFFFFFFull || T >= 0x7FFFFFFFull) return ctx->fail(SB_ERR_INVALID, "too many pages in one call");
+    sh = a;
+    if (sh.P >= 0x7FFFFFFFull || sh.T >= 0x7FFFFFFFull) return ctx->fail(SB_ERR_INVALID, "too many pages in one call");
+    return SB_OK;
+}
 
-    // ---- table layout
-    uint64_t pages_bytes = 0;
-    for (uint64_t i = 0; i < n; i++) pages_bytes += cols[i].pages_len;
-    const size_t zs_extra = (size_t)std::min<uint64_t>(1u << 20, pages_bytes / 256 + 64);
+// ---- launch hints: what a call launches, sizes or leaves out because of what the context's earlier intervals met.  The
+// state has one writer (update_read_hints, from sb_ctx_synchronize) and one reader (read_hints, once per call); a page that
+// needed a kernel which was left out stays undone and the interval is replayed with no_hints set (KIND_REPLAY).
+struct ReadHints {
+    bool zb_on = false;         // the block-parallel Zstd pipeline is launched
+    bool zs_on = false;         // ... and the frame scan of long multi-frame Zstd buffers (sb_decode.hip)
+    bool zrec_wanted = false;   // the lane-per-frame record arena
+    uint32_t zb_skipped = 0;    // DecodeArgs.zb_skipped
+    uint32_t read_skips = 0;    // DecodeArgs.read_skips
+    enum { LZG_NONE, LZG_SKIPPED, LZG_POOL } lzg = LZG_NONE;   // no page long enough / left out on the hint / pool sized and grids set
+    bool lzg_launch = false;    // launch_lzg launches the chain
+};
+
+// The producer: `kinds` is Status.kinds of the interval that a synchronize has just closed
+static void update_read_hints(sb_ctx* ctx, uint32_t kinds) {
+    ctx->kinds_seen |= kinds & KIND_ZSTD;
+    // what the LAST interval's read calls met decides what the next ones launch: a context that read Zstd pages once and
+    // LZ4 / plain pages ever since stops paying for the block pipeline's launches (7 kernels, ~40 us of a 0.6 ms call)
+    // (two read intervals in a row without one: a nested reader alternates level calls — no Zstd — and leaf calls)
+    if (kinds & KIND_ZSTD) {
+        ctx->zstd_recent = true;
+        ctx->zstd_idle = 0;
+    } else if (ctx->read_calls && ++ctx->zstd_idle >= 2) {
+        ctx->zstd_recent = false;
+    }
+    if (ctx->read_calls) {
+        ctx->qa_idle = (kinds & KIND_QUEUE_A) ? 0 : ctx->qa_idle + 1;
+        ctx->tiles_idle = (kinds & KIND_TILES) ? 0 : ctx->tiles_idle + 1;
+    }
+    ctx->read_calls = 0;
+    // (three intervals with long pages and no such block before the chain is dropped: a reader that alternates giant-LZ4
+    // columns with long plain ones keeps it; a wrong 2 costs a replay, not a one-workgroup walk)
+    if (kinds & KIND_LZ4_GIANT) {
+        ctx->lzg_state = 1;
+        ctx->lzg_idle = 0;
+    } else if (ctx->lzg_long_pages && ctx->lzg_state == 0) {
+        ctx->lzg_state = 2;
+    } else if (ctx->lzg_long_pages && ctx->lzg_state == 1 && ++ctx->lzg_idle >= 3) {
+        ctx->lzg_state = 2;
+    }
+    ctx->lzg_long_pages = false;
+    // (not sticky: what the calls since the last synchronize looked like decides the order of the next call's entropy kernels)
+    if (kinds & KIND_ZSTD) ctx->zb_seq_long = (kinds & KIND_ZSEQ_LONG) != 0;
+}
+
+// The consumer.  Only a READ call consults every hint and counts as a call of its interval: a sizes call launches what
+// values_len depends on, the Freq second pass runs inside a synchronize (not a call of the next interval), a filter call
+// consults no launch hint and leaves the read calls' hint state alone.
+static ReadHints read_hints(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh) {
+    ReadHints h;
+    // the block-parallel Zstd pipeline: in a context whose last read intervals met Zstd buffers
+    h.zb_on = ctx->zb_mode == 1 || (ctx->zb_mode == 2 && (ctx->zstd_recent || ctx->no_hints || mode.filter()));
+    if (!mode.freq_pass() && !mode.filter()) ctx->read_calls++;
+    // long multi-frame Zstd buffers (a one-page column written by this library): frames found by a scan (sb_decode.hip)
+    h.zs_on = h.zb_on && !mode.sizes() && sh.max_page_len >= (1u << 20);
+    h.zb_skipped = (!h.zb_on && ctx->zb_mode == 2 && !mode.sizes() && sh.max_page_len >= (1u << 20)) ? 1u : 0u;
+    // (the lane-per-frame record arena only for calls that can hold >= 4 x INFLATE_POOL frames of 16 KiB, and only in a
+    // context that has met Zstd pages: LZ4 / plain / Dict-only readers never pay for it)
+    h.zrec_wanted = sh.pages_bytes >= (48ull << 20) && (ctx->zb_mode == 1 || ctx->zstd_recent);
+    // the inflate kernels of queue A / the tile kernel of primitives are left out when the last read interval queued nothing
+    // for them (C2: four launches that found nothing to do, ~30 us of a 0.9 ms read); k_plan asks for the replay otherwise
+    if (!ctx->no_hints && mode.kind == ReadMode::READ) {
+        if (ctx->qa_idle >= 2) h.read_skips |= RSKIP_QUEUE_A;
+        if (ctx->tiles_idle >= 2) h.read_skips |= RSKIP_TILES;
+    }
+    // LZ4 blocks of megabytes (a one-page column): block-parallel (sb_lz4_giant.h) — tables and entries in a pool of their own
+    if (!mode.sizes() && sh.max_page_len >= LZG_MIN) {
+        const bool none_met = ctx->lzg_state == 2 && !ctx->no_hints;   // the context's last intervals met no LZ4 block of megabytes
+        // none met: no pool, no launches; k_inflate_lz4_big leaves such a block alone and asks for the replay (it used to
+        // walk it with one workgroup: 0.8 s for 68 MB)
+        h.lzg = none_met && !mode.filter() ? ReadHints::LZG_SKIPPED : ReadHints::LZG_POOL;
+        // OPEN POINT, kept as it was found: a filter call in such a context sizes the pool and sets the grids, is NOT marked
+        // lzg_skipped, and launches nothing all the same (launch_lzg used to read lzg_state for itself)
+        h.lzg_launch = h.lzg == ReadHints::LZG_POOL && !none_met;
+        // (noted here, before anything of the call can fail: a call that fails later — tables, staging, page_offsets, pools,
+        // upload, or the giant-LZ4 pool itself — has still shown its long pages; it used to be noted after all of those)
+        if (!mode.filter()) ctx->lzg_long_pages = true;
+    }
+    return h;
+}
+
+// Where the call's tables sit, on the device (ctx->tables) and — up to `upload` — in the staging slot, whose next n words
+// receive the results.  A pure function of shape, hints and mode.
+struct ReadLayout {
+    size_t cols, tasks, fcols, lits, upload, descs, tiles, jobs_a, jobs_b, jobs_z, counts, vlen, zb_counts, zb_frames, zs, rle, bpg, total;
+    size_t job_cap;        // queue entries: 2 per page + room for the frames of Zstd buffers that are several frames (one entry per frame)
+    bool want_z;           // queue Z (calls with binary columns that produce values): Zstd payloads known to k_parse, entropy stages with queue A's
+    uint64_t zs_seg_cap;
+    uint32_t rle_parts;    // long RLE pages: few pages of many rows are shared by several workgroups each (sb_decode.hip: k_rle_sums)
+};
+static ReadLayout read_layout(uint64_t n, const ReadShape& sh, const ReadHints& h, const ReadMode& mode) {
+    ReadLayout L;
+    const uint64_t P = sh.P;
+    const size_t zs_extra = (size_t)std::min<uint64_t>(1u << 20, sh.pages_bytes / 256 + 64);
     size_t off = 0;
-    const size_t o_cols = off;
+    L.cols = off;
     off = align_up(off + n * sizeof(ColDesc), 64);
-    const size_t o_tasks = off;
+    L.tasks = off;
     off = align_up(off + P * sizeof(PageTask), 64);
-    const size_t o_fcols = off;
-    if (filt) off = align_up(off + n * sizeof(FilterCol), 64);
-    const size_t o_lits = off;
-    if (lits) off = align_up(off + lits->size(), 64);
-    const size_t upload_bytes = off;
-    const size_t o_descs = off;
+    L.fcols = off;
+    if (mode.filter()) off = align_up(off + n * sizeof(FilterCol), 64);
+    L.lits = off;
+    if (mode.lits) off = align_up(off + mode.lits->size(), 64);
+    L.upload = off;
+    L.descs = off;
     off = align_up(off + P * sizeof(PageDesc), 64);
-    const size_t o_tiles = off;
-    off = align_up(off + T * sizeof(TileTask), 64);
-    // queue entries: 2 per page + room for the frames of Zstd buffers that are several frames (one entry per frame)
-    const size_t job_cap = 2 * P + zs_extra;
-    const size_t o_jobs_a = off;
-    off = align_up(off + job_cap * sizeof(InflateJob), 64);
-    const size_t o_jobs_b = off;
-    off = align_up(off + job_cap * sizeof(InflateJob), 64);
-    // queue Z (calls with binary columns that produce values): Zstd payloads known to k_parse, entropy stages with queue A's
-    const bool want_z = any_binary && !sizes_only;
-    const size_t o_jobs_z = off;
-    if (want_z) off = align_up(off + job_cap * sizeof(InflateJob), 64);
-    const size_t o_counts = off;
+    L.tiles = off;
+    off = align_up(off + sh.T * sizeof(TileTask), 64);
+    L.job_cap = 2 * P + zs_extra;
+    L.jobs_a = off;
+    off = align_up(off + L.job_cap * sizeof(InflateJob), 64);
+    L.jobs_b = off;
+    off = align_up(off + L.job_cap * sizeof(InflateJob), 64);
+    L.want_z = sh.any_binary && !mode.sizes();
+    L.jobs_z = off;
+    if (L.want_z) off = align_up(off + L.job_cap * sizeof(InflateJob), 64);
+    L.counts = off;
     off = align_up(off + 64, 64);
-    const size_t o_vlen = off;
+    L.vlen = off;
     off = align_up(off + n * sizeof(uint64_t), 64);
     // the block-parallel Zstd pipeline: frames + counters here, blocks / literals / records in pools of their own
-    // (a filter call consults no launch hint and leaves the read calls' hint state alone)
-    const bool zb_on = ctx->zb_mode == 1 || (ctx->zb_mode == 2 && (ctx->zstd_recent || ctx->no_hints || filt));
-    if (!ctx->in_freq_pass && !filt) ctx->read_calls++;   // (the Freq second pass runs inside a synchronize: not a call of the next interval)
-    const size_t o_zb_counts = off;
-    if (zb_on) off = align_up(off + 64, 64);
-    const size_t o_zb_frames = off;
-    if (zb_on) off = align_up(off + job_cap * sizeof(ZbFrame), 64);
-    // long multi-frame Zstd buffers (a one-page column written by this library): frames found by a scan (sb_decode.hip)
-    const bool zs_on = zb_on && !sizes_only && max_page_len >= (1u << 20);
-    const uint64_t zs_seg_cap = zs_on ? pages_bytes / 16384 + 2 * P + 64 : 0;
-    const size_t o_zs = off;
-    if (zs_on) off = align_up(off + 256 + zs_seg_cap * 32, 64);
-    // long RLE pages: few pages of many rows are shared by several workgroups each (sb_decode.hip: k_rle_sums)
-    const uint32_t rle_parts = (!sizes_only && max_page_rows >= (1u << 18) && P > 0 && P <= 1024) ? (uint32_t)std::min<uint64_t>(256, 2048 / P) : 1u;
-    const size_t o_rle = off;
-    if (rle_parts > 1) off = align_up(off + P * rle_parts * sizeof(uint64_t), 64);
-    const size_t o_bpg = off;
-    if (rle_parts > 1) off = align_up(off + P * sizeof(uint32_t), 64);
-    if (!ensure(ctx, ctx->tables, off)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(tables) failed");
+    L.zb_counts = off;
+    if (h.zb_on) off = align_up(off + 64, 64);
+    L.zb_frames = off;
+    if (h.zb_on) off = align_up(off + L.job_cap * sizeof(ZbFrame), 64);
+    L.zs_seg_cap = h.zs_on ? sh.pages_bytes / 16384 + 2 * P + 64 : 0;
+    L.zs = off;
+    if (h.zs_on) off = align_up(off + 256 + L.zs_seg_cap * 32, 64);
+    L.rle_parts = (!mode.sizes() && sh.max_page_rows >= (1u << 18) && P > 0 && P <= 1024) ? (uint32_t)std::min<uint64_t>(256, 2048 / P) : 1u;
+    L.rle = off;
+    if (L.rle_parts > 1) off = align_up(off + P * L.rle_parts * sizeof(uint64_t), 64);
+    L.bpg = off;
+    if (L.rle_parts > 1) off = align_up(off + P * sizeof(uint32_t), 64);
+    L.total = off;
+    return L;
+}
 
-    StageSlot* slot = acquire_slot(ctx, upload_bytes + n * sizeof(uint64_t));
-    if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
-    ColDesc* hc = (ColDesc*)(slot->host + o_cols);
-    PageTask* ht = (PageTask*)(slot->host + o_tasks);
-
-    // SB_MEM_HOST: stage inputs/outputs in device temporaries
-    std::vector<uint8_t*> dev_pages(n, nullptr), dev_values(n, nullptr), dev_validity(n, nullptr), dev_offsets(n, nullptr);
-    if (mem == SB_MEM_HOST) {
-        for (uint64_t i = 0; i < n; i++) {
-            sb_column_read& c = cols[i];
-            auto alloc = [&](size_t bytes, uint8_t** out) -> bool {
-                *out = nullptr;
-                if (!bytes) return true;
-                return (*out = ctx->stage_alloc(bytes)) != nullptr;
-            };
-            if (!alloc(c.pages_len, &dev_pages[i])) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(pages) failed");
-            if (c.pages_len &&
-                hipMemcpyAsync(dev_pages[i], c.pages, c.pages_len, hipMemcpyHostToDevice, s) != hipSuccess)
-                return ctx->fail(SB_ERR_EXTERNAL, "H2D pages failed");
-            if (!sizes_only) {
-                if (!alloc(c.values_capacity, &dev_values[i]) || !alloc(c.is_nullable ? c.validity_capacity : 0, &dev_validity[i]) ||
-                    !alloc(is_binary_t(c.physical_type) ? c.offsets_capacity : 0, &dev_offsets[i]))
-                    return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(outputs) failed");
-            }
+// The device buffers of each column: the caller's own (SB_MEM_DEVICE), or, for SB_MEM_HOST, device temporaries: the pages
+// are staged over PCIe here, the outputs are copied back once they are written (queue_copybacks)
+struct ReadBufs {
+    const uint8_t* pages;
+    uint8_t *values, *validity, *offsets;
+};
+static int32_t stage_read_cols(sb_ctx* ctx, hipStream_t s, const sb_column_read* cols, uint64_t n, int32_t mem, const ReadMode& mode,
+                               std::vector<ReadBufs>& bufs) {
+    bufs.assign(n, ReadBufs{});
+    if (mem != SB_MEM_HOST) {
+        for (uint64_t i = 0; i < n; i++) bufs[i] = {cols[i].pages, (uint8_t*)cols[i].values, cols[i].validity, (uint8_t*)cols[i].offsets};
+        return SB_OK;
+    }
+    auto alloc = [&](size_t bytes, uint8_t** out) -> bool {
+        *out = nullptr;
+        if (!bytes) return true;
+        return (*out = ctx->stage_alloc(bytes)) != nullptr;
+    };
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_column_read& c = cols[i];
+        ReadBufs& b = bufs[i];
+        uint8_t* pages = nullptr;
+        if (!alloc(c.pages_len, &pages)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(pages) failed");
+        b.pages = pages;
+        if (c.pages_len && hipMemcpyAsync(pages, c.pages, c.pages_len, hipMemcpyHostToDevice, s) != hipSuccess)
+            return ctx->fail(SB_ERR_EXTERNAL, "H2D pages failed");
+        if (mode.sizes()) continue;
+        if (!alloc(c.values_capacity, &b.values) || !alloc(c.is_nullable ? c.validity_capacity : 0, &b.validity) ||
+            !alloc(is_binary_t(c.physical_type) ? c.offsets_capacity : 0, &b.offsets))
+            return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(outputs) failed");
+    }
+    return SB_OK;
+}
+// ... and what goes back from them (SB_MEM_HOST calls that produce values; sb_ctx_synchronize and the groups of
+// sb_read_columns issue the copies)
+static void queue_copybacks(sb_ctx* ctx, sb_column_read* cols, uint64_t n, const std::vector<ReadBufs>& bufs) {
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_column_read& c = cols[i];
+        const ReadBufs& b = bufs[i];
+        const uint32_t w = type_width(c.physical_type);
+        if (c.is_nullable && c.rows) ctx->copybacks.push_back({c.validity, b.validity, (size_t)((c.rows + 7) / 8)});
+        if (is_binary_t(c.physical_type)) {
+            ctx->copybacks.push_back({c.offsets, b.offsets, (size_t)((c.rows + 1) * w)});
+            ctx->copybacks.push_back({c.values, b.values, (size_t)c.values_capacity, &cols[i].values_len});  // (set just before, from `pending`)
+        } else if (c.physical_type == SB_TYPE_BOOLEAN) {
+            ctx->copybacks.push_back({c.values, b.values, (size_t)((c.rows + 7) / 8)});
+        } else if (c.physical_type != SB_TYPE_NULL) {
+            ctx->copybacks.push_back({c.values, b.values, (size_t)(c.rows * w)});
         }
     }
+}
 
+// The call's tables in the staging slot: ColDesc per column, PageTask per page (with the page's share of the scratch
+// buffer, which is grown to fit), and for a filter call its FilterCol per column and the literals
+static int32_t fill_read_tables(sb_ctx* ctx, uint8_t* host, const ReadLayout& L, const sb_column_read* cols, uint64_t n,
+                                const std::vector<ReadBufs>& bufs, const ReadMode& mode) {
+    ColDesc* hc = (ColDesc*)(host + L.cols);
+    PageTask* ht = (PageTask*)(host + L.tasks);
     size_t scratch_off = 0;
     uint64_t page_i = 0, tile_i = 0;
     for (uint64_t i = 0; i < n; i++) {
         const sb_column_read& c = cols[i];
         ColDesc& d = hc[i];
         memset(&d, 0, sizeof d);
-        d.pages = mem == SB_MEM_HOST ? dev_pages[i] : c.pages;
+        d.pages = bufs[i].pages;
         d.pages_len = c.pages_len;
-        d.values = mem == SB_MEM_HOST ? dev_values[i] : (uint8_t*)c.values;
-        d.values_cap = sizes_only ? ~0ull : c.values_capacity;
-        d.validity = mem == SB_MEM_HOST ? dev_validity[i] : c.validity;
-        d.offsets = mem == SB_MEM_HOST ? dev_offsets[i] : (uint8_t*)c.offsets;
+        d.values = bufs[i].values;
+        d.values_cap = mode.sizes() ? ~0ull : c.values_capacity;
+        d.validity = bufs[i].validity;
+        d.offsets = bufs[i].offsets;
         d.offsets_cap = c.offsets_capacity;
         d.rows = c.rows;
         d.ptype = c.physical_type;
@@ -719,211 +796,226 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
             if (c.metas[p].num_values % 32) d.bits_aligned = 0;
         for (uint64_t p = 0; p < c.n_pages; p++, page_i++) {
             PageTask& t = ht[page_i];
-            const uint64_t N = c.metas[p].num_values, L = c.metas[p].length;
+            const uint64_t N = c.metas[p].num_values, len = c.metas[p].length;
             const uint64_t ntiles = (N + TILE_ROWS - 1) / TILE_ROWS;
             t.in_off = c.page_offsets ? c.page_offsets[p] : in_off;
-            t.length = L;
-            if (c.page_offsets && t.in_off + L > c.pages_len) return ctx->fail(SB_ERR_IO, "page_offsets + length exceeds pages_len");
+            t.length = len;
+            if (c.page_offsets && t.in_off + len > c.pages_len) return ctx->fail(SB_ERR_IO, "page_offsets + length exceeds pages_len");
             t.num_values = N;
             t.out_row = out_row;
             t.col = (uint32_t)i;
             t.first_tile = (uint32_t)tile_i;
             t.aux_off = scratch_off;
-            scratch_off += align_up((L / 4 + N / 128 + 4 * ntiles + 16) * 4, 16);   // (4 * ntiles: tile_k0 / tile_base + tile_bytes, and the u64 tile totals of a long binary Dict page)
-            if (filt && is_binary_t(c.physical_type)) scratch_off += filter_bin_table_words(L) * 4;   // (a bit per dictionary entry: sb_filter_bin.h)
+            scratch_off += align_up((len / 4 + N / 128 + 4 * ntiles + 16) * 4, 16);   // (4 * ntiles: tile_k0 / tile_base + tile_bytes, and the u64 tile totals of a long binary Dict page)
+            if (mode.filter() && is_binary_t(c.physical_type)) scratch_off += filter_bin_table_words(len) * 4;   // (a bit per dictionary entry: sb_filter_bin.h)
             t.infl_off = scratch_off;
             scratch_off += align_up((N + 1) * 8 + 16, 16);
-            in_off += L;
+            in_off += len;
             out_row += N;
             tile_i += ntiles;
         }
         if (in_off > c.pages_len) return ctx->fail(SB_ERR_IO, "sum of PageMeta.length exceeds pages_len");
     }
-    if (filt) {
-        FilterCol* hfc = (FilterCol*)(slot->host + o_fcols);
-        memcpy(hfc, filt, n * sizeof(FilterCol));
-        if (lits && !lits->empty()) memcpy(slot->host + o_lits, lits->data(), lits->size());
+    if (mode.filter()) {
+        FilterCol* hfc = (FilterCol*)(host + L.fcols);
+        memcpy(hfc, mode.filt, n * sizeof(FilterCol));
+        if (mode.lits && !mode.lits->empty()) memcpy(host + L.lits, mode.lits->data(), mode.lits->size());
         for (uint64_t i = 0; i < n; i++)
-            if (hfc[i].kind == FK_BYTES) hfc[i].lit += (uint64_t)(uintptr_t)(ctx->tables.p + o_lits);
+            if (hfc[i].kind == FK_BYTES) hfc[i].lit += (uint64_t)(uintptr_t)(ctx->tables.p + L.lits);
     }
     if (!ensure(ctx, ctx->scratch, scratch_off + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(scratch) failed");
+    return SB_OK;
+}
+
+// The Zstd decoders' areas: the per-wave literal buffers of the inflate pool (every call), the block pipeline's pools (sized
+// per call; all zero: not launched) and the lane-per-frame record arena
+struct ZbCaps {
+    uint64_t block = 0, lit = 0, rec = 0;
+};
+static int32_t size_zb_pools(sb_ctx* ctx, const sb_column_read* cols, uint64_t n, const ReadMode& mode, const ReadShape& sh,
+                             const ReadHints& h, size_t job_cap, ZbCaps& zb) {
     // the inflate pool's per-wave areas: a literal buffer of one block, and (calls with at least 4 queue entries per pool
     // wave: batches) the arena of pre-decoded Zstd sequences
     if (!ensure(ctx, ctx->zlit, (size_t)INFLATE_POOL * (128 * 1024 + 64))) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(zlit) failed");
-    // (the lane-per-frame record arena only for calls that can hold >= 4 x INFLATE_POOL frames of 16 KiB, and only in a
-    // context that has met Zstd pages: LZ4 / plain / Dict-only readers never pay for it)
-    const bool zrec_wanted = pages_bytes >= (48ull << 20) && (ctx->zb_mode == 1 || ctx->zstd_recent);
-    uint64_t zb_block_cap = 0, zb_lit_cap = 0, zb_rec_cap = 0;
-    if (zb_on) {
+    if (h.zb_on) {
         // blocks: libzstd's are 128 KiB of content (sub-blocks of a few KiB when it splits them); literals: at most the
         // output (a Huffman stream expands <= 8 x); records: one per >= 3 output bytes, in practice one per >= 2 stream bytes.
         // A frame that does not fit is decoded by the one-wave path.
+        const uint64_t pages_bytes = sh.pages_bytes;
         uint64_t out_bytes = 0;
         for (uint64_t i = 0; i < n; i++) {
             const uint64_t rows = cols[i].rows;
-            out_bytes += sizes_only ? rows * 8 + 64 : cols[i].values_capacity + (is_binary_t(cols[i].physical_type) ? cols[i].offsets_capacity : 0) + rows * 8 + 64;
+            out_bytes += mode.sizes() ? rows * 8 + 64 : cols[i].values_capacity + (is_binary_t(cols[i].physical_type) ? cols[i].offsets_capacity : 0) + rows * 8 + 64;
         }
         // Sized from the OUTPUT, not from the stream: a 128 KiB block of repetitive data is a few hundred stream bytes, RLE
         // literals expand 1 byte to 128 KiB, RLE / repeat-mode tables spend well under a byte per sequence.
-        zb_block_cap = std::min<uint64_t>(std::max<uint64_t>(pages_bytes / 2048, out_bytes / 8192) + 2 * job_cap + 64, 1u << 23);
+        zb.block = std::min<uint64_t>(std::max<uint64_t>(pages_bytes / 2048, out_bytes / 8192) + 2 * job_cap + 64, 1u << 23);
         // ... with a ceiling all the same: a C2-shaped read (4 GB out of 250 MB of pages) asked for ~20 GB.  Literals at most
         // 8 x the pages + 256 MB (what Huffman streams expand to; blocks of RLE literals beyond that overflow the pool), records
         // at most 2^28 (3 GB; a cap by the stream's bytes is wrong: small integers in repeat mode are several sequences per stream
         // byte); what does not fit goes to the frame-serial decoder (ZbCounts, tests/test_gpu_zstd_blocks.py).
-        zb_lit_cap = std::min<uint64_t>(out_bytes, 8 * pages_bytes + (256ull << 20)) + 16 * zb_block_cap + (1u << 16);
-        zb_rec_cap = std::min<uint64_t>(std::min<uint64_t>(4 * pages_bytes, out_bytes / 3), 1ull << 28) + (1u << 14);
+        zb.lit = std::min<uint64_t>(out_bytes, 8 * pages_bytes + (256ull << 20)) + 16 * zb.block + (1u << 16);
+        zb.rec = std::min<uint64_t>(std::min<uint64_t>(4 * pages_bytes, out_bytes / 3), 1ull << 28) + (1u << 14);
         if (ctx->zb_pool_div > 1) {
-            zb_block_cap = std::max<uint64_t>(zb_block_cap / ctx->zb_pool_div, 4);
-            zb_lit_cap = std::max<uint64_t>(zb_lit_cap / ctx->zb_pool_div, 4096);
-            zb_rec_cap = std::max<uint64_t>(zb_rec_cap / ctx->zb_pool_div, 64);
+            zb.block = std::max<uint64_t>(zb.block / ctx->zb_pool_div, 4);
+            zb.lit = std::max<uint64_t>(zb.lit / ctx->zb_pool_div, 4096);
+            zb.rec = std::max<uint64_t>(zb.rec / ctx->zb_pool_div, 64);
         }
-        if (!ensure(ctx, ctx->zb_blocks, zb_block_cap * (sizeof(ZbBlock) + 16)) || !ensure(ctx, ctx->zb_lit, zb_lit_cap + 64) ||
-            !ensure(ctx, ctx->zb_rec, zb_rec_cap * 12 + 16))
+        if (!ensure(ctx, ctx->zb_blocks, zb.block * (sizeof(ZbBlock) + 16)) || !ensure(ctx, ctx->zb_lit, zb.lit + 64) ||
+            !ensure(ctx, ctx->zb_rec, zb.rec * 12 + 16))
             return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(zstd block pools) failed");
     }
-    if (zrec_wanted && !ensure(ctx, ctx->zrec, (size_t)INFLATE_POOL * ZREC_PER_WAVE * 8))
+    if (h.zrec_wanted && !ensure(ctx, ctx->zrec, (size_t)INFLATE_POOL * ZREC_PER_WAVE * 8))
         return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(zrec) failed");
+    return SB_OK;
+}
 
+// The pool of the giant-LZ4 chain and the grids of its kernels (all zero: not in this call — also when the pool cannot be had)
+struct LzgPool {
+    LzgArgs lzg;
+    uint32_t chunks = 0, wins = 0, rounds = 0, jobs = 0;
+};
+static LzgPool size_lzg_pool(sb_ctx* ctx, const sb_column_read* cols, uint64_t n, const ReadShape& sh, const ReadHints& h) {
+    LzgPool g;
+    if (h.lzg != ReadHints::LZG_POOL) return g;
+    // the pool holds what the (at most LZG_JOBS) picked blocks need: 16 bytes per compressed byte and 4 per output byte of
+    // the largest candidate pages — not of every page of the call (128 plain 1 M-row columns pinned 27 GB that way)
+    uint64_t out_max = 0;
+    std::vector<std::pair<uint64_t, uint64_t>> cand;   // (page bytes, output bytes of its column's share)
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t o = std::max<uint64_t>(cols[i].values_capacity, (cols[i].rows + 1) * 8);
+        out_max = std::max(out_max, o);
+        for (uint64_t k = 0; k < cols[i].n_pages; k++)
+            if (cols[i].metas[k].length >= LZG_MIN) cand.push_back({cols[i].metas[k].length, o + (is_binary_t(cols[i].physical_type) ? (cols[i].rows + 1) * 8 : 0)});
+    }
+    std::sort(cand.begin(), cand.end(), [](const std::pair<uint64_t, uint64_t>& x, const std::pair<uint64_t, uint64_t>& y) { return x.first + x.second > y.first + y.second; });
+    uint64_t pages_sel = 0, out_sel = 0;
+    for (size_t q = 0; q < cand.size() && q < 2 * LZG_JOBS; q++) {   // (a page holds up to two blocks: queue A and queue B)
+        pages_sel += cand[q].first;
+        out_sel += cand[q].second;
+    }
+    const uint64_t pool = pages_sel * 16 + pages_sel / 512 + LZG_JOBS * (uint64_t)LZG_LITS * 16 + out_sel * 4 + out_sel / 2048 + (LZG_JOBS + 1) * (6 * 256 + (uint64_t)LZG_CH * 8 + 4096) +
+                          LZG_JOBS * sizeof(LzgJob) + 1024;
+    if (!ensure(ctx, ctx->lzg_pool, pool)) return g;
+    g.lzg.jobs = (LzgJob*)ctx->lzg_pool.p;
+    g.lzg.njobs = (uint32_t*)(ctx->lzg_pool.p + LZG_JOBS * sizeof(LzgJob));
+    const uint64_t head = (LZG_JOBS * sizeof(LzgJob) + 64 + 255) & ~255ull;
+    g.lzg.pool = ctx->lzg_pool.p + head;
+    g.lzg.pool_bytes = pool - head;
+    g.lzg.st = ctx->d_status;
+    g.chunks = (uint32_t)((sh.max_page_len + LZG_CH - 1) / LZG_CH);
+    g.jobs = (uint32_t)std::min<uint64_t>(sh.lzg_pages, LZG_JOBS);
+    g.wins = (uint32_t)std::min<uint64_t>((out_max + LZG_WIN - 1) / LZG_WIN, 0x7FFFFFFFu);
+    uint32_t bits = 1;
+    while ((1ull << bits) < out_max + 1 && bits < 32) bits++;
+    g.rounds = bits / 4 + 2;   // (a launch of k_lzg_jump is LZG_PASSES passes; a chain halves per pass at least — in practice a launch or two)
+    return g;
+}
+
+// Room in the interval's Freq log for every page of this call to be a Freq page (null: the call logs none)
+static int32_t reserve_freq_log(sb_ctx* ctx, hipStream_t s, const ReadMode& mode, uint64_t P, sb_ctx::FreqLog*& log) {
+    log = nullptr;
+    if (mode.sizes() || mode.freq_pass() || !P) return SB_OK;
+    log = ctx->freq_logs.empty() ? nullptr : &ctx->freq_logs.back();
+    if (!log || (uint64_t)log->reserved + P > log->cap) {
+        sb_ctx::FreqLog nl;
+        nl.cap = (uint32_t)std::max<uint64_t>(8192, 2 * P);
+        if (hipMalloc((void**)&nl.dev, 16 + (size_t)nl.cap * sizeof(FreqEntry)) != hipSuccess)
+            return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(freq log) failed");
+        (void)hipMemsetAsync(nl.dev, 0, 16, s);
+        ctx->freq_logs.push_back(nl);
+        log = &ctx->freq_logs.back();
+    }
+    log->reserved += (uint32_t)P;
+    return SB_OK;
+}
+
+// The kernels' arguments, from layout, hints and pools (what a call does not use keeps DecodeArgs' defaults)
+static DecodeArgs fill_decode_args(sb_ctx* ctx, uint64_t n, const ReadMode& mode, const ReadShape& sh, const ReadHints& h, const ReadLayout& L,
+                                   const ZbCaps& zb, const LzgPool& g, const sb_ctx::FreqLog* log) {
     uint8_t* tb = ctx->tables.p;
-    hipError_t e = hipMemcpyAsync(tb, slot->host, upload_bytes, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return check_hip(ctx, e, "table upload");
-
     DecodeArgs a;
     a.zlit = ctx->zlit.p;
-    a.zrec = zrec_wanted ? (uint64_t*)ctx->zrec.p : nullptr;
-    a.cols = (const ColDesc*)(tb + o_cols);
-    a.tasks = (const PageTask*)(tb + o_tasks);
-    a.descs = (PageDesc*)(tb + o_descs);
-    a.tiles = (TileTask*)(tb + o_tiles);
+    if (h.zrec_wanted) a.zrec = (uint64_t*)ctx->zrec.p;
+    a.cols = (const ColDesc*)(tb + L.cols);
+    a.tasks = (const PageTask*)(tb + L.tasks);
+    a.descs = (PageDesc*)(tb + L.descs);
+    a.tiles = (TileTask*)(tb + L.tiles);
     a.scratch = ctx->scratch.p;
     a.status = ctx->d_status;
-    a.jobs_a = (InflateJob*)(tb + o_jobs_a);
-    a.jobs_b = (InflateJob*)(tb + o_jobs_b);
-    a.jobs_z = want_z ? (InflateJob*)(tb + o_jobs_z) : nullptr;
-    a.job_counts = (uint32_t*)(tb + o_counts);
-    a.n_pages = (uint32_t)P;
+    a.jobs_a = (InflateJob*)(tb + L.jobs_a);
+    a.jobs_b = (InflateJob*)(tb + L.jobs_b);
+    if (L.want_z) a.jobs_z = (InflateJob*)(tb + L.jobs_z);
+    a.job_counts = (uint32_t*)(tb + L.counts);
+    a.job_cap_a = a.job_cap_b = (uint32_t)L.job_cap;
+    a.n_pages = (uint32_t)sh.P;
     a.n_cols = (uint32_t)n;
-    a.n_tiles = (uint32_t)T;
+    a.n_tiles = (uint32_t)sh.T;
+    a.sizes_only = mode.sizes() ? 1u : 0u;
+    a.defer_payloads = (!mode.sizes() && sh.any_binary) ? 1u : 0u;
+    a.no_freq = mode.freq_pass() ? 1u : 0u;
     // LZ4 blocks for the workgroup decoder: in a call with few blocks every block of 16 KiB and more (a lone wave's latency
     // is what the call waits for); in a call that fills the one-wave pool several times over only the blocks of 128 KiB and
     // more (64 KiB pages of incompressible values — the reference's bench shape — stay with the one-wave copy path)
-    const uint32_t big_min = 2 * P >= 4096 ? 2 * LZ4_BIG_MIN : LZ4_BIG_MIN / 4;
-    a.lz4_big_min = max_page_len >= big_min ? big_min : 0xFFFFFFFFu;
-    // LZ4 blocks of megabytes (a one-page column): block-parallel (sb_lz4_giant.h) — tables and entries in a pool of their own
-    memset(&a.lzg, 0, sizeof a.lzg);
-    a.lzg_chunks = a.lzg_wins = a.lzg_rounds = a.lzg_jobs = 0;
-    a.lzg_skipped = 0;
-    // the inflate kernels of queue A / the tile kernel of primitives are left out when the last read interval queued nothing
-    // for them (C2: four launches that found nothing to do, ~30 us of a 0.9 ms read); k_plan asks for the replay otherwise
-    a.read_skips = 0;
-    if (!ctx->no_hints && !ctx->in_freq_pass && !sizes_only && !filt) {
-        if (ctx->qa_idle >= 2) a.read_skips |= RSKIP_QUEUE_A;
-        if (ctx->tiles_idle >= 2) a.read_skips |= RSKIP_TILES;
+    const uint32_t big_min = 2 * sh.P >= 4096 ? 2 * LZ4_BIG_MIN : LZ4_BIG_MIN / 4;
+    a.lz4_big_min = sh.max_page_len >= big_min ? big_min : 0xFFFFFFFFu;
+    a.read_skips = h.read_skips;
+    a.zb_skipped = h.zb_skipped;
+    a.lzg_skipped = h.lzg == ReadHints::LZG_SKIPPED ? 1u : 0u;
+    a.lzg = g.lzg;
+    a.lzg_chunks = g.chunks;
+    a.lzg_wins = g.wins;
+    a.lzg_rounds = g.rounds;
+    a.lzg_jobs = g.jobs;
+    a.rle_parts = L.rle_parts;
+    if (L.rle_parts > 1) {
+        a.rle_sums = (uint64_t*)(tb + L.rle);
+        a.bp_guess = (uint32_t*)(tb + L.bpg);
     }
-    a.zb_skipped = (!zb_on && ctx->zb_mode == 2 && !sizes_only && max_page_len >= (1u << 20)) ? 1u : 0u;
-    if (!sizes_only && max_page_len >= LZG_MIN && ctx->lzg_state == 2 && !ctx->no_hints && !filt) {
-        // the context's last intervals met no LZ4 block of megabytes: no pool, no launches; k_inflate_lz4_big leaves such
-        // a block alone and asks for the replay (it used to walk it with one workgroup: 0.8 s for 68 MB)
-        a.lzg_skipped = 1;
-        ctx->lzg_long_pages = true;
-    } else if (!sizes_only && max_page_len >= LZG_MIN) {
-        // the pool holds what the (at most LZG_JOBS) picked blocks need: 16 bytes per compressed byte and 4 per output byte of
-        // the largest candidate pages — not of every page of the call (128 plain 1 M-row columns pinned 27 GB that way)
-        uint64_t out_max = 0;
-        std::vector<std::pair<uint64_t, uint64_t>> cand;   // (page bytes, output bytes of its column's share)
-        for (uint64_t i = 0; i < n; i++) {
-            const uint64_t o = std::max<uint64_t>(cols[i].values_capacity, (cols[i].rows + 1) * 8);
-            out_max = std::max(out_max, o);
-            for (uint64_t k = 0; k < cols[i].n_pages; k++)
-                if (cols[i].metas[k].length >= LZG_MIN) cand.push_back({cols[i].metas[k].length, o + (is_binary_t(cols[i].physical_type) ? (cols[i].rows + 1) * 8 : 0)});
-        }
-        std::sort(cand.begin(), cand.end(), [](const std::pair<uint64_t, uint64_t>& x, const std::pair<uint64_t, uint64_t>& y) { return x.first + x.second > y.first + y.second; });
-        uint64_t pages_sel = 0, out_sel = 0;
-        for (size_t q = 0; q < cand.size() && q < 2 * LZG_JOBS; q++) {   // (a page holds up to two blocks: queue A and queue B)
-            pages_sel += cand[q].first;
-            out_sel += cand[q].second;
-        }
-        const uint64_t pool = pages_sel * 16 + pages_sel / 512 + LZG_JOBS * (uint64_t)LZG_LITS * 16 + out_sel * 4 + out_sel / 2048 + (LZG_JOBS + 1) * (6 * 256 + (uint64_t)LZG_CH * 8 + 4096) +
-                              LZG_JOBS * sizeof(LzgJob) + 1024;
-        if (ensure(ctx, ctx->lzg_pool, pool)) {
-            a.lzg.jobs = (LzgJob*)ctx->lzg_pool.p;
-            a.lzg.njobs = (uint32_t*)(ctx->lzg_pool.p + LZG_JOBS * sizeof(LzgJob));
-            const uint64_t head = (LZG_JOBS * sizeof(LzgJob) + 64 + 255) & ~255ull;
-            a.lzg.pool = ctx->lzg_pool.p + head;
-            a.lzg.pool_bytes = pool - head;
-            a.lzg.st = ctx->d_status;
-            a.lzg_chunks = (uint32_t)((max_page_len + LZG_CH - 1) / LZG_CH);
-            a.lzg_jobs = (uint32_t)std::min<uint64_t>(lzg_pages, LZG_JOBS);
-            if (!filt) ctx->lzg_long_pages = true;
-            a.lzg_wins = (uint32_t)std::min<uint64_t>((out_max + LZG_WIN - 1) / LZG_WIN, 0x7FFFFFFFu);
-            uint32_t bits = 1;
-            while ((1ull << bits) < out_max + 1 && bits < 32) bits++;
-            a.lzg_rounds = bits / 4 + 2;   // (a launch of k_lzg_jump is LZG_PASSES passes; a chain halves per pass at least — in practice a launch or two)
-        }
+    if (h.zs_on) {
+        a.zs_hdr = (uint32_t*)(tb + L.zs);
+        a.zs_segs = (uint32_t*)(tb + L.zs + 256);
+        a.zs_seg_cap = (uint32_t)std::min<uint64_t>(L.zs_seg_cap, 0x7FFFFFFFu);
     }
-    a.rle_parts = rle_parts;
-    a.rle_sums = rle_parts > 1 ? (uint64_t*)(tb + o_rle) : nullptr;
-    a.bp_guess = rle_parts > 1 ? (uint32_t*)(tb + o_bpg) : nullptr;
-    a.zs_hdr = a.zs_segs = nullptr;
-    a.zs_seg_cap = 0;
-    if (zs_on) {
-        a.zs_hdr = (uint32_t*)(tb + o_zs);
-        a.zs_segs = (uint32_t*)(tb + o_zs + 256);
-        a.zs_seg_cap = (uint32_t)std::min<uint64_t>(zs_seg_cap, 0x7FFFFFFFu);
-        (void)hipMemsetAsync(tb + o_zs, 0, 256 + zs_seg_cap * 32, s);
-    }
-    memset(&a.zb, 0, sizeof a.zb);
-    if (zb_on) {
+    if (h.zb_on) {
         a.zb.blocks = (ZbBlock*)ctx->zb_blocks.p;
-        a.zb.lists = (uint32_t*)(ctx->zb_blocks.p + zb_block_cap * sizeof(ZbBlock));
-        a.zb.frames = (ZbFrame*)(tb + o_zb_frames);
+        a.zb.lists = (uint32_t*)(ctx->zb_blocks.p + zb.block * sizeof(ZbBlock));
+        a.zb.frames = (ZbFrame*)(tb + L.zb_frames);
         a.zb.lit = ctx->zb_lit.p;
         a.zb.rec = (uint64_t*)ctx->zb_rec.p;
-        a.zb.counters = (uint32_t*)(tb + o_zb_counts);
-        a.zb.block_cap = (uint32_t)zb_block_cap;
-        a.zb.frame_cap = (uint32_t)std::min<uint64_t>(job_cap, 0x7FFFFFFFu);
-        a.zb.lit_cap = zb_lit_cap;
-        a.zb.rec_cap = zb_rec_cap;
+        a.zb.counters = (uint32_t*)(tb + L.zb_counts);
+        a.zb.block_cap = (uint32_t)zb.block;
+        a.zb.frame_cap = (uint32_t)std::min<uint64_t>(L.job_cap, 0x7FFFFFFFu);
+        a.zb.lit_cap = zb.lit;
+        a.zb.rec_cap = zb.rec;
         a.zb.min_csize = ctx->zb_min_csize;
         a.zb.wg_exec = ctx->zb_wg_exec;
         a.zb.stats = ctx->zb_stats;
         a.zb.kinds = &ctx->d_status->kinds;
     }
-    a.freq_log = nullptr;
-    a.freq_count = nullptr;
-    a.freq_cap = 0;
-    a.no_freq = ctx->in_freq_pass ? 1u : 0u;
-    if (!sizes_only && !ctx->in_freq_pass && P) {  // room for every page of this call to be a Freq page
-        sb_ctx::FreqLog* log = ctx->freq_logs.empty() ? nullptr : &ctx->freq_logs.back();
-        if (!log || (uint64_t)log->reserved + P > log->cap) {
-            sb_ctx::FreqLog nl;
-            nl.cap = (uint32_t)std::max<uint64_t>(8192, 2 * P);
-            if (hipMalloc((void**)&nl.dev, 16 + (size_t)nl.cap * sizeof(FreqEntry)) != hipSuccess)
-                return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(freq log) failed");
-            (void)hipMemsetAsync(nl.dev, 0, 16, s);
-            ctx->freq_logs.push_back(nl);
-            log = &ctx->freq_logs.back();
-        }
-        log->reserved += (uint32_t)P;
+    if (log) {
         a.freq_count = (uint32_t*)log->dev;
         a.freq_log = (FreqEntry*)(log->dev + 16);
         a.freq_cap = log->cap;
     }
-    uint64_t* d_vlen = (uint64_t*)(tb + o_vlen);
+    return a;
+}
 
-    a.sizes_only = sizes_only ? 1u : 0u;
-    a.defer_payloads = (!sizes_only && any_binary) ? 1u : 0u;
-    a.job_cap_a = a.job_cap_b = (uint32_t)job_cap;
-    if (sizes_only) {
-        if (P) launch_parse_sizes(ctx, a, d_vlen);
-    } else if (filt) {
-        FilterLaunch fl{(const FilterCol*)(tb + o_fcols), d_vlen, false, false, false, false};
+// The launches of the three kinds of call (hc: the call's columns, host copy)
+static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, const ReadHints& h, const ReadLayout& L, const DecodeArgs& a,
+                        const ColDesc* hc, uint64_t n) {
+    const hipStream_t s = ctx->stream;
+    uint64_t* d_vlen = (uint64_t*)(ctx->tables.p + L.vlen);   // values_len / bits set per column
+    if (mode.sizes()) {
+        if (sh.P) launch_parse_sizes(ctx, a, d_vlen);
+    } else if (mode.filter()) {
+        FilterLaunch fl{(const FilterCol*)(ctx->tables.p + L.fcols), d_vlen, false, false, false, false};
         for (uint64_t i = 0; i < n; i++) {
-            const bool null_op = filt[i].op >= SB_PRED_IS_NULL;
-            (null_op ? fl.any_null : filt[i].kind == FK_BYTES ? fl.any_bin : fl.any_cmp) = true;
-            if (filt[i].combine == SB_SEL_SET) fl.any_set = true;
+            const bool null_op = mode.filt[i].op >= SB_PRED_IS_NULL;
+            (null_op ? fl.any_null : mode.filt[i].kind == FK_BYTES ? fl.any_bin : fl.any_cmp) = true;
+            if (mode.filt[i].combine == SB_SEL_SET) fl.any_set = true;
         }
-        if (P) launch_decode(ctx, a, any_binary, any_prim, d_vlen, &fl);
+        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, &fl);
     } else {
         // bitmaps are assembled with OR at page seams: start from zero
         for (uint64_t i = 0; i < n; i++) {
@@ -932,19 +1024,23 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
             if (d.nullable && d.validity && d.rows) (void)hipMemsetAsync(d.validity, 0, (d.rows + 31) / 32 * 4, s);
             if (d.ptype == SB_TYPE_BOOLEAN && d.values && d.rows) (void)hipMemsetAsync(d.values, 0, (d.rows + 31) / 32 * 4, s);
         }
-        if (P) launch_decode(ctx, a, any_binary, any_prim, d_vlen, nullptr);
+        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr);
     }
-    e = hipGetLastError();
-    if (e != hipSuccess) return check_hip(ctx, e, "decode launch");
+}
 
-    // results: values_len per column
-    uint8_t* hv = slot->host + upload_bytes;
-    if (P && (any_binary || sizes_only || filt)) {   // (a filter call: the bits set per column)
-        e = hipMemcpyAsync(hv, d_vlen, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+// Results: values_len per column (a filter call: the bits set per column) into the slot's n words behind the upload;
+// sb_ctx_synchronize hands them to the callers' structs
+static int32_t queue_read_results(sb_ctx* ctx, StageSlot* slot, const ReadLayout& L, const ReadMode& mode, const ReadShape& sh,
+                                  sb_column_read* cols, uint64_t n) {
+    const hipStream_t s = ctx->stream;
+    const ColDesc* hc = (const ColDesc*)(slot->host + L.cols);
+    uint8_t* hv = slot->host + L.upload;
+    if (sh.P && (sh.any_binary || mode.sizes() || mode.filter())) {
+        hipError_t e = hipMemcpyAsync(hv, ctx->tables.p + L.vlen, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
         if (e != hipSuccess) return check_hip(ctx, e, "values_len readback");
     } else {
         for (uint64_t i = 0; i < n; i++) {  // fixed-width columns: rows * width (booleans: bitmap bytes)
-            const uint64_t v = !P ? 0 : hc[i].ptype == SB_TYPE_BOOLEAN ? (hc[i].rows + 7) / 8 : hc[i].rows * hc[i].width;
+            const uint64_t v = !sh.P ? 0 : hc[i].ptype == SB_TYPE_BOOLEAN ? (hc[i].rows + 7) / 8 : hc[i].rows * hc[i].width;
             memcpy(hv + i * sizeof(uint64_t), &v, sizeof v);
         }
     }
@@ -952,25 +1048,46 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
     slot->in_flight = true;
     for (uint64_t i = 0; i < n; i++) {
         Pending pd;
-        pd.kind = filt ? Pending::FILTER_COL : Pending::READ_COL;
-        pd.user = filt ? (void*)sel_out[i] : (void*)&cols[i];
+        pd.kind = mode.filter() ? Pending::FILTER_COL : Pending::READ_COL;
+        pd.user = mode.filter() ? (void*)mode.sel_out[i] : (void*)&cols[i];
         pd.host = hv + i * sizeof(uint64_t);
         pd.n = 0;
         ctx->pending.push_back(pd);
-        if (mem == SB_MEM_HOST && !sizes_only) {
-            const sb_column_read& c = cols[i];
-            const uint32_t w = type_width(c.physical_type);
-            if (c.is_nullable && c.rows) ctx->copybacks.push_back({c.validity, dev_validity[i], (size_t)((c.rows + 7) / 8)});
-            if (is_binary_t(c.physical_type)) {
-                ctx->copybacks.push_back({c.offsets, dev_offsets[i], (size_t)((c.rows + 1) * w)});
-                ctx->copybacks.push_back({c.values, dev_values[i], (size_t)c.values_capacity, &cols[i].values_len});  // (set just before, from `pending`)
-            } else if (c.physical_type == SB_TYPE_BOOLEAN) {
-                ctx->copybacks.push_back({c.values, dev_values[i], (size_t)((c.rows + 7) / 8)});
-            } else if (c.physical_type != SB_TYPE_NULL) {
-                ctx->copybacks.push_back({c.values, dev_values[i], (size_t)(c.rows * w)});
-            }
-        }
     }
+    return SB_OK;
+}
+
+static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, const ReadMode& mode) {
+    if (!ctx || (!cols && n)) return SB_ERR_INVALID;
+    if (n == 0) return SB_OK;
+    (void)hipSetDevice(ctx->device);
+    const hipStream_t s = ctx->stream;
+    ReadShape sh;
+    int32_t rc = read_shape(ctx, cols, n, mode, sh);
+    if (rc != SB_OK) return rc;
+    const ReadHints h = read_hints(ctx, mode, sh);
+    const ReadLayout L = read_layout(n, sh, h, mode);
+    if (!ensure(ctx, ctx->tables, L.total)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(tables) failed");
+    StageSlot* slot = acquire_slot(ctx, L.upload + n * sizeof(uint64_t));
+    if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
+    std::vector<ReadBufs> bufs;
+    if ((rc = stage_read_cols(ctx, s, cols, n, mem, mode, bufs)) != SB_OK) return rc;
+    if ((rc = fill_read_tables(ctx, slot->host, L, cols, n, bufs, mode)) != SB_OK) return rc;
+    ZbCaps zb;
+    if ((rc = size_zb_pools(ctx, cols, n, mode, sh, h, L.job_cap, zb)) != SB_OK) return rc;
+    uint8_t* tb = ctx->tables.p;
+    hipError_t e = hipMemcpyAsync(tb, slot->host, L.upload, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return check_hip(ctx, e, "table upload");
+    const LzgPool lzg = size_lzg_pool(ctx, cols, n, sh, h);
+    if (h.zs_on) (void)hipMemsetAsync(tb + L.zs, 0, 256 + L.zs_seg_cap * 32, s);
+    sb_ctx::FreqLog* log = nullptr;
+    if ((rc = reserve_freq_log(ctx, s, mode, sh.P, log)) != SB_OK) return rc;
+    const DecodeArgs a = fill_decode_args(ctx, n, mode, sh, h, L, zb, lzg, log);
+    launch_read(ctx, mode, sh, h, L, a, (const ColDesc*)(slot->host + L.cols), n);
+    e = hipGetLastError();
+    if (e != hipSuccess) return check_hip(ctx, e, "decode launch");
+    if ((rc = queue_read_results(ctx, slot, L, mode, sh, cols, n)) != SB_OK) return rc;
+    if (mem == SB_MEM_HOST && !mode.sizes()) queue_copybacks(ctx, cols, n, bufs);
     return SB_OK;
 }
 
@@ -992,12 +1109,12 @@ int32_t sb_read_columns(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t m
     }
     hipStream_t cs = groups > 1 ? ctx->copy_stream_get() : nullptr;
     if (!cs) {
-        rc = read_columns_impl(ctx, cols, n, mem, false);
+        rc = read_columns_impl(ctx, cols, n, mem, ReadMode{ReadMode::READ});
     } else {
         const uint64_t per = (n + groups - 1) / groups;
         for (uint64_t g0 = 0; g0 < n && rc == SB_OK; g0 += per) {
             const size_t cb0 = ctx->copybacks.size();
-            rc = read_columns_impl(ctx, cols + g0, std::min<uint64_t>(per, n - g0), mem, false);
+            rc = read_columns_impl(ctx, cols + g0, std::min<uint64_t>(per, n - g0), mem, ReadMode{ReadMode::READ});
             if (rc != SB_OK) break;
             hipEvent_t ev = ctx->next_pipe_event();
             if (!ev || hipEventRecord(ev, ctx->stream) != hipSuccess || hipStreamWaitEvent(cs, ev, 0) != hipSuccess) continue;   // (copied at the synchronize)
@@ -1008,7 +1125,7 @@ int32_t sb_read_columns(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t m
             }
         }
     }
-    if (rc == SB_OK && ctx && n && !ctx->in_replay) ctx->calls.push_back(sb_ctx::Call{0, cols, n, sb_write_options{}, mem});
+    if (rc == SB_OK && ctx && n && !ctx->in_replay) ctx->calls.push_back(sb_ctx::Call{sb_ctx::Call::READ, cols, n, sb_write_options{}, mem});
     return rc;
 }
 
@@ -1020,6 +1137,20 @@ static bool filter_comparable(int32_t t) {
 // The replay of an interval in which a filter call met a primitive Freq page (KIND_FILTER_FREQ): the numeric comparison
 // columns are decoded like a read — values and validity into the staging area, the exceptions of Freq pages by the second
 // pass, which needs the host and so cannot run inside the enqueue-only call — and compared from there.
+// The pages of a filter column as a read column (outputs: none yet)
+static sb_column_read read_col_of(const sb_column_filter_var& u) {
+    sb_column_read r;
+    memset(&r, 0, sizeof r);
+    r.physical_type = u.physical_type;
+    r.is_nullable = u.is_nullable;
+    r.pages = u.pages;
+    r.pages_len = u.pages_len;
+    r.metas = u.metas;
+    r.n_pages = u.n_pages;
+    r.page_offsets = u.page_offsets;
+    return r;
+}
+
 static int32_t filter_columns_decoded(sb_ctx* ctx, sb_column_filter_var* const* users, const FilterCol* hf, uint64_t* const* sel_out, uint64_t m) {
     hipStream_t s = ctx->stream;
     ctx->filter_tmp.emplace_back(m);
@@ -1035,21 +1166,13 @@ static int32_t filter_columns_decoded(sb_ctx* ctx, sb_column_filter_var* const* 
     if (!ensure(ctx, ctx->filter_stage, total + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
     for (uint64_t i = 0; i < m; i++) {
         const sb_column_filter_var& u = *users[i];
-        sb_column_read& r = rr[i];
-        memset(&r, 0, sizeof r);
-        r.physical_type = u.physical_type;
-        r.is_nullable = u.is_nullable;
-        r.pages = u.pages;
-        r.pages_len = u.pages_len;
-        r.metas = u.metas;
-        r.n_pages = u.n_pages;
-        r.page_offsets = u.page_offsets;
+        sb_column_read& r = rr[i] = read_col_of(u);
         r.values = ctx->filter_stage.p + o_val[i];
         r.values_capacity = u.rows * type_width(u.physical_type);
         r.validity = ctx->filter_stage.p + o_bits[i];
         r.validity_capacity = (u.rows + 31) / 32 * 4;
     }
-    int32_t rc = read_columns_impl(ctx, rr.data(), m, SB_MEM_DEVICE, false);
+    int32_t rc = read_columns_impl(ctx, rr.data(), m, SB_MEM_DEVICE, ReadMode{ReadMode::READ});
     if (rc != SB_OK) return rc;
     if (hipStreamSynchronize(s) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "filter replay: synchronize failed");
     rc = freq_second_pass(ctx);
@@ -1199,22 +1322,15 @@ static int32_t filter_impl(sb_ctx* ctx, const sb_column_filter_var* cols, uint64
     for (uint64_t i = 0; i < n; i++) {
         const sb_column_filter_var& c = *users[i];
         const bool null_op = c.op == SB_PRED_IS_NULL || c.op == SB_PRED_IS_NOT_NULL;
-        sb_column_read& r = rc_cols[i];
-        memset(&r, 0, sizeof r);
-        r.physical_type = null_op ? SB_TYPE_NULL : c.physical_type;   // (no page body is parsed, queued or planned for a null test)
-        r.is_nullable = c.is_nullable;
-        r.pages = c.pages;
-        r.pages_len = c.pages_len;
-        r.metas = c.metas;
-        r.n_pages = c.n_pages;
-        r.page_offsets = c.page_offsets;
+        sb_column_read& r = rc_cols[i] = read_col_of(c);
+        if (null_op) r.physical_type = SB_TYPE_NULL;   // (no page body is parsed, queued or planned for a null test)
         if (!null_op) {
             r.values = ctx->filter_stage.p + so;
             r.values_capacity = is_binary_t(c.physical_type) ? c.stage_capacity : c.rows * type_width(c.physical_type);
             so += align_up(r.values_capacity, 64);
         }
     }
-    return read_columns_impl(ctx, rc_cols.data(), n, SB_MEM_DEVICE, false, hf.data(), sel_out.data(), &lits);
+    return read_columns_impl(ctx, rc_cols.data(), n, SB_MEM_DEVICE, ReadMode{ReadMode::FILTER, hf.data(), sel_out.data(), &lits});
 }
 
 int32_t sb_filter_columns_var(sb_ctx* ctx, sb_column_filter_var* cols, uint64_t n, int32_t mem) {
@@ -1227,7 +1343,7 @@ int32_t sb_filter_columns_var(sb_ctx* ctx, sb_column_filter_var* cols, uint64_t 
     std::vector<uint64_t*> results(n);
     for (uint64_t i = 0; i < n; i++) results[i] = &cols[i].rows;   // { rows, selected }
     const int32_t rc = filter_impl(ctx, cols, results.data(), n);
-    if (rc == SB_OK && !ctx->in_replay) ctx->calls.push_back(sb_ctx::Call{3, cols, n, sb_write_options{}, mem});
+    if (rc == SB_OK && !ctx->in_replay) ctx->calls.push_back(sb_ctx::Call{sb_ctx::Call::FILTER_VAR, cols, n, sb_write_options{}, mem});
     return rc;
 }
 
@@ -1267,12 +1383,12 @@ int32_t sb_filter_columns(sb_ctx* ctx, sb_column_filter* cols, uint64_t n, int32
         results[i] = &c.rows;
     }
     const int32_t rc = filter_impl(ctx, v.data(), results.data(), n);
-    if (rc == SB_OK && !ctx->in_replay) ctx->calls.push_back(sb_ctx::Call{2, cols, n, sb_write_options{}, mem});
+    if (rc == SB_OK && !ctx->in_replay) ctx->calls.push_back(sb_ctx::Call{sb_ctx::Call::FILTER, cols, n, sb_write_options{}, mem});
     return rc;
 }
 
 int32_t sb_read_columns_sizes(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem) {
-    int32_t rc = read_columns_impl(ctx, cols, n, mem, true);
+    int32_t rc = read_columns_impl(ctx, cols, n, mem, ReadMode{ReadMode::SIZES});
     if (rc != SB_OK) return rc;
     return sb_ctx_synchronize(ctx);
 }

@@ -173,19 +173,19 @@ struct ZbFrame {
     uint32_t wg;            // executed by zb_exec_wg (many short sequences) instead of zb_exec
     const uint8_t* base;    // the queue entry's buffer
 };
-struct ZbPools {
-    ZbBlock* blocks;
-    ZbFrame* frames;
-    uint8_t* lit;
-    uint64_t* rec;          // 12 bytes per sequence: literal length, match length, offset value (rec_pos counts sequences)
-    uint32_t* counters;     // [0] blocks, [1] frames, [4..5] literal bytes, [6..7] records, [8..11] blocks with sequences per size class
-    uint32_t* lists;        // zb_hdr: the blocks with sequences, by size class (4 x block_cap indices)
-    uint32_t block_cap, frame_cap;
-    uint64_t lit_cap, rec_cap;
-    uint32_t min_csize;     // frames shorter than this stay with the one-wave / lane-per-frame paths
-    uint32_t wg_exec;       // 0: every frame through the wave executor (SB_ZSTD_BLOCKS_WG=0)
-    unsigned long long* stats;   // totals of the context: [0] frames decoded, [1] frames handed back, [2] blocks, [3] sequences
-    uint32_t* kinds;             // Status.kinds of the call
+struct ZbPools {             // (the defaults: the pipeline is not launched)
+    ZbBlock* blocks = nullptr;
+    ZbFrame* frames = nullptr;
+    uint8_t* lit = nullptr;
+    uint64_t* rec = nullptr;          // 12 bytes per sequence: literal length, match length, offset value (rec_pos counts sequences)
+    uint32_t* counters = nullptr;     // [0] blocks, [1] frames, [4..5] literal bytes, [6..7] records, [8..11] blocks with sequences per size class
+    uint32_t* lists = nullptr;        // zb_hdr: the blocks with sequences, by size class (4 x block_cap indices)
+    uint32_t block_cap = 0, frame_cap = 0;
+    uint64_t lit_cap = 0, rec_cap = 0;
+    uint32_t min_csize = 0;     // frames shorter than this stay with the one-wave / lane-per-frame paths
+    uint32_t wg_exec = 0;       // 0: every frame through the wave executor (SB_ZSTD_BLOCKS_WG=0)
+    unsigned long long* stats = nullptr;   // totals of the context: [0] frames decoded, [1] frames handed back, [2] blocks, [3] sequences
+    uint32_t* kinds = nullptr;             // Status.kinds of the call
 };
 
 
@@ -216,62 +216,64 @@ struct LzgJob {
     uint32_t nlits, pad0;
 };
 struct LzgArgs {
-    LzgJob* jobs;           // LZG_JOBS
-    uint32_t* njobs;
-    uint8_t* pool;
-    uint64_t pool_bytes;
-    Status* st;
+    LzgJob* jobs = nullptr;           // LZG_JOBS
+    uint32_t* njobs = nullptr;
+    uint8_t* pool = nullptr;
+    uint64_t pool_bytes = 0;
+    Status* st = nullptr;
 };
 
 
 struct DecodeArgs {
-    const ColDesc* cols;
-    const PageTask* tasks;
-    PageDesc* descs;
-    TileTask* tiles;
-    uint8_t* scratch;
-    Status* status;
-    InflateJob* jobs_a;  // capacity job_cap_a
-    InflateJob* jobs_b;  // capacity job_cap_b
+    const ColDesc* cols = nullptr;
+    const PageTask* tasks = nullptr;
+    PageDesc* descs = nullptr;
+    TileTask* tiles = nullptr;
+    uint8_t* scratch = nullptr;
+    Status* status = nullptr;
+    InflateJob* jobs_a = nullptr;  // capacity job_cap_a
+    InflateJob* jobs_b = nullptr;  // capacity job_cap_b
     // queue Z (calls with binary columns): the Zstd payloads nothing in the planning steps waits for — Basic pages of
     // primitives (absolute dst) and the VALUE blocks of Basic binary pages, whose place in the column's values buffer is only
     // known after k_colscan (JOB_REL: dst is an offset from the page's value base).  k_parse fills it, so the block-parallel
     // Zstd pipeline runs its entropy stages for queue A and queue Z in ONE pass, before k_plan; the frames of queue Z are
     // executed after k_colscan.  null: no such queue in this call.
-    InflateJob* jobs_z;
-    uint32_t* job_counts;  // [0] = queue A, [1] = queue B, [2] tiles, [3] planned pages, [4] page-level RLE, [5] / [6] workgroups of k_parse / k_colscan that are done, [8] / [9] / [11] lengths of A / B / Z when complete, [10] = queue Z, [12] = binary Dict pages whose tile totals k_plan left to k_bin_tile_sums
-    uint8_t* zlit;         // Zstd literal buffers, one per inflate wave
-    uint64_t* zrec;        // Zstd sequence records, one arena per inflate wave (k_inflate's lane-per-frame pre-decode)
-    uint32_t n_pages;
-    uint32_t n_cols;
-    uint32_t n_tiles;
-    FreqEntry* freq_log;   // Freq pages found by k_parse (shared by the calls of one synchronize interval)
-    uint32_t* freq_count;
-    uint32_t freq_cap;
-    uint32_t no_freq;      // second pass: an exceptions block never holds a Freq block (freq.rs:78-79)
-    uint32_t sizes_only;   // sb_read_columns_sizes: only what values_len depends on is inflated (nested index blocks)
-    uint32_t defer_payloads;  // the call has binary columns (queue B runs): Basic payloads nothing waits for go there too
-    uint32_t job_cap_a, job_cap_b;  // entries of the two job queues (2 * n_pages + room for the frames of split Zstd buffers)
-    uint32_t lz4_big_min;  // LZ4 blocks of at least this many compressed bytes go to k_inflate_lz4_big (0xFFFFFFFF: the call has no page that long)
+    InflateJob* jobs_z = nullptr;
+    uint32_t* job_counts = nullptr;  // [0] = queue A, [1] = queue B, [2] tiles, [3] planned pages, [4] page-level RLE, [5] / [6] workgroups of k_parse / k_colscan that are done, [8] / [9] / [11] lengths of A / B / Z when complete, [10] = queue Z, [12] = binary Dict pages whose tile totals k_plan left to k_bin_tile_sums
+    uint8_t* zlit = nullptr;         // Zstd literal buffers, one per inflate wave
+    uint64_t* zrec = nullptr;        // Zstd sequence records, one arena per inflate wave (k_inflate's lane-per-frame pre-decode)
+    uint32_t n_pages = 0;
+    uint32_t n_cols = 0;
+    uint32_t n_tiles = 0;
+    FreqEntry* freq_log = nullptr;   // Freq pages found by k_parse (shared by the calls of one synchronize interval)
+    uint32_t* freq_count = nullptr;
+    uint32_t freq_cap = 0;
+    uint32_t no_freq = 0;      // second pass: an exceptions block never holds a Freq block (freq.rs:78-79)
+    uint32_t sizes_only = 0;   // sb_read_columns_sizes: only what values_len depends on is inflated (nested index blocks)
+    uint32_t defer_payloads = 0;  // the call has binary columns (queue B runs): Basic payloads nothing waits for go there too
+    uint32_t job_cap_a = 0, job_cap_b = 0;  // entries of the two job queues (2 * n_pages + room for the frames of split Zstd buffers)
+    uint32_t lz4_big_min = 0xFFFFFFFFu;  // LZ4 blocks of at least this many compressed bytes go to k_inflate_lz4_big (0xFFFFFFFF: the call has no page that long)
     ZbPools zb;            // block-parallel Zstd pipeline (zb.blocks == nullptr: not launched for this call)
     // frame split of LONG multi-frame Zstd buffers (k_zsplit_scan / k_zsplit_chain; null: every buffer is walked by one lane):
     // zs_hdr[0] = entries listed, [1] = segment records handed out, [16 + 2 i], [17 + 2 i] = (queue entry, first record) of
     // listed entry i; zs_segs: records of 8 words (count | 7 positions of the frame magic inside a 16 KiB segment)
-    uint32_t* zs_hdr;
-    uint32_t* zs_segs;
-    uint32_t zs_seg_cap;
+    uint32_t* zs_hdr = nullptr;
+    uint32_t* zs_segs = nullptr;
+    uint32_t zs_seg_cap = 0;
     // long RLE pages (a call with few pages of >= 2^18 rows): `rle_parts` workgroups per page, rle_sums[page * parts + part]
-    uint32_t rle_parts;
-    uint64_t* rle_sums;
+    uint32_t rle_parts = 0;
+    uint64_t* rle_sums = nullptr;
     // long bit-packed pages (the same calls): bp_guess[page] = blocks from the first on that share its width (k_bp_guess)
-    uint32_t* bp_guess;
+    uint32_t* bp_guess = nullptr;
     // LZ4 blocks of LZG_MIN compressed bytes and more, block-parallel (sb_lz4_giant.h); lzg.jobs == nullptr: not in this call
     LzgArgs lzg;
-    uint32_t lzg_chunks, lzg_wins, lzg_rounds, lzg_jobs;   // grid sizes: the longest page / the largest output of the call / pages long enough
-    uint32_t zb_skipped;    // the block-parallel Zstd pipeline was left out on a hint (the context's last intervals read no Zstd buffer): a Zstd buffer of a megabyte or more asks for the replay instead of going frame by frame through the one-wave decoder (20 ms for a 96 MB page against 1.3)
-    uint32_t read_skips;    // RSKIP_* bits: kernels left out because the context's last read interval had no work for them (k_plan asks for the replay when this call has)
-    uint32_t lzg_skipped;   // the call has pages long enough but the context's last intervals met no such block: the chain is not launched, a block that shows up after all asks for a replay (KIND_REPLAY)
+    uint32_t lzg_chunks = 0, lzg_wins = 0, lzg_rounds = 0, lzg_jobs = 0;   // grid sizes: the longest page / the largest output of the call / pages long enough
+    uint32_t zb_skipped = 0;    // the block-parallel Zstd pipeline was left out on a hint (the context's last intervals read no Zstd buffer): a Zstd buffer of a megabyte or more asks for the replay instead of going frame by frame through the one-wave decoder (20 ms for a 96 MB page against 1.3)
+    uint32_t read_skips = 0;    // RSKIP_* bits: kernels left out because the context's last read interval had no work for them (k_plan asks for the replay when this call has)
+    uint32_t lzg_skipped = 0;   // the call has pages long enough but the context's last intervals met no such block: the chain is not launched, a block that shows up after all asks for a replay (KIND_REPLAY)
 };
+// (passed to the kernels by value: the member initialisers above are the "off" state of a call and change nothing in that)
+static_assert(sizeof(DecodeArgs) == 368 && __is_trivially_copyable(DecodeArgs), "DecodeArgs is a kernel argument");
 // one column of a filter call (sb_filter_columns, sb_filter.h), next to its ColDesc
 struct FilterCol {
     uint32_t* sel;     // the selection bitmap, in 32-bit words

@@ -3028,13 +3028,13 @@ void debug_lzx_timers(uint64_t* out8) { (void)hipMemcpyFromSymbol(out8, HIP_SYMB
 #endif
 
 // LZ4 blocks of LZG_MIN compressed bytes and more of one queue, block-parallel (sb_lz4_giant.h)
-static void launch_lzg(sb_ctx* ctx, const DecodeArgs& a, InflateJob* q, const uint32_t* nq, uint32_t cap) {
+static void launch_lzg(sb_ctx* ctx, const DecodeArgs& a, bool lzg_on, InflateJob* q, const uint32_t* nq, uint32_t cap) {
     if (!a.lzg.jobs || !a.lzg_chunks) return;
     // Twenty launches over grids sized for the longest page cost a call without such blocks ~0.1 ms (a plain 1 M-row page
     // is long enough to qualify), so a context launches them only once it has met an LZ4 block of megabytes: the first call
     // with long pages looks (one host round trip, once per context), later calls go by what the last interval met
-    // (Status.kinds, read at every synchronize).
-    if (ctx->lzg_state == 2 && !ctx->no_hints) return;
+    // (Status.kinds, read at every synchronize: lzg_on is read_hints' word on that, sb_api.hip).
+    if (!lzg_on) return;
     hipStream_t s = ctx->stream;
     const LzgArgs g = a.lzg;
     const uint32_t NJ = std::max<uint32_t>(1u, a.lzg_jobs);
@@ -3075,7 +3075,7 @@ static void launch_lzg(sb_ctx* ctx, const DecodeArgs& a, InflateJob* q, const ui
 #include "sb_filter_bin.h"
 namespace sb {
 
-void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, uint64_t* col_values_len, const FilterLaunch* flt) {
+void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt) {
     hipStream_t s = ctx->stream;
     (void)hipMemsetAsync(a.job_counts, 0, 16 * sizeof(uint32_t), s);
     const bool qa = !(a.read_skips & RSKIP_QUEUE_A);
@@ -3094,7 +3094,7 @@ void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_p
         KScope k(ctx, "k_inflate_lz4");
         k_inflate_lz4<<<min(a.zs_segs ? a.job_cap_a : 2 * a.n_pages, LZ4_POOL), 64, 0, s>>>(a.jobs_a, a.job_counts, a.status, a.lz4_big_min, a.job_cap_a);
     }
-    launch_lzg(ctx, a, a.jobs_a, a.job_counts, a.job_cap_a);
+    launch_lzg(ctx, a, lzg_on, a.jobs_a, a.job_counts, a.job_cap_a);
     if (a.lz4_big_min != 0xFFFFFFFFu) {
         KScope k(ctx, "k_inflate_lz4_big");
         k_inflate_lz4_big<<<min(a.zs_segs ? a.job_cap_a : 2 * a.n_pages, LZ4_BIG_POOL), LB_T, 0, s>>>(a.jobs_a, a.job_counts, a.status, a.lz4_big_min, a.job_cap_a, a.lzg_skipped);
@@ -3132,7 +3132,7 @@ void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_p
         KScope k2(ctx, "k_inflate_lz4(values)");
         k_inflate_lz4<<<min(a.zs_segs ? a.job_cap_a : 2 * a.n_pages, LZ4_POOL), 64, 0, s>>>(a.jobs_b, a.job_counts + 1, a.status, a.lz4_big_min, a.job_cap_a);
     }
-    if (any_binary) launch_lzg(ctx, a, a.jobs_b, a.job_counts + 1, a.job_cap_a);
+    if (any_binary) launch_lzg(ctx, a, lzg_on, a.jobs_b, a.job_counts + 1, a.job_cap_a);
     if (any_binary && a.lz4_big_min != 0xFFFFFFFFu) {
         KScope k(ctx, "k_inflate_lz4_big(values)");
         k_inflate_lz4_big<<<min(a.zs_segs ? a.job_cap_a : 2 * a.n_pages, LZ4_BIG_POOL), LB_T, 0, s>>>(a.jobs_b, a.job_counts + 1, a.status, a.lz4_big_min, a.job_cap_a, a.lzg_skipped);

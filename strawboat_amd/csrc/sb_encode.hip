@@ -5330,35 +5330,6 @@ __global__ void __launch_bounds__(WG) k_enc_compact(EncodeArgs a) {
 using namespace sb;
 
 // ------------------------------------------------------------------------------ host side
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-static uint32_t enc_type_width(int32_t t) {
-    switch (t) {
-        case SB_TYPE_INT8:
-        case SB_TYPE_UINT8:
-            return 1;
-        case SB_TYPE_INT16:
-        case SB_TYPE_UINT16:
-            return 2;
-        case SB_TYPE_INT32:
-        case SB_TYPE_UINT32:
-        case SB_TYPE_FLOAT32:
-        case SB_TYPE_BINARY:
-            return 4;
-        case SB_TYPE_INT64:
-        case SB_TYPE_UINT64:
-        case SB_TYPE_FLOAT64:
-        case SB_TYPE_LARGE_BINARY:
-            return 8;
-        case SB_TYPE_INT128:
-            return 16;
-        case SB_TYPE_INT256:
-            return 32;
-    }
-    return 0;
-}
-static bool enc_is_binary(int32_t t) { return t == SB_TYPE_BINARY || t == SB_TYPE_LARGE_BINARY; }
-
 // page arithmetic of encode_chunk (src/write/common.rs:54-58,79-86)
 static uint64_t page_size_of(uint64_t rows, const sb_write_options* o) {
     uint64_t ps = o && o->max_page_size ? o->max_page_size : rows;
@@ -5367,10 +5338,10 @@ static uint64_t page_size_of(uint64_t rows, const sb_write_options* o) {
 
 // worst-case bytes of one page's fixed part (everything but binary value bytes)
 static uint64_t slot_fixed_bytes(int32_t ptype, int32_t nullable, uint64_t N) {
-    const uint64_t w = enc_type_width(ptype);
+    const uint64_t w = type_width(ptype);
     uint64_t b = 64 + (nullable ? def_section_bytes(N) : 0);
     if (ptype == SB_TYPE_BOOLEAN) return b + 9 + 5 * N + 16;  // RLE worst case: 5 bytes per row
-    if (enc_is_binary(ptype)) return b + 9 + (N + 1) * w + 9 + 9 + N * 8 + 4 + 8 * N + 64;  // + value share
+    if (is_binary_t(ptype)) return b + 9 + (N + 1) * w + 9 + 9 + N * 8 + 4 + 8 * N + 64;  // + value share
     // max(None, RLE = N*(4+w), Dict = 9 + 8N + 4 + N*w)
     return b + 9 + 9 + N * (w + 8) + 4 + 64;
 }
@@ -5390,7 +5361,7 @@ uint64_t sb_write_bound(int32_t physical_type, int32_t is_nullable, uint64_t row
     if (n_pages) *n_pages = np;
     uint64_t total = 0;
     for (uint64_t r = 0; r < rows; r += ps) total += slot_fixed_bytes(physical_type, is_nullable, r + ps > rows ? rows - r : ps);
-    if (enc_is_binary(physical_type)) total += values_len + values_len / 64 + 64 * np;
+    if (is_binary_t(physical_type)) total += values_len + values_len / 64 + 64 * np;
     return total;
 }
 
@@ -5437,7 +5408,7 @@ int32_t sb_write_columns(sb_ctx* ctx, sb_column_write* cols, uint64_t n, const s
             ppd0 = pd0; ppd1 = ctx->pending.size(); pcb0 = cb0; pcb1 = ctx->copybacks.size();
         }
     }
-    if (rc == SB_OK && ctx && n && !ctx->in_replay) ctx->calls.push_back(sb_ctx::Call{1, cols, n, *opts, mem});   // (for a replay: sb_host.h)
+    if (rc == SB_OK && ctx && n && !ctx->in_replay) ctx->calls.push_back(sb_ctx::Call{sb_ctx::Call::WRITE, cols, n, *opts, mem});   // (for a replay: sb_host.h)
     return rc;
 }
 
@@ -5539,9 +5510,9 @@ static int32_t validate_cols(sb_ctx* ctx, const sb_column_write* cols, uint64_t 
         // compresses an empty leaf block per page.
         if (c.rows == 0 && !(c.page_rows && c.n_pages_in))
             return ctx->fail(SB_ERR_OUT_OF_SPEC, "encode_chunk on an empty chunk panics upstream");
-        if (c.rows && c.physical_type != SB_TYPE_NULL && !c.values && !(enc_is_binary(c.physical_type) && c.values_len == 0))
+        if (c.rows && c.physical_type != SB_TYPE_NULL && !c.values && !(is_binary_t(c.physical_type) && c.values_len == 0))
             return ctx->fail(SB_ERR_INVALID, "values is null");  // (a binary column of empty strings has no value bytes)
-        if (enc_is_binary(c.physical_type) && !c.offsets) return ctx->fail(SB_ERR_INVALID, "offsets is null");
+        if (is_binary_t(c.physical_type) && !c.offsets) return ctx->fail(SB_ERR_INVALID, "offsets is null");
         const uint64_t np = pages_of(c, opts);
         if (np > c.n_pages_capacity || !c.out_metas) return ctx->fail(SB_ERR_INVALID, "out_metas too small");
         if (!c.out_pages && c.physical_type != SB_TYPE_NULL) return ctx->fail(SB_ERR_INVALID, "out_pages is null");
@@ -5579,8 +5550,8 @@ static int32_t build_plan(sb_ctx* ctx, hipStream_t s, const sb_column_write* col
             for (uint64_t q = 0; q < np; q++) mx = std::max<uint64_t>(mx, c.page_rows[q]);
         max_tiles = std::max<uint64_t>(max_tiles, (mx + TILE_ROWS - 1) / TILE_ROWS);
         if (!sh.lz_possible || c.physical_type == SB_TYPE_NULL) continue;
-        const bool bin = enc_is_binary(c.physical_type);
-        const uint64_t w = enc_type_width(c.physical_type);
+        const bool bin = is_binary_t(c.physical_type);
+        const uint64_t w = type_width(c.physical_type);
         for (uint64_t q = 0, r = 0; q < np; q++) {
             const uint64_t N = c.page_rows ? c.page_rows[q] : std::min<uint64_t>(ps, c.rows - r);
             r += N;
@@ -5628,8 +5599,8 @@ static int32_t build_plan(sb_ctx* ctx, hipStream_t s, const sb_column_write* col
     bool any_tiles = false, any_pages = false, any_compact = false, any_lz4 = false;
     for (uint64_t i = 0; i < n; i++) {
         const sb_column_write& c = cols[i];
-        const uint64_t ps = page_size_of(c.rows, opts), width = enc_type_width(c.physical_type);
-        const bool bin = enc_is_binary(c.physical_type);
+        const uint64_t ps = page_size_of(c.rows, opts), width = type_width(c.physical_type);
+        const bool bin = is_binary_t(c.physical_type);
         // sizes known up front => write straight to the final position
         const bool direct = !adaptive && !bin && (codec == SB_CODEC_NONE || codec == SB_CODEC_ONEVALUE) &&
                             c.physical_type != SB_TYPE_NULL;
@@ -5743,7 +5714,7 @@ static int32_t build_plan(sb_ctx* ctx, hipStream_t s, const sb_column_write* col
         if (p.bigx_off == 1) {
             scratch_off = align_up(scratch_off, 64);
             p.bigx_off = scratch_off;
-            scratch_off += no_dict ? BIGX_HEAD : dbig_layout(p.rows, enc_is_binary(c.physical_type)).total;
+            scratch_off += no_dict ? BIGX_HEAD : dbig_layout(p.rows, is_binary_t(c.physical_type)).total;
         }
         if (p.zst_off == 0) {   // (one block is at most 128 KiB whatever the page holds)
             scratch_off = align_up(scratch_off, 16);
@@ -5765,7 +5736,7 @@ static int32_t build_plan(sb_ctx* ctx, hipStream_t s, const sb_column_write* col
         }
         if (!p.direct) {
             uint64_t cap = std::max<uint64_t>(slot_fixed_bytes(c.physical_type, c.is_nullable, p.rows), p.slot_cap);
-            if (enc_is_binary(c.physical_type)) cap += c.values_len;
+            if (is_binary_t(c.physical_type)) cap += c.values_len;
             max_chunks = std::max<uint64_t>(max_chunks, (cap + COMPACT_CHUNK - 1) / COMPACT_CHUNK);
         }
     }
@@ -5827,12 +5798,12 @@ static int32_t stage_cols(sb_ctx* ctx, hipStream_t s, sb_column_write* cols, uin
     for (uint64_t i = 0; i < n; i++) {
         const sb_column_write& c = cols[i];
         ColBufs& b = bufs[i];
-        const uint32_t w = enc_type_width(c.physical_type);
+        const uint32_t w = type_width(c.physical_type);
         size_t vbytes = c.physical_type == SB_TYPE_BOOLEAN ? (size_t)((c.values_bit_offset + c.rows + 7) / 8)
-                        : enc_is_binary(c.physical_type) ? (size_t)c.values_len : (size_t)(c.rows * w);
+                        : is_binary_t(c.physical_type) ? (size_t)c.values_len : (size_t)(c.rows * w);
         if (!stage_in(c.values, vbytes, &b.values) ||
             !stage_in(c.validity, (size_t)((c.validity_bit_offset + c.rows + 7) / 8), &b.validity) ||
-            !stage_in(enc_is_binary(c.physical_type) ? c.offsets : nullptr, (size_t)((c.rows + 1) * w), &b.offsets))
+            !stage_in(is_binary_t(c.physical_type) ? c.offsets : nullptr, (size_t)((c.rows + 1) * w), &b.offsets))
             return ctx->fail(SB_ERR_EXTERNAL, "staging of host buffers failed");
         if (c.page_heads && c.page_head_bytes) {  // nested level sections travel like every other DEVICE buffer
             size_t hb = 0;
@@ -5867,7 +5838,7 @@ static void fill_cols(EncCol* hc, const sb_column_write* cols, uint64_t n, const
         d.rows = c.rows;
         d.ptype = c.physical_type;
         d.nullable = c.is_nullable;
-        d.width = enc_type_width(c.physical_type);
+        d.width = type_width(c.physical_type);
         d.first_page = plan.col_first[i];
         d.n_pages = plan.col_pages[i];
         d.fkind = c.physical_type == SB_TYPE_FLOAT32 ? 1 : c.physical_type == SB_TYPE_FLOAT64 ? 2 : 0;
@@ -6079,7 +6050,7 @@ static void launch_selectors(EncLaunch& L, int kd, hipStream_t st) {
     if (kd == 4 || kd == 8) {  // statistics + speculative RLE in one pass
         bool any_f = false, any_i = false;
         for (uint64_t i = 0; i < L.n; i++)
-            if ((int)L.hc[i].width == kd && L.hc[i].ptype != SB_TYPE_BOOLEAN && !enc_is_binary(L.hc[i].ptype)) {
+            if ((int)L.hc[i].width == kd && L.hc[i].ptype != SB_TYPE_BOOLEAN && !is_binary_t(L.hc[i].ptype)) {
                 any_f |= L.hc[i].fkind != 0;
                 any_i |= L.hc[i].fkind == 0;
             }
@@ -6291,9 +6262,9 @@ static void launch_freq(EncLaunch& L) {
     for (int kd : L.kinds) has4 |= kd == 4;
     for (uint64_t i = 0; i < L.n; i++) {  // only integers get there: a mostly-one-value float column takes Freq itself
         const EncCol& d = L.hc[i];
-        wide |= (d.fkind == 0 || L.sh.dict_freq) && d.ptype != SB_TYPE_BOOLEAN && d.ptype != SB_TYPE_NULL && !enc_is_binary(d.ptype) &&
+        wide |= (d.fkind == 0 || L.sh.dict_freq) && d.ptype != SB_TYPE_BOOLEAN && d.ptype != SB_TYPE_NULL && !is_binary_t(d.ptype) &&
                 (d.width <= 2 || d.width >= 8);
-        wide |= enc_is_binary(d.ptype);
+        wide |= is_binary_t(d.ptype);
     }
     if (!has4 && wide && (L.sh.adaptive || L.sh.dict_freq) && !L.sh.forbids(SB_CODEC_DICT)) {  // Freq-coded u32 indices of Dict pages
         KScope k(L.ctx, K_ENC_FREQ);

@@ -41,6 +41,36 @@ struct ProfSpan {
     hipEvent_t a, b;
 };
 
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// bytes per value (binary types: per offset; Boolean and Null: 0)
+inline uint32_t type_width(int32_t t) {
+    switch (t) {
+        case SB_TYPE_INT8:
+        case SB_TYPE_UINT8:
+            return 1;
+        case SB_TYPE_INT16:
+        case SB_TYPE_UINT16:
+            return 2;
+        case SB_TYPE_INT32:
+        case SB_TYPE_UINT32:
+        case SB_TYPE_FLOAT32:
+        case SB_TYPE_BINARY:
+            return 4;
+        case SB_TYPE_INT64:
+        case SB_TYPE_UINT64:
+        case SB_TYPE_FLOAT64:
+        case SB_TYPE_LARGE_BINARY:
+            return 8;
+        case SB_TYPE_INT128:
+            return 16;
+        case SB_TYPE_INT256:
+            return 32;
+    }
+    return 0;
+}
+inline bool is_binary_t(int32_t t) { return t == SB_TYPE_BINARY || t == SB_TYPE_LARGE_BINARY; }
+
 }  // namespace sb
 
 struct sb_ctx {
@@ -162,7 +192,6 @@ struct sb_ctx {
         uint32_t cap = 0, reserved = 0;
     };
     std::vector<FreqLog> freq_logs;
-    bool in_freq_pass = false;
     std::vector<sb_column_read> freq_cols;  // the second pass's one-page columns (alive until synchronize returns)
     std::vector<sb_page_meta> freq_metas;
 
@@ -206,7 +235,7 @@ struct sb_ctx {
     // never a one-workgroup walk over a million-row page.  (The callers' column arrays and buffers live until the
     // synchronize anyway: the results are written into them there.)
     struct Call {
-        int kind;   // 0 read, 1 write, 2 filter (sb_filter_columns), 3 filter (sb_filter_columns_var)
+        enum Kind { READ, WRITE, FILTER, FILTER_VAR } kind;   // sb_read_columns, sb_write_columns, sb_filter_columns, sb_filter_columns_var
         void* cols;
         uint64_t n;
         sb_write_options opts;
