@@ -82,17 +82,17 @@ StageSlot* acquire_slot(sb_ctx* ctx, size_t need) {
     // (more than NSLOTS calls since the last synchronize): move them to heap storage owned by the
     // Pending entry before the slot is rewritten or freed.
     if (s.host)
-        for (auto& p : ctx->pending) {
+        for (auto& p : ctx->iv.pending) {
             if (p.host < s.host || p.host >= s.host + s.cap) continue;
             const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL) ? 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R) ? (size_t)p.bytes
                                                                                                    : (size_t)(2 * p.n + 1) * 8;
-            ctx->rescued.emplace_back(p.host, p.host + nb);
-            p.host = ctx->rescued.back().data();
+            ctx->iv.rescued.emplace_back(p.host, p.host + nb);
+            p.host = ctx->iv.rescued.back().data();
         }
     if (s.cap < need) {
         // hipHostFree waits for the device: inside an enqueue it would drain the pipeline once per slot whenever a context
         // moves on to larger calls (the eight slots outgrown one after the other: +0.25 ms on each of the next eight calls)
-        if (s.host) ctx->stale_host.push_back(s.host);
+        if (s.host) ctx->iv.stale_host.push_back(s.host);
         ctx->slot_cap_max = std::max(ctx->slot_cap_max, need + need / 4 + 4096);
         size_t cap = ctx->slot_cap_max;
         if (hipHostMalloc((void**)&s.host, cap, hipHostMallocDefault) != hipSuccess) {
@@ -174,10 +174,10 @@ void sb_ctx_destroy(sb_ctx* ctx) {
         if (s.host) (void)hipHostFree(s.host);
         if (s.done) (void)hipEventDestroy(s.done);
     }
-    for (void* p : ctx->stale_host) (void)hipHostFree(p);
-    for (void* p : ctx->temp_dev) (void)hipFree(p);
+    for (void* p : ctx->iv.stale_host) (void)hipHostFree(p);
+    for (void* p : ctx->iv.temp_dev) (void)hipFree(p);
     ctx->stage_release();
-    for (auto& sp : ctx->spans) {
+    for (auto& sp : ctx->iv.spans) {
         (void)hipEventDestroy(sp.a);
         (void)hipEventDestroy(sp.b);
     }
@@ -226,20 +226,49 @@ struct ReadMode {
 static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, const ReadMode& mode);
 static void update_read_hints(sb_ctx* ctx, uint32_t kinds);   // (next to read_hints, its reader)
 
+// ---- sb_ctx_synchronize, step by step: status read -> replay? -> the interval's result -> Freq second pass -> profile ->
+// results to the callers -> SB_MEM_HOST copies back -> release.  
+
+// The status word travels with the stream: d_status -> h_status once everything queued has run.  The device only ever sets
+// bits of `kinds`: the word is cleared here so that it describes the calls of ONE interval (the host's kinds_seen keeps what
+// must stay).  feed_hints: the read at the end of an interval, whose kinds the next read calls go by; the Freq second pass
+// reads the word too, and what that pass met is not what the next interval's calls met.
+static hipError_t read_status(sb_ctx* ctx, bool feed_hints) {
+    hipError_t e = hipMemcpyAsync(ctx->h_status, ctx->d_status, sizeof(Status), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return e;
+    if (feed_hints) update_read_hints(ctx, ctx->h_status->kinds);
+    if (ctx->h_status->kinds) (void)hipMemsetAsync(&ctx->d_status->kinds, 0, sizeof ctx->d_status->kinds, ctx->stream);
+    return hipSuccess;
+}
+
+// The device raised an error (h_status->code): it becomes the result and last_error unless the host failed first (`rc`, whose
+// text stays); the device's word is cleared either way.  Returns the result.
+static int32_t take_device_error(sb_ctx* ctx, int32_t rc) {
+    if (ctx->h_status->code == 0) return rc;
+    if (rc == SB_OK) {
+        char buf[160];
+        rc = ctx->h_status->code;
+        ctx->last_error = status_text(*ctx->h_status, buf, sizeof buf);
+    }
+    (void)hipMemsetAsync(ctx->d_status, 0, sizeof(Status), ctx->stream);
+    return rc;
+}
+
 // Freq pages (integer/freq.rs:90-127) found by the decode calls of this synchronize interval: their
 // exception blocks are ordinary BLOCK<T>s, so they go through the decoder once more as one-page
 // columns that land in a temporary buffer; k_freq_scatter then writes them over the top value.
 // Only runs when k_parse logged a Freq page; costs one 4-byte readback per log otherwise.
-static int32_t freq_second_pass(sb_ctx* ctx) {
-    struct Batch {
-        const FreqEntry* d_entries;
-        uint32_t n;
-        uint8_t* ex_base;
-        uint64_t* d_off;
-    };
-    std::vector<Batch> batches;
-    ctx->freq_cols.clear();
-    ctx->freq_metas.clear();
+struct FreqBatch {   // the entries of one log that met Freq pages, and where their exceptions are decoded to
+    const FreqEntry* d_entries;
+    uint32_t n;
+    uint8_t* ex_base;
+    uint64_t* d_off;
+};
+// ... the logs read back: a batch per log, and every entry's exception block as a one-page column (iv.freq_cols / freq_metas)
+static int32_t read_freq_logs(sb_ctx* ctx, std::vector<FreqBatch>& batches) {
+    ctx->iv.freq_cols.clear();
+    ctx->iv.freq_metas.clear();
     for (auto& log : ctx->freq_logs) {
         if (!log.reserved) continue;
         log.reserved = 0;
@@ -257,13 +286,13 @@ static int32_t freq_second_pass(sb_ctx* ctx) {
             ex_off[i] = total;
             total += ((uint64_t)ents[i].n_exceptions * ents[i].width + 15) / 16 * 16;
         }
-        Batch b;
+        FreqBatch b;
         b.d_entries = (const FreqEntry*)(log.dev + 16);
         b.n = cnt;
         if (hipMalloc((void**)&b.ex_base, total + 64) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(freq exceptions) failed");
-        ctx->temp_dev.push_back(b.ex_base);
+        ctx->iv.temp_dev.push_back(b.ex_base);
         if (hipMalloc((void**)&b.d_off, (size_t)cnt * 8) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(freq offsets) failed");
-        ctx->temp_dev.push_back(b.d_off);
+        ctx->iv.temp_dev.push_back(b.d_off);
         if (hipMemcpy(b.d_off, ex_off.data(), (size_t)cnt * 8, hipMemcpyHostToDevice) != hipSuccess)
             return ctx->fail(SB_ERR_EXTERNAL, "freq offsets upload failed");
         for (uint32_t i = 0; i < cnt; i++) {
@@ -276,32 +305,30 @@ static int32_t freq_second_pass(sb_ctx* ctx) {
             c.n_pages = 1;
             c.values = b.ex_base + ex_off[i];
             c.values_capacity = (uint64_t)ents[i].n_exceptions * ents[i].width;
-            ctx->freq_cols.push_back(c);
+            ctx->iv.freq_cols.push_back(c);
             sb_page_meta m;
             m.length = ents[i].nested_len;
             m.num_values = ents[i].n_exceptions;
-            ctx->freq_metas.push_back(m);
+            ctx->iv.freq_metas.push_back(m);
         }
         batches.push_back(b);
     }
-    if (batches.empty()) return SB_OK;
-    ctx->freq_pass_ran = true;
-    for (size_t i = 0; i < ctx->freq_cols.size(); i++) ctx->freq_cols[i].metas = &ctx->freq_metas[i];
-    int32_t rc = read_columns_impl(ctx, ctx->freq_cols.data(), ctx->freq_cols.size(), SB_MEM_DEVICE, ReadMode{ReadMode::FREQ_PASS});
+    for (size_t i = 0; i < ctx->iv.freq_cols.size(); i++) ctx->iv.freq_cols[i].metas = &ctx->iv.freq_metas[i];
+    return SB_OK;
+}
+// ... and the pass proper: decode the exception blocks, scatter them, see what the device says.  Also called by a filter
+// replay's decode (filter_columns_decoded), between its read and its comparison.
+static int32_t freq_second_pass(sb_ctx* ctx) {
+    std::vector<FreqBatch> batches;
+    int32_t rc = read_freq_logs(ctx, batches);
+    if (rc != SB_OK || batches.empty()) return rc;
+    ctx->iv.freq_pass_ran = true;
+    rc = read_columns_impl(ctx, ctx->iv.freq_cols.data(), ctx->iv.freq_cols.size(), SB_MEM_DEVICE, ReadMode{ReadMode::FREQ_PASS});
     if (rc != SB_OK) return rc;
-    for (const Batch& b : batches) launch_freq_scatter(ctx, b.d_entries, b.n, b.d_off, b.ex_base);
-    hipError_t e = hipMemcpyAsync(ctx->h_status, ctx->d_status, sizeof(Status), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    for (const FreqBatch& b : batches) launch_freq_scatter(ctx, b.d_entries, b.n, b.d_off, b.ex_base);
+    const hipError_t e = read_status(ctx, false);   // (KIND_REPLAY bits of the pass are cleared with the rest and not acted on)
     if (e != hipSuccess) return check_hip(ctx, e, "freq second pass");
-    // (what this pass met is not what the next interval's calls met: the word was cleared before the pass was queued)
-    if (ctx->h_status->kinds) (void)hipMemsetAsync(&ctx->d_status->kinds, 0, sizeof ctx->d_status->kinds, ctx->stream);
-    if (ctx->h_status->code != 0) {
-        char buf[160];
-        rc = ctx->h_status->code;
-        ctx->last_error = status_text(*ctx->h_status, buf, sizeof buf);
-        (void)hipMemsetAsync(ctx->d_status, 0, sizeof(Status), ctx->stream);
-    }
-    return rc;
+    return take_device_error(ctx, SB_OK);
 }
 
 // the Freq records of the interval point into buffers the caller may reuse: drop them all
@@ -312,164 +339,152 @@ static void clear_freq_logs(sb_ctx* ctx) {
     }
 }
 // What the end of an interval and the start of its replay share, once the stream (and the copy stream) is drained and
-// nothing reads the interval's buffers any more
-static void release_interval(sb_ctx* ctx) {
+// nothing reads the interval's buffers any more: the interval's own state (Interval::reset says what a replay keeps) and
+// the context's staging, which the next calls use from the start again
+static void release_interval(sb_ctx* ctx, sb_ctx::Interval::Reset how) {
     for (auto& s : ctx->slots) s.in_flight = false;
-    for (void* p : ctx->stale_host) (void)hipHostFree(p);
-    ctx->stale_host.clear();
-    ctx->copybacks.clear();
-    ctx->pipe_ev_used = 0;
-    for (void* p : ctx->temp_dev) (void)hipFree(p);
-    ctx->temp_dev.clear();
+    ctx->iv.reset(how);
     ctx->stage_rewind();
-    ctx->filter_tmp.clear();
 }
 
-int32_t sb_ctx_synchronize(sb_ctx* ctx) {
-    if (!ctx) return SB_ERR_INVALID;
-    (void)hipSetDevice(ctx->device);
-    int32_t rc = ctx->sticky;
-    // status word travels with the stream
-    hipError_t e = hipMemcpyAsync(ctx->h_status, ctx->d_status, sizeof(Status), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) {
-        update_read_hints(ctx, ctx->h_status->kinds);
-        // the device only ever sets bits: the word is cleared here so that it describes the calls of ONE interval (the host's
-        // kinds_seen keeps what must stay)
-        if (ctx->h_status->kinds) (void)hipMemsetAsync(&ctx->d_status->kinds, 0, sizeof ctx->d_status->kinds, ctx->stream);
-    }
-    // A page was left undone because a kernel it needed had been skipped on a hint (KIND_REPLAY): drop what the interval
-    // produced and issue its calls again with every kernel launched.  One extra pass instead of a one-workgroup walk.
-    // (an error code of such an interval is not looked at: kernels behind a skipped one may have met what it did not produce;
-    // a real error shows again in the replay)
-    if (e == hipSuccess && (ctx->h_status->kinds & KIND_REPLAY) && rc == SB_OK && !ctx->in_replay && !ctx->calls.empty()) {
-        if (ctx->h_status->code != 0) (void)hipMemsetAsync(ctx->d_status, 0, sizeof(Status), ctx->stream);
-        for (auto& sp : ctx->spans) {   // (recycled, not timed)
-            ctx->free_events.push_back(sp.a);
-            ctx->free_events.push_back(sp.b);
-        }
-        ctx->spans.clear();
-        {   // (the page records of enqueued level calls stay: those calls are not issued again)
-            std::vector<Pending> keep;
-            for (auto& p : ctx->pending)
-                if (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R) {
-                    ctx->rescued.emplace_back(p.host, p.host + p.bytes);
-                    p.host = ctx->rescued.back().data();
-                    keep.push_back(p);
-                }
-            ctx->pending.swap(keep);
-        }
-        if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);   // (copies of groups that ran: overwritten by the replay's)
-        release_interval(ctx);
-        clear_freq_logs(ctx);
-        ctx->filter_freq = (ctx->h_status->kinds & KIND_FILTER_FREQ) != 0;
-        std::vector<sb_ctx::Call> calls;
-        calls.swap(ctx->calls);
-        const bool saved = ctx->no_hints;
-        ctx->no_hints = true;
-        ctx->in_replay = true;
-        ctx->replays++;
-        if (ctx->h_status->kinds & KIND_REPLAY_LZG) ctx->lzg_state = 1;
-        for (auto& cl : calls) {
-            switch (cl.kind) {
-                case sb_ctx::Call::READ: rc = sb_read_columns(ctx, (sb_column_read*)cl.cols, cl.n, cl.mem); break;
-                case sb_ctx::Call::WRITE: rc = sb_write_columns(ctx, (sb_column_write*)cl.cols, cl.n, &cl.opts, cl.mem); break;
-                case sb_ctx::Call::FILTER: rc = sb_filter_columns(ctx, (sb_column_filter*)cl.cols, cl.n, cl.mem); break;
-                case sb_ctx::Call::FILTER_VAR: rc = sb_filter_columns_var(ctx, (sb_column_filter_var*)cl.cols, cl.n, cl.mem); break;
-            }
-            if (rc != SB_OK) break;
-        }
-        ctx->no_hints = saved;
-        ctx->filter_freq = false;
-        if (rc != SB_OK) ctx->sticky = rc;
-        rc = sb_ctx_synchronize(ctx);
-        ctx->in_replay = false;
-        return rc;
-    }
-    ctx->calls.clear();
-    if (e != hipSuccess) {
-        rc = check_hip(ctx, e, "sb_ctx_synchronize");
-    } else if (ctx->h_status->code != 0) {
-        char buf[160];
-        if (!rc) {
-            rc = ctx->h_status->code;
-            ctx->last_error = status_text(*ctx->h_status, buf, sizeof buf);
-        }
-        (void)hipMemsetAsync(ctx->d_status, 0, sizeof(Status), ctx->stream);
-    }
-    if (rc == SB_OK) rc = freq_second_pass(ctx);
-    if (rc != SB_OK) {   // a failed interval
-        clear_freq_logs(ctx);
-        (void)hipStreamSynchronize(ctx->stream);
-    }
-    for (auto& sp : ctx->spans) {
+// The events of the profiled launches go back to the pool; timed: their spans are added to the profile first
+static void recycle_spans(sb_ctx* ctx, bool timed) {
+    for (auto& sp : ctx->iv.spans) {
         float ms = 0;
-        if (hipEventElapsedTime(&ms, sp.a, sp.b) == hipSuccess) {
+        if (timed && hipEventElapsedTime(&ms, sp.a, sp.b) == hipSuccess) {
             ctx->prof[sp.id].ms += ms;
             ctx->prof[sp.id].n += 1;
         }
         ctx->free_events.push_back(sp.a);
         ctx->free_events.push_back(sp.b);
     }
-    ctx->spans.clear();
-    for (auto& p : ctx->pending) {
-        if (p.kind == Pending::READ_COL) {
-            sb_column_read* c = (sb_column_read*)p.user;
-            uint64_t v;
-            memcpy(&v, p.host, 8);
-            c->values_len = v;
-        } else if (p.kind == Pending::FILTER_COL) {
-            memcpy(p.user, p.host, 8);
-        } else if (p.kind == Pending::ENC_HINT) {
-            if (ctx->enc_plan.valid && ctx->enc_plan.key == p.n && rc == SB_OK) {
-                uint32_t now[32];
-                memcpy(now, p.host, 128);
-                for (int i = 0; i < 32; i++) ctx->enc_plan.last_counts[i] = std::max(now[i], ctx->enc_plan.prev_counts[i]);
-                memcpy(ctx->enc_plan.prev_counts, now, 128);
-                ctx->enc_plan.counts_valid = true;
-            }
-        } else if (p.kind == Pending::NESTED_W) {
+    ctx->iv.spans.clear();
+}
+
+// A page was left undone because a kernel it needed had been skipped on a hint (KIND_REPLAY): one extra pass with every
+// kernel launched instead of a one-workgroup walk.  Not for an interval that failed on the host, not twice in a row, and
+// only if there is a call to issue again (enqueued level calls are not kept).
+static bool needs_replay(const sb_ctx* ctx, hipError_t e, int32_t rc) {
+    return e == hipSuccess && (ctx->h_status->kinds & KIND_REPLAY) && rc == SB_OK && !ctx->in_replay && !ctx->iv.calls.empty();
+}
+// Drops what the interval produced and issues its calls again, without launch hints, then synchronizes for good.
+// (an error code of such an interval is not looked at: kernels behind a skipped one may have met what it did not produce;
+// a real error shows again in the replay)
+static int32_t replay_interval(sb_ctx* ctx) {
+    if (ctx->h_status->code != 0) (void)hipMemsetAsync(ctx->d_status, 0, sizeof(Status), ctx->stream);
+    recycle_spans(ctx, false);
+    if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);   // (copies of groups that ran: overwritten by the replay's)
+    std::vector<sb_ctx::Call> calls;
+    calls.swap(ctx->iv.calls);
+    release_interval(ctx, sb_ctx::Interval::REPLAY);
+    clear_freq_logs(ctx);
+    ctx->filter_freq = (ctx->h_status->kinds & KIND_FILTER_FREQ) != 0;
+    const bool saved = ctx->no_hints;
+    ctx->no_hints = true;
+    ctx->in_replay = true;   // (the entry points: such a call is not recorded again)
+    ctx->replays++;
+    if (ctx->h_status->kinds & KIND_REPLAY_LZG) ctx->lzg_state = 1;
+    int32_t rc = SB_OK;
+    for (auto& cl : calls)
+        if ((rc = reissue(ctx, cl)) != SB_OK) break;
+    ctx->no_hints = saved;
+    ctx->filter_freq = false;
+    if (rc != SB_OK) ctx->iv.sticky = rc;
+    rc = sb_ctx_synchronize(ctx);   // (in_replay: this one ends the interval whatever the device says)
+    ctx->in_replay = false;
+    return rc;
+}
+
+// ---- the results of the interval's calls -> the callers' structs, by Pending::Kind (the table in sb_host.h)
+static void deliver_read_col(const Pending& p) {
+    uint64_t v;
+    memcpy(&v, p.host, 8);
+    ((sb_column_read*)p.user)->values_len = v;
+}
+static void deliver_filter_col(const Pending& p) { memcpy(p.user, p.host, 8); }
+static void deliver_write_col(const Pending& p) {
+    sb_column_write* c = (sb_column_write*)p.user;
+    const uint64_t* lens = (const uint64_t*)p.host;  // [n_pages lengths][n_pages num_values][total]
+    for (uint64_t i = 0; i < p.n && i < c->n_pages_capacity; i++) {
+        c->out_metas[i].length = lens[i];
+        c->out_metas[i].num_values = lens[p.n + i];
+    }
+    c->n_pages = p.n;
+    c->out_len = lens[2 * p.n];
+}
+// the pages per codec of a write call, for the next call with its plan (EncPlan::last_counts): only if that plan is still
+// the context's
+static void apply_enc_hint(sb_ctx* ctx, const Pending& p) {
+    if (!ctx->enc_plan.valid || ctx->enc_plan.key != p.n) return;
+    uint32_t now[32];
+    memcpy(now, p.host, 128);
+    for (int i = 0; i < 32; i++) ctx->enc_plan.last_counts[i] = std::max(now[i], ctx->enc_plan.prev_counts[i]);
+    memcpy(ctx->enc_plan.prev_counts, now, 128);
+    ctx->enc_plan.counts_valid = true;
+}
+// `rc`: the interval's result; sizes and lengths are handed over even when it failed, hints and page records are not
+static void deliver_pending(sb_ctx* ctx, const Pending& p, int32_t rc) {
+    switch (p.kind) {
+        case Pending::READ_COL: deliver_read_col(p); break;
+        case Pending::FILTER_COL: deliver_filter_col(p); break;
+        case Pending::WRITE_COL: deliver_write_col(p); break;
+        case Pending::ENC_HINT:
+            if (rc == SB_OK) apply_enc_hint(ctx, p);
+            break;
+        case Pending::NESTED_W:
             if (rc == SB_OK) nested_write_finish((sb_nested_levels_write*)p.user, p.n, p.host);
-        } else if (p.kind == Pending::NESTED_R) {
+            break;
+        case Pending::NESTED_R:
             if (rc == SB_OK) nested_read_finish((sb_nested_levels_read*)p.user, p.n, p.host);
-        } else {
-            sb_column_write* c = (sb_column_write*)p.user;
-            const uint64_t* lens = (const uint64_t*)p.host;  // [n_pages lengths][n_pages num_values][total]
-            for (uint64_t i = 0; i < p.n && i < c->n_pages_capacity; i++) {
-                c->out_metas[i].length = lens[i];
-                c->out_metas[i].num_values = lens[p.n + i];
-            }
-            c->n_pages = p.n;
-            c->out_len = lens[2 * p.n];
+            break;
+    }
+}
+
+// SB_MEM_HOST: what was not sent back while the interval ran (all copies on the copy stream, one wait).  A copy that a group
+// issued early is repeated if the Freq second pass ran, which wrote the buffers after it.  Returns the interval's result.
+static int32_t finish_copybacks(sb_ctx* ctx, int32_t rc) {
+    // (the stream exists only in contexts that serve host-memory calls: one more stream in the process changes how the
+    // runtime maps streams to hardware queues — C4's side streams lost their overlap, 1.03 -> 1.55 ms per read)
+    hipStream_t cs = ctx->iv.copybacks.empty() ? ctx->copy_stream : ctx->copy_stream_get();
+    bool any = false;
+    for (auto& cb : ctx->iv.copybacks) {
+        if (cb.issued && !ctx->iv.freq_pass_ran) {
+            any = true;
+            continue;
+        }
+        const size_t nb = cb.used ? (size_t)std::min<uint64_t>(cb.n, *cb.used) : cb.n;
+        if (rc == SB_OK && nb) {
+            hipError_t ce = cs ? hipMemcpyAsync(cb.host, cb.dev, nb, hipMemcpyDeviceToHost, cs) : hipMemcpy(cb.host, cb.dev, nb, hipMemcpyDeviceToHost);
+            if (ce != hipSuccess) rc = check_hip(ctx, ce, "copy back");
+            any = true;
         }
     }
-    ctx->pending.clear();
-    ctx->rescued.clear();
-    {   // SB_MEM_HOST: what was not sent back while the interval ran (all copies on the copy stream, one wait)
-        // (the stream exists only in contexts that serve host-memory calls: one more stream in the process changes how the
-        // runtime maps streams to hardware queues — C4's side streams lost their overlap, 1.03 -> 1.55 ms per read)
-        hipStream_t cs = ctx->copybacks.empty() ? ctx->copy_stream : ctx->copy_stream_get();
-        bool any = false;
-        for (auto& cb : ctx->copybacks) {
-            if (cb.issued && !ctx->freq_pass_ran) {
-                any = true;
-                continue;
-            }
-            const size_t nb = cb.used ? (size_t)std::min<uint64_t>(cb.n, *cb.used) : cb.n;
-            if (rc == SB_OK && nb) {
-                hipError_t ce = cs ? hipMemcpyAsync(cb.host, cb.dev, nb, hipMemcpyDeviceToHost, cs) : hipMemcpy(cb.host, cb.dev, nb, hipMemcpyDeviceToHost);
-                if (ce != hipSuccess) rc = check_hip(ctx, ce, "copy back");
-                any = true;
-            }
-        }
-        if (any && cs) {
-            hipError_t ce = hipStreamSynchronize(cs);
-            if (ce != hipSuccess && rc == SB_OK) rc = check_hip(ctx, ce, "copy back");
-        }
+    if (any && cs) {
+        hipError_t ce = hipStreamSynchronize(cs);
+        if (ce != hipSuccess && rc == SB_OK) rc = check_hip(ctx, ce, "copy back");
     }
-    release_interval(ctx);
-    ctx->freq_pass_ran = false;
-    ctx->sticky = 0;
+    return rc;
+}
+
+int32_t sb_ctx_synchronize(sb_ctx* ctx) {
+    if (!ctx) return SB_ERR_INVALID;
+    (void)hipSetDevice(ctx->device);
+    int32_t rc = ctx->iv.sticky;   // a call of the interval failed on the host
+    const hipError_t e = read_status(ctx, true);
+    if (needs_replay(ctx, e, rc)) return replay_interval(ctx);
+    if (e != hipSuccess)
+        rc = check_hip(ctx, e, "sb_ctx_synchronize");
+    else
+        rc = take_device_error(ctx, rc);
+    if (rc == SB_OK) rc = freq_second_pass(ctx);
+    if (rc != SB_OK) {   // a failed interval
+        clear_freq_logs(ctx);
+        (void)hipStreamSynchronize(ctx->stream);
+    }
+    recycle_spans(ctx, true);
+    for (const Pending& p : ctx->iv.pending) deliver_pending(ctx, p, rc);
+    rc = finish_copybacks(ctx, rc);
+    release_interval(ctx, sb_ctx::Interval::END);
     return rc;
 }
 
@@ -753,14 +768,14 @@ static void queue_copybacks(sb_ctx* ctx, sb_column_read* cols, uint64_t n, const
         const sb_column_read& c = cols[i];
         const ReadBufs& b = bufs[i];
         const uint32_t w = type_width(c.physical_type);
-        if (c.is_nullable && c.rows) ctx->copybacks.push_back({c.validity, b.validity, (size_t)((c.rows + 7) / 8)});
+        if (c.is_nullable && c.rows) ctx->iv.copybacks.push_back({c.validity, b.validity, (size_t)((c.rows + 7) / 8)});
         if (is_binary_t(c.physical_type)) {
-            ctx->copybacks.push_back({c.offsets, b.offsets, (size_t)((c.rows + 1) * w)});
-            ctx->copybacks.push_back({c.values, b.values, (size_t)c.values_capacity, &cols[i].values_len});  // (set just before, from `pending`)
+            ctx->iv.copybacks.push_back({c.offsets, b.offsets, (size_t)((c.rows + 1) * w)});
+            ctx->iv.copybacks.push_back({c.values, b.values, (size_t)c.values_capacity, &cols[i].values_len});  // (set just before, from `pending`)
         } else if (c.physical_type == SB_TYPE_BOOLEAN) {
-            ctx->copybacks.push_back({c.values, b.values, (size_t)((c.rows + 7) / 8)});
+            ctx->iv.copybacks.push_back({c.values, b.values, (size_t)((c.rows + 7) / 8)});
         } else if (c.physical_type != SB_TYPE_NULL) {
-            ctx->copybacks.push_back({c.values, b.values, (size_t)(c.rows * w)});
+            ctx->iv.copybacks.push_back({c.values, b.values, (size_t)(c.rows * w)});
         }
     }
 }
@@ -1052,7 +1067,7 @@ static int32_t queue_read_results(sb_ctx* ctx, StageSlot* slot, const ReadLayout
         pd.user = mode.filter() ? (void*)mode.sel_out[i] : (void*)&cols[i];
         pd.host = hv + i * sizeof(uint64_t);
         pd.n = 0;
-        ctx->pending.push_back(pd);
+        ctx->iv.pending.push_back(pd);
     }
     return SB_OK;
 }
@@ -1113,19 +1128,19 @@ int32_t sb_read_columns(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t m
     } else {
         const uint64_t per = (n + groups - 1) / groups;
         for (uint64_t g0 = 0; g0 < n && rc == SB_OK; g0 += per) {
-            const size_t cb0 = ctx->copybacks.size();
+            const size_t cb0 = ctx->iv.copybacks.size();
             rc = read_columns_impl(ctx, cols + g0, std::min<uint64_t>(per, n - g0), mem, ReadMode{ReadMode::READ});
             if (rc != SB_OK) break;
             hipEvent_t ev = ctx->next_pipe_event();
             if (!ev || hipEventRecord(ev, ctx->stream) != hipSuccess || hipStreamWaitEvent(cs, ev, 0) != hipSuccess) continue;   // (copied at the synchronize)
-            for (size_t k = cb0; k < ctx->copybacks.size(); k++) {
-                auto& cb = ctx->copybacks[k];
+            for (size_t k = cb0; k < ctx->iv.copybacks.size(); k++) {
+                auto& cb = ctx->iv.copybacks[k];
                 if (cb.used || !cb.n) continue;
                 if (hipMemcpyAsync(cb.host, cb.dev, cb.n, hipMemcpyDeviceToHost, cs) == hipSuccess) cb.issued = true;
             }
         }
     }
-    if (rc == SB_OK && ctx && n && !ctx->in_replay) ctx->calls.push_back(sb_ctx::Call{sb_ctx::Call::READ, cols, n, sb_write_options{}, mem});
+    if (rc == SB_OK && ctx && n && !ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::READ, cols, n, sb_write_options{}, mem});
     return rc;
 }
 
@@ -1153,8 +1168,8 @@ static sb_column_read read_col_of(const sb_column_filter_var& u) {
 
 static int32_t filter_columns_decoded(sb_ctx* ctx, sb_column_filter_var* const* users, const FilterCol* hf, uint64_t* const* sel_out, uint64_t m) {
     hipStream_t s = ctx->stream;
-    ctx->filter_tmp.emplace_back(m);
-    std::vector<sb_column_read>& rr = ctx->filter_tmp.back();
+    ctx->iv.filter_tmp.emplace_back(m);
+    std::vector<sb_column_read>& rr = ctx->iv.filter_tmp.back();
     size_t total = 0;
     std::vector<size_t> o_val(m), o_bits(m);
     for (uint64_t i = 0; i < m; i++) {
@@ -1179,7 +1194,7 @@ static int32_t filter_columns_decoded(sb_ctx* ctx, sb_column_filter_var* const* 
     if (rc != SB_OK) return rc;
     uint64_t* d_counts = nullptr;
     if (hipMalloc((void**)&d_counts, m * sizeof(uint64_t)) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter counts) failed");
-    ctx->temp_dev.push_back(d_counts);
+    ctx->iv.temp_dev.push_back(d_counts);
     StageSlot* slot = acquire_slot(ctx, m * sizeof(uint64_t));
     if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
     for (uint64_t i = 0; i < m; i++) {
@@ -1199,7 +1214,7 @@ static int32_t filter_columns_decoded(sb_ctx* ctx, sb_column_filter_var* const* 
         pd.user = sel_out[i];
         pd.host = slot->host + i * sizeof(uint64_t);
         pd.n = 0;
-        ctx->pending.push_back(pd);
+        ctx->iv.pending.push_back(pd);
     }
     return SB_OK;
 }
@@ -1343,7 +1358,7 @@ int32_t sb_filter_columns_var(sb_ctx* ctx, sb_column_filter_var* cols, uint64_t 
     std::vector<uint64_t*> results(n);
     for (uint64_t i = 0; i < n; i++) results[i] = &cols[i].rows;   // { rows, selected }
     const int32_t rc = filter_impl(ctx, cols, results.data(), n);
-    if (rc == SB_OK && !ctx->in_replay) ctx->calls.push_back(sb_ctx::Call{sb_ctx::Call::FILTER_VAR, cols, n, sb_write_options{}, mem});
+    if (rc == SB_OK && !ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::FILTER_VAR, cols, n, sb_write_options{}, mem});
     return rc;
 }
 
@@ -1383,7 +1398,7 @@ int32_t sb_filter_columns(sb_ctx* ctx, sb_column_filter* cols, uint64_t n, int32
         results[i] = &c.rows;
     }
     const int32_t rc = filter_impl(ctx, v.data(), results.data(), n);
-    if (rc == SB_OK && !ctx->in_replay) ctx->calls.push_back(sb_ctx::Call{sb_ctx::Call::FILTER, cols, n, sb_write_options{}, mem});
+    if (rc == SB_OK && !ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::FILTER, cols, n, sb_write_options{}, mem});
     return rc;
 }
 

@@ -5372,10 +5372,10 @@ uint64_t sb_write_bound(int32_t physical_type, int32_t is_nullable, uint64_t row
 static void send_group_pages(sb_ctx* ctx, hipStream_t cs, sb::StageSlot* slot, size_t pd0, size_t pd1, size_t cb0, size_t cb1) {
     if (!slot || !slot->done || hipEventSynchronize(slot->done) != hipSuccess) return;
     for (size_t k = cb0; k < cb1; k++) {
-        auto& cb = ctx->copybacks[k];
+        auto& cb = ctx->iv.copybacks[k];
         if (cb.issued || !cb.used) continue;
         for (size_t q = pd0; q < pd1; q++) {
-            const Pending& p = ctx->pending[q];
+            const Pending& p = ctx->iv.pending[q];
             if (p.kind != Pending::WRITE_COL || &((sb_column_write*)p.user)->out_len != cb.used) continue;
             const uint64_t* lens = (const uint64_t*)p.host;   // [n_pages lengths][n_pages num_values][total]
             const size_t nb = (size_t)std::min<uint64_t>(cb.n, lens[2 * p.n]);
@@ -5400,15 +5400,15 @@ int32_t sb_write_columns(sb_ctx* ctx, sb_column_write* cols, uint64_t n, const s
         sb::StageSlot* prev_slot = nullptr;
         size_t ppd0 = 0, ppd1 = 0, pcb0 = 0, pcb1 = 0;
         for (uint64_t g0 = 0; g0 < n; g0 += per) {
-            const size_t pd0 = ctx->pending.size(), cb0 = ctx->copybacks.size();
+            const size_t pd0 = ctx->iv.pending.size(), cb0 = ctx->iv.copybacks.size();
             rc = write_columns_impl(ctx, cols + g0, std::min<uint64_t>(per, n - g0), opts, mem);
             if (rc != SB_OK) break;
             if (prev_slot) send_group_pages(ctx, cs, prev_slot, ppd0, ppd1, pcb0, pcb1);   // (this group's copies in are queued behind it)
-            prev_slot = ctx->last_slot;
-            ppd0 = pd0; ppd1 = ctx->pending.size(); pcb0 = cb0; pcb1 = ctx->copybacks.size();
+            prev_slot = ctx->iv.last_slot;
+            ppd0 = pd0; ppd1 = ctx->iv.pending.size(); pcb0 = cb0; pcb1 = ctx->iv.copybacks.size();
         }
     }
-    if (rc == SB_OK && ctx && n && !ctx->in_replay) ctx->calls.push_back(sb_ctx::Call{sb_ctx::Call::WRITE, cols, n, *opts, mem});   // (for a replay: sb_host.h)
+    if (rc == SB_OK && ctx && n && !ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::WRITE, cols, n, *opts, mem});   // (for a replay: sb_host.h)
     return rc;
 }
 
@@ -5813,7 +5813,7 @@ static int32_t stage_cols(sb_ctx* ctx, hipStream_t s, sb_column_write* cols, uin
         if (c.out_capacity) {
             if (!(b.out = ctx->stage_alloc(c.out_capacity)))
                 return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(out_pages) failed");
-            ctx->copybacks.push_back({c.out_pages, b.out, (size_t)c.out_capacity, &cols[i].out_len});
+            ctx->iv.copybacks.push_back({c.out_pages, b.out, (size_t)c.out_capacity, &cols[i].out_len});
         }
     }
     return SB_OK;
@@ -6387,18 +6387,18 @@ static int32_t write_columns_impl(sb_ctx* ctx, sb_column_write* cols, uint64_t n
         pd.user = nullptr;
         pd.host = slot->host + T.hcounts;
         pd.n = plan.key;
-        ctx->pending.push_back(pd);
+        ctx->iv.pending.push_back(pd);
     }
     (void)hipEventRecord(slot->done, s);
     slot->in_flight = true;
-    ctx->last_slot = slot;
+    ctx->iv.last_slot = slot;
     for (uint64_t i = 0; i < n; i++) {
         Pending pd;
         pd.kind = Pending::WRITE_COL;
         pd.user = &cols[i];
         pd.host = hres + plan.hro[i] * sizeof(uint64_t);
         pd.n = hc[i].n_pages;
-        ctx->pending.push_back(pd);
+        ctx->iv.pending.push_back(pd);
     }
     return SB_OK;
 }

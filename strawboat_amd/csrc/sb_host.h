@@ -22,13 +22,21 @@ struct StageSlot {
     bool in_flight = false;
 };
 
-struct Pending {  // results to hand back to the caller's structs at synchronize
-    enum Kind { READ_COL, WRITE_COL, ENC_HINT, NESTED_W, NESTED_R, FILTER_COL } kind;   // ENC_HINT: the codec counts of a write call (n = the plan's key), 32 words
-                                                                           // NESTED_W / _R: the page records of an enqueued level call (user = its items, n = how many)
-    void* user;            // sb_column_read* / sb_column_write* / FILTER_COL: the caller's `selected` (8 bytes, the bits set)
-    const uint8_t* host;   // where the readback lands (pinned)
-    uint64_t n;            // WRITE_COL: number of pages
-    uint64_t bytes = 0;    // NESTED_*: bytes of the readback at `host`
+// A result to hand back to the caller's structs at synchronize (sb_api.hip: deliver_pending), read back into pinned memory:
+//   kind        user                          host                                        n               bytes
+//   READ_COL    sb_column_read*               8 bytes: values_len                         0               -
+//   FILTER_COL  the caller's `selected`       8 bytes: the bits set                       0               -
+//   WRITE_COL   sb_column_write*              u64 [n lengths][n num_values][out_len]      pages           -
+//   ENC_HINT    null                          32 words: pages per codec of a write call   the plan's key  -
+//   NESTED_W    sb_nested_levels_write[n]     the page records of an enqueued level call  items           of the records
+//   NESTED_R    sb_nested_levels_read[n]      the page records of an enqueued level call  items           of the records
+// (acquire_slot sizes what it moves out of a recycled slot by this table)
+struct Pending {
+    enum Kind { READ_COL, WRITE_COL, ENC_HINT, NESTED_W, NESTED_R, FILTER_COL } kind;
+    void* user;
+    const uint8_t* host;
+    uint64_t n;
+    uint64_t bytes = 0;
 };
 
 enum KernelId {
@@ -78,7 +86,6 @@ struct sb_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     std::string last_error;
-    int32_t sticky = 0;  // first host-side error since the last synchronize
 
     int lzg_state = 0;        // sb_lz4_giant.h: 0 = not known yet, 1 = this context meets LZ4 blocks of megabytes, 2 = it does not
     bool lzg_long_pages = false;   // a call since the last synchronize had pages long enough
@@ -89,7 +96,6 @@ struct sb_ctx {
     sb::DevBuf staging;  // device staging for SB_MEM_HOST callers
     sb::DevBuf filter_stage;   // sb_filter_columns: where the inflate queues put the values of LZ4 / Zstd / Snappy / Patas pages (no caller's buffer to inflate into)
     bool filter_freq = false;  // replay of an interval in which a filter call met a Freq page: filter calls decode into filter_stage first
-    std::deque<std::vector<sb_column_read>> filter_tmp;   // the read columns of those decodes (alive until the synchronize returns)
     sb::DevBuf zlit;     // Zstd literal buffers (fixed pool of inflate waves)
     sb::DevBuf zrec;     // Zstd sequence records (one arena per inflate wave; allocated by the first batch-sized read)
     sb::Status* d_status = nullptr;
@@ -114,10 +120,7 @@ struct sb_ctx {
     sb::StageSlot slots[NSLOTS];
     int next_slot = 0;
     size_t slot_cap_max = 0;                // largest staging request so far: a slot that grows, grows to this
-    std::vector<void*> stale_host;          // outgrown staging buffers, freed at the next synchronize (hipHostFree drains the device)
 
-    std::vector<sb::Pending> pending;
-    std::deque<std::vector<uint8_t>> rescued;  // readbacks moved out of a recycled staging slot (acquire_slot)
     // SB_MEM_HOST copies to hand back after the stream drains: (host dst, device src, bytes)
     struct Copyback {
         void* host;
@@ -129,24 +132,19 @@ struct sb_ctx {
     };
     uint32_t host_groups_max = 8;        // SB_HOST_GROUPS (1: SB_MEM_HOST calls are never cut into groups)
     hipStream_t copy_stream = nullptr;   // D2H copies of SB_MEM_HOST calls
-    std::vector<hipEvent_t> pipe_ev;     // "group's kernels done" events of the open interval
-    size_t pipe_ev_used = 0;
-    sb::StageSlot* last_slot = nullptr;  // the staging slot of the last enqueued write call (its `done` event = results are back)
-    bool freq_pass_ran = false;          // this synchronize ran the Freq second pass (copies issued early are repeated)
+    std::vector<hipEvent_t> pipe_ev;     // "group's kernels done" events (iv.pipe_ev_used of them belong to the open interval)
     hipEvent_t next_pipe_event() {
-        if (pipe_ev_used == pipe_ev.size()) {
+        if (iv.pipe_ev_used == pipe_ev.size()) {
             hipEvent_t e = nullptr;
             if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr;
             pipe_ev.push_back(e);
         }
-        return pipe_ev[pipe_ev_used++];
+        return pipe_ev[iv.pipe_ev_used++];
     }
     hipStream_t copy_stream_get() {
         if (!copy_stream && hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking) != hipSuccess) copy_stream = nullptr;
         return copy_stream;
     }
-    std::vector<Copyback> copybacks;
-    std::vector<void*> temp_dev;  // device temporaries to free at synchronize
     // SB_MEM_HOST staging areas: carved out of chunks that stay allocated (hipMalloc / hipFree per buffer and call
     // cost more than the PCIe copies); every carve-out lives until the next synchronize, which rewinds the chunks
     struct StageChunk {
@@ -192,12 +190,9 @@ struct sb_ctx {
         uint32_t cap = 0, reserved = 0;
     };
     std::vector<FreqLog> freq_logs;
-    std::vector<sb_column_read> freq_cols;  // the second pass's one-page columns (alive until synchronize returns)
-    std::vector<sb_page_meta> freq_metas;
 
     // optional per-kernel HIP-event timing (sb_ctx_profile)
     bool profile = false;
-    std::vector<sb::ProfSpan> spans;
     std::vector<hipEvent_t> free_events;
     // The page table of the last write call (sb_write_columns): page arithmetic, scratch layout and launch shape depend only
     // on the columns' types, row counts, paging and the options — not on their buffers — so a writer that sends chunk after
@@ -241,7 +236,62 @@ struct sb_ctx {
         sb_write_options opts;
         int32_t mem;
     };
-    std::vector<Call> calls;
+    // The open synchronize interval: everything that lives from the first enqueue after a synchronize to the end of the next
+    // one.  reset() is the only place that ends these lifetimes, and it resets nothing else; what survives intervals on
+    // purpose (the hint counters with read_calls / lzg_long_pages, which update_read_hints consumes; enc_plan; the pools;
+    // free_events; pipe_ev; the Freq logs' buffers) stays outside.
+    struct Interval {
+        int32_t sticky = 0;                        // first host-side error since the last synchronize
+        std::vector<Call> calls;                   // (above)
+        std::vector<sb::Pending> pending;
+        std::deque<std::vector<uint8_t>> rescued;  // readbacks moved out of a recycled staging slot (acquire_slot) or kept for a replay
+        std::vector<Copyback> copybacks;
+        std::vector<void*> temp_dev;               // device temporaries
+        std::vector<void*> stale_host;             // outgrown staging buffers (hipHostFree drains the device: not inside an enqueue)
+        std::deque<std::vector<sb_column_read>> filter_tmp;   // the read columns of a filter replay's decodes (filter_freq)
+        size_t pipe_ev_used = 0;
+        sb::StageSlot* last_slot = nullptr;        // the staging slot of the last enqueued write call (its `done` event = results are back)
+        bool freq_pass_ran = false;                // this synchronize ran the Freq second pass (copies issued early are repeated)
+        std::vector<sb_column_read> freq_cols;     // the second pass's one-page columns (their READ_COL pendings point here)
+        std::vector<sb_page_meta> freq_metas;
+        std::vector<sb::ProfSpan> spans;           // (sb_ctx_profile) the launches to time; recycle_spans hands their events back
+
+        // END: the interval is over, its results are delivered.  REPLAY: its calls are about to be issued again (the caller has
+        // taken `calls` out): the page records of enqueued level calls stay pending, because those calls are not issued again
+        // -- copied into `rescued`, since the staging slots are free to be reused -- and every other pending result is dropped;
+        // `rescued` therefore stays too.  That is the whole difference.  (sticky is 0 in a replay: an interval that failed on the
+        // host is not replayed.)  Called with the stream and the copy stream drained.
+        enum Reset { END, REPLAY };
+        void reset(Reset how) {
+            if (how == REPLAY) {
+                std::vector<sb::Pending> keep;
+                for (auto& p : pending)
+                    if (p.kind == sb::Pending::NESTED_W || p.kind == sb::Pending::NESTED_R) {
+                        rescued.emplace_back(p.host, p.host + p.bytes);
+                        p.host = rescued.back().data();
+                        keep.push_back(p);
+                    }
+                pending.swap(keep);
+            } else {
+                pending.clear();
+                rescued.clear();
+            }
+            sticky = 0;
+            calls.clear();
+            for (void* p : stale_host) (void)hipHostFree(p);
+            stale_host.clear();
+            copybacks.clear();
+            pipe_ev_used = 0;
+            for (void* p : temp_dev) (void)hipFree(p);
+            temp_dev.clear();
+            filter_tmp.clear();
+            last_slot = nullptr;
+            freq_pass_ran = false;
+            freq_cols.clear();
+            freq_metas.clear();
+            spans.clear();   // (empty already: recycle_spans has handed the events back)
+        }
+    } iv;
     bool no_hints = false, in_replay = false;   // no_hints: SB_NO_HINTS=1, and during a replay
     uint64_t replays = 0;                       // sb_ctx_replays
     bool bin_fused = true;   // SB_BIN_FUSED=0: binary pages through the round-3 chain (A/B measurements, tests)
@@ -271,10 +321,21 @@ struct sb_ctx {
 
     int32_t fail(int32_t code, const std::string& msg) {
         last_error = msg;
-        if (!sticky) sticky = code;
+        if (!iv.sticky) iv.sticky = code;
         return code;
     }
 };
+
+// issues a call of the interval again (a replay: sb_api.hip, replay_interval)
+inline int32_t reissue(sb_ctx* ctx, sb_ctx::Call& cl) {
+    switch (cl.kind) {
+        case sb_ctx::Call::READ: return sb_read_columns(ctx, (sb_column_read*)cl.cols, cl.n, cl.mem);
+        case sb_ctx::Call::WRITE: return sb_write_columns(ctx, (sb_column_write*)cl.cols, cl.n, &cl.opts, cl.mem);
+        case sb_ctx::Call::FILTER: return sb_filter_columns(ctx, (sb_column_filter*)cl.cols, cl.n, cl.mem);
+        case sb_ctx::Call::FILTER_VAR: return sb_filter_columns_var(ctx, (sb_column_filter_var*)cl.cols, cl.n, cl.mem);
+    }
+    return SB_ERR_INVALID;
+}
 
 namespace sb {
 // brackets one kernel launch with events when profiling is on
@@ -302,7 +363,7 @@ struct KScope {
     ~KScope() {
         if (!ctx->profile) return;
         (void)hipEventRecord(sp.b, ctx->stream);
-        ctx->spans.push_back(sp);
+        ctx->iv.spans.push_back(sp);
     }
 };
 bool ensure(sb_ctx* ctx, DevBuf& b, size_t need);
