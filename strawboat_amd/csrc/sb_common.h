@@ -451,6 +451,15 @@ __device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v) {
     return v;
 }
 
+// exclusive scan on top of `carry` (wave-uniform), which leaves with the wave's total added: one step of a scan that a wave
+// makes 64 entries at a time
+__device__ __forceinline__ uint64_t wave_excl_scan64(uint64_t v, uint64_t& carry) {
+    const uint64_t incl = wave_incl_scan64(v);
+    const uint64_t excl = carry + incl - v;
+    carry += __shfl(incl, 63, 64);
+    return excl;
+}
+
 // Inclusive scan of the TILE_ROWS u32 entries of `a` (sidx layout), in place.  Thread t owns
 // entries [16t, 16t+16).  `wsum` is a 4-entry LDS scratch.  Returns the tile total.
 __device__ __forceinline__ uint32_t tile_incl_scan(uint32_t* a, uint32_t* wsum) {

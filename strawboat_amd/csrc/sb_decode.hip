@@ -29,6 +29,8 @@ namespace sb {
 
 __device__ __forceinline__ bool is_basic(uint32_t c) { return c <= 3; }
 __device__ __forceinline__ bool is_binary(int32_t t) { return t == SB_TYPE_BINARY || t == SB_TYPE_LARGE_BINARY; }
+// the 32 rows of a wave's ballot that lane 0 (rows 0 .. 31) or lane 32 (rows 32 .. 63) puts as one word
+__device__ __forceinline__ uint32_t ballot_half(uint64_t m) { return (threadIdx.x & 32) ? (uint32_t)(m >> 32) : (uint32_t)m; }
 
 __device__ __forceinline__ void push_job(InflateJob* q, uint32_t* cnt, const uint8_t* src, uint32_t csize,
                                          uint8_t* dst, uint32_t out_len, uint32_t codec, uint32_t page);
@@ -497,6 +499,38 @@ __device__ __forceinline__ bool rle_by_page(const ColDesc& c, const PageDesc& d)
            c.width <= 8;
 }
 
+// ---- def-level section of a nullable page: u32 def_len | ULEB128((ceil(N/8)<<1)|1) | bits  (read_basic.rs:36-63).
+// `cur` .. `end` is the page.  code == 0: `bits` are the validity bits of its N rows (null for a page of no rows that has
+// none) and `next` is the first byte behind the section; else the error and its site, which the caller raises its own way
+// (k_parse per lane, k_filter_null per workgroup).
+struct DefLevels {
+    const uint8_t* bits;
+    const uint8_t* next;
+    int32_t code;
+    uint32_t site;
+};
+__device__ __forceinline__ DefLevels parse_def_levels(const uint8_t* cur, const uint8_t* end, uint64_t N) {
+    if (end - cur < 4) return {nullptr, cur, SB_ERR_IO, 2};
+    const uint32_t def_len = ldu32(cur);
+    cur += 4;
+    if ((uint64_t)(end - cur) < def_len) return {nullptr, cur, SB_ERR_IO, 3};
+    if (def_len == 0) return {nullptr, cur, N != 0 ? SB_ERR_OUT_OF_SPEC : 0, 4};  // reference: validity length mismatch
+    uint64_t ind = 0;
+    uint32_t sh = 0, k = 0;
+    for (;;) {
+        if (k >= def_len || k >= 10) return {nullptr, cur, SB_ERR_OUT_OF_SPEC, 5};
+        uint8_t b = cur[k++];
+        ind |= (uint64_t)(b & 0x7F) << sh;
+        sh += 7;
+        if (!(b & 0x80)) break;
+    }
+    if (!(ind & 1)) return {nullptr, cur, SB_ERR_OUT_OF_SPEC, 6};  // RLE run: unreachable!() upstream
+    uint64_t nbytes = ind >> 1;
+    if (nbytes > def_len - k) nbytes = def_len - k;
+    if (nbytes * 8 < N) return {nullptr, cur, SB_ERR_OUT_OF_SPEC, 7};
+    return {cur + k, cur + def_len, 0, 0};
+}
+
 // (what a page asks of the wave afterwards: its tile entries)
 struct TileReq {
     uint32_t need, base, ntiles, col;
@@ -522,31 +556,11 @@ __device__ __forceinline__ TileReq parse_page(const DecodeArgs& a, const uint32_
     if (t.in_off + t.length > c.pages_len) FAIL(SB_ERR_IO, 1);
     const uint8_t* cur = c.pages + t.in_off;
     const uint8_t* end = cur + t.length;
-    // ---- def-level section: u32 def_len | ULEB128((ceil(N/8)<<1)|1) | bits  (read_basic.rs:36-63)
     if (c.nullable) {
-        if (end - cur < 4) FAIL(SB_ERR_IO, 2);
-        const uint32_t def_len = ldu32(cur);
-        cur += 4;
-        if ((uint64_t)(end - cur) < def_len) FAIL(SB_ERR_IO, 3);
-        if (def_len == 0) {
-            if (N != 0) FAIL(SB_ERR_OUT_OF_SPEC, 4);  // reference: validity length mismatch
-        } else {
-            uint64_t ind = 0;
-            uint32_t sh = 0, k = 0;
-            for (;;) {
-                if (k >= def_len || k >= 10) FAIL(SB_ERR_OUT_OF_SPEC, 5);
-                uint8_t b = cur[k++];
-                ind |= (uint64_t)(b & 0x7F) << sh;
-                sh += 7;
-                if (!(b & 0x80)) break;
-            }
-            if (!(ind & 1)) FAIL(SB_ERR_OUT_OF_SPEC, 6);  // RLE run: unreachable!() upstream
-            uint64_t nbytes = ind >> 1;
-            if (nbytes > def_len - k) nbytes = def_len - k;
-            if (nbytes * 8 < N) FAIL(SB_ERR_OUT_OF_SPEC, 7);
-            d.def_bits = cur + k;
-        }
-        cur += def_len;
+        const DefLevels dl = parse_def_levels(cur, end, N);
+        if (dl.code) FAIL(dl.code, dl.site);
+        d.def_bits = dl.bits;
+        cur = dl.next;
     }
     // ---- first block header
     if (end - cur < 9) FAIL(SB_ERR_IO, 8);
@@ -2266,6 +2280,32 @@ __global__ void __launch_bounds__(WG) k_bin_tile_scan(DecodeArgs a) {
 // One WAVE per column, a lane per page, 64 pages per step: the bases are exclusive wave scans of the pages' value bytes and
 // last offsets plus the carry of the steps before.  (One thread per column walked its pages one dependent load after the
 // other: 76 us for the 153 pages of a C4 column, and a column of many short pages by the millisecond.)
+// This walk is scan_column_pages, which the filter's k_filter_bin_base shares.  The kernel says what it sums — bytes(d) of the
+// pages that are ok — and what it keeps of the outcome: place(p, d, in, base, fits), called by ALL lanes (`in` false for the
+// lanes behind the column's last page), `base` the page's place in the column's value area and `fits` whether its bytes end
+// within values_cap.  The walk itself queues the compressed value blocks (Basic, not None) of the ok pages that fit into
+// queue B, to be inflated at `base`, and raises a column whose bytes exceed values_cap; it returns their total.
+template <class B, class Pl>
+__device__ __forceinline__ uint64_t scan_column_pages(const DecodeArgs& a, const ColDesc& c, B bytes, Pl place) {
+    const uint32_t lane = threadIdx.x & 63;
+    uint64_t vbase = 0;   // (wave-uniform carry)
+    for (uint32_t k0 = 0; k0 < c.n_pages; k0 += 64) {
+        const bool in = k0 + lane < c.n_pages;
+        const uint32_t p = c.first_page + min(k0 + lane, c.n_pages - 1);
+        const PageDesc d = a.descs[p];
+        const bool was_ok = in && d.ok;
+        // a page that was not ok adds nothing; one that does not fit still counts (the column's total is reported)
+        const uint64_t vb = was_ok ? bytes(d) : 0;
+        const uint64_t my_vbase = wave_excl_scan64(vb, vbase);
+        const bool fits = my_vbase + vb <= c.values_cap;
+        place(p, d, in, my_vbase, fits);
+        // (a Zstd block is in queue Z already when the call has one — k_parse, JOB_REL: its place is val_base)
+        const bool job = was_ok && fits && is_basic(d.codec) && d.codec != SB_CODEC_NONE && !(d.codec == SB_CODEC_ZSTD && a.jobs_z);
+        push_job_if(job, a.jobs_b, a.job_counts + 1, d.vbody, d.vcsize, c.values + my_vbase, d.vusize, d.codec, p);
+    }
+    if (lane == 0 && vbase > c.values_cap) raise(a.status, SB_ERR_INVALID, c.first_page, 300);
+    return vbase;
+}
 __device__ __forceinline__ void colscan_column(const DecodeArgs& a, uint64_t* col_values_len, const uint32_t ci) {
     const uint32_t lane = threadIdx.x & 63;
     const ColDesc c = a.cols[ci];
@@ -2273,42 +2313,20 @@ __device__ __forceinline__ void colscan_column(const DecodeArgs& a, uint64_t* co
         if (lane == 0) col_values_len[ci] = c.ptype == SB_TYPE_BOOLEAN ? (c.rows + 7) / 8 : c.rows * c.width;
         return;
     }
-    uint64_t vbase = 0, obase = 0;   // (wave-uniform carries)
-    for (uint32_t k0 = 0; k0 < c.n_pages; k0 += 64) {
-        const bool in = k0 + lane < c.n_pages;
-        const uint32_t p = c.first_page + min(k0 + lane, c.n_pages - 1);
-        const PageDesc d = a.descs[p];
-        const bool was_ok = in && d.ok;
-        // a page that was not ok adds nothing; one that does not fit still counts (the column's values_len is reported)
-        const uint64_t vb = was_ok ? d.val_bytes : 0, ob = was_ok ? d.off_last : 0;
-        uint64_t vi = vb, oi = ob;
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint64_t uv = __shfl_up(vi, o, 64), uo = __shfl_up(oi, o, 64);
-            if ((int)lane >= o) {
-                vi += uv;
-                oi += uo;
-            }
-        }
-        const uint64_t my_vbase = vbase + vi - vb;
-        // page 0's offsets are taken verbatim (incl. offsets[0]); later pages add the running last offset
-        const uint64_t my_obase = obase + oi - ob;
-        // a page whose value bytes do not fit the caller's buffer is not expanded at all (the tile kernels
-        // skip !ok pages): nothing is written past values_cap, the column's values_len is still reported
-        const bool fits = my_vbase + d.val_bytes <= c.values_cap;
-        if (in) {
-            a.descs[p].val_base = my_vbase;
+    uint64_t obase = 0;
+    const uint64_t values_len = scan_column_pages(
+        a, c, [](const PageDesc& d) { return d.val_bytes; },
+        [&](uint32_t p, const PageDesc& d, bool in, uint64_t base, bool fits) {
+            // page 0's offsets are taken verbatim (incl. offsets[0]); later pages add the running last offset
+            const uint64_t my_obase = wave_excl_scan64(in && d.ok ? d.off_last : 0, obase);
+            if (!in) return;
+            a.descs[p].val_base = base;
             a.descs[p].off_base = my_obase;
+            // a page whose value bytes do not fit the caller's buffer is not expanded at all (the tile kernels
+            // skip !ok pages): nothing is written past values_cap, the column's values_len is still reported
             if (!fits && d.ok) a.descs[p].ok = 0;
-        }
-        const bool job = was_ok && fits && is_basic(d.codec) && d.codec != SB_CODEC_NONE && !(d.codec == SB_CODEC_ZSTD && a.jobs_z);
-        push_job_if(job, a.jobs_b, a.job_counts + 1, d.vbody, d.vcsize, c.values + my_vbase, d.vusize, d.codec, p);
-        vbase += __shfl(vi, 63, 64);
-        obase += __shfl(oi, 63, 64);
-    }
-    if (lane == 0) {
-        col_values_len[ci] = vbase;
-        if (vbase > c.values_cap) raise(a.status, SB_ERR_INVALID, c.first_page, 300);
-    }
+        });
+    if (lane == 0) col_values_len[ci] = values_len;
 }
 __global__ void __launch_bounds__(64) k_colscan(DecodeArgs a, uint64_t* col_values_len) {
     const uint32_t ci = blockIdx.x;   // (one wave per column)
@@ -2519,8 +2537,7 @@ __device__ void expand_bool(const ColDesc& c, const PageTask& t, const PageDesc&
             }
             const uint64_t m = __ballot(bit);
             if ((tid & 31) == 0 && i < rows) {
-                const uint32_t half = (tid & 32) ? (uint32_t)(m >> 32) : (uint32_t)m;
-                bitmap_put(c.values, t.out_row + r0 + i, half, min(32u, rows - i), c.bits_aligned);
+                bitmap_put(c.values, t.out_row + r0 + i, ballot_half(m), min(32u, rows - i), c.bits_aligned);
             }
         }
     }
@@ -2722,20 +2739,38 @@ __global__ void __launch_bounds__(WG) k_expand(DecodeArgs a) {
 constexpr int RLE_RPT = 4;                      // runs per thread per chunk
 constexpr uint32_t RLE_CHUNK = WG * RLE_RPT;    // 1024 runs
 
-template <int W>
-__device__ void expand_rle_page(const ColDesc& c, const PageTask& t, const PageDesc& d, uint32_t* s_flag, uint8_t* s_vals_raw,
-                                uint32_t* s_w, uint64_t* s_w64, Status* st, uint32_t page, uint32_t part = 0, uint32_t parts = 1,
-                                const uint64_t* sums = nullptr /* rows covered by each part's runs (k_rle_sums), parts > 1 */) {
-    constexpr int REC = 4 + W;
+// A long page is shared by `parts` workgroups (grid y): each takes a range of run chunks — run records [b0, b1) — and
+// its first row comes from the sums of the ranges before it (k_rle_sums, which cuts the page with this same function).
+struct RlePart {
+    uint32_t b0;   // (a page has fewer than 2^32 / 5 records and a part starts at most one range behind them)
+    uint64_t b1;   // ~0 for the part that owns the end: it reports runs that stop short of N
+    bool none;     // a later part of a page whose runs end before it
+};
+__device__ __forceinline__ RlePart rle_part(uint32_t max_runs, uint32_t part, uint32_t parts) {
+    const uint32_t nchunks = (max_runs + RLE_CHUNK - 1) / RLE_CHUNK, cpp = (nchunks + parts - 1) / parts;
+    const uint32_t b0 = part * cpp * RLE_CHUNK;
+    const bool owns_end = (uint64_t)(part + 1) * cpp >= nchunks;
+    return {b0, owns_end ? ~0ull : (uint64_t)(part + 1) * cpp * RLE_CHUNK, part && b0 >= max_runs};
+}
+
+// The walk of k_expand_rle and k_filter_rle.  What the kernel wants of it is a policy P:
+//   P::Rec                       what is kept of a run and staged in LDS (p.s_rec, RLE_CHUNK entries)
+//   p.rec_bytes()                4 + the width of a value: the stride of the run records
+//   p.load(v, in)                the Rec of the run whose value is at v (`in` false: behind the page's last record)
+//   p.rows(tile_lo, lo, hi, A)   by the whole workgroup, for rows [lo, hi) of the tile that starts at tile_lo:
+//                                row r belongs to run p.s_rec[A + s_flag[sidx(r - tile_lo)]] of the chunk
+template <class P>
+__device__ void rle_page_walk(const P& p, const ColDesc& c, const PageTask& t, const PageDesc& d, uint32_t* s_flag, uint32_t* s_w,
+                              uint64_t* s_w64, Status* st, uint32_t page, uint32_t part, uint32_t parts,
+                              const uint64_t* sums /* rows covered by each part's runs (k_rle_sums), parts > 1 */) {
+    const uint32_t REC = p.rec_bytes();
     const int tid = threadIdx.x;
     const uint64_t N = t.num_values;
-    uint8_t* dst = c.values + t.out_row * W;
     const uint8_t* body = d.body;
     const uint8_t* page_end = c.pages + t.in_off + t.length;
     const uint32_t max_runs = (uint32_t)((uint64_t)(page_end - body) / REC);
-    Val<W>* s_vals = (Val<W>*)s_vals_raw;
     uint32_t ncnt[RLE_RPT];
-    Val<W> nval[RLE_RPT];
+    typename P::Rec nrec[RLE_RPT];
     auto fetch = [&](uint32_t base) {
 #pragma unroll
         for (int j = 0; j < RLE_RPT; j++) {
@@ -2743,20 +2778,15 @@ __device__ void expand_rle_page(const ColDesc& c, const PageTask& t, const PageD
             const bool in = k < max_runs;
             const uint8_t* r = body + (uint64_t)(in ? k : 0) * REC;
             ncnt[j] = in ? ldu32(r) : 0;
-            nval[j] = in ? ld_val<W>(r + 4) : Val<W>{};
+            nrec[j] = p.load(r + 4, in);
         }
     };
-    // a long page is shared by `parts` workgroups: each takes a range of run chunks, its first row comes from the sums of
-    // the ranges before it
-    const uint32_t nchunks = (max_runs + RLE_CHUNK - 1) / RLE_CHUNK, cpp = (nchunks + parts - 1) / parts;
-    const uint32_t b0 = part * cpp * RLE_CHUNK;
-    const bool owns_end = (uint64_t)(part + 1) * cpp >= nchunks;
-    const uint64_t b1 = owns_end ? ~0ull : (uint64_t)(part + 1) * cpp * RLE_CHUNK;
-    if (part && b0 >= max_runs) return;   // (the part that owns the end reports runs that stop short of N)
+    const RlePart pt = rle_part(max_runs, part, parts);
+    if (pt.none) return;
     uint64_t carry = 0;  // rows covered by the chunks before this one
     for (uint32_t q = 0; q < part; q++) carry += sums[q];
-    if (max_runs) fetch(b0);
-    for (uint64_t base64 = b0; carry < N && base64 < b1; base64 += RLE_CHUNK) {
+    if (max_runs) fetch(pt.b0);
+    for (uint64_t base64 = pt.b0; carry < N && base64 < pt.b1; base64 += RLE_CHUNK) {
         const uint32_t base = (uint32_t)base64;
         if (base64 >= max_runs) {
             if (tid == 0) raise(st, SB_ERR_IO, page, 200);  // runs end before N rows (read_u32 EOF upstream)
@@ -2766,7 +2796,7 @@ __device__ void expand_rle_page(const ColDesc& c, const PageTask& t, const PageD
 #pragma unroll
         for (int j = 0; j < RLE_RPT; j++) {
             cnt[j] = ncnt[j];
-            s_vals[tid * RLE_RPT + j] = nval[j];
+            p.s_rec[tid * RLE_RPT + j] = nrec[j];
         }
         if (base + RLE_CHUNK < max_runs) fetch(base + RLE_CHUNK);
         // start rows of my runs
@@ -2777,7 +2807,7 @@ __device__ void expand_rle_page(const ColDesc& c, const PageTask& t, const PageD
             loc[j] = run;
         }
         const uint64_t incl = wave_incl_scan64(run);
-        __syncthreads();  // previous chunk's readers of s_w64 / s_vals are done; my s_vals stores are ordered before the tile loop's barriers
+        __syncthreads();  // previous chunk's readers of s_w64 / s_rec are done; my s_rec stores are ordered before the tile loop's barriers
         if ((tid & 63) == 63) s_w64[tid >> 6] = incl;
         __syncthreads();
         uint64_t pre = carry + incl - run;
@@ -2795,6 +2825,7 @@ __device__ void expand_rle_page(const ColDesc& c, const PageTask& t, const PageD
 #pragma unroll
         for (int j = 0; j < RLE_RPT; j++)
             if (start[j] < N && start[j] + cnt[j] > N) raise(st, SB_ERR_OUT_OF_SPEC, page, 202);
+        // (a chunk's rows start and end anywhere in a tile: p.rows gets the part of the tile that is the chunk's)
         for (uint64_t tile_lo = S0 / TILE_ROWS * TILE_ROWS; tile_lo < S1; tile_lo += TILE_ROWS) {
             const uint64_t lo = max(S0, tile_lo), hi = min(S1, tile_lo + TILE_ROWS);
             static_assert(SIDX_WORDS % 4 == 0, "16-byte clears");
@@ -2817,11 +2848,7 @@ __device__ void expand_rle_page(const ColDesc& c, const PageTask& t, const PageD
             const uint32_t A = s_w[0] + s_w[1] + s_w[2] + s_w[3] - 1;
             __syncthreads();
             tile_incl_scan(s_flag, s_w);
-            const uint32_t off = (uint32_t)(lo - tile_lo);
-            emit_rows<W>(dst + lo * W, (uint32_t)(hi - lo), [&](uint32_t i) {
-                const uint32_t k = A + s_flag[sidx((int)(off + i))];
-                return s_vals[k];
-            });
+            p.rows(tile_lo, lo, hi, A, s_flag);
             __syncthreads();  // s_flag / s_w are reused by the next tile
         }
         carry += chunk_total;
@@ -2830,6 +2857,26 @@ __device__ void expand_rle_page(const ColDesc& c, const PageTask& t, const PageD
             return;
         }
     }
+}
+
+// k_expand_rle's policy: a run is its value; rows gather their run's value from LDS, 16-byte stores
+template <int W>
+struct RleExpand {
+    using Rec = Val<W>;
+    Val<W>* s_rec;
+    uint8_t* dst;   // the page's first row in the column's values
+    __device__ __forceinline__ uint32_t rec_bytes() const { return 4 + W; }
+    __device__ __forceinline__ Val<W> load(const uint8_t* v, bool in) const { return in ? ld_val<W>(v) : Val<W>{}; }
+    __device__ __forceinline__ void rows(uint64_t tile_lo, uint64_t lo, uint64_t hi, uint32_t A, const uint32_t* s_flag) const {
+        const uint32_t off = (uint32_t)(lo - tile_lo);
+        emit_rows<W>(dst + lo * W, (uint32_t)(hi - lo), [&](uint32_t i) { return s_rec[A + s_flag[sidx((int)(off + i))]]; });
+    }
+};
+template <int W>
+__device__ __forceinline__ void expand_rle_page(const ColDesc& c, const PageTask& t, const PageDesc& d, uint32_t* s_flag, uint8_t* s_vals,
+                                                uint32_t* s_w, uint64_t* s_w64, Status* st, uint32_t page, uint32_t part, uint32_t parts,
+                                                const uint64_t* sums) {
+    rle_page_walk(RleExpand<W>{(Val<W>*)s_vals, c.values + t.out_row * W}, c, t, d, s_flag, s_w, s_w64, st, page, part, parts, sums);
 }
 
 // the page's def-level bits -> the column's validity bitmap (all tiles at once)
@@ -2881,7 +2928,7 @@ __global__ void __launch_bounds__(WG) k_expand_rle(DecodeArgs a) {
     }
 }
 
-// rows covered by the runs of every part of a long RLE page (grid = pages x parts, parts > 1: see expand_rle_page)
+// rows covered by the runs of every part of a long RLE page (grid = pages x parts, parts > 1: see rle_part)
 __global__ void __launch_bounds__(WG) k_rle_sums(DecodeArgs a) {
     __shared__ uint64_t s_w64[4];
     if (a.job_counts[4] == 0) return;
@@ -2893,10 +2940,10 @@ __global__ void __launch_bounds__(WG) k_rle_sums(DecodeArgs a) {
     const uint32_t REC = 4 + c.width;
     const uint8_t* page_end = c.pages + t.in_off + t.length;
     const uint32_t max_runs = (uint32_t)((uint64_t)(page_end - d.body) / REC);
-    const uint32_t nchunks = (max_runs + RLE_CHUNK - 1) / RLE_CHUNK, cpp = (nchunks + parts - 1) / parts;
-    const uint64_t r0 = (uint64_t)part * cpp * RLE_CHUNK, r1 = min((uint64_t)max_runs, r0 + (uint64_t)cpp * RLE_CHUNK);
-    uint64_t sum = 0;
-    for (uint64_t k = r0 + threadIdx.x; k < r1; k += WG) sum += ldu32(d.body + k * REC);
+    const RlePart pt = rle_part(max_runs, part, parts);
+    const uint64_t r1 = min((uint64_t)max_runs, pt.b1);
+    uint64_t sum = 0;   // (stays 0 for a part behind the page's last run)
+    for (uint64_t k = (uint64_t)pt.b0 + threadIdx.x; k < r1; k += WG) sum += ldu32(d.body + k * REC);
     sum = wave_incl_scan64(sum);
     if ((threadIdx.x & 63) == 63) s_w64[threadIdx.x >> 6] = sum;
     __syncthreads();

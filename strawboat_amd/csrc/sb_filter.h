@@ -108,13 +108,31 @@ __device__ __forceinline__ void filter_span(const FilterSink& k, uint64_t lo, ui
             const uint64_t row = g0 + (uint64_t)u * WG + tid;
             const uint64_t m = __ballot(bit[u]);
             if ((tid & 31) == 0 && row < hi && row + 32 > lo) {
-                uint32_t half = (tid & 32) ? (uint32_t)(m >> 32) : (uint32_t)m;
+                uint32_t half = ballot_half(m);
                 if (k.def_bits) half &= tile_bits_load(k.def_bits, row, k.N);
                 const uint64_t glo = max(row, lo), ghi = min(row + 32, hi);
                 sel_put(k.sel, k.out_row + glo, half >> (uint32_t)(glo - row), (uint32_t)(ghi - glo), k.combine);
             }
         }
     }
+}
+
+// Rows [lo, hi) of a tile whose dictionary indices are in s_a (u32_tile_to_lds): a row whose index e is below D satisfies
+// what look(e) says — a bit of a table (tab_bit) or the compare of the gathered entry — and a row whose index is not
+// satisfies nothing.  True when there was such a row: the caller raises it at the site where a read finds it.
+__device__ __forceinline__ bool tab_bit(const uint32_t* tab, uint32_t e) { return (tab[e >> 5] >> (e & 31)) & 1u; }
+template <class L>
+__device__ __forceinline__ bool filter_dict_rows(const FilterSink& k, uint64_t lo, uint64_t hi, const uint32_t* s_a, uint32_t D, L look) {
+    bool bad = false;
+    filter_span(k, lo, hi, [&](uint64_t r) {
+        const uint32_t e = s_a[sidx((int)(r - lo))];
+        if (e >= D) {
+            bad = true;
+            return false;
+        }
+        return look(e);
+    });
+    return bad;
 }
 
 // ---- tiles of None / OneValue / Dict / bit-packed / inflated pages (the pages k_expand has tiles for)
@@ -160,31 +178,17 @@ __device__ void filter_tile(const DecodeArgs& a, const FilterCol* fcols, uint32_
             u32_tile_to_lds(is, tt.tile, rows, s_a, s_w);
             const uint8_t* dict = d.dict;
             const uint32_t D = d.dict_n;
-            bool bad = false;
+            bool bad;
             if (D <= FILTER_DICT_BITS) {
                 for (uint32_t e0 = 0; e0 < D; e0 += WG) {
                     const uint32_t e = e0 + threadIdx.x;
                     const uint64_t m = __ballot(e < D && flt_eval(cmp, flt_load(dict + (uint64_t)e * w, w)));
-                    if ((threadIdx.x & 31) == 0 && e < D) s_tab[e >> 5] = (threadIdx.x & 32) ? (uint32_t)(m >> 32) : (uint32_t)m;
+                    if ((threadIdx.x & 31) == 0 && e < D) s_tab[e >> 5] = ballot_half(m);
                 }
                 __syncthreads();
-                filter_span(k, lo, hi, [&](uint64_t r) {
-                    const uint32_t e = s_a[sidx((int)(r - lo))];
-                    if (e >= D) {
-                        bad = true;
-                        return false;
-                    }
-                    return ((s_tab[e >> 5] >> (e & 31)) & 1u) != 0;
-                });
-            } else {
-                filter_span(k, lo, hi, [&](uint64_t r) {
-                    const uint32_t e = s_a[sidx((int)(r - lo))];
-                    if (e >= D) {
-                        bad = true;
-                        return false;
-                    }
-                    return flt_eval(cmp, flt_load(dict + (uint64_t)e * w, w));
-                });
+                bad = filter_dict_rows(k, lo, hi, s_a, D, [&](uint32_t e) { return tab_bit(s_tab, e); });
+            } else {   // the row's entry is gathered and compared, as the decoder gathers it
+                bad = filter_dict_rows(k, lo, hi, s_a, D, [&](uint32_t e) { return flt_eval(cmp, flt_load(dict + (uint64_t)e * w, w)); });
             }
             if (bad) raise(a.status, SB_ERR_OUT_OF_SPEC, tt.page, 400);
             break;
@@ -214,106 +218,20 @@ __global__ void __launch_bounds__(WG) k_filter(DecodeArgs a, const FilterCol* fc
     }
 }
 
-// ---- RLE pages, one workgroup per page (or per part of a long page): expand_rle_page's walk with the values of a chunk's
-// runs replaced by their predicate bytes; the rows of a chunk start and end anywhere in a selection word, which filter_span
-// and sel_put allow for
-__device__ void filter_rle_page(const ColDesc& c, const PageTask& t, const PageDesc& d, const FilterSink& k, const FilterCmp& cmp,
-                                uint32_t* s_flag, uint8_t* s_pred, uint32_t* s_w, uint64_t* s_w64, Status* st, uint32_t page,
-                                uint32_t part, uint32_t parts, const uint64_t* sums) {
-    const uint32_t w = c.width, REC = 4 + w;
-    const int tid = threadIdx.x;
-    const uint64_t N = t.num_values;
-    const uint8_t* body = d.body;
-    const uint8_t* page_end = c.pages + t.in_off + t.length;
-    const uint32_t max_runs = (uint32_t)((uint64_t)(page_end - body) / REC);
-    uint32_t ncnt[RLE_RPT];
-    bool nbit[RLE_RPT];
-    auto fetch = [&](uint32_t base) {
-#pragma unroll
-        for (int j = 0; j < RLE_RPT; j++) {
-            const uint32_t r = base + (uint32_t)tid * RLE_RPT + j;
-            const bool in = r < max_runs;
-            const uint8_t* rec = body + (uint64_t)(in ? r : 0) * REC;
-            ncnt[j] = in ? ldu32(rec) : 0;
-            nbit[j] = in && flt_eval(cmp, flt_load(rec + 4, w));
-        }
-    };
-    const uint32_t nchunks = (max_runs + RLE_CHUNK - 1) / RLE_CHUNK, cpp = (nchunks + parts - 1) / parts;
-    const uint32_t b0 = part * cpp * RLE_CHUNK;
-    const bool owns_end = (uint64_t)(part + 1) * cpp >= nchunks;
-    const uint64_t b1 = owns_end ? ~0ull : (uint64_t)(part + 1) * cpp * RLE_CHUNK;
-    if (part && b0 >= max_runs) return;
-    uint64_t carry = 0;
-    for (uint32_t q = 0; q < part; q++) carry += sums[q];
-    if (max_runs) fetch(b0);
-    for (uint64_t base64 = b0; carry < N && base64 < b1; base64 += RLE_CHUNK) {
-        const uint32_t base = (uint32_t)base64;
-        if (base64 >= max_runs) {
-            if (tid == 0) raise(st, SB_ERR_IO, page, 200);
-            return;
-        }
-        uint32_t cnt[RLE_RPT];
-        bool bit[RLE_RPT];
-#pragma unroll
-        for (int j = 0; j < RLE_RPT; j++) {
-            cnt[j] = ncnt[j];
-            bit[j] = nbit[j];
-        }
-        if (base + RLE_CHUNK < max_runs) fetch(base + RLE_CHUNK);
-        uint64_t loc[RLE_RPT], run = 0;
-#pragma unroll
-        for (int j = 0; j < RLE_RPT; j++) {
-            run += cnt[j];
-            loc[j] = run;
-        }
-        const uint64_t incl = wave_incl_scan64(run);
-        __syncthreads();  // the previous chunk's readers of s_w64 / s_pred are done
-#pragma unroll
-        for (int j = 0; j < RLE_RPT; j++) s_pred[tid * RLE_RPT + j] = bit[j] ? 1 : 0;
-        if ((tid & 63) == 63) s_w64[tid >> 6] = incl;
-        __syncthreads();
-        uint64_t pre = carry + incl - run;
-        const int wv = tid >> 6;
-        if (wv > 0) pre += s_w64[0];
-        if (wv > 1) pre += s_w64[1];
-        if (wv > 2) pre += s_w64[2];
-        const uint64_t chunk_total = s_w64[0] + s_w64[1] + s_w64[2] + s_w64[3];
-        uint64_t start[RLE_RPT];
-#pragma unroll
-        for (int j = 0; j < RLE_RPT; j++) start[j] = pre + (j ? loc[j - 1] : 0);
-        const uint64_t S0 = carry, S1 = min(N, carry + chunk_total);
-#pragma unroll
-        for (int j = 0; j < RLE_RPT; j++)
-            if (start[j] < N && start[j] + cnt[j] > N) raise(st, SB_ERR_OUT_OF_SPEC, page, 202);
-        for (uint64_t tile_lo = S0 / TILE_ROWS * TILE_ROWS; tile_lo < S1; tile_lo += TILE_ROWS) {
-            const uint64_t lo = max(S0, tile_lo), hi = min(S1, tile_lo + TILE_ROWS);
-            for (int i = tid; i < SIDX_WORDS / 4; i += WG) ((u32x4*)s_flag)[i] = u32x4{0, 0, 0, 0};
-            uint32_t le = 0;
-#pragma unroll
-            for (int j = 0; j < RLE_RPT; j++) le += (base + (uint32_t)tid * RLE_RPT + j < max_runs && start[j] <= lo) ? 1u : 0u;
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < RLE_RPT; j++)
-                if (base + (uint32_t)tid * RLE_RPT + j < max_runs && start[j] > lo && start[j] < hi)
-                    atomicAdd(&s_flag[sidx((int)(start[j] - tile_lo))], 1u);
-            uint32_t v = le;
-#pragma unroll
-            for (int dlt = 32; dlt > 0; dlt >>= 1) v += __shfl_down(v, dlt, 64);
-            if ((tid & 63) == 0) s_w[tid >> 6] = v;
-            __syncthreads();
-            const uint32_t A = s_w[0] + s_w[1] + s_w[2] + s_w[3] - 1;
-            __syncthreads();
-            tile_incl_scan(s_flag, s_w);
-            filter_span(k, lo, hi, [&](uint64_t r) { return s_pred[A + s_flag[sidx((int)(r - tile_lo))]] != 0; });
-            __syncthreads();  // s_flag / s_w are reused by the next tile
-        }
-        carry += chunk_total;
-        if (chunk_total == 0 && base + RLE_CHUNK >= max_runs && carry < N) {
-            if (tid == 0) raise(st, SB_ERR_IO, page, 200);
-            return;
-        }
+// ---- RLE pages, one workgroup per page (or per part of a long page): rle_page_walk (sb_decode.hip) with this policy.
+// A run is one predicate BYTE, its value compared once; rows gather their run's byte.  The rows of a chunk start and end
+// anywhere in a selection word, which filter_span and sel_put allow for.
+struct RleFilter {
+    using Rec = uint8_t;
+    uint8_t* s_rec;
+    FilterSink k;
+    FilterCmp cmp;
+    __device__ __forceinline__ uint32_t rec_bytes() const { return 4 + cmp.w; }
+    __device__ __forceinline__ uint8_t load(const uint8_t* v, bool in) const { return in && flt_eval(cmp, flt_load(v, cmp.w)); }
+    __device__ __forceinline__ void rows(uint64_t tile_lo, uint64_t lo, uint64_t hi, uint32_t A, const uint32_t* s_flag) const {
+        filter_span(k, lo, hi, [&](uint64_t r) { return s_rec[A + s_flag[sidx((int)(r - tile_lo))]] != 0; });
     }
-}
+};
 
 __global__ void __launch_bounds__(WG) k_filter_rle(DecodeArgs a, const FilterCol* fcols) {
     __shared__ __attribute__((aligned(16))) uint32_t s_flag[SIDX_WORDS];
@@ -330,12 +248,12 @@ __global__ void __launch_bounds__(WG) k_filter_rle(DecodeArgs a, const FilterCol
     if (f.op >= SB_PRED_IS_NULL) return;
     const uint32_t part = blockIdx.y, parts = gridDim.y;
     const uint64_t* sums = parts > 1 ? a.rle_sums + (uint64_t)p * parts : nullptr;
-    const FilterSink k{f.sel, d.def_bits, t.out_row, t.num_values, f.combine};
-    filter_rle_page(c, t, d, k, filter_cmp(f, c.width), s_flag, s_pred, s_w, s_w64, a.status, p, part, parts, sums);
+    const RleFilter pol{s_pred, FilterSink{f.sel, d.def_bits, t.out_row, t.num_values, f.combine}, filter_cmp(f, c.width)};
+    rle_page_walk(pol, c, t, d, s_flag, s_w, s_w64, a.status, p, part, parts, sums);
 }
 
 // ---- IS_NULL / IS_NOT_NULL: the def-level section of every page of such a column (u32 def_len | ULEB128 | bits,
-// read_basic.rs:36-63; the checks and their sites are k_parse's), one workgroup per page
+// parse_def_levels, which k_parse reads it with as well), one workgroup per page
 __global__ void __launch_bounds__(WG) k_filter_null(DecodeArgs a, const FilterCol* fcols) {
     const uint32_t p = blockIdx.x;
     const PageTask t = a.tasks[p];
@@ -345,36 +263,15 @@ __global__ void __launch_bounds__(WG) k_filter_null(DecodeArgs a, const FilterCo
     const uint64_t N = t.num_values;
     if (!N) return;
     const uint8_t* def = nullptr;
-#define NFAIL(code, tag)                                           \
-    do {                                                           \
-        if (threadIdx.x == 0) raise(a.status, (code), p, (tag));   \
-        return;                                                    \
-    } while (0)
     if (f.ptype != SB_TYPE_NULL && c.nullable) {
-        if (t.in_off + t.length > c.pages_len) NFAIL(SB_ERR_IO, 1);
-        const uint8_t* cur = c.pages + t.in_off;
-        const uint8_t* end = cur + t.length;
-        if (end - cur < 4) NFAIL(SB_ERR_IO, 2);
-        const uint32_t def_len = ldu32(cur);
-        cur += 4;
-        if ((uint64_t)(end - cur) < def_len) NFAIL(SB_ERR_IO, 3);
-        if (def_len == 0) NFAIL(SB_ERR_OUT_OF_SPEC, 4);
-        uint64_t ind = 0;
-        uint32_t sh = 0, n = 0;
-        for (;;) {
-            if (n >= def_len || n >= 10) NFAIL(SB_ERR_OUT_OF_SPEC, 5);
-            const uint8_t b = cur[n++];
-            ind |= (uint64_t)(b & 0x7F) << sh;
-            sh += 7;
-            if (!(b & 0x80)) break;
+        DefLevels dl{nullptr, nullptr, SB_ERR_IO, 1};   // (site 1 is k_parse's as well: the page lies in the column's bytes)
+        if (t.in_off + t.length <= c.pages_len) dl = parse_def_levels(c.pages + t.in_off, c.pages + t.in_off + t.length, N);
+        if (dl.code) {
+            if (threadIdx.x == 0) raise(a.status, dl.code, p, dl.site);
+            return;
         }
-        if (!(ind & 1)) NFAIL(SB_ERR_OUT_OF_SPEC, 6);
-        uint64_t nbytes = ind >> 1;
-        if (nbytes > def_len - n) nbytes = def_len - n;
-        if (nbytes * 8 < N) NFAIL(SB_ERR_OUT_OF_SPEC, 7);
-        def = cur + n;
+        def = dl.bits;
     }
-#undef NFAIL
     const uint32_t none = f.ptype == SB_TYPE_NULL ? 0u : 0xFFFFFFFFu;   // validity of a page without a def-level section
     const uint64_t nwords = (N + 31) / 32;
     for (uint64_t g = threadIdx.x; g < nwords; g += WG) {

@@ -70,36 +70,20 @@ __device__ __forceinline__ bool bin_eval(const uint8_t* v, uint32_t len, const B
     return (l.mask >> r) & 1u;
 }
 
-// ---- where the inflated value blocks of a column go: one wave per column (k_colscan's walk with vusize for the pages whose
-// values block is compressed and 0 for the others; no offset bases, no values_len)
+// ---- where the inflated value blocks of a column go: one wave per column, scan_column_pages (sb_decode.hip) summing vusize
+// for the pages whose values block is compressed and 0 for the others; no offset bases, no values_len
 __global__ void __launch_bounds__(64) k_filter_bin_base(DecodeArgs a, const FilterCol* fcols) {
-    const uint32_t ci = blockIdx.x, lane = threadIdx.x & 63;
+    const uint32_t ci = blockIdx.x;
     const ColDesc c = a.cols[ci];
     if (is_binary(c.ptype) && fcols[ci].kind == FK_BYTES) {
-        uint64_t vbase = 0;
-        for (uint32_t k0 = 0; k0 < c.n_pages; k0 += 64) {
-            const bool in = k0 + lane < c.n_pages;
-            const uint32_t p = c.first_page + min(k0 + lane, c.n_pages - 1);
-            const PageDesc d = a.descs[p];
-            const bool staged = in && d.ok && is_basic(d.codec) && d.codec != SB_CODEC_NONE;
-            const uint64_t vb = staged ? d.vusize : 0;
-            uint64_t vi = vb;
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint64_t uv = __shfl_up(vi, o, 64);
-                if ((int)lane >= o) vi += uv;
-            }
-            const uint64_t my_vbase = vbase + vi - vb;
-            const bool fits = my_vbase + vb <= c.values_cap;
-            if (staged) {
-                a.descs[p].val_base = my_vbase;
-                if (!fits) a.descs[p].ok = 0;   // (nothing is inflated or compared; the column raises below)
-            }
-            // (a Zstd block is in queue Z already when the call has one — k_parse, JOB_REL: its place is val_base)
-            const bool job = staged && fits && !(d.codec == SB_CODEC_ZSTD && a.jobs_z);
-            push_job_if(job, a.jobs_b, a.job_counts + 1, d.vbody, d.vcsize, c.values + my_vbase, d.vusize, d.codec, p);
-            vbase += __shfl(vi, 63, 64);
-        }
-        if (lane == 0 && vbase > c.values_cap) raise(a.status, SB_ERR_INVALID, c.first_page, 300);
+        auto staged = [](const PageDesc& d) { return is_basic(d.codec) && d.codec != SB_CODEC_NONE; };
+        scan_column_pages(
+            a, c, [&](const PageDesc& d) { return staged(d) ? d.vusize : 0u; },
+            [&](uint32_t p, const PageDesc& d, bool in, uint64_t base, bool fits) {
+                if (!(in && d.ok && staged(d))) return;
+                a.descs[p].val_base = base;
+                if (!fits) a.descs[p].ok = 0;   // (nothing is inflated or compared; the column raises)
+            });
     }
     if (last_workgroup_done(&a.job_counts[6]) && threadIdx.x == 0)   // queue B is complete: its length for k_zstd_split
         a.job_counts[9] = __hip_atomic_load(&a.job_counts[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -150,7 +134,7 @@ __global__ void __launch_bounds__(WG) k_filter_bin_entries(DecodeArgs a, const F
             b = bin_eval(d.dict + eo + 8, len, lit);
         }
         const uint64_t m = __ballot(b);
-        if ((threadIdx.x & 31) == 0 && e < bd.D) gst32(bd.bits + (e >> 5), (threadIdx.x & 32) ? (uint32_t)(m >> 32) : (uint32_t)m);
+        if ((threadIdx.x & 31) == 0 && e < bd.D) gst32(bd.bits + (e >> 5), ballot_half(m));
     }
 }
 
@@ -201,28 +185,14 @@ __device__ void filter_bin_tile(const DecodeArgs& a, const FilterCol* fcols, uin
         U32Stream is{d.isrc, (const uint32_t*)(a.scratch + t.aux_off), d.icodec, d.n_runs, t.num_values};
         u32_tile_to_lds(is, tt.tile, rows, s_a, s_w);
         const uint32_t D = bd.D;
-        bool bad = false;
+        bool bad;
         if (D <= FILTER_DICT_BITS) {
             for (uint32_t g = threadIdx.x; g < (D + 31) / 32; g += WG) s_tab[g] = gld32(bd.bits + g);
             __syncthreads();
-            filter_span(k, lo, hi, [&](uint64_t r) {
-                const uint32_t e = s_a[sidx((int)(r - lo))];
-                if (e >= D) {
-                    bad = true;
-                    return false;
-                }
-                return ((s_tab[e >> 5] >> (e & 31)) & 1u) != 0;
-            });
+            bad = filter_dict_rows(k, lo, hi, s_a, D, [&](uint32_t e) { return tab_bit(s_tab, e); });
         } else {
             const uint32_t* bits = bd.bits;
-            filter_span(k, lo, hi, [&](uint64_t r) {
-                const uint32_t e = s_a[sidx((int)(r - lo))];
-                if (e >= D) {
-                    bad = true;
-                    return false;
-                }
-                return ((gld32(bits + (e >> 5)) >> (e & 31)) & 1u) != 0;
-            });
+            bad = filter_dict_rows(k, lo, hi, s_a, D, [&](uint32_t e) { return ((gld32(bits + (e >> 5)) >> (e & 31)) & 1u) != 0; });
         }
         if (bad) raise(a.status, SB_ERR_OUT_OF_SPEC, tt.page, 222);   // (where a read finds it: plan_bin_dict / k_bin_tile_sums)
     }

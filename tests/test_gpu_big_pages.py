@@ -202,21 +202,28 @@ def test_damaged_long_rle_page(gpu_ctx):
     col = CASES["runs_i64"]
     pages, metas = gen.oracle_write(col, ratio=2.0, forbidden=())
     assert S.stat_column(col["ptype"], col["nullable"], pages, metas)[0].tolist() == [S.RLE]
-    for pos, val in ((9 + 12 * 1000, 7), (9 + 12 * 5000, 0xFF), (pages.size - 12, 1)):   # a count in the middle, a huge one, the last run
-        bad = pages.copy()
-        bad[pos] = (int(bad[pos]) + val) & 0xFF
+    def agree(ptype, bad, metas, what):
         try:
-            want = gen.oracle_read(col, bad, metas)["values"]
+            want = S.read_column(ptype, False, bad, metas)["values"]
         except Exception:
             want = None
         try:
-            got = read.read_simple(gpu_ctx, read.ColumnPages(col["ptype"], False, torch.from_numpy(bad).to(gpu_ctx.torch_device), metas)).values_numpy()
+            got = read.read_simple(gpu_ctx, read.ColumnPages(ptype, False, torch.from_numpy(bad).to(gpu_ctx.torch_device), metas)).values_numpy()
         except NativeError:
             got = None
         if want is None:
-            assert got is None, "the oracle refuses the page damaged at byte %d, the device decoded it" % pos
+            assert got is None, "the oracle refuses %s, the device decoded it" % what
         else:
-            assert got is not None and np.array_equal(got, want)
+            assert got is not None and np.array_equal(got, want), what
+
+    for pos, val in ((9 + 12 * 1000, 7), (9 + 12 * 5000, 0xFF), (pages.size - 12, 1)):   # a count in the middle, a huge one, the last run
+        bad = pages.copy()
+        bad[pos] = (int(bad[pos]) + val) & 0xFF
+        agree(col["ptype"], bad, metas, "the page damaged at byte %d" % pos)
+    # a hand-built page: zero-count runs on both sides of a border between two chunks of runs, which two parts of the page take
+    from tests.test_gpu_decode import LONG_RLE_ROWS, _rle_long_page
+    page = _rle_long_page().copy()
+    agree(S.T_I64, page, np.array([[page.size, LONG_RLE_ROWS]], np.uint64), "the hand-built page")
     dec_check(gpu_ctx, col, ratio=2.0, forbidden=())   # the context still works
 
 

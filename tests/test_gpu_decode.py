@@ -133,9 +133,11 @@ def _decode_rle_pages(ctx, ptype, page_list, rows_list):
     return got
 
 
-@pytest.mark.parametrize("ptype,dtype,w", [(S.T_U8, np.uint8, 1), (S.T_I16, np.int16, 2), (S.T_I32, np.int32, 4),
-                                           (S.T_F64, np.float64, 8)])
-def test_rle_hand_built_pages(gpu_ctx, ptype, dtype, w):
+RLE_WIDTHS = [(S.T_U8, np.uint8, 1), (S.T_I16, np.int16, 2), (S.T_I32, np.int32, 4), (S.T_F64, np.float64, 8)]
+
+
+def _rle_hand_built_column(w, dtype):
+    """(pages, rows of each) of a three-page column; tests/test_gpu_filter.py runs it through the filter as well"""
     rng = np.random.default_rng(5)
     # zero-count runs, a run that overshoots the page, > 1024 runs (several chunks), rows % 4096 != 0
     runs = [(0, 99), (3, 1), (0, 2), (0, 3), (5000, 4)] + [(int(c), int(v)) for c, v in zip(rng.integers(0, 9, 3000), rng.integers(0, 100, 3000))]
@@ -143,21 +145,50 @@ def test_rle_hand_built_pages(gpu_ctx, ptype, dtype, w):
     one = [(12345, 42)]                       # a page that is one run
     # three pages with odd row counts: the second and third start at odd output rows; trailing runs
     # after the page is full are never read (the decoder stops at N rows)
-    _decode_rle_pages(gpu_ctx, ptype, [_rle_page(runs, w, dtype), _rle_page(one + [(7, 1)], w, dtype), _rle_page(runs[:50], w, dtype)],
-                      [n1, 12345, sum(c for c, _ in runs[:50])])
+    return ([_rle_page(runs, w, dtype), _rle_page(one + [(7, 1)], w, dtype), _rle_page(runs[:50], w, dtype)],
+            [n1, 12345, sum(c for c, _ in runs[:50])])
+
+
+LONG_RLE_ROWS = (1 << 18) + 5   # 2^18 rows is the shortest page that several workgroups share (rle_parts > 1)
+
+
+def _rle_long_page():
+    """one Int64 page of LONG_RLE_ROWS rows in about 8300 runs of about 32 rows: nine chunks of 1024 runs, each of them a
+    part of its own when the page is a call's only one.  Runs 1023 and 1024 have count 0: a zero-count run on each side
+    of a chunk border that is a part border too."""
+    rng = np.random.default_rng(18)
+    counts = rng.integers(1, 63, 8600)
+    counts[1023] = counts[1024] = 0
+    n = int(np.searchsorted(np.cumsum(counts), LONG_RLE_ROWS)) + 1   # the run that reaches the last row ends there
+    counts = counts[:n]
+    counts[-1] -= int(counts.sum()) - LONG_RLE_ROWS
+    assert n > 8 * 1024 and counts[-1] > 0 and int(counts.sum()) == LONG_RLE_ROWS
+    return _rle_page(list(zip(counts.tolist(), rng.integers(-1000, 1000, n).tolist())), 8, np.int64)
+
+
+@pytest.mark.parametrize("ptype,dtype,w", RLE_WIDTHS)
+def test_rle_hand_built_pages(gpu_ctx, ptype, dtype, w):
+    _decode_rle_pages(gpu_ctx, ptype, *_rle_hand_built_column(w, dtype))
+
+
+# (ptype, dtype, width, runs, rows of the page): tests/test_gpu_filter.py feeds the same pages to the filter
+RLE_OVERSHOOT = (S.T_I64, np.int64, 8, [(10, 1), (10, 2)], 16)
+RLE_SHORT = (S.T_I32, np.int32, 4, [(10, 1), (0, 2), (5, 3)], 16)
 
 
 def test_rle_run_overshooting_the_page_is_out_of_spec(gpu_ctx):
     from strawboat_amd._native import NativeError
+    ptype, dtype, w, runs, rows = RLE_OVERSHOOT
     with pytest.raises(NativeError) as e:  # upstream: assert on the decoded length (read/array/integer.rs:81)
-        _decode_rle_pages(gpu_ctx, S.T_I64, [_rle_page([(10, 1), (10, 2)], 8, np.int64)], [16])
+        _decode_rle_pages(gpu_ctx, ptype, [_rle_page(runs, w, dtype)], [rows])
     assert e.value.code == -1
 
 
 def test_rle_runs_end_before_the_page_is_full(gpu_ctx):
     from strawboat_amd._native import NativeError
+    ptype, dtype, w, runs, rows = RLE_SHORT
     with pytest.raises(NativeError) as e:  # read_u32 hits EOF upstream (integer/rle.rs:128-131)
-        _decode_rle_pages(gpu_ctx, S.T_I32, [_rle_page([(10, 1), (0, 2), (5, 3)], 4, np.int32)], [16])
+        _decode_rle_pages(gpu_ctx, ptype, [_rle_page(runs, w, dtype)], [rows])
     assert e.value.code == -3
 
 

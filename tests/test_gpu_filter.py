@@ -8,6 +8,7 @@ import pytest
 
 from oracle import sbo as S
 from tests import gen
+from tests.test_gpu_decode import LONG_RLE_ROWS, RLE_OVERSHOOT, RLE_SHORT, RLE_WIDTHS, _rle_hand_built_column, _rle_long_page, _rle_page
 
 pytestmark = pytest.mark.gpu
 
@@ -85,6 +86,19 @@ def six_ops(col):
     return [(op, lit) for lit in literals_of(col) for op in OPS6]
 
 
+def hand_built(ptype, page_list, rows_list):
+    """(col, pages, metas) of hand-built pages of a column without nulls; the literals come from the oracle's decode, or
+    col is None where the oracle refuses the pages"""
+    pages = np.concatenate(page_list)
+    metas = np.array([[p.size, n] for p, n in zip(page_list, rows_list)], np.uint64)
+    col = dict(ptype=ptype, nullable=False, rows=sum(rows_list), validity=None, offsets=None)
+    try:
+        col["values"] = oracle_column(col, pages, metas)[0]
+    except Exception:
+        col = None
+    return col, pages, metas
+
+
 # ---- 1
 @pytest.mark.parametrize("ptype", CMP_TYPES)
 @pytest.mark.parametrize("codec", [S.NONE, S.RLE, S.DICT, S.ONEVALUE])
@@ -100,6 +114,14 @@ def test_prim_codecs(gpu_ctx, ptype, codec):
 
 
 # ---- 2
+@pytest.mark.parametrize("ptype,dtype,w", RLE_WIDTHS)
+def test_rle_hand_built_pages(gpu_ctx, ptype, dtype, w):
+    """the decoder's hand-built column (zero-count runs, a 5000-row run, three chunks of short runs, pages that start at
+    odd rows, runs behind a full page) through the filter's policy of the RLE page walk"""
+    col, pages, metas = hand_built(ptype, *_rle_hand_built_column(w, dtype))
+    check_pages(gpu_ctx, col, pages, metas, six_ops(col))
+
+
 @pytest.mark.parametrize("ptype", [S.T_I32, S.T_U32])
 @pytest.mark.parametrize("codec", [S.BITPACK, S.DELTABP])
 def test_bitpacking(gpu_ctx, ptype, codec):
@@ -295,6 +317,13 @@ def test_long_pages(gpu_ctx, codec):
     pages, metas = gen.oracle_write(col, force_codec=codec)
     assert metas.shape[0] == 1
     check_pages(gpu_ctx, col, pages, metas, six_ops(col))
+    if codec == S.RLE:   # hand-built: zero-count runs on both sides of a border between two parts of the page
+        col, pages, metas = hand_built(S.T_I64, [_rle_long_page()], [LONG_RLE_ROWS])
+        if col is None:   # the oracle's values or the oracle's refusal, never a difference
+            import strawboat_amd as sb
+            assert filter_code(gpu_ctx, upload(gpu_ctx, dict(ptype=S.T_I64, nullable=False), pages, metas), sb.Predicate("lt", 0)) != 0
+        else:
+            check_pages(gpu_ctx, col, pages, metas, six_ops(col))
 
 
 def test_empty_column_and_one_row_page(gpu_ctx):
@@ -389,6 +418,28 @@ def test_corrupt_pages_raise_what_the_decoder_raises(gpu_ctx):
         want = read_code(gpu_ctx, cp)
         assert want == -1
         assert filter_code(gpu_ctx, cp, sb.Predicate("lt", 30)) == want
+    # hand-built RLE pages: a run that overshoots the page, runs that end before the page is full
+    for (ptype, dtype, w, runs, rows), code in ((RLE_OVERSHOOT, -1), (RLE_SHORT, -3)):
+        page = _rle_page(runs, w, dtype).copy()
+        cp = upload(gpu_ctx, dict(ptype=ptype, nullable=False), page, np.array([[page.size, rows]], np.uint64))
+        assert read_code(gpu_ctx, cp) == code
+        assert filter_code(gpu_ctx, cp, sb.Predicate("lt", 2)) == code
+    # a corrupt def-level section (u32 def_len | ULEB128 | bits): the null tests read it themselves, the comparisons and the
+    # decoder through k_parse, and all three refuse it alike
+    col = gen.prim(S.T_I64, 3000, uniq=60, null_density=0.2, seed=9)
+    pages, metas = gen.oracle_write(col, max_page_size=1 << 20, force_codec=S.NONE)
+    assert metas.shape[0] == 1 and int(np.frombuffer(pages[:4].tobytes(), np.uint32)[0]) == 2 + 375 and pages[4] & 0x80
+    for what, pos, patch in (("def_len larger than the page", 0, np.uint32(0xFFFFFF00).tobytes()),
+                             ("def_len == 0 with rows", 0, np.uint32(0).tobytes()),
+                             ("an even ULEB128 indicator", 4, bytes([pages[4] & 0xFE])),
+                             ("a bit count below N", 4, bytes([(1 << 1) | 1]))):   # one byte: 8 bits for 3000 rows
+        bad = pages.copy()
+        bad[pos:pos + len(patch)] = np.frombuffer(patch, np.uint8)
+        cp = upload(gpu_ctx, col, bad, metas)
+        want = read_code(gpu_ctx, cp)
+        assert want != 0, what
+        assert filter_code(gpu_ctx, cp, sb.Predicate("is_null")) == want, what
+        assert filter_code(gpu_ctx, cp, sb.Predicate("lt", 30)) == want, what
     # the context still works
     col = gen.prim(S.T_I64, 9000, uniq=60)
     check(gpu_ctx, col, six_ops(col), max_page_size=3000, force_codec=S.DICT)
