@@ -23,16 +23,20 @@ def to_device_column(ctx, col):
                         up(col["offsets"]))
 
 
+def write_options(**opt):
+    from strawboat_amd import WriteOptions
+    return WriteOptions(default_compression=opt.get("default_compression", 0),
+                        default_compress_ratio=opt.get("ratio"), max_page_size=opt.get("max_page_size"),
+                        forbidden_compressions=list(opt.get("forbidden", ())), force_codec=opt.get("force_codec", -1),
+                        force_index_codec=opt.get("force_index_codec", -1), rng_seed=opt.get("rng_seed", 42),
+                        debug_verify_fail=opt.get("debug_verify_fail", False),
+                        lz4_exact=opt.get("lz4_exact", True))   # byte parity with the oracle (== liblz4) needs the exact parse;
+                                                                # lz4_exact=False = the default (parallel) encoder bench.py times
+
+
 def gpu_encode(ctx, col, **opt):
-    from strawboat_amd import write, WriteOptions
-    wo = WriteOptions(default_compression=opt.get("default_compression", 0),
-                      default_compress_ratio=opt.get("ratio"), max_page_size=opt.get("max_page_size"),
-                      forbidden_compressions=list(opt.get("forbidden", ())), force_codec=opt.get("force_codec", -1),
-                      force_index_codec=opt.get("force_index_codec", -1), rng_seed=opt.get("rng_seed", 42),
-                      debug_verify_fail=opt.get("debug_verify_fail", False),
-                      lz4_exact=opt.get("lz4_exact", True))   # byte parity with the oracle (== liblz4) needs the exact parse;
-                                                              # lz4_exact=False = the default (parallel) encoder bench.py times
-    return write.write(ctx, to_device_column(ctx, col), wo)
+    from strawboat_amd import write
+    return write.write(ctx, to_device_column(ctx, col), write_options(**opt))
 
 
 def check(ctx, col, **opt):

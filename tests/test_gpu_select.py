@@ -13,11 +13,13 @@ pytestmark = pytest.mark.gpu
 NOT_ON_DEVICE = ()  # every codec has a device encoder now: the reference's default options (nothing forbidden)
 
 
-def check(ctx, col, **opt):
+def check(ctx, col, enc=None, **opt):
+    """enc: the column's EncodedColumn where the caller encoded it already (several columns in one encode_columns call)"""
     opt.setdefault("forbidden", NOT_ON_DEVICE)
     want_pages, want_metas = gen.oracle_write(col, **opt)
     want_codecs, want_inner = S.stat_column(col["ptype"], col["nullable"], want_pages, want_metas)
-    enc = gpu_encode(ctx, col, **opt)
+    if enc is None:
+        enc = gpu_encode(ctx, col, **opt)
     got_metas = enc.metas_array()
     got = enc.pages_numpy()
     got_codecs, got_inner = S.stat_column(col["ptype"], col["nullable"], got, got_metas)
