@@ -5,6 +5,9 @@
 //   hipcc --offload-arch=gfx950 -O3 -DSB_RUNS_DMA=0                scripts/micro/runs_dma.hip -o /tmp/runs_base
 //   hipcc --offload-arch=gfx950 -O3 -DSB_RUNS_DMA=1 -DSB_RUNS_OCC=2 scripts/micro/runs_dma.hip -o /tmp/runs_dma2
 // (link line as for runs_timeline.hip: + sb_api.hip sb_decode.hip sb_nested.hip sb_file.cpp sb_schema.cpp)
+// Round 7 took SB_RUNS_DMA and SB_RUNS_TOUCH out of sb_select_runs.h (both address a thread's 16 consecutive rows; the result is
+// on record in profiles/r05_runs_dma_micro.txt): with -DSB_RUNS_DMA=0 -DSB_RUNS_TOUCH=0 this file still times the kernel as built,
+// the two experiments need the tree of the commit before.
 #include "../../strawboat_amd/csrc/sb_encode.hip"
 #include <cstdio>
 #include <random>

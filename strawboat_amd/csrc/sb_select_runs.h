@@ -18,19 +18,49 @@
 // SIMD (1.58 ms on C2 instead of 1.10) or drops the kernel to 3 waves / SIMD (1.33 ms) — the other three
 // workgroups of the CU are what hides the load latency.  More workgroups per CU do not help either (measured, round 2,
 // with a 16 KiB key set so that LDS allows 6): 5 waves / SIMD (96 VGPRs, 252 B of scratch) 1.22 ms, 6 waves / SIMD
-// (80 VGPRs, 320 B of scratch) 1.38 ms, against 1.19 ms on the same box — the kernel is bound by instruction issue.
+// (80 VGPRs, 320 B of scratch) 1.38 ms, against 1.19 ms on the same box.
+//
+// Rounds 2-6 read that as "bound by instruction issue".  What round 7 measured instead:
+//   * In isolation the SHAPE of the row loads costs nothing.  scripts/micro/runs_loads.hip (profiles/runs_loads_micro.txt): load
+//     a chunk + compare every row with the row before, same geometry and LDS footprint as this kernel, streams 4.29 GB in
+//     0.688 ms (6.25 TB/s) with thread = 16 consecutive rows (a wave-level load touches 64 lines, 16 bytes of each) and in
+//     0.694 ms with lane-contiguous 16-byte pieces (1 KiB, 8 lines): equal within the spread of ten launches (2 %).  A kernel
+//     that only loads hides whatever a 64-line load costs; loading and comparing run at the HBM rate either way.
+//   * In THIS kernel the same change of layout (SB_RUNS_LANE_ROWS=1, below) is worth 11 % on C2: 1.152 -> 1.030 ms per
+//     launch, step 2.217 -> 2.073 ms, same bytes (profiles/r07_c2_kernel_stats_parent.csv, r07_c2_kernel_stats.csv,
+//     r07_c2_headline_runs.txt).  Not through fewer instructions: profiles/r07_c2_issue_counters.json counts MORE of them
+//     (VALU +4 %, SALU +56 %: counts and ranks became scalar; LDS +27 %: sixteen guarded store pairs instead of a loop over
+//     the set bits).  What fell is the load phase: the address units are busy 31 % less (TA_TA_BUSY) and stalled by the
+//     cache 75 % less (TA_ADDR_STALLED_BY_TC_CYCLES), waves wait for an instruction to return 43 % less
+//     (SQ_WAIT_INST_ANY).  A chunk is a chain of phases (load, compare, barrier, compact, barrier, run step) that only the
+//     three other workgroups of the CU overlap, so how long a wave's eight loads take to come back is on the chain even
+//     though the bandwidth was never short.  Neither "issue-bound" nor "bound by 64-line loads" describes it: the kernel
+//     is bound by the LATENCY of its chain of phases, and the loads were the longest link that could be shortened
+//     without touching the run step.
 //
 // A chunk (4096 rows) with more than RUNS_CAP raw runs (runs shorter than ~6 rows on average) makes
 // the page FALL BACK to select_rle_page (k_enc_select_rle runs after this kernel and takes the pages
 // marked CODEC_PENDING): lane = run pays off only when there are runs.
-#ifndef SB_RUNS_TOUCH
-#define SB_RUNS_TOUCH 0   // EXPERIMENT (scripts/micro/runs_dma.hip): one dword of the NEXT chunk's 128 bytes per thread, to have them in L2
-#endif
-#ifndef SB_RUNS_DMA
-#define SB_RUNS_DMA 0
+#ifndef SB_RUNS_LANE_ROWS
+#define SB_RUNS_LANE_ROWS 1   // 1: a wave's loads are lane-contiguous (1 KiB per instruction); 0: thread = 16 consecutive rows, as first built
 #endif
 constexpr int32_t CODEC_PENDING = -100;
 constexpr uint32_t RUNS_CAP = 640;
+
+#if SB_RUNS_LANE_ROWS
+// lane l takes lane l - 1's value, lane 0 takes `lane0`: v_mov_b32 with DPP wave_shr:1 keeps the old value of a lane nobody feeds
+template <int W>
+__device__ __forceinline__ Val<W> wave_shr1_val(const Val<W>& v, const Val<W>& lane0) {
+    int a[W / 4], o[W / 4], b[W / 4];
+    __builtin_memcpy(a, &v, W);
+    __builtin_memcpy(o, &lane0, W);
+#pragma unroll
+    for (int k = 0; k < W / 4; k++) b[k] = __builtin_amdgcn_update_dpp(o[k], a[k], 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
+    Val<W> r;
+    __builtin_memcpy(&r, b, W);
+    return r;
+}
+#endif
 
 template <int W, int FK>
 __device__ uint32_t select_runs_page(const EncodeArgs& a, const EncCol& c, const EncPage& p, uint32_t page, const SelectOpts& o,
@@ -98,11 +128,42 @@ __device__ uint32_t select_runs_page(const EncodeArgs& a, const EncCol& c, const
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
     };
     uint32_t par = 0;
-    // rows of one chunk (thread = K consecutive rows), the row before a wave's first row, and a validity word
+    // rows of one chunk, the row before a wave's first row, and a validity word
     Val<W> v[K];
     Val<W> pv0 = val_zero<W>();
     uint32_t vword = 0;
+#if SB_RUNS_LANE_ROWS
+    // A wave owns rows [1024 w, 1024 w + 1024) of the chunk; piece u (16 bytes = PR rows) of lane l holds rows
+    // 1024 w + u * 64 * PR + l * PR + i in v[u * PR + i]: a wave-level load is 1 KiB contiguous, 8 lines instead of 64.
+    constexpr int PR = 16 / W, NP = K / PR;
+    const uint32_t wrow = (uint32_t)w * (64 * K), lrow = wrow + (uint32_t)lane * PR;
     auto request = [&](uint64_t cb) {
+        const uint32_t n = (uint32_t)min((uint64_t)CHUNK, N - cb);
+        if (wrow + 64 * K <= n) {  // (wave-uniform) every piece of the wave lies inside the page
+#pragma unroll
+            for (int u = 0; u < NP; u++) {
+                const u32x4 q = ldu128(vals + (cb + lrow + (uint32_t)u * 64 * PR) * W);
+                __builtin_memcpy(&v[u * PR], &q, 16);
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < NP; u++) {
+                const uint32_t r = lrow + (uint32_t)u * 64 * PR;
+                if (r + PR <= n) {  // the whole piece lies inside the page: no 16-byte load reaches past row n - 1
+                    const u32x4 q = ldu128(vals + (cb + r) * W);
+                    __builtin_memcpy(&v[u * PR], &q, 16);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < PR; i++) v[u * PR + i] = getv(cb + (r + i < n ? r + i : n - 1));
+                }
+            }
+        }
+        if (lane == 0) pv0 = getv(cb + wrow > 0 ? min(cb + wrow - 1, N - 1) : 0);
+        vword = 0xFFFFFFFFu;
+        if (t < (int)(CHUNK / 32) && (uint32_t)t * 32 < n && vv.bits) vword = bits32(vv.bits, vv.off + cb + (uint32_t)t * 32, vtotal);
+    };
+#else
+    auto request = [&](uint64_t cb) {  // thread = K consecutive rows
         const uint32_t n = (uint32_t)min((uint64_t)CHUNK, N - cb);
         const uint32_t r0 = (uint32_t)t * K;
         if (r0 + K <= n) {
@@ -119,56 +180,12 @@ __device__ uint32_t select_runs_page(const EncodeArgs& a, const EncCol& c, const
         vword = 0xFFFFFFFFu;
         if (t < (int)(CHUNK / 32) && (uint32_t)t * 32 < n && vv.bits) vword = bits32(vv.bits, vv.off + cb + (uint32_t)t * 32, vtotal);
     };
-#if SB_RUNS_DMA
-    // EXPERIMENT (scripts/micro/runs_dma.hip): the rows of chunk k + 1 travel HBM -> LDS with
-    // global_load_lds_dwordx4 while chunk k is worked on — no VGPRs are held for them — and are read out of the stage
-    // (8 x ds_read_b128 per thread, conflict-free: the stage is [wave][piece][lane] x 16 bytes, the layout the DMA writes)
-    // at the top of the next iteration.  One stage of CHUNK * W bytes (32 KB for 8-byte values) on top of the 32 KB key
-    // set: 2 workgroups per CU instead of 4.
-    __shared__ __attribute__((aligned(16))) uint8_t dma_stage[CHUNK * W];
-    constexpr int NV_DMA = K * W / 16;
-    auto dma_issue = [&](uint64_t cb) {
-        const uint8_t* g = vals + (cb + (uint64_t)t * K) * W;
-#pragma unroll
-        for (int u = 0; u < NV_DMA; u++)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + 16 * u),
-                                             (__attribute__((address_space(3))) void*)(dma_stage + ((w * NV_DMA + u) * 64) * 16), 16, 0, 0);
-    };
-    if (N >= CHUNK) dma_issue(0);
 #endif
     STL(0);
     for (uint64_t cb = 0; cb < N; cb += CHUNK) {
         XTL(0);
-#if SB_RUNS_DMA
-        if (N - cb >= CHUNK) {
-            __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): my pieces have landed
-            {
-                u32x4 q[NV_DMA];
-#pragma unroll
-                for (int u = 0; u < NV_DMA; u++) q[u] = *(const u32x4*)(dma_stage + ((w * NV_DMA + u) * 64 + lane) * 16);
-                __builtin_memcpy(v, q, K * W);
-            }
-            if (lane == 0) pv0 = getv(cb + (uint64_t)t * K > 0 ? cb + (uint64_t)t * K - 1 : 0);
-            vword = 0xFFFFFFFFu;
-            if (t < (int)(CHUNK / 32) && vv.bits) vword = bits32(vv.bits, vv.off + cb + (uint32_t)t * 32, vtotal);
-            // (a wave reads only what it wrote: no barrier between the read-out and the next issue)
-            if (N - (cb + CHUNK) >= CHUNK && cb + CHUNK < N) dma_issue(cb + CHUNK);
-        } else {
-            request(cb);
-        }
-#else
         request(cb);
-#endif
-#if SB_RUNS_TOUCH
-        uint32_t touch = 0;
-        if (cb + CHUNK + (uint64_t)(t + 1) * K <= N) {
-            const uint8_t* tp = vals + (cb + CHUNK + (uint64_t)t * K) * W;
-            asm volatile("global_load_dword %0, %1, off" : "=v"(touch) : "v"(tp) : "memory");
-        }
-#endif
         const uint32_t n = (uint32_t)min((uint64_t)CHUNK, N - cb);
-        const uint32_t r0 = (uint32_t)t * K;
-        const uint32_t mine = r0 < n ? min((uint32_t)K, n - r0) : 0u;
         // ---- step 1: where do the bits change?
         if (t < (int)(CHUNK / 32)) {  // the chunk's validity words (null count rides along)
             const uint32_t b0 = (uint32_t)t * 32;
@@ -181,6 +198,40 @@ __device__ uint32_t select_runs_page(const EncodeArgs& a, const EncCol& c, const
             }
             s_vb[t] = word;
         }
+        uint32_t* s_rc = s_x + par * 16 + 12;  // [4] raw runs starting in each wave
+#if SB_RUNS_LANE_ROWS
+        if (t == 0) rvals[0] = pv0;
+        // Row i > 0 of a piece compares with the row before it in the same lane, row 0 with the last row of the lane below
+        // (lane 0: of lane 63 in the piece before, or the row before the wave's first).  A compare is wave-wide, so its
+        // result IS the ballot: the changes of (piece, row) as a lane mask, their counts scalar.
+        bool chg[K];
+        uint32_t cnt_p[NP];
+        uint32_t cnt_w = 0;
+        {
+            Val<W> carry = readlane_val<W>(pv0, 0);
+#pragma unroll
+            for (int u = 0; u < NP; u++) {
+                uint32_t c = 0;
+#pragma unroll
+                for (int i = 0; i < PR; i++) {
+                    const Val<W> pr = i ? v[u * PR + i - 1] : wave_shr1_val<W>(v[u * PR + PR - 1], carry);
+                    bool ne = !bits_eq<W>(v[u * PR + i], pr);
+                    if (u == 0 && i == 0) ne = ne || t == 0;  // every chunk starts a run: the list is per chunk (a raw run that
+                                                              // continues from the chunk before may hold its first valid row here)
+                    ne = ne && lrow + (uint32_t)(u * 64 * PR + i) < n;
+                    chg[u * PR + i] = ne;
+                    c += (uint32_t)__popcll(__ballot(ne));
+                }
+                cnt_p[u] = c;
+                cnt_w += c;
+                carry = readlane_val<W>(v[u * PR + PR - 1], 63);
+            }
+        }
+        XTL(1);
+        if (lane == 0) s_rc[w] = cnt_w;
+#else
+        const uint32_t r0 = (uint32_t)t * K;
+        const uint32_t mine = r0 < n ? min((uint32_t)K, n - r0) : 0u;
         Val<W> pvrow = shfl_val<W>(v[K - 1], (lane + 63) & 63);
         if (lane == 0) pvrow = pv0;
         if (t == 0) rvals[0] = pvrow;
@@ -197,10 +248,10 @@ __device__ uint32_t select_runs_page(const EncodeArgs& a, const EncCol& c, const
             rbm &= mine >= (uint32_t)K ? 0xFFFFu : ((1u << mine) - 1);
         }
         XTL(1);
-        uint32_t* s_rc = s_x + par * 16 + 12;  // [4] raw runs starting in each wave
         const uint32_t cnt1 = (uint32_t)__popc(rbm);
         const uint32_t incl1 = wave_incl_scan(cnt1);
         if (lane == 63) s_rc[w] = incl1;
+#endif
         lds_barrier();
         XTL(2);
         const uint32_t total = s_rc[0] + s_rc[1] + s_rc[2] + s_rc[3];
@@ -208,6 +259,30 @@ __device__ uint32_t select_runs_page(const EncodeArgs& a, const EncCol& c, const
             *fallback = true;
             return 0;
         }
+#if SB_RUNS_LANE_ROWS
+        {   // the list stays in row order: wave, piece, lane, row.  Stores from registers with constant indices, under the
+            // compare's own mask
+            uint32_t base = 0;
+            for (int pw = 0; pw < 3; pw++)
+                if (pw < w) base += s_rc[pw];
+#pragma unroll
+            for (int u = 0; u < NP; u++) {
+                uint32_t at = base;
+#pragma unroll
+                for (int i = 0; i < PR; i++) at += mbcnt64(__ballot(chg[u * PR + i]));
+#pragma unroll
+                for (int i = 0; i < PR; i++) {
+                    if (chg[u * PR + i]) {
+                        runs[at] = (uint16_t)(lrow + (uint32_t)(u * 64 * PR + i));
+                        rvals[1 + at] = v[u * PR + i];
+                    }
+                    at += chg[u * PR + i];
+                }
+                base += cnt_p[u];
+            }
+            if (t == 0) runs[total] = (uint16_t)n;  // (n <= 4096 fits)
+        }
+#else
         {
             uint32_t at = incl1 - cnt1;
             for (int pw = 0; pw < 3; pw++)
@@ -225,6 +300,7 @@ __device__ uint32_t select_runs_page(const EncodeArgs& a, const EncCol& c, const
             }
             if (t == 0) runs[total] = (uint16_t)n;  // (n <= 4096 fits)
         }
+#endif
         XTL(3);
         lds_barrier();
         XTL(4);
@@ -357,10 +433,6 @@ __device__ uint32_t select_runs_page(const EncodeArgs& a, const EncCol& c, const
             }
         }
         XTL(10);
-#if SB_RUNS_TOUCH
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (long landed: the chunk's own loads were waited for above)
-        asm volatile("" ::"v"(touch));                      // the register stays the load's until here
-#endif
         if (!spec) lds_barrier();  // (the run list and the validity words are rewritten by the next chunk)
         // runs shorter than 4 rows on average: RLE is unlikely to be chosen, stop paying for it
         if ((uint64_t)nrec * 4 > cb + n + 256) spec = false;
