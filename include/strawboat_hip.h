@@ -250,6 +250,53 @@ typedef struct sb_column_filter_var {
 
 int32_t sb_filter_columns_var(sb_ctx* ctx, sb_column_filter_var* cols, uint64_t n, int32_t mem);
 
+/* ------------------------------------------------------------------ selected read
+ * The second half of the filter: the pages of a payload column and a selection bitmap go in, the selected rows come
+ * out packed.  Output row k is the column's row at the k-th set bit of `selection` below `rows`: its `values` are the
+ * bytes sb_read_columns writes for that row (the slot of a null row included), its validity bit is bit k of `validity`.
+ * Selection bits at positions >= rows are ignored.  Bits >= selected of the last validity word written are 0; validity
+ * words behind it and `values` bytes behind values_len are not touched.
+ *
+ * Types: INT8..INT64, UINT8..UINT64, FLOAT32, FLOAT64.  Boolean, Int128, Int256, Binary, LargeBinary and Null:
+ * SB_ERR_NYI at the call, nothing is enqueued and no buffer is touched.
+ *
+ * `selected` is not known at the call when the bitmap comes from a filter call of the same interval, so the output
+ * capacities are checked on the device: a column whose values_capacity < selected * width or (nullable) whose
+ * validity_capacity < 4*ceil(selected/32) raises SB_ERR_INVALID at the synchronize, and nothing is written outside the
+ * capacities given.  rows * width and 4*ceil(rows/32) are always enough.  `selected` and `values_len` are filled in
+ * even then: they say what the buffers have to hold.
+ *
+ * Refused at the call (SB_ERR_INVALID, nothing enqueued): a null or misaligned `selection`, selection_capacity below
+ * 4*ceil(rows/32), a nullable column without `validity`, `values` / `validity` buffers of one call that overlap each
+ * other or any `selection` of the call (columns may share ONE selection: that is the usual case).  SB_MEM_HOST: SB_ERR_NYI.
+ *
+ * Enqueued like sb_read_columns and sb_filter_columns; page errors are the decoder's, with its codes, at the
+ * synchronize (a corrupt page without a selected row may or may not raise).  The call is part of its synchronize
+ * interval: when the interval is issued again (sb_ctx_replays) it is issued again in its place, behind the filter calls
+ * that write its bitmap, and gives the same bytes.  `selection` is an INPUT: like the pages it must stay unmodified by
+ * the caller until the synchronize.  The call consults no launch hint of the read path and leaves its counters alone. */
+typedef struct sb_column_read_selected {
+    int32_t physical_type;   /* SB_TYPE_* */
+    int32_t is_nullable;
+    const uint8_t* pages;    /* DEVICE */
+    uint64_t pages_len;
+    const sb_page_meta* metas; /* HOST */
+    uint64_t n_pages;
+    const uint64_t* page_offsets; /* optional (HOST) */
+    const uint8_t* selection;     /* DEVICE, input: LSB-first bitmap, 4-byte aligned, as the filter calls write it */
+    uint64_t selection_capacity;  /* >= 4*ceil(rows/32) bytes */
+    void* values;            /* DEVICE: selected * width bytes are written */
+    uint64_t values_capacity;
+    uint8_t* validity;       /* DEVICE, 4-byte aligned: ceil(selected/8) bytes, written in 32-bit words; required iff is_nullable */
+    uint64_t validity_capacity;
+    /* results (HOST, valid after sb_ctx_synchronize) */
+    uint64_t rows;           /* sum of num_values */
+    uint64_t selected;       /* bits set in `selection` below `rows` */
+    uint64_t values_len;     /* selected * width */
+} sb_column_read_selected;   /* 120 bytes */
+
+int32_t sb_read_selected(sb_ctx* ctx, sb_column_read_selected* cols, uint64_t n, int32_t mem);
+
 /* ------------------------------------------------------------------ encode
  * Replaces, per leaf column, the page loop of NativeWriter::encode_chunk
  * (src/write/common.rs:54-109): page slicing, then per page write::write -> write_simple

@@ -9,6 +9,7 @@ from .types import (ColumnMeta, CommonCompression, Compression, PageMeta, Physic
 from .context import Context  # noqa: F401
 from . import filter, read, shard, write  # noqa: F401
 from .filter import Predicate, Selection, filter_columns  # noqa: F401
+from .read_selected import ReadSelectedBatch, SelectedArray, read_selected  # noqa: F401
 
-__all__ = ["Context", "read", "write", "filter", "Predicate", "Selection", "filter_columns", "WriteOptions", "PageMeta", "ColumnMeta", "Compression",
+__all__ = ["Context", "read", "write", "filter", "Predicate", "Selection", "filter_columns", "read_selected", "ReadSelectedBatch", "SelectedArray", "WriteOptions", "PageMeta", "ColumnMeta", "Compression",
            "CommonCompression", "PhysicalType"]

@@ -8,7 +8,10 @@
 
 namespace sb {
 
-void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt);
+void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
+                   const SelLaunch* rsel);
+void launch_rsel_plain(sb_ctx* ctx, const SelCol* scols, uint32_t n_cols, uint64_t* counts, bool any_nullable, const uint64_t* rows,
+                       const uint8_t* const* values, const uint8_t* const* validity);
 void launch_filter_plain(sb_ctx* ctx, const FilterCol& f, const uint8_t* values, const uint8_t* validity, uint64_t rows, uint32_t w, uint64_t* count);
 void launch_parse_sizes(sb_ctx* ctx, const DecodeArgs& a, uint64_t* col_values_len);
 void launch_freq_scatter(sb_ctx* ctx, const FreqEntry* entries, uint32_t n, const uint64_t* ex_off, const uint8_t* ex_base);
@@ -84,7 +87,7 @@ StageSlot* acquire_slot(sb_ctx* ctx, size_t need) {
     if (s.host)
         for (auto& p : ctx->iv.pending) {
             if (p.host < s.host || p.host >= s.host + s.cap) continue;
-            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL) ? 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R) ? (size_t)p.bytes
+            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R) ? (size_t)p.bytes
                                                                                                    : (size_t)(2 * p.n + 1) * 8;
             ctx->iv.rescued.emplace_back(p.host, p.host + nb);
             p.host = ctx->iv.rescued.back().data();
@@ -214,14 +217,21 @@ void* sb_ctx_stream(sb_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 // What kind of call read_columns_impl serves: built at the entry points, read by every step of the call
 struct ReadMode {
     // sb_read_columns (and the decode of a filter replay) / sb_read_columns_sizes / the Freq second pass, from inside a
-    // synchronize / sb_filter_columns[_var], whose columns end in the filter kernels
-    enum Kind { READ, SIZES, FREQ_PASS, FILTER } kind;
+    // synchronize / sb_filter_columns[_var], whose columns end in the filter kernels / sb_read_selected, whose columns end
+    // in the selected-read kernels
+    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED } kind;
     const FilterCol* filt = nullptr;             // FILTER: one per column
     uint64_t* const* sel_out = nullptr;          // ... sel_out[i]: the caller's `selected`
     const std::vector<uint8_t>* lits = nullptr;  // ... the literals of the FK_BYTES columns, FilterCol.lit being the offset of each
     bool sizes() const { return kind == SIZES; }
     bool freq_pass() const { return kind == FREQ_PASS; }
+    const SelCol* selc = nullptr;                // SELECTED: one per column (rank: filled in with the call's tables)
+    sb_column_read_selected* const* sel_users = nullptr;   // ... the callers' structs
     bool filter() const { return kind == FILTER; }
+    bool selected() const { return kind == SELECTED; }
+    // the columns end in a sink of their own: `values` is a share of the staging area, there is no validity buffer, and
+    // the call neither consults nor feeds the launch hints of the read path
+    bool sink() const { return kind == FILTER || kind == SELECTED; }
 };
 static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, const ReadMode& mode);
 static void update_read_hints(sb_ctx* ctx, uint32_t kinds);   // (next to read_hints, its reader)
@@ -402,6 +412,13 @@ static void deliver_read_col(const Pending& p) {
     ((sb_column_read*)p.user)->values_len = v;
 }
 static void deliver_filter_col(const Pending& p) { memcpy(p.user, p.host, 8); }
+static void deliver_rsel_col(const Pending& p) {
+    uint64_t v;
+    memcpy(&v, p.host, 8);
+    sb_column_read_selected* c = (sb_column_read_selected*)p.user;
+    c->selected = v;
+    c->values_len = v * type_width(c->physical_type);
+}
 static void deliver_write_col(const Pending& p) {
     sb_column_write* c = (sb_column_write*)p.user;
     const uint64_t* lens = (const uint64_t*)p.host;  // [n_pages lengths][n_pages num_values][total]
@@ -427,6 +444,7 @@ static void deliver_pending(sb_ctx* ctx, const Pending& p, int32_t rc) {
     switch (p.kind) {
         case Pending::READ_COL: deliver_read_col(p); break;
         case Pending::FILTER_COL: deliver_filter_col(p); break;
+        case Pending::RSEL_COL: deliver_rsel_col(p); break;
         case Pending::WRITE_COL: deliver_write_col(p); break;
         case Pending::ENC_HINT:
             if (rc == SB_OK) apply_enc_hint(ctx, p);
@@ -571,7 +589,7 @@ static int32_t read_shape(sb_ctx* ctx, sb_column_read* cols, uint64_t n, const R
         if (!mode.sizes() && c.physical_type != SB_TYPE_NULL && rows) {
             const uint32_t w = type_width(c.physical_type);
             if (!c.values) return ctx->fail(SB_ERR_INVALID, "values is null");
-            if (c.is_nullable && !mode.filter() && (!c.validity || c.validity_capacity < (rows + 31) / 32 * 4))
+            if (c.is_nullable && !mode.sink() && (!c.validity || c.validity_capacity < (rows + 31) / 32 * 4))
                 return ctx->fail(SB_ERR_INVALID, "validity buffer missing or smaller than 4*ceil(rows/32) bytes");
             if (is_binary_t(c.physical_type) && mode.filter()) {
                 // (a filter call writes no offsets; `values` is the column's share of the staging area)
@@ -642,8 +660,8 @@ static void update_read_hints(sb_ctx* ctx, uint32_t kinds) {
 static ReadHints read_hints(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh) {
     ReadHints h;
     // the block-parallel Zstd pipeline: in a context whose last read intervals met Zstd buffers
-    h.zb_on = ctx->zb_mode == 1 || (ctx->zb_mode == 2 && (ctx->zstd_recent || ctx->no_hints || mode.filter()));
-    if (!mode.freq_pass() && !mode.filter()) ctx->read_calls++;
+    h.zb_on = ctx->zb_mode == 1 || (ctx->zb_mode == 2 && (ctx->zstd_recent || ctx->no_hints || mode.sink()));
+    if (!mode.freq_pass() && !mode.sink()) ctx->read_calls++;
     // long multi-frame Zstd buffers (a one-page column written by this library): frames found by a scan (sb_decode.hip)
     h.zs_on = h.zb_on && !mode.sizes() && sh.max_page_len >= (1u << 20);
     h.zb_skipped = (!h.zb_on && ctx->zb_mode == 2 && !mode.sizes() && sh.max_page_len >= (1u << 20)) ? 1u : 0u;
@@ -661,13 +679,13 @@ static ReadHints read_hints(sb_ctx* ctx, const ReadMode& mode, const ReadShape& 
         const bool none_met = ctx->lzg_state == 2 && !ctx->no_hints;   // the context's last intervals met no LZ4 block of megabytes
         // none met: no pool, no launches; k_inflate_lz4_big leaves such a block alone and asks for the replay (it used to
         // walk it with one workgroup: 0.8 s for 68 MB)
-        h.lzg = none_met && !mode.filter() ? ReadHints::LZG_SKIPPED : ReadHints::LZG_POOL;
+        h.lzg = none_met && !mode.sink() ? ReadHints::LZG_SKIPPED : ReadHints::LZG_POOL;
         // OPEN POINT, kept as it was found: a filter call in such a context sizes the pool and sets the grids, is NOT marked
         // lzg_skipped, and launches nothing all the same (launch_lzg used to read lzg_state for itself)
         h.lzg_launch = h.lzg == ReadHints::LZG_POOL && !none_met;
         // (noted here, before anything of the call can fail: a call that fails later — tables, staging, page_offsets, pools,
         // upload, or the giant-LZ4 pool itself — has still shown its long pages; it used to be noted after all of those)
-        if (!mode.filter()) ctx->lzg_long_pages = true;
+        if (!mode.sink()) ctx->lzg_long_pages = true;
     }
     return h;
 }
@@ -692,6 +710,7 @@ static ReadLayout read_layout(uint64_t n, const ReadShape& sh, const ReadHints& 
     off = align_up(off + P * sizeof(PageTask), 64);
     L.fcols = off;
     if (mode.filter()) off = align_up(off + n * sizeof(FilterCol), 64);
+    if (mode.selected()) off = align_up(off + n * sizeof(SelCol), 64);   // (in the filter columns' place)
     L.lits = off;
     if (mode.lits) off = align_up(off + mode.lits->size(), 64);
     L.upload = off;
@@ -838,7 +857,14 @@ static int32_t fill_read_tables(sb_ctx* ctx, uint8_t* host, const ReadLayout& L,
         for (uint64_t i = 0; i < n; i++)
             if (hfc[i].kind == FK_BYTES) hfc[i].lit += (uint64_t)(uintptr_t)(ctx->tables.p + L.lits);
     }
+    SelCol* hsc = mode.selected() ? (SelCol*)(host + L.fcols) : nullptr;
+    for (uint64_t i = 0; hsc && i < n; i++) {   // the rank tables: behind the pages' areas, sized by the rows
+        hsc[i] = mode.selc[i];
+        hsc[i].rank = (uint64_t*)scratch_off;   // (an offset until the buffer is known)
+        scratch_off += align_up(rsel_rank_words(cols[i].rows) * 8, 16);
+    }
     if (!ensure(ctx, ctx->scratch, scratch_off + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(scratch) failed");
+    for (uint64_t i = 0; hsc && i < n; i++) hsc[i].rank = (uint64_t*)(ctx->scratch.p + (size_t)hsc[i].rank);
     return SB_OK;
 }
 
@@ -1030,7 +1056,12 @@ static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, 
             (null_op ? fl.any_null : mode.filt[i].kind == FK_BYTES ? fl.any_bin : fl.any_cmp) = true;
             if (mode.filt[i].combine == SB_SEL_SET) fl.any_set = true;
         }
-        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, &fl);
+        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, &fl, nullptr);
+    } else if (mode.selected()) {
+        SelLaunch sl{(const SelCol*)(ctx->tables.p + L.fcols), d_vlen, false};
+        for (uint64_t i = 0; i < n; i++)
+            if (mode.selc[i].validity) sl.any_nullable = true;
+        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, &sl);
     } else {
         // bitmaps are assembled with OR at page seams: start from zero
         for (uint64_t i = 0; i < n; i++) {
@@ -1039,7 +1070,7 @@ static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, 
             if (d.nullable && d.validity && d.rows) (void)hipMemsetAsync(d.validity, 0, (d.rows + 31) / 32 * 4, s);
             if (d.ptype == SB_TYPE_BOOLEAN && d.values && d.rows) (void)hipMemsetAsync(d.values, 0, (d.rows + 31) / 32 * 4, s);
         }
-        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr);
+        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, nullptr);
     }
 }
 
@@ -1050,7 +1081,7 @@ static int32_t queue_read_results(sb_ctx* ctx, StageSlot* slot, const ReadLayout
     const hipStream_t s = ctx->stream;
     const ColDesc* hc = (const ColDesc*)(slot->host + L.cols);
     uint8_t* hv = slot->host + L.upload;
-    if (sh.P && (sh.any_binary || mode.sizes() || mode.filter())) {
+    if (sh.P && (sh.any_binary || mode.sizes() || mode.sink())) {
         hipError_t e = hipMemcpyAsync(hv, ctx->tables.p + L.vlen, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
         if (e != hipSuccess) return check_hip(ctx, e, "values_len readback");
     } else {
@@ -1063,8 +1094,8 @@ static int32_t queue_read_results(sb_ctx* ctx, StageSlot* slot, const ReadLayout
     slot->in_flight = true;
     for (uint64_t i = 0; i < n; i++) {
         Pending pd;
-        pd.kind = mode.filter() ? Pending::FILTER_COL : Pending::READ_COL;
-        pd.user = mode.filter() ? (void*)mode.sel_out[i] : (void*)&cols[i];
+        pd.kind = mode.filter() ? Pending::FILTER_COL : mode.selected() ? Pending::RSEL_COL : Pending::READ_COL;
+        pd.user = mode.filter() ? (void*)mode.sel_out[i] : mode.selected() ? (void*)mode.sel_users[i] : (void*)&cols[i];
         pd.host = hv + i * sizeof(uint64_t);
         pd.n = 0;
         ctx->iv.pending.push_back(pd);
@@ -1399,6 +1430,177 @@ int32_t sb_filter_columns(sb_ctx* ctx, sb_column_filter* cols, uint64_t n, int32
     }
     const int32_t rc = filter_impl(ctx, v.data(), results.data(), n);
     if (rc == SB_OK && !ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::FILTER, cols, n, sb_write_options{}, mem});
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------ selected read
+static sb_column_read read_col_of(const sb_column_read_selected& u) {
+    sb_column_read r;
+    memset(&r, 0, sizeof r);
+    r.physical_type = u.physical_type;
+    r.is_nullable = u.is_nullable;
+    r.pages = u.pages;
+    r.pages_len = u.pages_len;
+    r.metas = u.metas;
+    r.n_pages = u.n_pages;
+    r.page_offsets = u.page_offsets;
+    return r;
+}
+
+// The replay of an interval in which a Freq page was met by a call that ends in a sink (KIND_FILTER_FREQ): like
+// filter_columns_decoded, the columns are decoded like a read into the staging area — values, validity, the Freq second
+// pass — and k_rsel_plain compacts them from there with the same sink.
+static int32_t rsel_columns_decoded(sb_ctx* ctx, sb_column_read_selected* cols, std::vector<SelCol>& hs, uint64_t n) {
+    hipStream_t s = ctx->stream;
+    ctx->iv.filter_tmp.emplace_back(n);
+    std::vector<sb_column_read>& rr = ctx->iv.filter_tmp.back();
+    size_t total = 0;
+    std::vector<size_t> o_val(n), o_bits(n);
+    for (uint64_t i = 0; i < n; i++) {
+        o_val[i] = total;
+        total += align_up(cols[i].rows * hs[i].w, 64);
+        o_bits[i] = total;
+        total += align_up((cols[i].rows + 31) / 32 * 4, 64);
+    }
+    if (!ensure(ctx, ctx->filter_stage, total + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
+    for (uint64_t i = 0; i < n; i++) {
+        sb_column_read& r = rr[i] = read_col_of(cols[i]);
+        r.values = ctx->filter_stage.p + o_val[i];
+        r.values_capacity = cols[i].rows * hs[i].w;
+        r.validity = ctx->filter_stage.p + o_bits[i];
+        r.validity_capacity = (cols[i].rows + 31) / 32 * 4;
+    }
+    int32_t rc = read_columns_impl(ctx, rr.data(), n, SB_MEM_DEVICE, ReadMode{ReadMode::READ});
+    if (rc != SB_OK) return rc;
+    if (hipStreamSynchronize(s) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "selected-read replay: synchronize failed");
+    rc = freq_second_pass(ctx);
+    if (rc != SB_OK) return rc;
+    // [SelCol per column][bits set per column][the rank tables]
+    size_t off = align_up(n * sizeof(SelCol), 64);
+    const size_t o_counts = off;
+    off = align_up(off + n * sizeof(uint64_t), 64);
+    std::vector<size_t> o_rank(n);
+    for (uint64_t i = 0; i < n; i++) {
+        o_rank[i] = off;
+        off += align_up(rsel_rank_words(cols[i].rows) * 8, 16);
+    }
+    uint8_t* dev = nullptr;
+    if (hipMalloc((void**)&dev, off) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(selected-read replay) failed");
+    ctx->iv.temp_dev.push_back(dev);
+    std::vector<uint64_t> rows(n);
+    std::vector<const uint8_t*> vals(n), bits(n);
+    bool any_nullable = false;
+    for (uint64_t i = 0; i < n; i++) {
+        hs[i].rank = (uint64_t*)(dev + o_rank[i]);
+        rows[i] = cols[i].rows;
+        vals[i] = (const uint8_t*)rr[i].values;
+        bits[i] = cols[i].is_nullable ? rr[i].validity : nullptr;
+        if (hs[i].validity) any_nullable = true;
+    }
+    if (hipMemcpy(dev, hs.data(), n * sizeof(SelCol), hipMemcpyHostToDevice) != hipSuccess)
+        return ctx->fail(SB_ERR_EXTERNAL, "selected-read replay: upload failed");
+    StageSlot* slot = acquire_slot(ctx, n * sizeof(uint64_t));
+    if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
+    uint64_t* d_counts = (uint64_t*)(dev + o_counts);
+    launch_rsel_plain(ctx, (const SelCol*)dev, (uint32_t)n, d_counts, any_nullable, rows.data(), vals.data(), bits.data());
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(slot->host, d_counts, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return check_hip(ctx, e, "selected-read replay");
+    (void)hipEventRecord(slot->done, s);
+    slot->in_flight = true;
+    for (uint64_t i = 0; i < n; i++) {
+        Pending pd;
+        pd.kind = Pending::RSEL_COL;
+        pd.user = &cols[i];
+        pd.host = slot->host + i * sizeof(uint64_t);
+        pd.n = 0;
+        ctx->iv.pending.push_back(pd);
+    }
+    return SB_OK;
+}
+
+int32_t sb_read_selected(sb_ctx* ctx, sb_column_read_selected* cols, uint64_t n, int32_t mem) {
+    if (!ctx || (!cols && n)) return SB_ERR_INVALID;
+    if (n == 0) return SB_OK;
+    // what is refused here is refused before anything is enqueued or written, and does not show again at the synchronize
+    auto refuse = [&](int32_t code, const char* msg) {
+        ctx->last_error = msg;
+        return code;
+    };
+    if (mem != SB_MEM_DEVICE) return refuse(SB_ERR_NYI, "sb_read_selected: SB_MEM_HOST is not implemented");
+    std::vector<uint64_t> rows(n);
+    struct Span {
+        const uint8_t* p;
+        uint64_t len;
+    };
+    std::vector<Span> outs, sels;
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_column_read_selected& c = cols[i];
+        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(SB_ERR_INVALID, "bad physical_type");
+        if (!filter_comparable(c.physical_type))
+            return refuse(SB_ERR_NYI, "sb_read_selected is implemented for 8- to 64-bit integers and floats");
+        if (c.n_pages && !c.metas) return refuse(SB_ERR_INVALID, "metas is null");
+        uint64_t r = 0;
+        for (uint64_t p = 0; p < c.n_pages; p++) r += c.metas[p].num_values;
+        rows[i] = r;
+        const uint64_t sel_bytes = (r + 31) / 32 * 4;
+        if (r && (!c.selection || ((uintptr_t)c.selection & 3) || c.selection_capacity < sel_bytes))
+            return refuse(SB_ERR_INVALID, "selection missing, not 4-byte aligned or smaller than 4*ceil(rows/32) bytes");
+        if (c.values_capacity && !c.values) return refuse(SB_ERR_INVALID, "values is null");
+        if (r && c.is_nullable && (!c.validity || ((uintptr_t)c.validity & 3)))
+            return refuse(SB_ERR_INVALID, "validity buffer of a nullable column missing or not 4-byte aligned");
+        if (r) sels.push_back({c.selection, sel_bytes});
+        if (c.values && c.values_capacity) outs.push_back({(const uint8_t*)c.values, c.values_capacity});
+        if (c.is_nullable && c.validity && c.validity_capacity) outs.push_back({c.validity, c.validity_capacity});
+    }
+    auto overlap = [](const Span& a, const Span& b) { return a.p < b.p + b.len && b.p < a.p + a.len; };
+    for (size_t i = 0; i < outs.size(); i++) {
+        for (size_t j = 0; j < i; j++)
+            if (overlap(outs[i], outs[j])) return refuse(SB_ERR_INVALID, "output buffers of one call overlap");
+        for (const Span& sp : sels)
+            if (overlap(outs[i], sp)) return refuse(SB_ERR_INVALID, "an output buffer overlaps a selection of the call");
+    }
+    std::vector<SelCol> hs(n);
+    std::vector<sb_column_read_selected*> users(n);
+    size_t stage = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        sb_column_read_selected& c = cols[i];
+        c.rows = rows[i];
+        c.selected = 0;
+        c.values_len = 0;
+        users[i] = &c;
+        SelCol& sc = hs[i];
+        memset(&sc, 0, sizeof sc);
+        sc.w = type_width(c.physical_type);
+        sc.sel = (const uint32_t*)c.selection;
+        sc.values = (uint8_t*)c.values;
+        sc.validity = c.is_nullable ? (uint32_t*)c.validity : nullptr;
+        sc.rows = rows[i];
+        sc.cap_rows = c.values ? c.values_capacity / sc.w : 0;
+        sc.cap_words = sc.validity ? c.validity_capacity / 4 : 0;
+        stage += align_up(rows[i] * sc.w, 64);
+    }
+    (void)hipSetDevice(ctx->device);
+    int32_t rc;
+    if (ctx->in_replay && ctx->filter_freq) {
+        rc = rsel_columns_decoded(ctx, cols, hs, n);
+    } else {
+        if (!ensure(ctx, ctx->filter_stage, stage + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
+        // the columns' shares of the staging area, as a filter comparison column has them
+        std::vector<sb_column_read> rc_cols(n);
+        size_t so = 0;
+        for (uint64_t i = 0; i < n; i++) {
+            sb_column_read& r = rc_cols[i] = read_col_of(cols[i]);
+            r.values = ctx->filter_stage.p + so;
+            r.values_capacity = rows[i] * hs[i].w;
+            so += align_up(r.values_capacity, 64);
+        }
+        ReadMode mode{ReadMode::SELECTED};
+        mode.selc = hs.data();
+        mode.sel_users = users.data();
+        rc = read_columns_impl(ctx, rc_cols.data(), n, SB_MEM_DEVICE, mode);
+    }
+    if (rc == SB_OK && !ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::READ_SEL, cols, n, sb_write_options{}, mem});
     return rc;
 }
 

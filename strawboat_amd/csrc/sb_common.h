@@ -292,6 +292,26 @@ struct FilterLaunch {   // what launch_decode needs to end a call with the filte
     bool any_cmp, any_null, any_set;
     bool any_bin;          // comparison columns of a binary type: k_filter_bin_base / _entries / k_filter_bin (sb_filter_bin.h)
 };
+// one column of a selected read (sb_read_selected, sb_read_sel.h), next to its ColDesc
+constexpr uint32_t RSEL_RANK_BLOCKS = 64;   // workgroups per column of the rank scan (k_rsel_sums / k_rsel_rank)
+struct SelCol {
+    const uint32_t* sel;   // the selection bitmap (input)
+    uint8_t* values;       // the caller's outputs ...
+    uint32_t* validity;    // ... (null: not nullable)
+    uint64_t* rank;        // [ceil(rows/32) + 1] bits set below each selection word (the last entry: below `rows`), then
+                           // RSEL_RANK_BLOCKS block sums
+    uint64_t rows;
+    uint64_t cap_rows;     // values_capacity / width: output rows the values buffer holds
+    uint64_t cap_words;    // validity_capacity / 4
+    uint32_t w;            // bytes per value
+    uint32_t pad;
+};
+__host__ __device__ inline uint64_t rsel_rank_words(uint64_t rows) { return (rows + 31) / 32 + 1 + RSEL_RANK_BLOCKS; }
+struct SelLaunch {   // what launch_decode needs to end a call with the selected-read kernels
+    const SelCol* scols;
+    uint64_t* counts;      // [n_cols]: bits set per column
+    bool any_nullable;
+};
 constexpr uint32_t FK_UNSIGNED = 0, FK_SIGNED = 1, FK_F32 = 2, FK_F64 = 3, FK_BYTES = 4;
 constexpr uint32_t FILTER_MASK_PREFIX = 16u;   // FilterCol.mask of SB_PRED_STARTS_WITH (the four relation bits are clear)
 // words of the bit table (a bit per dictionary entry) that a filter call reserves at the END of the aux area of every page

@@ -2753,7 +2753,7 @@ __device__ __forceinline__ RlePart rle_part(uint32_t max_runs, uint32_t part, ui
     return {b0, owns_end ? ~0ull : (uint64_t)(part + 1) * cpp * RLE_CHUNK, part && b0 >= max_runs};
 }
 
-// The walk of k_expand_rle and k_filter_rle.  What the kernel wants of it is a policy P:
+// The walk of k_expand_rle, k_filter_rle and k_rsel_rle (RleExpand, RleFilter, RleSelect).  What the kernel wants of it is a policy P:
 //   P::Rec                       what is kept of a run and staged in LDS (p.s_rec, RLE_CHUNK entries)
 //   p.rec_bytes()                4 + the width of a value: the stride of the run records
 //   p.load(v, in)                the Rec of the run whose value is at v (`in` false: behind the page's last record)
@@ -3120,9 +3120,11 @@ static void launch_lzg(sb_ctx* ctx, const DecodeArgs& a, bool lzg_on, InflateJob
 }  // namespace sb
 #include "sb_filter.h"
 #include "sb_filter_bin.h"
+#include "sb_read_sel.h"
 namespace sb {
 
-void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt) {
+void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
+                   const SelLaunch* rsel) {
     hipStream_t s = ctx->stream;
     (void)hipMemsetAsync(a.job_counts, 0, 16 * sizeof(uint32_t), s);
     const bool qa = !(a.read_skips & RSKIP_QUEUE_A);
@@ -3186,6 +3188,10 @@ void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_p
     }
     if (flt) {   // sb_filter_columns: the same pages, compared instead of stored
         launch_filter(ctx, a, *flt);
+        return;
+    }
+    if (rsel) {   // sb_read_selected: the same pages, the selected rows stored packed
+        launch_rsel(ctx, a, *rsel);
         return;
     }
     // the three expand kernels work on disjoint pages (page-level RLE, tiles of primitives, tiles of binary columns): side

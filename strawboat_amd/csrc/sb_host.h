@@ -26,13 +26,14 @@ struct StageSlot {
 //   kind        user                          host                                        n               bytes
 //   READ_COL    sb_column_read*               8 bytes: values_len                         0               -
 //   FILTER_COL  the caller's `selected`       8 bytes: the bits set                       0               -
+//   RSEL_COL    sb_column_read_selected*      8 bytes: the bits set (values_len follows)  0               -
 //   WRITE_COL   sb_column_write*              u64 [n lengths][n num_values][out_len]      pages           -
 //   ENC_HINT    null                          32 words: pages per codec of a write call   the plan's key  -
 //   NESTED_W    sb_nested_levels_write[n]     the page records of an enqueued level call  items           of the records
 //   NESTED_R    sb_nested_levels_read[n]      the page records of an enqueued level call  items           of the records
 // (acquire_slot sizes what it moves out of a recycled slot by this table)
 struct Pending {
-    enum Kind { READ_COL, WRITE_COL, ENC_HINT, NESTED_W, NESTED_R, FILTER_COL } kind;
+    enum Kind { READ_COL, WRITE_COL, ENC_HINT, NESTED_W, NESTED_R, FILTER_COL, RSEL_COL } kind;
     void* user;
     const uint8_t* host;
     uint64_t n;
@@ -95,7 +96,7 @@ struct sb_ctx {
     sb::DevBuf scratch;  // per-page aux + inflate areas, encode slots
     sb::DevBuf staging;  // device staging for SB_MEM_HOST callers
     sb::DevBuf filter_stage;   // sb_filter_columns: where the inflate queues put the values of LZ4 / Zstd / Snappy / Patas pages (no caller's buffer to inflate into)
-    bool filter_freq = false;  // replay of an interval in which a filter call met a Freq page: filter calls decode into filter_stage first
+    bool filter_freq = false;  // replay of an interval in which a filter or selected-read call met a Freq page: such calls decode into filter_stage first
     sb::DevBuf zlit;     // Zstd literal buffers (fixed pool of inflate waves)
     sb::DevBuf zrec;     // Zstd sequence records (one arena per inflate wave; allocated by the first batch-sized read)
     sb::Status* d_status = nullptr;
@@ -230,7 +231,7 @@ struct sb_ctx {
     // never a one-workgroup walk over a million-row page.  (The callers' column arrays and buffers live until the
     // synchronize anyway: the results are written into them there.)
     struct Call {
-        enum Kind { READ, WRITE, FILTER, FILTER_VAR } kind;   // sb_read_columns, sb_write_columns, sb_filter_columns, sb_filter_columns_var
+        enum Kind { READ, WRITE, FILTER, FILTER_VAR, READ_SEL } kind;   // sb_read_columns, sb_write_columns, sb_filter_columns, sb_filter_columns_var, sb_read_selected
         void* cols;
         uint64_t n;
         sb_write_options opts;
@@ -333,6 +334,7 @@ inline int32_t reissue(sb_ctx* ctx, sb_ctx::Call& cl) {
         case sb_ctx::Call::WRITE: return sb_write_columns(ctx, (sb_column_write*)cl.cols, cl.n, &cl.opts, cl.mem);
         case sb_ctx::Call::FILTER: return sb_filter_columns(ctx, (sb_column_filter*)cl.cols, cl.n, cl.mem);
         case sb_ctx::Call::FILTER_VAR: return sb_filter_columns_var(ctx, (sb_column_filter_var*)cl.cols, cl.n, cl.mem);
+        case sb_ctx::Call::READ_SEL: return sb_read_selected(ctx, (sb_column_read_selected*)cl.cols, cl.n, cl.mem);
     }
     return SB_ERR_INVALID;
 }
