@@ -132,7 +132,10 @@ typedef struct sb_column_read {
     const sb_page_meta* metas; /* HOST: ColumnMeta.pages */
     uint64_t n_pages;
     /* outputs (DEVICE).  Capacities in bytes; bitmaps are written in 32-bit words, so their buffers are
-     * 4-byte aligned with a capacity of 4*ceil(rows/32) (SB_ERR_INVALID otherwise). */
+     * 4-byte aligned with a capacity of 4*ceil(rows/32) (SB_ERR_INVALID otherwise).
+     * Alignment: `pages` may start at any byte (a pointer into a file buffer); `values` of a primitive column and `offsets`
+     * at the element's natural alignment (16 bytes for Int128 / Int256), the value bytes of a binary column at any byte.
+     * Nothing is written outside the capacities given, and no result depends on bytes outside a page's own. */
     void* values;            /* primitives: rows*w; boolean: ceil(rows/8) bitmap bytes; binary: value bytes */
     uint64_t values_capacity;
     uint8_t* validity;       /* ceil(rows/8) bitmap bytes, LSB-first; required iff is_nullable */
@@ -144,7 +147,8 @@ typedef struct sb_column_read {
     uint64_t values_len;     /* bytes produced in `values` */
     /* optional (HOST, n_pages entries): byte offset of every page's data inside `pages`.  NULL =
      * the pages are back to back.  Used for the leaf blocks of nested pages, which sit behind
-     * their level sections (sb_nested_read_levels reports the offsets). */
+     * their level sections (sb_nested_read_levels reports the offsets).  The offsets need not ascend; a page that does
+     * not lie inside [0, pages_len) is refused at the call (SB_ERR_IO, nothing enqueued). */
     const uint64_t* page_offsets;
 } sb_column_read;
 
@@ -184,7 +188,7 @@ int32_t sb_read_columns_sizes(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int
 typedef struct sb_column_filter {
     int32_t physical_type;   /* SB_TYPE_* */
     int32_t is_nullable;
-    const uint8_t* pages;    /* DEVICE: as in sb_column_read */
+    const uint8_t* pages;    /* DEVICE: as in sb_column_read, at any byte alignment */
     uint64_t pages_len;
     const sb_page_meta* metas; /* HOST */
     uint64_t n_pages;
@@ -231,7 +235,7 @@ int32_t sb_filter_columns(sb_ctx* ctx, sb_column_filter* cols, uint64_t n, int32
 typedef struct sb_column_filter_var {
     int32_t physical_type;   /* SB_TYPE_* */
     int32_t is_nullable;
-    const uint8_t* pages;    /* DEVICE */
+    const uint8_t* pages;    /* DEVICE, at any byte alignment */
     uint64_t pages_len;
     const sb_page_meta* metas; /* HOST */
     uint64_t n_pages;
@@ -278,14 +282,14 @@ int32_t sb_filter_columns_var(sb_ctx* ctx, sb_column_filter_var* cols, uint64_t 
 typedef struct sb_column_read_selected {
     int32_t physical_type;   /* SB_TYPE_* */
     int32_t is_nullable;
-    const uint8_t* pages;    /* DEVICE */
+    const uint8_t* pages;    /* DEVICE, at any byte alignment */
     uint64_t pages_len;
     const sb_page_meta* metas; /* HOST */
     uint64_t n_pages;
     const uint64_t* page_offsets; /* optional (HOST) */
     const uint8_t* selection;     /* DEVICE, input: LSB-first bitmap, 4-byte aligned, as the filter calls write it */
     uint64_t selection_capacity;  /* >= 4*ceil(rows/32) bytes */
-    void* values;            /* DEVICE: selected * width bytes are written */
+    void* values;            /* DEVICE, aligned to the type's width: selected * width bytes are written */
     uint64_t values_capacity;
     uint8_t* validity;       /* DEVICE, 4-byte aligned: ceil(selected/8) bytes, written in 32-bit words; required iff is_nullable */
     uint64_t validity_capacity;

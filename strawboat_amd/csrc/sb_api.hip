@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "sb_host.h"
+#include "sb_span.h"
 
 namespace sb {
 
@@ -834,7 +835,9 @@ static int32_t fill_read_tables(sb_ctx* ctx, uint8_t* host, const ReadLayout& L,
             const uint64_t ntiles = (N + TILE_ROWS - 1) / TILE_ROWS;
             t.in_off = c.page_offsets ? c.page_offsets[p] : in_off;
             t.length = len;
-            if (c.page_offsets && t.in_off + len > c.pages_len) return ctx->fail(SB_ERR_IO, "page_offsets + length exceeds pages_len");
+            // (every page, with or without page_offsets; in_off is the sum of the lengths before the page in both cases)
+            if (c.page_offsets && !page_span_ok(t.in_off, len, c.pages_len)) return ctx->fail(SB_ERR_IO, "page_offsets + length exceeds pages_len");
+            if (!page_span_ok(in_off, len, c.pages_len)) return ctx->fail(SB_ERR_IO, "sum of PageMeta.length exceeds pages_len");
             t.num_values = N;
             t.out_row = out_row;
             t.col = (uint32_t)i;
@@ -848,7 +851,6 @@ static int32_t fill_read_tables(sb_ctx* ctx, uint8_t* host, const ReadLayout& L,
             out_row += N;
             tile_i += ntiles;
         }
-        if (in_off > c.pages_len) return ctx->fail(SB_ERR_IO, "sum of PageMeta.length exceeds pages_len");
     }
     if (mode.filter()) {
         FilterCol* hfc = (FilterCol*)(host + L.fcols);

@@ -157,6 +157,7 @@ class FilterBatch:
                 c, r = arr[i], rarr[i]
                 c.physical_type, c.is_nullable = r.physical_type, r.is_nullable
                 c.pages, c.pages_len, c.metas, c.n_pages = r.pages, r.pages_len, r.metas, r.n_pages
+                c.page_offsets = r.page_offsets
                 c.op = OPS[pr.op]
                 c.combine = COMBINE[combine]
                 buf = C.create_string_buffer(literals[i], max(1, len(literals[i])))   # (read again by a replay: kept with the batch)

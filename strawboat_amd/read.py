@@ -24,6 +24,7 @@ class ColumnPages:
     is_nullable: bool
     pages: object            # torch.uint8 tensor on the context's device (or host numpy for mem='host')
     metas: Sequence          # PageMeta list or an array of shape [n, 2] (length, num_values)
+    page_offsets: Optional[np.ndarray] = None   # host uint64[n]: byte offset of every page inside `pages` (None: back to back)
 
     def metas_array(self):
         if isinstance(self.metas, np.ndarray):
@@ -94,6 +95,12 @@ def _prepare(ctx, columns):
         c.pages_len = pages.numel()
         c.metas = metas.ctypes.data_as(C.POINTER(N.PageMetaC))
         c.n_pages = metas.shape[0]
+        if col.page_offsets is not None:
+            po = np.ascontiguousarray(col.page_offsets, dtype=np.uint64).reshape(-1)
+            if po.size != metas.shape[0]:
+                raise ValueError("page_offsets has %d entries, the column %d pages" % (po.size, metas.shape[0]))
+            keep.append(po)
+            c.page_offsets = po.ctypes.data_as(C.c_void_p)
     return arr, keep
 
 

@@ -126,6 +126,7 @@ class ReadSelectedBatch:
                 c, r = arr[i], rarr[i]
                 c.physical_type, c.is_nullable = r.physical_type, r.is_nullable
                 c.pages, c.pages_len, c.metas, c.n_pages = r.pages, r.pages_len, r.metas, r.n_pages
+                c.page_offsets = r.page_offsets
                 rows = rows_of[i]
                 if out is not None:
                     o = out[i]
