@@ -301,6 +301,70 @@ typedef struct sb_column_read_selected {
 
 int32_t sb_read_selected(sb_ctx* ctx, sb_column_read_selected* cols, uint64_t n, int32_t mem);
 
+/* The same call for Binary / LargeBinary columns (Utf8 / LargeUtf8 are stored as these): a string payload column
+ * behind a filter.  Output row k is the column's row at the k-th set bit of `selection` below `rows`:
+ *   offsets[0] = 0 (written whenever the call is accepted, also with selected == 0);
+ *   offsets[k+1] - offsets[k] is the byte length sb_read_columns gives that row — the difference of its two offsets,
+ *   for a null row too, whatever the writer put there; offsets are int32 (Binary) or int64 (LargeBinary);
+ *   values[offsets[k] .. offsets[k+1]) are the row's bytes, back to back;
+ *   validity bit k as in sb_read_selected, the zero bits >= selected of the last word included.
+ * What is written, and where:
+ *   - nothing outside offsets_capacity, values_capacity and validity_capacity, ever;
+ *   - nothing behind (selected+1)*sizeof(offset), values_len or 4*ceil(selected/32) in an interval that runs once;
+ *   - EXCEPTION: an interval that is issued again (sb_ctx_replays) runs this call twice.  Where its bitmap is written
+ *     by a filter call of the same interval, the first run goes by the bitmap of the first pass — which can have more
+ *     bits set, a filter column with a primitive Freq page being left alone there — and what that run wrote INSIDE the
+ *     capacities stays behind the three marks above: the second run cannot restore bytes it does not know.  Below the
+ *     marks everything is the second run's.  A caller that needs the bytes behind the marks untouched hands in
+ *     capacities it can afford to have written, or reads the bitmap in an interval of its own.  (sb_read_selected
+ *     has the same property for values_len and its validity words.)
+ *
+ * Neither `selected` nor `values_len` is known at the call, so every capacity is checked on the device:
+ * offsets_capacity < (selected+1)*sizeof(offset) or (nullable) validity_capacity < 4*ceil(selected/32) raises
+ * SB_ERR_INVALID at the synchronize (site 500), values_capacity < values_len raises it too (site 510); a Binary column
+ * whose selected bytes exceed INT32_MAX raises SB_ERR_OUT_OF_SPEC (site 511).  Nothing outside the capacities given is
+ * written in any of these cases, and `selected` and `values_len` are filled in all the same: they say what to allocate.
+ * Always enough: (rows+1)*sizeof(offset), 4*ceil(rows/32), and the column's values_len from sb_read_columns_sizes.
+ * The value blocks of LZ4 / Zstd / Snappy pages are inflated into the context's staging area first, whatever the
+ * selection: `stage_capacity` as in sb_column_filter_var (0 = 4 * pages_len).
+ *
+ * Refused at the call, nothing enqueued and no byte touched: a type that is not Binary / LargeBinary (numeric columns:
+ * sb_read_selected on the same stream) and SB_MEM_HOST (SB_ERR_NYI); a null or misaligned `selection`, a short
+ * selection_capacity, a nullable column without `validity`, `offsets` null, not aligned to its entries or smaller than
+ * one entry, values_capacity > 0 with null `values`, any two of the call's `values` / `validity` / `offsets` buffers
+ * that overlap each other or a selection of the call (SB_ERR_INVALID).  Columns may share ONE selection.
+ *
+ * Enqueued, replayed and reported like sb_read_selected: part of its synchronize interval, issued again in its place
+ * when the interval is (sb_ctx_replays) and the same bytes then; it never asks for a replay itself (a Freq page of
+ * strings is read as a Dict page); no launch hint consulted, the read path's counters left alone.  Page errors are the
+ * decoder's; a Dict index beyond the dictionary on a SELECTED row is SB_ERR_OUT_OF_SPEC, on another row this call's
+ * own kernels do not look at it (a corrupt page without a selected row may or may not raise, as in sb_read_selected).
+ * The selected rows of a page that raised get the length 0. */
+typedef struct sb_column_read_selected_var {
+    int32_t physical_type;   /* SB_TYPE_BINARY | SB_TYPE_LARGE_BINARY */
+    int32_t is_nullable;
+    const uint8_t* pages;    /* DEVICE, at any byte alignment */
+    uint64_t pages_len;
+    const sb_page_meta* metas; /* HOST */
+    uint64_t n_pages;
+    const uint64_t* page_offsets; /* optional (HOST), as in sb_column_read */
+    const uint8_t* selection;     /* DEVICE, input: as in sb_column_read_selected */
+    uint64_t selection_capacity;  /* >= 4*ceil(rows/32) bytes */
+    uint8_t* values;         /* DEVICE, any byte alignment: the selected rows' bytes, back to back */
+    uint64_t values_capacity;
+    uint8_t* validity;       /* DEVICE, 4-byte aligned: ceil(selected/8) bytes, written in 32-bit words; required iff is_nullable */
+    uint64_t validity_capacity;
+    void* offsets;           /* DEVICE, aligned to int32 / int64: selected + 1 offsets */
+    uint64_t offsets_capacity;
+    uint64_t stage_capacity; /* as in sb_column_filter_var; 0 = 4 * pages_len */
+    /* results (HOST, valid after sb_ctx_synchronize) */
+    uint64_t rows;           /* sum of num_values */
+    uint64_t selected;       /* bits set in `selection` below `rows` */
+    uint64_t values_len;     /* bytes of the selected rows */
+} sb_column_read_selected_var;   /* 144 bytes */
+
+int32_t sb_read_selected_var(sb_ctx* ctx, sb_column_read_selected_var* cols, uint64_t n, int32_t mem);
+
 /* ------------------------------------------------------------------ encode
  * Replaces, per leaf column, the page loop of NativeWriter::encode_chunk
  * (src/write/common.rs:54-109): page slicing, then per page write::write -> write_simple

@@ -22,7 +22,8 @@ EXPORTS = ("sb_version", "sb_ctx_create", "sb_ctx_destroy", "sb_ctx_synchronize"
            "sb_file_writer_write_column", "sb_file_writer_finish", "sb_file_writer_close", "sb_file_reader_open",
            "sb_file_reader_n_columns", "sb_file_reader_column", "sb_file_reader_schema", "sb_file_reader_read_pages",
            "sb_file_reader_close", "sb_stat_page", "sb_schema_last_error", "sb_schema_to_bytes", "sb_schema_from_bytes",
-           "sb_schema_metadata_from_bytes", "sb_filter_columns", "sb_filter_columns_var", "sb_read_selected")
+           "sb_schema_metadata_from_bytes", "sb_filter_columns", "sb_filter_columns_var", "sb_read_selected",
+           "sb_read_selected_var")
 
 SB_PRED_EQ, SB_PRED_NE, SB_PRED_LT, SB_PRED_LE, SB_PRED_GT, SB_PRED_GE, SB_PRED_IS_NULL, SB_PRED_IS_NOT_NULL = range(8)
 SB_PRED_STARTS_WITH = 8   # binary types only (sb_filter_columns_var)
@@ -71,6 +72,16 @@ class ColumnReadSelectedC(C.Structure):
                 ("page_offsets", C.c_void_p), ("selection", C.c_void_p), ("selection_capacity", C.c_uint64),
                 ("values", C.c_void_p), ("values_capacity", C.c_uint64), ("validity", C.c_void_p),
                 ("validity_capacity", C.c_uint64), ("rows", C.c_uint64), ("selected", C.c_uint64),
+                ("values_len", C.c_uint64)]
+
+
+class ColumnReadSelectedVarC(C.Structure):
+    _fields_ = [("physical_type", C.c_int32), ("is_nullable", C.c_int32), ("pages", C.c_void_p),
+                ("pages_len", C.c_uint64), ("metas", C.POINTER(PageMetaC)), ("n_pages", C.c_uint64),
+                ("page_offsets", C.c_void_p), ("selection", C.c_void_p), ("selection_capacity", C.c_uint64),
+                ("values", C.c_void_p), ("values_capacity", C.c_uint64), ("validity", C.c_void_p),
+                ("validity_capacity", C.c_uint64), ("offsets", C.c_void_p), ("offsets_capacity", C.c_uint64),
+                ("stage_capacity", C.c_uint64), ("rows", C.c_uint64), ("selected", C.c_uint64),
                 ("values_len", C.c_uint64)]
 
 
@@ -167,6 +178,8 @@ def load():
     L.sb_filter_columns_var.argtypes = [C.c_void_p, C.POINTER(ColumnFilterVarC), C.c_uint64, C.c_int32]
     L.sb_read_selected.restype = C.c_int32
     L.sb_read_selected.argtypes = [C.c_void_p, C.POINTER(ColumnReadSelectedC), C.c_uint64, C.c_int32]
+    L.sb_read_selected_var.restype = C.c_int32
+    L.sb_read_selected_var.argtypes = [C.c_void_p, C.POINTER(ColumnReadSelectedVarC), C.c_uint64, C.c_int32]
     L.sb_read_columns_sizes.restype = C.c_int32
     L.sb_read_columns_sizes.argtypes = [C.c_void_p, C.POINTER(ColumnReadC), C.c_uint64, C.c_int32]
     L.sb_write_bound.restype = C.c_uint64

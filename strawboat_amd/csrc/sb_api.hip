@@ -13,6 +13,7 @@ void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_p
                    const SelLaunch* rsel);
 void launch_rsel_plain(sb_ctx* ctx, const SelCol* scols, uint32_t n_cols, uint64_t* counts, bool any_nullable, const uint64_t* rows,
                        const uint8_t* const* values, const uint8_t* const* validity);
+void launch_rsel_bin(sb_ctx* ctx, const DecodeArgs& a, const SelLaunch& sl);
 void launch_filter_plain(sb_ctx* ctx, const FilterCol& f, const uint8_t* values, const uint8_t* validity, uint64_t rows, uint32_t w, uint64_t* count);
 void launch_parse_sizes(sb_ctx* ctx, const DecodeArgs& a, uint64_t* col_values_len);
 void launch_freq_scatter(sb_ctx* ctx, const FreqEntry* entries, uint32_t n, const uint64_t* ex_off, const uint8_t* ex_base);
@@ -88,7 +89,7 @@ StageSlot* acquire_slot(sb_ctx* ctx, size_t need) {
     if (s.host)
         for (auto& p : ctx->iv.pending) {
             if (p.host < s.host || p.host >= s.host + s.cap) continue;
-            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R) ? (size_t)p.bytes
+            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R) ? (size_t)p.bytes
                                                                                                    : (size_t)(2 * p.n + 1) * 8;
             ctx->iv.rescued.emplace_back(p.host, p.host + nb);
             p.host = ctx->iv.rescued.back().data();
@@ -219,8 +220,8 @@ void* sb_ctx_stream(sb_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 struct ReadMode {
     // sb_read_columns (and the decode of a filter replay) / sb_read_columns_sizes / the Freq second pass, from inside a
     // synchronize / sb_filter_columns[_var], whose columns end in the filter kernels / sb_read_selected, whose columns end
-    // in the selected-read kernels
-    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED } kind;
+    // in the selected-read kernels / sb_read_selected_var, whose binary columns end in those of sb_read_sel_bin.h
+    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR } kind;
     const FilterCol* filt = nullptr;             // FILTER: one per column
     uint64_t* const* sel_out = nullptr;          // ... sel_out[i]: the caller's `selected`
     const std::vector<uint8_t>* lits = nullptr;  // ... the literals of the FK_BYTES columns, FilterCol.lit being the offset of each
@@ -228,11 +229,19 @@ struct ReadMode {
     bool freq_pass() const { return kind == FREQ_PASS; }
     const SelCol* selc = nullptr;                // SELECTED: one per column (rank: filled in with the call's tables)
     sb_column_read_selected* const* sel_users = nullptr;   // ... the callers' structs
+    const SelBin* selb = nullptr;                // SELECTED_VAR: one per column beside selc (sums: filled in with the call's tables)
+    sb_column_read_selected_var* const* selv_users = nullptr;   // ... the callers' structs
     bool filter() const { return kind == FILTER; }
     bool selected() const { return kind == SELECTED; }
+    bool selected_var() const { return kind == SELECTED_VAR; }
+    bool ranked() const { return kind == SELECTED || kind == SELECTED_VAR; }   // a SelCol and a rank table per column
+    // binary columns whose value blocks are staged and compared or gathered: no offsets are written by the read's kernels
+    bool bin_staged() const { return kind == FILTER || kind == SELECTED_VAR; }
     // the columns end in a sink of their own: `values` is a share of the staging area, there is no validity buffer, and
     // the call neither consults nor feeds the launch hints of the read path
-    bool sink() const { return kind == FILTER || kind == SELECTED; }
+    bool sink() const { return kind == FILTER || kind == SELECTED || kind == SELECTED_VAR; }
+    // words of 8 bytes that come back per column: { selected, values_len } for a SELECTED_VAR call
+    uint64_t result_words() const { return kind == SELECTED_VAR ? 2 : 1; }
 };
 static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, const ReadMode& mode);
 static void update_read_hints(sb_ctx* ctx, uint32_t kinds);   // (next to read_hints, its reader)
@@ -420,6 +429,13 @@ static void deliver_rsel_col(const Pending& p) {
     c->selected = v;
     c->values_len = v * type_width(c->physical_type);
 }
+static void deliver_rsel_var_col(const Pending& p) {
+    uint64_t v[2];
+    memcpy(v, p.host, 16);
+    sb_column_read_selected_var* c = (sb_column_read_selected_var*)p.user;
+    c->selected = v[0];
+    c->values_len = v[1];
+}
 static void deliver_write_col(const Pending& p) {
     sb_column_write* c = (sb_column_write*)p.user;
     const uint64_t* lens = (const uint64_t*)p.host;  // [n_pages lengths][n_pages num_values][total]
@@ -446,6 +462,7 @@ static void deliver_pending(sb_ctx* ctx, const Pending& p, int32_t rc) {
         case Pending::READ_COL: deliver_read_col(p); break;
         case Pending::FILTER_COL: deliver_filter_col(p); break;
         case Pending::RSEL_COL: deliver_rsel_col(p); break;
+        case Pending::RSEL_VAR_COL: deliver_rsel_var_col(p); break;
         case Pending::WRITE_COL: deliver_write_col(p); break;
         case Pending::ENC_HINT:
             if (rc == SB_OK) apply_enc_hint(ctx, p);
@@ -592,8 +609,8 @@ static int32_t read_shape(sb_ctx* ctx, sb_column_read* cols, uint64_t n, const R
             if (!c.values) return ctx->fail(SB_ERR_INVALID, "values is null");
             if (c.is_nullable && !mode.sink() && (!c.validity || c.validity_capacity < (rows + 31) / 32 * 4))
                 return ctx->fail(SB_ERR_INVALID, "validity buffer missing or smaller than 4*ceil(rows/32) bytes");
-            if (is_binary_t(c.physical_type) && mode.filter()) {
-                // (a filter call writes no offsets; `values` is the column's share of the staging area)
+            if (is_binary_t(c.physical_type) && mode.bin_staged()) {
+                // (a filter call writes no offsets, a selected read its own; `values` is the column's share of the staging area)
             } else if (is_binary_t(c.physical_type)) {
                 if (!c.offsets || c.offsets_capacity < (rows + 1) * w)
                     return ctx->fail(SB_ERR_INVALID, "offsets buffer missing or too small");
@@ -694,7 +711,7 @@ static ReadHints read_hints(sb_ctx* ctx, const ReadMode& mode, const ReadShape& 
 // Where the call's tables sit, on the device (ctx->tables) and — up to `upload` — in the staging slot, whose next n words
 // receive the results.  A pure function of shape, hints and mode.
 struct ReadLayout {
-    size_t cols, tasks, fcols, lits, upload, descs, tiles, jobs_a, jobs_b, jobs_z, counts, vlen, zb_counts, zb_frames, zs, rle, bpg, total;
+    size_t cols, tasks, fcols, bcols, lits, upload, descs, tiles, jobs_a, jobs_b, jobs_z, counts, vlen, zb_counts, zb_frames, zs, rle, bpg, total;
     size_t job_cap;        // queue entries: 2 per page + room for the frames of Zstd buffers that are several frames (one entry per frame)
     bool want_z;           // queue Z (calls with binary columns that produce values): Zstd payloads known to k_parse, entropy stages with queue A's
     uint64_t zs_seg_cap;
@@ -711,7 +728,9 @@ static ReadLayout read_layout(uint64_t n, const ReadShape& sh, const ReadHints& 
     off = align_up(off + P * sizeof(PageTask), 64);
     L.fcols = off;
     if (mode.filter()) off = align_up(off + n * sizeof(FilterCol), 64);
-    if (mode.selected()) off = align_up(off + n * sizeof(SelCol), 64);   // (in the filter columns' place)
+    if (mode.ranked()) off = align_up(off + n * sizeof(SelCol), 64);   // (in the filter columns' place)
+    L.bcols = off;
+    if (mode.selected_var()) off = align_up(off + n * sizeof(SelBin), 64);
     L.lits = off;
     if (mode.lits) off = align_up(off + mode.lits->size(), 64);
     L.upload = off;
@@ -729,8 +748,8 @@ static ReadLayout read_layout(uint64_t n, const ReadShape& sh, const ReadHints& 
     if (L.want_z) off = align_up(off + L.job_cap * sizeof(InflateJob), 64);
     L.counts = off;
     off = align_up(off + 64, 64);
-    L.vlen = off;
-    off = align_up(off + n * sizeof(uint64_t), 64);
+    L.vlen = off;   // (a SELECTED_VAR call: the n bit counts of the rank kernels, then its { selected, values_len } per column)
+    off = align_up(off + n * sizeof(uint64_t) * (mode.selected_var() ? 3 : 1), 64);
     // the block-parallel Zstd pipeline: frames + counters here, blocks / literals / records in pools of their own
     L.zb_counts = off;
     if (h.zb_on) off = align_up(off + 64, 64);
@@ -859,14 +878,21 @@ static int32_t fill_read_tables(sb_ctx* ctx, uint8_t* host, const ReadLayout& L,
         for (uint64_t i = 0; i < n; i++)
             if (hfc[i].kind == FK_BYTES) hfc[i].lit += (uint64_t)(uintptr_t)(ctx->tables.p + L.lits);
     }
-    SelCol* hsc = mode.selected() ? (SelCol*)(host + L.fcols) : nullptr;
+    SelCol* hsc = mode.ranked() ? (SelCol*)(host + L.fcols) : nullptr;
     for (uint64_t i = 0; hsc && i < n; i++) {   // the rank tables: behind the pages' areas, sized by the rows
         hsc[i] = mode.selc[i];
         hsc[i].rank = (uint64_t*)scratch_off;   // (an offset until the buffer is known)
         scratch_off += align_up(rsel_rank_words(cols[i].rows) * 8, 16);
     }
+    SelBin* hsb = mode.selected_var() ? (SelBin*)(host + L.bcols) : nullptr;
+    for (uint64_t i = 0; hsb && i < n; i++) {   // ... and behind them the sums of the length scan, the columns' back to back
+        hsb[i] = mode.selb[i];
+        hsb[i].sums = (uint64_t*)scratch_off;
+        scratch_off += RSEL_BIN_SUM_WORDS * 8;
+    }
     if (!ensure(ctx, ctx->scratch, scratch_off + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(scratch) failed");
     for (uint64_t i = 0; hsc && i < n; i++) hsc[i].rank = (uint64_t*)(ctx->scratch.p + (size_t)hsc[i].rank);
+    for (uint64_t i = 0; hsb && i < n; i++) hsb[i].sums = (uint64_t*)(ctx->scratch.p + (size_t)hsb[i].sums);
     return SB_OK;
 }
 
@@ -1044,9 +1070,9 @@ static DecodeArgs fill_decode_args(sb_ctx* ctx, uint64_t n, const ReadMode& mode
     return a;
 }
 
-// The launches of the three kinds of call (hc: the call's columns, host copy)
+// The launches of the kinds of call (hc: the call's columns, host copy; hb: the SelBin of a SELECTED_VAR call, host copy)
 static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, const ReadHints& h, const ReadLayout& L, const DecodeArgs& a,
-                        const ColDesc* hc, uint64_t n) {
+                        const ColDesc* hc, const SelBin* hb, uint64_t n) {
     const hipStream_t s = ctx->stream;
     uint64_t* d_vlen = (uint64_t*)(ctx->tables.p + L.vlen);   // values_len / bits set per column
     if (mode.sizes()) {
@@ -1064,6 +1090,15 @@ static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, 
         for (uint64_t i = 0; i < n; i++)
             if (mode.selc[i].validity) sl.any_nullable = true;
         if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, &sl);
+    } else if (mode.selected_var()) {
+        SelLaunch sl{(const SelCol*)(ctx->tables.p + L.fcols), d_vlen, false, (const SelBin*)(ctx->tables.p + L.bcols), d_vlen + n};
+        for (uint64_t i = 0; i < n; i++)
+            if (mode.selc[i].validity) sl.any_nullable = true;
+        // (the columns' sums are one area: fill_read_tables; what is zeroed is the byte count of the rows without an offset)
+        (void)hipMemsetAsync(hb[0].sums, 0, n * RSEL_BIN_SUM_WORDS * 8, s);
+        // a call without a page still has a result: offsets[0] = 0, selected = values_len = 0
+        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, &sl);
+        else launch_rsel_bin(ctx, a, sl);
     } else {
         // bitmaps are assembled with OR at page seams: start from zero
         for (uint64_t i = 0; i < n; i++) {
@@ -1083,7 +1118,10 @@ static int32_t queue_read_results(sb_ctx* ctx, StageSlot* slot, const ReadLayout
     const hipStream_t s = ctx->stream;
     const ColDesc* hc = (const ColDesc*)(slot->host + L.cols);
     uint8_t* hv = slot->host + L.upload;
-    if (sh.P && (sh.any_binary || mode.sizes() || mode.sink())) {
+    if (mode.selected_var()) {   // { selected, values_len } per column, behind the n bit counts; also of a call without a page
+        hipError_t e = hipMemcpyAsync(hv, ctx->tables.p + L.vlen + n * sizeof(uint64_t), 2 * n * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+        if (e != hipSuccess) return check_hip(ctx, e, "values_len readback");
+    } else if (sh.P && (sh.any_binary || mode.sizes() || mode.sink())) {
         hipError_t e = hipMemcpyAsync(hv, ctx->tables.p + L.vlen, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
         if (e != hipSuccess) return check_hip(ctx, e, "values_len readback");
     } else {
@@ -1096,9 +1134,9 @@ static int32_t queue_read_results(sb_ctx* ctx, StageSlot* slot, const ReadLayout
     slot->in_flight = true;
     for (uint64_t i = 0; i < n; i++) {
         Pending pd;
-        pd.kind = mode.filter() ? Pending::FILTER_COL : mode.selected() ? Pending::RSEL_COL : Pending::READ_COL;
-        pd.user = mode.filter() ? (void*)mode.sel_out[i] : mode.selected() ? (void*)mode.sel_users[i] : (void*)&cols[i];
-        pd.host = hv + i * sizeof(uint64_t);
+        pd.kind = mode.filter() ? Pending::FILTER_COL : mode.selected() ? Pending::RSEL_COL : mode.selected_var() ? Pending::RSEL_VAR_COL : Pending::READ_COL;
+        pd.user = mode.filter() ? (void*)mode.sel_out[i] : mode.selected() ? (void*)mode.sel_users[i] : mode.selected_var() ? (void*)mode.selv_users[i] : (void*)&cols[i];
+        pd.host = hv + i * sizeof(uint64_t) * mode.result_words();
         pd.n = 0;
         ctx->iv.pending.push_back(pd);
     }
@@ -1116,7 +1154,7 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
     const ReadHints h = read_hints(ctx, mode, sh);
     const ReadLayout L = read_layout(n, sh, h, mode);
     if (!ensure(ctx, ctx->tables, L.total)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(tables) failed");
-    StageSlot* slot = acquire_slot(ctx, L.upload + n * sizeof(uint64_t));
+    StageSlot* slot = acquire_slot(ctx, L.upload + n * sizeof(uint64_t) * mode.result_words());
     if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
     std::vector<ReadBufs> bufs;
     if ((rc = stage_read_cols(ctx, s, cols, n, mem, mode, bufs)) != SB_OK) return rc;
@@ -1131,7 +1169,7 @@ static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, 
     sb_ctx::FreqLog* log = nullptr;
     if ((rc = reserve_freq_log(ctx, s, mode, sh.P, log)) != SB_OK) return rc;
     const DecodeArgs a = fill_decode_args(ctx, n, mode, sh, h, L, zb, lzg, log);
-    launch_read(ctx, mode, sh, h, L, a, (const ColDesc*)(slot->host + L.cols), n);
+    launch_read(ctx, mode, sh, h, L, a, (const ColDesc*)(slot->host + L.cols), (const SelBin*)(slot->host + L.bcols), n);
     e = hipGetLastError();
     if (e != hipSuccess) return check_hip(ctx, e, "decode launch");
     if ((rc = queue_read_results(ctx, slot, L, mode, sh, cols, n)) != SB_OK) return rc;
@@ -1521,6 +1559,45 @@ static int32_t rsel_columns_decoded(sb_ctx* ctx, sb_column_read_selected* cols, 
     return SB_OK;
 }
 
+// What sb_read_selected and sb_read_selected_var check of a column's arguments behind their own type checks, and of
+// the call's buffers together: one definition, so that the two entry points refuse the same things.  The message of the
+// refusal (SB_ERR_INVALID) or null.
+extern "C++" {   // (a template: not inside the C linkage of the entry points)
+struct SelSpan {
+    const uint8_t* p;
+    uint64_t len;
+};
+struct SelSpans {
+    std::vector<SelSpan> outs, sels;   // the outputs and the selections of the call (an entry point adds outputs of its own)
+};
+template <class Col>
+static const char* sel_check_column(const Col& c, SelSpans& sp, uint64_t* rows) {
+    if (c.n_pages && !c.metas) return "metas is null";
+    uint64_t r = 0;
+    for (uint64_t p = 0; p < c.n_pages; p++) r += c.metas[p].num_values;
+    *rows = r;
+    const uint64_t sel_bytes = (r + 31) / 32 * 4;
+    if (r && (!c.selection || ((uintptr_t)c.selection & 3) || c.selection_capacity < sel_bytes))
+        return "selection missing, not 4-byte aligned or smaller than 4*ceil(rows/32) bytes";
+    if (c.values_capacity && !c.values) return "values is null";
+    if (r && c.is_nullable && (!c.validity || ((uintptr_t)c.validity & 3))) return "validity buffer of a nullable column missing or not 4-byte aligned";
+    if (r) sp.sels.push_back({c.selection, sel_bytes});
+    if (c.values && c.values_capacity) sp.outs.push_back({(const uint8_t*)c.values, c.values_capacity});
+    if (c.is_nullable && c.validity && c.validity_capacity) sp.outs.push_back({c.validity, c.validity_capacity});
+    return nullptr;
+}
+static const char* sel_check_overlaps(const SelSpans& sp) {
+    auto overlap = [](const SelSpan& a, const SelSpan& b) { return a.p < b.p + b.len && b.p < a.p + a.len; };
+    for (size_t i = 0; i < sp.outs.size(); i++) {
+        for (size_t j = 0; j < i; j++)
+            if (overlap(sp.outs[i], sp.outs[j])) return "output buffers of one call overlap";
+        for (const SelSpan& s : sp.sels)
+            if (overlap(sp.outs[i], s)) return "an output buffer overlaps a selection of the call";
+    }
+    return nullptr;
+}
+}   // extern "C++"
+
 int32_t sb_read_selected(sb_ctx* ctx, sb_column_read_selected* cols, uint64_t n, int32_t mem) {
     if (!ctx || (!cols && n)) return SB_ERR_INVALID;
     if (n == 0) return SB_OK;
@@ -1531,37 +1608,15 @@ int32_t sb_read_selected(sb_ctx* ctx, sb_column_read_selected* cols, uint64_t n,
     };
     if (mem != SB_MEM_DEVICE) return refuse(SB_ERR_NYI, "sb_read_selected: SB_MEM_HOST is not implemented");
     std::vector<uint64_t> rows(n);
-    struct Span {
-        const uint8_t* p;
-        uint64_t len;
-    };
-    std::vector<Span> outs, sels;
+    SelSpans sp;
     for (uint64_t i = 0; i < n; i++) {
         const sb_column_read_selected& c = cols[i];
         if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(SB_ERR_INVALID, "bad physical_type");
         if (!filter_comparable(c.physical_type))
             return refuse(SB_ERR_NYI, "sb_read_selected is implemented for 8- to 64-bit integers and floats");
-        if (c.n_pages && !c.metas) return refuse(SB_ERR_INVALID, "metas is null");
-        uint64_t r = 0;
-        for (uint64_t p = 0; p < c.n_pages; p++) r += c.metas[p].num_values;
-        rows[i] = r;
-        const uint64_t sel_bytes = (r + 31) / 32 * 4;
-        if (r && (!c.selection || ((uintptr_t)c.selection & 3) || c.selection_capacity < sel_bytes))
-            return refuse(SB_ERR_INVALID, "selection missing, not 4-byte aligned or smaller than 4*ceil(rows/32) bytes");
-        if (c.values_capacity && !c.values) return refuse(SB_ERR_INVALID, "values is null");
-        if (r && c.is_nullable && (!c.validity || ((uintptr_t)c.validity & 3)))
-            return refuse(SB_ERR_INVALID, "validity buffer of a nullable column missing or not 4-byte aligned");
-        if (r) sels.push_back({c.selection, sel_bytes});
-        if (c.values && c.values_capacity) outs.push_back({(const uint8_t*)c.values, c.values_capacity});
-        if (c.is_nullable && c.validity && c.validity_capacity) outs.push_back({c.validity, c.validity_capacity});
+        if (const char* msg = sel_check_column(c, sp, &rows[i])) return refuse(SB_ERR_INVALID, msg);
     }
-    auto overlap = [](const Span& a, const Span& b) { return a.p < b.p + b.len && b.p < a.p + a.len; };
-    for (size_t i = 0; i < outs.size(); i++) {
-        for (size_t j = 0; j < i; j++)
-            if (overlap(outs[i], outs[j])) return refuse(SB_ERR_INVALID, "output buffers of one call overlap");
-        for (const Span& sp : sels)
-            if (overlap(outs[i], sp)) return refuse(SB_ERR_INVALID, "an output buffer overlaps a selection of the call");
-    }
+    if (const char* msg = sel_check_overlaps(sp)) return refuse(SB_ERR_INVALID, msg);
     std::vector<SelCol> hs(n);
     std::vector<sb_column_read_selected*> users(n);
     size_t stage = 0;
@@ -1603,6 +1658,96 @@ int32_t sb_read_selected(sb_ctx* ctx, sb_column_read_selected* cols, uint64_t n,
         rc = read_columns_impl(ctx, rc_cols.data(), n, SB_MEM_DEVICE, mode);
     }
     if (rc == SB_OK && !ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::READ_SEL, cols, n, sb_write_options{}, mem});
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------ selected read, binary columns
+static sb_column_read read_col_of(const sb_column_read_selected_var& u) {
+    sb_column_read r;
+    memset(&r, 0, sizeof r);
+    r.physical_type = u.physical_type;
+    r.is_nullable = u.is_nullable;
+    r.pages = u.pages;
+    r.pages_len = u.pages_len;
+    r.metas = u.metas;
+    r.n_pages = u.n_pages;
+    r.page_offsets = u.page_offsets;
+    return r;
+}
+
+// The binary columns of a selected read are what the binary columns of a filter call are up to k_plan: a share of the
+// staging area for the inflated value blocks, Freq pages as virtual Dict pages.  So the call never asks for the Freq
+// replay, and in an interval that is replayed for someone else's primitive Freq page (ctx->filter_freq) it takes this
+// same path, as filter_impl does for its binary columns.
+int32_t sb_read_selected_var(sb_ctx* ctx, sb_column_read_selected_var* cols, uint64_t n, int32_t mem) {
+    if (!ctx || (!cols && n)) return SB_ERR_INVALID;
+    if (n == 0) return SB_OK;
+    // what is refused here is refused before anything is enqueued or written, and does not show again at the synchronize
+    auto refuse = [&](int32_t code, const char* msg) {
+        ctx->last_error = msg;
+        return code;
+    };
+    if (mem != SB_MEM_DEVICE) return refuse(SB_ERR_NYI, "sb_read_selected_var: SB_MEM_HOST is not implemented");
+    std::vector<uint64_t> rows(n);
+    SelSpans sp;
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_column_read_selected_var& c = cols[i];
+        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(SB_ERR_INVALID, "bad physical_type");
+        if (!is_binary_t(c.physical_type))
+            return refuse(SB_ERR_NYI, "sb_read_selected_var is implemented for Binary and LargeBinary: numbers go through sb_read_selected");
+        if (const char* msg = sel_check_column(c, sp, &rows[i])) return refuse(SB_ERR_INVALID, msg);
+        const uint32_t osize = type_width(c.physical_type);
+        // (offsets[0] is written by every accepted call, so a buffer without room for it counts as missing)
+        if (!c.offsets || ((uintptr_t)c.offsets & (osize - 1)) || c.offsets_capacity < osize)
+            return refuse(SB_ERR_INVALID, "offsets missing, not aligned to its entries or smaller than one entry");
+        sp.outs.push_back({(const uint8_t*)c.offsets, c.offsets_capacity});
+    }
+    if (const char* msg = sel_check_overlaps(sp)) return refuse(SB_ERR_INVALID, msg);
+    std::vector<SelCol> hs(n);
+    std::vector<SelBin> hb(n);
+    std::vector<sb_column_read_selected_var*> users(n);
+    std::vector<uint64_t> stage_cap(n);
+    size_t stage = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        sb_column_read_selected_var& c = cols[i];
+        c.rows = rows[i];
+        c.selected = 0;
+        c.values_len = 0;
+        users[i] = &c;
+        SelCol& sc = hs[i];
+        memset(&sc, 0, sizeof sc);
+        sc.w = type_width(c.physical_type);
+        sc.sel = (const uint32_t*)c.selection;
+        sc.values = c.values;
+        sc.validity = c.is_nullable ? (uint32_t*)c.validity : nullptr;
+        sc.rows = rows[i];
+        sc.cap_rows = c.offsets_capacity / sc.w - 1;
+        sc.cap_words = sc.validity ? c.validity_capacity / 4 : 0;
+        SelBin& bc = hb[i];
+        memset(&bc, 0, sizeof bc);
+        bc.offsets = (uint8_t*)c.offsets;
+        bc.values_cap = c.values ? c.values_capacity : 0;
+        bc.osize = sc.w;
+        stage_cap[i] = c.stage_capacity ? c.stage_capacity : 4 * c.pages_len;   // (the caller's field stays as given: a replay reads it again)
+        stage += align_up(stage_cap[i], 64);
+    }
+    (void)hipSetDevice(ctx->device);
+    if (!ensure(ctx, ctx->filter_stage, stage + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
+    // the columns' shares of the staging area, as a binary filter column has them
+    std::vector<sb_column_read> rc_cols(n);
+    size_t so = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        sb_column_read& r = rc_cols[i] = read_col_of(cols[i]);
+        r.values = ctx->filter_stage.p + so;
+        r.values_capacity = stage_cap[i];
+        so += align_up(stage_cap[i], 64);
+    }
+    ReadMode mode{ReadMode::SELECTED_VAR};
+    mode.selc = hs.data();
+    mode.selb = hb.data();
+    mode.selv_users = users.data();
+    const int32_t rc = read_columns_impl(ctx, rc_cols.data(), n, SB_MEM_DEVICE, mode);
+    if (rc == SB_OK && !ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::READ_SEL_VAR, cols, n, sb_write_options{}, mem});
     return rc;
 }
 

@@ -307,10 +307,23 @@ struct SelCol {
     uint32_t pad;
 };
 __host__ __device__ inline uint64_t rsel_rank_words(uint64_t rows) { return (rows + 31) / 32 + 1 + RSEL_RANK_BLOCKS; }
+// ... and what a column of sb_read_selected_var (sb_read_sel_bin.h) has beside its SelCol, whose `values` are the
+// caller's value bytes, whose cap_rows is offsets_capacity / osize - 1 and whose w is osize
+struct SelBin {
+    uint8_t* offsets;      // the caller's offsets: selected + 1 entries of osize bytes
+    uint64_t* sums;        // RSEL_RANK_BLOCKS block sums of the length scan, then one word (zeroed by the call): the bytes of
+                           // the selected rows at and behind cap_rows, which have no offset to be counted through
+    uint64_t values_cap;   // values_capacity
+    uint32_t osize;        // 4 (Binary) or 8 (LargeBinary)
+    uint32_t pad;
+};
+constexpr uint32_t RSEL_BIN_SUM_WORDS = RSEL_RANK_BLOCKS + 1;
 struct SelLaunch {   // what launch_decode needs to end a call with the selected-read kernels
     const SelCol* scols;
     uint64_t* counts;      // [n_cols]: bits set per column
     bool any_nullable;
+    const SelBin* bcols = nullptr;   // sb_read_selected_var: one per column (null: sb_read_selected)
+    uint64_t* results = nullptr;     // ... [n_cols][2]: { selected, values_len }
 };
 constexpr uint32_t FK_UNSIGNED = 0, FK_SIGNED = 1, FK_F32 = 2, FK_F64 = 3, FK_BYTES = 4;
 constexpr uint32_t FILTER_MASK_PREFIX = 16u;   // FilterCol.mask of SB_PRED_STARTS_WITH (the four relation bits are clear)

@@ -2627,6 +2627,7 @@ __device__ void expand_binary(const ColDesc& c, const PageTask& t, const PageDes
                 const uint32_t len = endb - (i ? s_len[sidx((int)i - 1)] : 0u);
                 const uint8_t* sp = d.dict + eo;
                 uint8_t* dp = vdst + (endb - len);
+                // (the ladder below is also bin_move, sb_read_sel_bin.h: a change to one belongs in the other)
                 if (len >= 16) {
                     uint32_t b = 0;
                     for (; b + 16 <= len; b += 16) stu128(dp + b, ldu128(sp + b));
@@ -3121,6 +3122,7 @@ static void launch_lzg(sb_ctx* ctx, const DecodeArgs& a, bool lzg_on, InflateJob
 #include "sb_filter.h"
 #include "sb_filter_bin.h"
 #include "sb_read_sel.h"
+#include "sb_read_sel_bin.h"
 namespace sb {
 
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
@@ -3156,16 +3158,21 @@ void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_p
         }
         k_plan<<<a.n_pages, WG, 0, s>>>(a);
     }
+    const bool rsel_bin = rsel && rsel->bcols;   // sb_read_selected_var: binary columns as a filter call has them
     if (any_binary && flt) {   // no tile totals, no bases but those of the value blocks to inflate (sb_filter_bin.h)
         launch_filter_bin_base(ctx, a, flt->fcols);
         launch_zstd_split(a, a.jobs_b, a.job_counts + 1, a.job_counts + 9, a.job_cap_b, s);
     }
-    if (any_binary && !flt && a.n_tiles >= BIN_DEFER_TILES) {   // long binary Dict pages: the tiles' value bytes by a workgroup per tile
+    if (any_binary && rsel_bin) {   // ... the same scan for every column (sb_read_sel_bin.h)
+        launch_rsel_bin_base(ctx, a);
+        launch_zstd_split(a, a.jobs_b, a.job_counts + 1, a.job_counts + 9, a.job_cap_b, s);
+    }
+    if (any_binary && !flt && !rsel_bin && a.n_tiles >= BIN_DEFER_TILES) {   // long binary Dict pages: the tiles' value bytes by a workgroup per tile
         KScope k(ctx, "k_bin_tile_sums");
         k_bin_tile_sums<<<min(a.n_tiles, TILE_GRID), WG, 0, s>>>(a);
         k_bin_tile_scan<<<min((a.n_pages + WG / 64 - 1) / (WG / 64), 1024u), WG, 0, s>>>(a);
     }
-    if (any_binary && !flt) {  // (without binary columns the host knows every values_len itself)
+    if (any_binary && !flt && !rsel_bin) {  // (without binary columns the host knows every values_len itself)
         KScope k(ctx, K_COLSCAN);
         k_colscan<<<a.n_cols, 64, 0, s>>>(a, col_values_len);
         launch_zstd_split(a, a.jobs_b, a.job_counts + 1, a.job_counts + 9, a.job_cap_b, s);
@@ -3188,6 +3195,10 @@ void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_p
     }
     if (flt) {   // sb_filter_columns: the same pages, compared instead of stored
         launch_filter(ctx, a, *flt);
+        return;
+    }
+    if (rsel_bin) {   // sb_read_selected_var: offsets and bytes of the selected rows
+        launch_rsel_bin(ctx, a, *rsel);
         return;
     }
     if (rsel) {   // sb_read_selected: the same pages, the selected rows stored packed

@@ -71,22 +71,27 @@ __device__ __forceinline__ bool bin_eval(const uint8_t* v, uint32_t len, const B
 }
 
 // ---- where the inflated value blocks of a column go: one wave per column, scan_column_pages (sb_decode.hip) summing vusize
-// for the pages whose values block is compressed and 0 for the others; no offset bases, no values_len
+// for the pages whose values block is compressed and 0 for the others; no offset bases, no values_len.  (bin_base_column /
+// bin_base_done: the body, which the selected read of binary columns launches for itself — k_rsel_bin_base, sb_read_sel_bin.h)
+__device__ __forceinline__ void bin_base_column(const DecodeArgs& a, const ColDesc& c) {
+    auto staged = [](const PageDesc& d) { return is_basic(d.codec) && d.codec != SB_CODEC_NONE; };
+    scan_column_pages(
+        a, c, [&](const PageDesc& d) { return staged(d) ? d.vusize : 0u; },
+        [&](uint32_t p, const PageDesc& d, bool in, uint64_t base, bool fits) {
+            if (!(in && d.ok && staged(d))) return;
+            a.descs[p].val_base = base;
+            if (!fits) a.descs[p].ok = 0;   // (nothing is inflated or compared; the column raises)
+        });
+}
+__device__ __forceinline__ void bin_base_done(const DecodeArgs& a) {
+    if (last_workgroup_done(&a.job_counts[6]) && threadIdx.x == 0)   // queue B is complete: its length for k_zstd_split
+        a.job_counts[9] = __hip_atomic_load(&a.job_counts[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 __global__ void __launch_bounds__(64) k_filter_bin_base(DecodeArgs a, const FilterCol* fcols) {
     const uint32_t ci = blockIdx.x;
     const ColDesc c = a.cols[ci];
-    if (is_binary(c.ptype) && fcols[ci].kind == FK_BYTES) {
-        auto staged = [](const PageDesc& d) { return is_basic(d.codec) && d.codec != SB_CODEC_NONE; };
-        scan_column_pages(
-            a, c, [&](const PageDesc& d) { return staged(d) ? d.vusize : 0u; },
-            [&](uint32_t p, const PageDesc& d, bool in, uint64_t base, bool fits) {
-                if (!(in && d.ok && staged(d))) return;
-                a.descs[p].val_base = base;
-                if (!fits) a.descs[p].ok = 0;   // (nothing is inflated or compared; the column raises)
-            });
-    }
-    if (last_workgroup_done(&a.job_counts[6]) && threadIdx.x == 0)   // queue B is complete: its length for k_zstd_split
-        a.job_counts[9] = __hip_atomic_load(&a.job_counts[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (is_binary(c.ptype) && fcols[ci].kind == FK_BYTES) bin_base_column(a, c);
+    bin_base_done(a);
 }
 
 // ---- Dict / Freq pages: k_plan's entry offsets and the page's bit table

@@ -10,6 +10,8 @@
 //   k_rsel_rle / k_rsel         the walks of k_expand_rle / k_expand with sel_span as the sink (below)
 //   k_rsel_plain                the replay of a call that met a Freq page: the column decoded like a read into the staging
 //                               area, compacted from there
+// (Binary / LargeBinary columns — sb_read_selected_var — use the rank kernels and sel_rows / sel_validity from here and
+// have their own sinks: sb_read_sel_bin.h)
 // A rank per WORD (8 bytes per 32 rows, a quarter of a byte per row) rather than a rank per TILE_ROWS block: pages start
 // anywhere in a word and RLE chunks anywhere in a tile, so a block rank would leave every lane a popcount over up to 128
 // words; with the word rank a lane's output row is one load and one popcount, and a tile's "any row selected?" is two.
@@ -59,16 +61,40 @@ __device__ __forceinline__ uint32_t sel_word96(uint64_t x, uint32_t sh, uint32_t
     return sh ? (uint32_t)(x >> (64 - sh)) : 0u;
 }
 
-// Rows [lo, hi) of a page, value_of(row) per SELECTED row, by the whole workgroup: a lane per row.  The lane loads its
-// row's selection word; its output row is the word's rank plus the set bits below its own.  The selected lanes of a wave
-// own consecutive output rows, so their stores are one contiguous range.  Validity without an atomic per row: the
-// selected lanes write their bit to popc-compacted positions of the wave's LDS strip, every lane reads back its own
-// position, the ballot of that is the <= 64 validity bits of output rows [k0, k0 + n), and lanes 0..2 put the (at most
-// three) words they touch — a word wholly inside the range with a plain store, a word shared with another wave, tile or
-// page with atomicOr into the buffer k_rsel_clear zeroed (the discipline of sel_put).  Every store is guarded by the
-// capacities of the column's buffers.  No barrier inside: a wave without a selected row moves on at once.
-template <class V>
-__device__ __forceinline__ void sel_span(const SelSink& k, uint64_t lo, uint64_t hi, V value_of) {
+// Rows [lo, hi) of a page, put(row, output row) by every SELECTED lane, by the whole workgroup: a lane per row.  The lane
+// loads its row's selection word; its output row is the word's rank plus the set bits below its own.  The selected lanes
+// of a wave own consecutive output rows, so what they store is one contiguous range.  Validity (sel_validity) follows when
+// the column has a validity buffer.  No barrier inside: a wave without a selected row moves on at once.
+//
+// sel_validity, the validity half, by the whole wave and without an atomic per row: the selected lanes write their bit to
+// popc-compacted positions of the wave's LDS strip, every lane reads back its own position, the ballot of that is the
+// <= 64 validity bits of output rows [k0, k0 + n), and lanes 0..2 put the (at most three) words they touch — a word wholly
+// inside the range with a plain store, a word shared with another wave, tile or page with atomicOr into the buffer
+// k_rsel_clear zeroed (the discipline of sel_put).  Guarded by the capacity of the validity buffer.
+__device__ __forceinline__ void sel_validity(const SelSink& k, uint32_t* strip, uint32_t lane, bool on, uint64_t m, uint64_t ko, uint64_t r) {
+    uint32_t v = 0;
+    if (on) v = k.def_bits ? (uint32_t)(ldu8(k.def_bits + (r >> 3)) >> (r & 7)) & 1u : 1u;
+    const uint32_t pos = (uint32_t)__popcll(m & ((1ull << lane) - 1)), n = (uint32_t)__popcll(m);
+    const uint64_t k0 = __shfl(ko, __ffsll((long long)m) - 1, 64);
+    __builtin_amdgcn_wave_barrier();
+    if (on) strip[pos] = v;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    const uint64_t bits = __ballot(lane < n && strip[lane] != 0);
+    __builtin_amdgcn_wave_barrier();
+    if (lane < 3) {
+        const uint32_t sh = (uint32_t)(k0 & 31);
+        const uint64_t wi = (k0 >> 5) + lane;
+        const uint32_t wm = sel_word96(n == 64 ? ~0ull : (1ull << n) - 1, sh, lane), wb = sel_word96(bits, sh, lane);
+        if (wm && wi < k.s.cap_words) {
+            if (wm == 0xFFFFFFFFu) gst32(k.s.validity + wi, wb);
+            else if (wb) atomicOr(k.s.validity + wi, wb);
+        }
+    }
+}
+template <class P>
+__device__ __forceinline__ void sel_rows(const SelSink& k, uint64_t lo, uint64_t hi, P put) {
     const uint32_t tid = threadIdx.x, lane = tid & 63;
     uint32_t* strip = k.s_strip + (tid & ~63u);
     for (uint64_t g0 = lo; g0 < hi; g0 += WG) {
@@ -82,30 +108,18 @@ __device__ __forceinline__ void sel_span(const SelSink& k, uint64_t lo, uint64_t
         uint64_t ko = 0;
         if (on) {
             ko = gld64(k.s.rank + (c >> 5)) + (uint64_t)__popc(word & ((1u << b) - 1));
-            if (ko < k.s.cap_rows) sel_store(k.s.values + ko * k.s.w, value_of(r), k.s.w);
+            put(r, ko);
         }
         if (!k.s.validity) continue;
-        uint32_t v = 0;
-        if (on) v = k.def_bits ? (uint32_t)(ldu8(k.def_bits + (r >> 3)) >> (r & 7)) & 1u : 1u;
-        const uint32_t pos = (uint32_t)__popcll(m & ((1ull << lane) - 1)), n = (uint32_t)__popcll(m);
-        const uint64_t k0 = __shfl(ko, __ffsll((long long)m) - 1, 64);
-        __builtin_amdgcn_wave_barrier();
-        if (on) strip[pos] = v;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        const uint64_t bits = __ballot(lane < n && strip[lane] != 0);
-        __builtin_amdgcn_wave_barrier();
-        if (lane < 3) {
-            const uint32_t sh = (uint32_t)(k0 & 31);
-            const uint64_t wi = (k0 >> 5) + lane;
-            const uint32_t wm = sel_word96(n == 64 ? ~0ull : (1ull << n) - 1, sh, lane), wb = sel_word96(bits, sh, lane);
-            if (wm && wi < k.s.cap_words) {
-                if (wm == 0xFFFFFFFFu) gst32(k.s.validity + wi, wb);
-                else if (wb) atomicOr(k.s.validity + wi, wb);
-            }
-        }
+        sel_validity(k, strip, lane, on, m, ko, r);
     }
+}
+// the sink of the fixed-width columns: value_of(row), stored with one w-byte store below the capacity of the values buffer
+template <class V>
+__device__ __forceinline__ void sel_span(const SelSink& k, uint64_t lo, uint64_t hi, V value_of) {
+    sel_rows(k, lo, hi, [&](uint64_t r, uint64_t ko) {
+        if (ko < k.s.cap_rows) sel_store(k.s.values + ko * k.s.w, value_of(r), k.s.w);
+    });
 }
 
 // ---- tiles of None / OneValue / Dict / bit-packed / inflated pages (the pages k_expand and k_filter have tiles for)
