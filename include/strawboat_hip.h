@@ -365,6 +365,74 @@ typedef struct sb_column_read_selected_var {
 
 int32_t sb_read_selected_var(sb_ctx* ctx, sb_column_read_selected_var* cols, uint64_t n, int32_t mem);
 
+/* ------------------------------------------------------------------ aggregate
+ * The third thing a scan does with a block: SELECT count(y), min(y), max(y), sum(y) ... WHERE x < 5 wants no row, only a
+ * few scalars per column.  The pages of a column and (optionally) a selection bitmap go in; count, min, max and sum of the
+ * LIVE rows come back in the struct.  A row is live if its selection bit is set and it is not null.  Selection bits at
+ * positions >= rows are ignored; `selection` == NULL selects every row; a non-nullable column has no null row; every row
+ * of a SB_TYPE_NULL column is null.
+ *
+ * rows / selected / count / nans are always filled (SB_AGG_COUNT asks for nothing more); the other fields are written as
+ * 0 where `ops` lacks their bit.
+ *   MIN / MAX  over the live rows that are not NaN.  Integers compare by the physical type's signedness; floats compare
+ *              numerically with -0.0 < +0.0, so the result's bits are determined.  The stored bytes are the bytes of a
+ *              row that has that value, little endian, in the first `width` bytes; the bytes behind `width` are 0, and
+ *              with no such row (count - nans == 0) all 8 bytes are 0.
+ *   SUM        integers: the exact sum of the live rows as a 128-bit two's-complement number (values sign- or
+ *              zero-extended by type; sum_hi is the high word).  Float32 / Float64: the sum of ALL live rows, NaN and
+ *              +-inf included, accumulated in double: its bits in sum_lo, sum_hi = 0.  No floating-point atomics: partial
+ *              sums are combined in an order fixed by the launch shape, so the same call gives the same bits every time
+ *              it is issued, a replayed interval included.
+ *   nans       the live rows that are NaN (0 for integers, and 0 where `ops` has none of MIN / MAX / SUM: no value is
+ *              looked at then).
+ *
+ * Types: MIN / MAX / SUM on INT8..INT64, UINT8..UINT64, FLOAT32, FLOAT64.  With `ops` of 0 or SB_AGG_COUNT alone every
+ * physical type is accepted, and only the def-level section of a page is looked at, as SB_PRED_IS_NULL does it.
+ *
+ * Refused at the call, nothing enqueued and no result field touched: MIN / MAX / SUM on Boolean, Int128, Int256, Binary,
+ * LargeBinary or Null, and SB_MEM_HOST (SB_ERR_NYI); unknown `ops` bits, `reserved` != 0, a bad physical_type, a non-null
+ * `selection` that is not 4-byte aligned or shorter than 4*ceil(rows/32), `metas` null with n_pages > 0 (SB_ERR_INVALID);
+ * a page outside [0, pages_len) (SB_ERR_IO).
+ *
+ * Enqueued like sb_read_selected: page errors are the decoder's, with its codes, at the synchronize (a corrupt page
+ * without a selected row may or may not raise); `rows` and `selected` are delivered even when the interval failed, the
+ * other results are unspecified then.  The call is part of its synchronize interval: when the interval is issued again
+ * (sb_ctx_replays) it is issued again in its place, behind the filter calls that write its bitmap.  A column with a
+ * primitive Freq page and MIN / MAX / SUM asks for that replay itself, as a filter comparison does.  `selection` is an
+ * INPUT: it must stay unmodified until the synchronize.  The call consults no launch hint of the read path and leaves its
+ * counters alone.
+ *
+ * Layout (pinned by tests/test_aggregate_host.py): 136 bytes; physical_type 0, is_nullable 4, pages 8, pages_len 16,
+ * metas 24, n_pages 32, page_offsets 40, selection 48, selection_capacity 56, ops 64, reserved 68, rows 72, selected 80,
+ * count 88, nans 96, min 104, max 112, sum_lo 120, sum_hi 128. */
+#define SB_AGG_COUNT 1u   /* rows / selected / count / nans: always filled, this bit asks for nothing more */
+#define SB_AGG_MIN   2u
+#define SB_AGG_MAX   4u
+#define SB_AGG_SUM   8u
+
+typedef struct sb_column_aggregate {
+    int32_t physical_type;   /* SB_TYPE_* */
+    int32_t is_nullable;
+    const uint8_t* pages;    /* DEVICE, at any byte alignment */
+    uint64_t pages_len;
+    const sb_page_meta* metas; /* HOST */
+    uint64_t n_pages;
+    const uint64_t* page_offsets; /* optional (HOST), as in sb_column_read */
+    const uint8_t* selection;     /* DEVICE, input: LSB-first bitmap, 4-byte aligned; NULL = every row */
+    uint64_t selection_capacity;  /* >= 4*ceil(rows/32) bytes when selection != NULL */
+    uint32_t ops;            /* SB_AGG_* bits */
+    uint32_t reserved;       /* must be 0 */
+    /* results (HOST, valid after sb_ctx_synchronize) */
+    uint64_t rows;           /* sum of num_values */
+    uint64_t selected;       /* bits set in `selection` below `rows` (== rows without a selection) */
+    uint64_t count;          /* selected rows that are not null */
+    uint64_t nans;           /* of those, float NaNs */
+    uint8_t min[8], max[8];  /* a value of the column's own type, little endian, in the first `width` bytes */
+    uint64_t sum_lo, sum_hi;
+} sb_column_aggregate;       /* 136 bytes */
+
+int32_t sb_aggregate_columns(sb_ctx* ctx, sb_column_aggregate* cols, uint64_t n, int32_t mem);
+
 /* ------------------------------------------------------------------ encode
  * Replaces, per leaf column, the page loop of NativeWriter::encode_chunk
  * (src/write/common.rs:54-109): page slicing, then per page write::write -> write_simple

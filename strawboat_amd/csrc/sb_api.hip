@@ -10,7 +10,10 @@
 namespace sb {
 
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
-                   const SelLaunch* rsel);
+                   const SelLaunch* rsel, const AggLaunch* agg);
+void launch_agg_finish(sb_ctx* ctx, const AggCol* acols, const AggPart* parts, uint64_t* results, uint32_t n_cols);
+void launch_agg_plain(sb_ctx* ctx, const AggCol* acols, uint32_t n_cols, AggPart* parts, const uint64_t* rows, const uint8_t* const* values,
+                      const uint8_t* const* validity);
 void launch_rsel_plain(sb_ctx* ctx, const SelCol* scols, uint32_t n_cols, uint64_t* counts, bool any_nullable, const uint64_t* rows,
                        const uint8_t* const* values, const uint8_t* const* validity);
 void launch_rsel_bin(sb_ctx* ctx, const DecodeArgs& a, const SelLaunch& sl);
@@ -89,7 +92,7 @@ StageSlot* acquire_slot(sb_ctx* ctx, size_t need) {
     if (s.host)
         for (auto& p : ctx->iv.pending) {
             if (p.host < s.host || p.host >= s.host + s.cap) continue;
-            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R) ? (size_t)p.bytes
+            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::AGG_COL ? AGG_RESULT_WORDS * 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R) ? (size_t)p.bytes
                                                                                                    : (size_t)(2 * p.n + 1) * 8;
             ctx->iv.rescued.emplace_back(p.host, p.host + nb);
             p.host = ctx->iv.rescued.back().data();
@@ -220,8 +223,9 @@ void* sb_ctx_stream(sb_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 struct ReadMode {
     // sb_read_columns (and the decode of a filter replay) / sb_read_columns_sizes / the Freq second pass, from inside a
     // synchronize / sb_filter_columns[_var], whose columns end in the filter kernels / sb_read_selected, whose columns end
-    // in the selected-read kernels / sb_read_selected_var, whose binary columns end in those of sb_read_sel_bin.h
-    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR } kind;
+    // in the selected-read kernels / sb_read_selected_var, whose binary columns end in those of sb_read_sel_bin.h /
+    // sb_aggregate_columns, whose columns end in the aggregate kernels
+    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR, AGGREGATE } kind;
     const FilterCol* filt = nullptr;             // FILTER: one per column
     uint64_t* const* sel_out = nullptr;          // ... sel_out[i]: the caller's `selected`
     const std::vector<uint8_t>* lits = nullptr;  // ... the literals of the FK_BYTES columns, FilterCol.lit being the offset of each
@@ -231,6 +235,9 @@ struct ReadMode {
     sb_column_read_selected* const* sel_users = nullptr;   // ... the callers' structs
     const SelBin* selb = nullptr;                // SELECTED_VAR: one per column beside selc (sums: filled in with the call's tables)
     sb_column_read_selected_var* const* selv_users = nullptr;   // ... the callers' structs
+    const AggCol* aggc = nullptr;                // AGGREGATE: one per column (the slots: filled in with the call's tables)
+    sb_column_aggregate* const* agg_users = nullptr;   // ... the callers' structs
+    bool aggregate() const { return kind == AGGREGATE; }
     bool filter() const { return kind == FILTER; }
     bool selected() const { return kind == SELECTED; }
     bool selected_var() const { return kind == SELECTED_VAR; }
@@ -239,9 +246,10 @@ struct ReadMode {
     bool bin_staged() const { return kind == FILTER || kind == SELECTED_VAR; }
     // the columns end in a sink of their own: `values` is a share of the staging area, there is no validity buffer, and
     // the call neither consults nor feeds the launch hints of the read path
-    bool sink() const { return kind == FILTER || kind == SELECTED || kind == SELECTED_VAR; }
-    // words of 8 bytes that come back per column: { selected, values_len } for a SELECTED_VAR call
-    uint64_t result_words() const { return kind == SELECTED_VAR ? 2 : 1; }
+    bool sink() const { return kind == FILTER || kind == SELECTED || kind == SELECTED_VAR || kind == AGGREGATE; }
+    // words of 8 bytes that come back per column: { selected, values_len } for a SELECTED_VAR call, the result record of
+    // an AGGREGATE call
+    uint64_t result_words() const { return kind == SELECTED_VAR ? 2 : kind == AGGREGATE ? AGG_RESULT_WORDS : 1; }
 };
 static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, const ReadMode& mode);
 static void update_read_hints(sb_ctx* ctx, uint32_t kinds);   // (next to read_hints, its reader)
@@ -436,6 +444,18 @@ static void deliver_rsel_var_col(const Pending& p) {
     c->selected = v[0];
     c->values_len = v[1];
 }
+static void deliver_agg_col(const Pending& p) {   // (k_agg_finish's record: sb_aggregate.h)
+    uint64_t v[AGG_RESULT_WORDS];
+    memcpy(v, p.host, sizeof v);
+    sb_column_aggregate* c = (sb_column_aggregate*)p.user;
+    c->selected = v[0];
+    c->count = v[1];
+    c->nans = v[2];
+    memcpy(c->min, &v[3], 8);
+    memcpy(c->max, &v[4], 8);
+    c->sum_lo = v[5];
+    c->sum_hi = v[6];
+}
 static void deliver_write_col(const Pending& p) {
     sb_column_write* c = (sb_column_write*)p.user;
     const uint64_t* lens = (const uint64_t*)p.host;  // [n_pages lengths][n_pages num_values][total]
@@ -463,6 +483,7 @@ static void deliver_pending(sb_ctx* ctx, const Pending& p, int32_t rc) {
         case Pending::FILTER_COL: deliver_filter_col(p); break;
         case Pending::RSEL_COL: deliver_rsel_col(p); break;
         case Pending::RSEL_VAR_COL: deliver_rsel_var_col(p); break;
+        case Pending::AGG_COL: deliver_agg_col(p); break;
         case Pending::WRITE_COL: deliver_write_col(p); break;
         case Pending::ENC_HINT:
             if (rc == SB_OK) apply_enc_hint(ctx, p);
@@ -711,7 +732,7 @@ static ReadHints read_hints(sb_ctx* ctx, const ReadMode& mode, const ReadShape& 
 // Where the call's tables sit, on the device (ctx->tables) and — up to `upload` — in the staging slot, whose next n words
 // receive the results.  A pure function of shape, hints and mode.
 struct ReadLayout {
-    size_t cols, tasks, fcols, bcols, lits, upload, descs, tiles, jobs_a, jobs_b, jobs_z, counts, vlen, zb_counts, zb_frames, zs, rle, bpg, total;
+    size_t cols, tasks, fcols, bcols, lits, upload, descs, tiles, jobs_a, jobs_b, jobs_z, counts, vlen, zb_counts, zb_frames, zs, rle, bpg, aggp, total;
     size_t job_cap;        // queue entries: 2 per page + room for the frames of Zstd buffers that are several frames (one entry per frame)
     bool want_z;           // queue Z (calls with binary columns that produce values): Zstd payloads known to k_parse, entropy stages with queue A's
     uint64_t zs_seg_cap;
@@ -729,6 +750,7 @@ static ReadLayout read_layout(uint64_t n, const ReadShape& sh, const ReadHints& 
     L.fcols = off;
     if (mode.filter()) off = align_up(off + n * sizeof(FilterCol), 64);
     if (mode.ranked()) off = align_up(off + n * sizeof(SelCol), 64);   // (in the filter columns' place)
+    if (mode.aggregate()) off = align_up(off + n * sizeof(AggCol), 64);   // (likewise)
     L.bcols = off;
     if (mode.selected_var()) off = align_up(off + n * sizeof(SelBin), 64);
     L.lits = off;
@@ -749,7 +771,7 @@ static ReadLayout read_layout(uint64_t n, const ReadShape& sh, const ReadHints& 
     L.counts = off;
     off = align_up(off + 64, 64);
     L.vlen = off;   // (a SELECTED_VAR call: the n bit counts of the rank kernels, then its { selected, values_len } per column)
-    off = align_up(off + n * sizeof(uint64_t) * (mode.selected_var() ? 3 : 1), 64);
+    off = align_up(off + n * sizeof(uint64_t) * (mode.selected_var() ? 3 : mode.result_words()), 64);
     // the block-parallel Zstd pipeline: frames + counters here, blocks / literals / records in pools of their own
     L.zb_counts = off;
     if (h.zb_on) off = align_up(off + 64, 64);
@@ -763,6 +785,8 @@ static ReadLayout read_layout(uint64_t n, const ReadShape& sh, const ReadHints& 
     if (L.rle_parts > 1) off = align_up(off + P * L.rle_parts * sizeof(uint64_t), 64);
     L.bpg = off;
     if (L.rle_parts > 1) off = align_up(off + P * sizeof(uint32_t), 64);
+    L.aggp = off;   // an AGGREGATE call's partial records: a slot per (page, RLE part), then a slot per tile
+    if (mode.aggregate()) off = align_up(off + (P * L.rle_parts + sh.T) * sizeof(AggPart), 64);
     L.total = off;
     return L;
 }
@@ -877,6 +901,20 @@ static int32_t fill_read_tables(sb_ctx* ctx, uint8_t* host, const ReadLayout& L,
         if (mode.lits && !mode.lits->empty()) memcpy(host + L.lits, mode.lits->data(), mode.lits->size());
         for (uint64_t i = 0; i < n; i++)
             if (hfc[i].kind == FK_BYTES) hfc[i].lit += (uint64_t)(uintptr_t)(ctx->tables.p + L.lits);
+    }
+    if (mode.aggregate()) {   // the columns' slots among the call's partial records (read_layout: L.aggp)
+        AggCol* hac = (AggCol*)(host + L.fcols);
+        memcpy(hac, mode.aggc, n * sizeof(AggCol));
+        uint64_t tile0 = 0;
+        for (uint64_t i = 0; i < n; i++) {
+            uint64_t ntiles = 0;
+            for (uint64_t p = 0; p < cols[i].n_pages; p++) ntiles += (cols[i].metas[p].num_values + TILE_ROWS - 1) / TILE_ROWS;
+            hac[i].page_slot0 = (uint64_t)hc[i].first_page * L.rle_parts;
+            hac[i].page_slots = cols[i].n_pages * L.rle_parts;
+            hac[i].tile_slot0 = page_i * L.rle_parts + tile0;
+            hac[i].tile_slots = ntiles;
+            tile0 += ntiles;
+        }
     }
     SelCol* hsc = mode.ranked() ? (SelCol*)(host + L.fcols) : nullptr;
     for (uint64_t i = 0; hsc && i < n; i++) {   // the rank tables: behind the pages' areas, sized by the rows
@@ -1084,12 +1122,12 @@ static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, 
             (null_op ? fl.any_null : mode.filt[i].kind == FK_BYTES ? fl.any_bin : fl.any_cmp) = true;
             if (mode.filt[i].combine == SB_SEL_SET) fl.any_set = true;
         }
-        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, &fl, nullptr);
+        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, &fl, nullptr, nullptr);
     } else if (mode.selected()) {
         SelLaunch sl{(const SelCol*)(ctx->tables.p + L.fcols), d_vlen, false};
         for (uint64_t i = 0; i < n; i++)
             if (mode.selc[i].validity) sl.any_nullable = true;
-        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, &sl);
+        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, &sl, nullptr);
     } else if (mode.selected_var()) {
         SelLaunch sl{(const SelCol*)(ctx->tables.p + L.fcols), d_vlen, false, (const SelBin*)(ctx->tables.p + L.bcols), d_vlen + n};
         for (uint64_t i = 0; i < n; i++)
@@ -1097,8 +1135,17 @@ static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, 
         // (the columns' sums are one area: fill_read_tables; what is zeroed is the byte count of the rows without an offset)
         (void)hipMemsetAsync(hb[0].sums, 0, n * RSEL_BIN_SUM_WORDS * 8, s);
         // a call without a page still has a result: offsets[0] = 0, selected = values_len = 0
-        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, &sl);
+        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, &sl, nullptr);
         else launch_rsel_bin(ctx, a, sl);
+    } else if (mode.aggregate()) {
+        AggLaunch al{(const AggCol*)(ctx->tables.p + L.fcols), (AggPart*)(ctx->tables.p + L.aggp), sh.P * L.rle_parts, false, false};
+        for (uint64_t i = 0; i < n; i++) ((mode.aggc[i].ops & AGG_VALUE_OPS) ? al.any_val : al.any_null) = true;
+        // an empty slot is all zero: a page that failed or a tile without a selected row writes none
+        const size_t slots = (size_t)(sh.P * L.rle_parts + sh.T);
+        if (slots) (void)hipMemsetAsync(al.parts, 0, slots * sizeof(AggPart), s);
+        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, nullptr, &al);
+        // (a call without a page still has a result: selected, and zeros)
+        launch_agg_finish(ctx, al.acols, al.parts, d_vlen, (uint32_t)n);
     } else {
         // bitmaps are assembled with OR at page seams: start from zero
         for (uint64_t i = 0; i < n; i++) {
@@ -1107,7 +1154,7 @@ static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, 
             if (d.nullable && d.validity && d.rows) (void)hipMemsetAsync(d.validity, 0, (d.rows + 31) / 32 * 4, s);
             if (d.ptype == SB_TYPE_BOOLEAN && d.values && d.rows) (void)hipMemsetAsync(d.values, 0, (d.rows + 31) / 32 * 4, s);
         }
-        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, nullptr);
+        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, nullptr, nullptr);
     }
 }
 
@@ -1118,7 +1165,10 @@ static int32_t queue_read_results(sb_ctx* ctx, StageSlot* slot, const ReadLayout
     const hipStream_t s = ctx->stream;
     const ColDesc* hc = (const ColDesc*)(slot->host + L.cols);
     uint8_t* hv = slot->host + L.upload;
-    if (mode.selected_var()) {   // { selected, values_len } per column, behind the n bit counts; also of a call without a page
+    if (mode.aggregate()) {   // the result records, also of a call without a page
+        hipError_t e = hipMemcpyAsync(hv, ctx->tables.p + L.vlen, n * AGG_RESULT_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+        if (e != hipSuccess) return check_hip(ctx, e, "aggregate readback");
+    } else if (mode.selected_var()) {   // { selected, values_len } per column, behind the n bit counts; also of a call without a page
         hipError_t e = hipMemcpyAsync(hv, ctx->tables.p + L.vlen + n * sizeof(uint64_t), 2 * n * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
         if (e != hipSuccess) return check_hip(ctx, e, "values_len readback");
     } else if (sh.P && (sh.any_binary || mode.sizes() || mode.sink())) {
@@ -1134,8 +1184,8 @@ static int32_t queue_read_results(sb_ctx* ctx, StageSlot* slot, const ReadLayout
     slot->in_flight = true;
     for (uint64_t i = 0; i < n; i++) {
         Pending pd;
-        pd.kind = mode.filter() ? Pending::FILTER_COL : mode.selected() ? Pending::RSEL_COL : mode.selected_var() ? Pending::RSEL_VAR_COL : Pending::READ_COL;
-        pd.user = mode.filter() ? (void*)mode.sel_out[i] : mode.selected() ? (void*)mode.sel_users[i] : mode.selected_var() ? (void*)mode.selv_users[i] : (void*)&cols[i];
+        pd.kind = mode.filter() ? Pending::FILTER_COL : mode.selected() ? Pending::RSEL_COL : mode.selected_var() ? Pending::RSEL_VAR_COL : mode.aggregate() ? Pending::AGG_COL : Pending::READ_COL;
+        pd.user = mode.filter() ? (void*)mode.sel_out[i] : mode.selected() ? (void*)mode.sel_users[i] : mode.selected_var() ? (void*)mode.selv_users[i] : mode.aggregate() ? (void*)mode.agg_users[i] : (void*)&cols[i];
         pd.host = hv + i * sizeof(uint64_t) * mode.result_words();
         pd.n = 0;
         ctx->iv.pending.push_back(pd);
@@ -1748,6 +1798,177 @@ int32_t sb_read_selected_var(sb_ctx* ctx, sb_column_read_selected_var* cols, uin
     mode.selv_users = users.data();
     const int32_t rc = read_columns_impl(ctx, rc_cols.data(), n, SB_MEM_DEVICE, mode);
     if (rc == SB_OK && !ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::READ_SEL_VAR, cols, n, sb_write_options{}, mem});
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------ aggregate
+static sb_column_read read_col_of(const sb_column_aggregate& u) {
+    sb_column_read r;
+    memset(&r, 0, sizeof r);
+    r.physical_type = u.physical_type;
+    r.is_nullable = u.is_nullable;
+    r.pages = u.pages;
+    r.pages_len = u.pages_len;
+    r.metas = u.metas;
+    r.n_pages = u.n_pages;
+    r.page_offsets = u.page_offsets;
+    return r;
+}
+
+// The replay of an interval in which a Freq page was met by a call that ends in a sink (KIND_FILTER_FREQ): the sibling of
+// rsel_columns_decoded.  The columns with a value op are decoded like a read into the staging area — values, validity, the
+// Freq second pass — and k_agg_plain reduces them from there with the same sink: a slot per TILE_ROWS rows.
+static int32_t agg_columns_decoded(sb_ctx* ctx, sb_column_aggregate* const* users, std::vector<AggCol>& hs, uint64_t n) {
+    hipStream_t s = ctx->stream;
+    ctx->iv.filter_tmp.emplace_back(n);
+    std::vector<sb_column_read>& rr = ctx->iv.filter_tmp.back();
+    size_t total = 0;
+    std::vector<size_t> o_val(n), o_bits(n);
+    for (uint64_t i = 0; i < n; i++) {
+        o_val[i] = total;
+        total += align_up(hs[i].rows * hs[i].w, 64);
+        o_bits[i] = total;
+        total += align_up((hs[i].rows + 31) / 32 * 4, 64);
+    }
+    if (!ensure(ctx, ctx->filter_stage, total + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
+    for (uint64_t i = 0; i < n; i++) {
+        sb_column_read& r = rr[i] = read_col_of(*users[i]);
+        r.values = ctx->filter_stage.p + o_val[i];
+        r.values_capacity = hs[i].rows * hs[i].w;
+        r.validity = ctx->filter_stage.p + o_bits[i];
+        r.validity_capacity = (hs[i].rows + 31) / 32 * 4;
+    }
+    int32_t rc = read_columns_impl(ctx, rr.data(), n, SB_MEM_DEVICE, ReadMode{ReadMode::READ});
+    if (rc != SB_OK) return rc;
+    if (hipStreamSynchronize(s) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "aggregate replay: synchronize failed");
+    rc = freq_second_pass(ctx);
+    if (rc != SB_OK) return rc;
+    // [AggCol per column][the result records][the partial records: a slot per TILE_ROWS rows]
+    size_t off = align_up(n * sizeof(AggCol), 64);
+    const size_t o_res = off;
+    off = align_up(off + n * AGG_RESULT_WORDS * sizeof(uint64_t), 64);
+    const size_t o_parts = off;
+    uint64_t slots = 0;
+    std::vector<uint64_t> rows(n);
+    std::vector<const uint8_t*> vals(n), bits(n);
+    for (uint64_t i = 0; i < n; i++) {
+        rows[i] = hs[i].rows;
+        vals[i] = (const uint8_t*)rr[i].values;
+        bits[i] = users[i]->is_nullable ? rr[i].validity : nullptr;
+        hs[i].page_slot0 = hs[i].page_slots = 0;
+        hs[i].tile_slot0 = slots;
+        hs[i].tile_slots = (rows[i] + TILE_ROWS - 1) / TILE_ROWS;
+        slots += hs[i].tile_slots;
+    }
+    off += (size_t)slots * sizeof(AggPart);
+    uint8_t* dev = nullptr;
+    if (hipMalloc((void**)&dev, off + 64) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(aggregate replay) failed");
+    ctx->iv.temp_dev.push_back(dev);
+    if (hipMemcpy(dev, hs.data(), n * sizeof(AggCol), hipMemcpyHostToDevice) != hipSuccess)
+        return ctx->fail(SB_ERR_EXTERNAL, "aggregate replay: upload failed");
+    StageSlot* slot = acquire_slot(ctx, n * AGG_RESULT_WORDS * sizeof(uint64_t));
+    if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
+    uint64_t* d_res = (uint64_t*)(dev + o_res);
+    launch_agg_plain(ctx, (const AggCol*)dev, (uint32_t)n, (AggPart*)(dev + o_parts), rows.data(), vals.data(), bits.data());
+    launch_agg_finish(ctx, (const AggCol*)dev, (const AggPart*)(dev + o_parts), d_res, (uint32_t)n);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(slot->host, d_res, n * AGG_RESULT_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return check_hip(ctx, e, "aggregate replay");
+    (void)hipEventRecord(slot->done, s);
+    slot->in_flight = true;
+    for (uint64_t i = 0; i < n; i++) {
+        Pending pd;
+        pd.kind = Pending::AGG_COL;
+        pd.user = users[i];
+        pd.host = slot->host + i * AGG_RESULT_WORDS * sizeof(uint64_t);
+        pd.n = 0;
+        ctx->iv.pending.push_back(pd);
+    }
+    return SB_OK;
+}
+
+int32_t sb_aggregate_columns(sb_ctx* ctx, sb_column_aggregate* cols, uint64_t n, int32_t mem) {
+    if (!ctx || (!cols && n)) return SB_ERR_INVALID;
+    if (n == 0) return SB_OK;
+    // what is refused here is refused before anything is enqueued or written, and does not show again at the synchronize
+    auto refuse = [&](int32_t code, const char* msg) {
+        ctx->last_error = msg;
+        return code;
+    };
+    if (mem != SB_MEM_DEVICE) return refuse(SB_ERR_NYI, "sb_aggregate_columns: SB_MEM_HOST is not implemented");
+    std::vector<AggCol> hs(n);
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_column_aggregate& c = cols[i];
+        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(SB_ERR_INVALID, "bad physical_type");
+        if (c.ops & ~(SB_AGG_COUNT | SB_AGG_MIN | SB_AGG_MAX | SB_AGG_SUM)) return refuse(SB_ERR_INVALID, "unknown ops bits");
+        if (c.reserved) return refuse(SB_ERR_INVALID, "reserved is not 0");
+        if ((c.ops & AGG_VALUE_OPS) && !filter_comparable(c.physical_type))
+            return refuse(SB_ERR_NYI, "min / max / sum are implemented for 8- to 64-bit integers and floats");
+        if (c.n_pages && !c.metas) return refuse(SB_ERR_INVALID, "metas is null");
+        uint64_t rows = 0;
+        for (uint64_t p = 0; p < c.n_pages; p++) rows += c.metas[p].num_values;
+        if (c.selection && (((uintptr_t)c.selection & 3) || c.selection_capacity < (rows + 31) / 32 * 4))
+            return refuse(SB_ERR_INVALID, "selection not 4-byte aligned or smaller than 4*ceil(rows/32) bytes");
+        AggCol& g = hs[i];
+        memset(&g, 0, sizeof g);
+        g.sel = (const uint32_t*)c.selection;
+        g.rows = rows;
+        g.ops = c.ops;
+        g.ptype = c.physical_type;
+        g.w = type_width(c.physical_type);
+        g.kind = c.physical_type == SB_TYPE_FLOAT32 ? FK_F32 : c.physical_type == SB_TYPE_FLOAT64 ? FK_F64 : c.physical_type <= SB_TYPE_INT64 ? FK_SIGNED : FK_UNSIGNED;
+    }
+    (void)hipSetDevice(ctx->device);
+    std::vector<sb_column_aggregate*> users(n);
+    for (uint64_t i = 0; i < n; i++) users[i] = &cols[i];
+    int32_t rc = SB_OK;
+    if (ctx->in_replay && ctx->filter_freq) {
+        // the columns without a value op as ever (no page body is looked at); the others through a full decode
+        std::vector<sb_column_aggregate*> u_val, u_rest;
+        std::vector<AggCol> g_val, g_rest;
+        for (uint64_t i = 0; i < n; i++) {
+            const bool dec = (hs[i].ops & AGG_VALUE_OPS) != 0;
+            (dec ? u_val : u_rest).push_back(users[i]);
+            (dec ? g_val : g_rest).push_back(hs[i]);
+        }
+        if (!u_val.empty()) rc = agg_columns_decoded(ctx, u_val.data(), g_val, u_val.size());
+        users.swap(u_rest);
+        hs.swap(g_rest);
+    }
+    if (rc == SB_OK && !users.empty()) {
+        const uint64_t m = users.size();
+        size_t stage = 0;
+        for (uint64_t i = 0; i < m; i++)
+            if (hs[i].ops & AGG_VALUE_OPS) stage += align_up(hs[i].rows * hs[i].w, 64);
+        if (!ensure(ctx, ctx->filter_stage, stage + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
+        // the columns' shares of the staging area, as a filter comparison column has them
+        std::vector<sb_column_read> rc_cols(m);
+        size_t so = 0;
+        for (uint64_t i = 0; i < m; i++) {
+            sb_column_read& r = rc_cols[i] = read_col_of(*users[i]);
+            if (!(hs[i].ops & AGG_VALUE_OPS)) {
+                r.physical_type = SB_TYPE_NULL;   // (no page body is parsed, queued or planned for a count)
+                continue;
+            }
+            r.values = ctx->filter_stage.p + so;
+            r.values_capacity = hs[i].rows * hs[i].w;
+            so += align_up(r.values_capacity, 64);
+        }
+        ReadMode mode{ReadMode::AGGREGATE};
+        mode.aggc = hs.data();
+        mode.agg_users = users.data();
+        rc = read_columns_impl(ctx, rc_cols.data(), m, SB_MEM_DEVICE, mode);
+    }
+    if (rc != SB_OK) return rc;
+    for (uint64_t i = 0; i < n; i++) {   // (after the last thing that can refuse the call: a page outside pages_len)
+        sb_column_aggregate& c = cols[i];
+        c.rows = 0;
+        for (uint64_t p = 0; p < c.n_pages; p++) c.rows += c.metas[p].num_values;
+        c.selected = c.count = c.nans = c.sum_lo = c.sum_hi = 0;
+        memset(c.min, 0, sizeof c.min);
+        memset(c.max, 0, sizeof c.max);
+    }
+    if (!ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::AGGREGATE, cols, n, sb_write_options{}, mem});
     return rc;
 }
 

@@ -325,6 +325,34 @@ struct SelLaunch {   // what launch_decode needs to end a call with the selected
     const SelBin* bcols = nullptr;   // sb_read_selected_var: one per column (null: sb_read_selected)
     uint64_t* results = nullptr;     // ... [n_cols][2]: { selected, values_len }
 };
+// one column of an aggregate call (sb_aggregate_columns, sb_aggregate.h), next to its ColDesc.  The kernels write partial
+// records (AggPart) into slots of one array of the call: a slot per (page, part of a long RLE page) — the RLE walk and the
+// count-only route — and a slot per tile; k_agg_finish combines a column's slots, in slot order, into its result record.
+constexpr uint32_t AGG_VALUE_OPS = 2u | 4u | 8u;   // SB_AGG_MIN | SB_AGG_MAX | SB_AGG_SUM: the column's values are looked at
+constexpr uint32_t AGG_RESULT_WORDS = 8;           // { selected, count, nans, min, max, sum_lo, sum_hi, 0 }
+struct AggCol {
+    const uint32_t* sel;   // the selection bitmap (input) or null: every row
+    uint64_t rows;
+    uint64_t page_slot0, page_slots;   // the column's slots in the call's array of partial records
+    uint64_t tile_slot0, tile_slots;
+    uint32_t ops;          // SB_AGG_*
+    uint32_t kind;         // how values order and add: FK_UNSIGNED / FK_SIGNED / FK_F32 / FK_F64
+    int32_t ptype;         // the column's physical type (a column without a value op is parsed as SB_TYPE_NULL: no page body is looked at)
+    uint32_t w;            // bytes per value
+};
+struct AggPart {           // 64 bytes; all zero: the slot was not written (a page that failed, a tile without a selected row)
+    uint64_t live;         // 1: written
+    uint64_t cnt, nans;    // live rows, NaNs among them
+    uint64_t kmin, kmax;   // order keys (agg_key) of the live rows that are not NaN; ~0 / 0: none
+    uint64_t s0, s1;       // integers: the 128-bit sum; floats: the bits of the double sum, 0
+    uint64_t pad;
+};
+struct AggLaunch {   // what launch_decode needs to end a call with the aggregate kernels
+    const AggCol* acols;
+    AggPart* parts;
+    uint64_t tile_base;    // the slot of the call's first tile (the page slots come first)
+    bool any_val, any_null;
+};
 constexpr uint32_t FK_UNSIGNED = 0, FK_SIGNED = 1, FK_F32 = 2, FK_F64 = 3, FK_BYTES = 4;
 constexpr uint32_t FILTER_MASK_PREFIX = 16u;   // FilterCol.mask of SB_PRED_STARTS_WITH (the four relation bits are clear)
 // words of the bit table (a bit per dictionary entry) that a filter call reserves at the END of the aux area of every page

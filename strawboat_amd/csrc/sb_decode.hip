@@ -2754,7 +2754,7 @@ __device__ __forceinline__ RlePart rle_part(uint32_t max_runs, uint32_t part, ui
     return {b0, owns_end ? ~0ull : (uint64_t)(part + 1) * cpp * RLE_CHUNK, part && b0 >= max_runs};
 }
 
-// The walk of k_expand_rle, k_filter_rle and k_rsel_rle (RleExpand, RleFilter, RleSelect).  What the kernel wants of it is a policy P:
+// The walk of k_expand_rle, k_filter_rle, k_rsel_rle and k_agg_rle (RleExpand, RleFilter, RleSelect, RleAggregate).  What the kernel wants of it is a policy P:
 //   P::Rec                       what is kept of a run and staged in LDS (p.s_rec, RLE_CHUNK entries)
 //   p.rec_bytes()                4 + the width of a value: the stride of the run records
 //   p.load(v, in)                the Rec of the run whose value is at v (`in` false: behind the page's last record)
@@ -3123,10 +3123,11 @@ static void launch_lzg(sb_ctx* ctx, const DecodeArgs& a, bool lzg_on, InflateJob
 #include "sb_filter_bin.h"
 #include "sb_read_sel.h"
 #include "sb_read_sel_bin.h"
+#include "sb_aggregate.h"
 namespace sb {
 
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
-                   const SelLaunch* rsel) {
+                   const SelLaunch* rsel, const AggLaunch* agg) {
     hipStream_t s = ctx->stream;
     (void)hipMemsetAsync(a.job_counts, 0, 16 * sizeof(uint32_t), s);
     const bool qa = !(a.read_skips & RSKIP_QUEUE_A);
@@ -3203,6 +3204,10 @@ void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_p
     }
     if (rsel) {   // sb_read_selected: the same pages, the selected rows stored packed
         launch_rsel(ctx, a, *rsel);
+        return;
+    }
+    if (agg) {   // sb_aggregate_columns: the same pages, reduced to a record per column
+        launch_agg(ctx, a, *agg);
         return;
     }
     // the three expand kernels work on disjoint pages (page-level RLE, tiles of primitives, tiles of binary columns): side

@@ -28,13 +28,14 @@ struct StageSlot {
 //   FILTER_COL  the caller's `selected`       8 bytes: the bits set                       0               -
 //   RSEL_COL    sb_column_read_selected*      8 bytes: the bits set (values_len follows)  0               -
 //   RSEL_VAR_COL sb_column_read_selected_var* 16 bytes: the bits set, values_len          0               -
+//   AGG_COL     sb_column_aggregate*          64 bytes: the result record (AGG_RESULT_WORDS)  0           -
 //   WRITE_COL   sb_column_write*              u64 [n lengths][n num_values][out_len]      pages           -
 //   ENC_HINT    null                          32 words: pages per codec of a write call   the plan's key  -
 //   NESTED_W    sb_nested_levels_write[n]     the page records of an enqueued level call  items           of the records
 //   NESTED_R    sb_nested_levels_read[n]      the page records of an enqueued level call  items           of the records
 // (acquire_slot sizes what it moves out of a recycled slot by this table)
 struct Pending {
-    enum Kind { READ_COL, WRITE_COL, ENC_HINT, NESTED_W, NESTED_R, FILTER_COL, RSEL_COL, RSEL_VAR_COL } kind;
+    enum Kind { READ_COL, WRITE_COL, ENC_HINT, NESTED_W, NESTED_R, FILTER_COL, RSEL_COL, RSEL_VAR_COL, AGG_COL } kind;
     void* user;
     const uint8_t* host;
     uint64_t n;
@@ -232,7 +233,7 @@ struct sb_ctx {
     // never a one-workgroup walk over a million-row page.  (The callers' column arrays and buffers live until the
     // synchronize anyway: the results are written into them there.)
     struct Call {
-        enum Kind { READ, WRITE, FILTER, FILTER_VAR, READ_SEL, READ_SEL_VAR } kind;   // sb_read_columns, sb_write_columns, sb_filter_columns, sb_filter_columns_var, sb_read_selected, sb_read_selected_var
+        enum Kind { READ, WRITE, FILTER, FILTER_VAR, READ_SEL, READ_SEL_VAR, AGGREGATE } kind;   // sb_read_columns, sb_write_columns, sb_filter_columns, sb_filter_columns_var, sb_read_selected, sb_read_selected_var, sb_aggregate_columns
         void* cols;
         uint64_t n;
         sb_write_options opts;
@@ -337,6 +338,7 @@ inline int32_t reissue(sb_ctx* ctx, sb_ctx::Call& cl) {
         case sb_ctx::Call::FILTER_VAR: return sb_filter_columns_var(ctx, (sb_column_filter_var*)cl.cols, cl.n, cl.mem);
         case sb_ctx::Call::READ_SEL: return sb_read_selected(ctx, (sb_column_read_selected*)cl.cols, cl.n, cl.mem);
         case sb_ctx::Call::READ_SEL_VAR: return sb_read_selected_var(ctx, (sb_column_read_selected_var*)cl.cols, cl.n, cl.mem);
+        case sb_ctx::Call::AGGREGATE: return sb_aggregate_columns(ctx, (sb_column_aggregate*)cl.cols, cl.n, cl.mem);
     }
     return SB_ERR_INVALID;
 }
