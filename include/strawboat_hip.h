@@ -492,7 +492,11 @@ int32_t sb_write_columns(sb_ctx* ctx, sb_column_write* cols, uint64_t n, const s
  *
  * sb_nested_level describes one node on the path root -> leaf (arrow2 `Nested`, to_nested in
  * src/write/serialize.rs:135): kind 0 primitive leaf, 1 list (i32 offsets), 2 large list (i64
- * offsets), 3 struct.  All pointers are DEVICE memory. */
+ * offsets), 3 struct.  All pointers are DEVICE memory.
+ *
+ * A path has at most SB_NESTED_MAX_DEPTH nodes, the leaf included.  Every write and read call below
+ * returns SB_ERR_INVALID for n_levels == 0 or n_levels > SB_NESTED_MAX_DEPTH: the call is refused
+ * before anything is launched, and no output is touched. */
 #define SB_NESTED_PRIMITIVE 0
 #define SB_NESTED_LIST 1
 #define SB_NESTED_LARGE_LIST 2
