@@ -433,6 +433,75 @@ typedef struct sb_column_aggregate {
 
 int32_t sb_aggregate_columns(sb_ctx* ctx, sb_column_aggregate* cols, uint64_t n, int32_t mem);
 
+/* ------------------------------------------------------------------ aggregate, grouped
+ * SELECT k, count(*), count(y), min(y), max(y), sum(y) ... WHERE x < 5 GROUP BY k.  sb_aggregate_columns with one more
+ * input: `group_ids`, one unsigned integer of `group_id_width` bytes per row of the column, on the device.  It is a key
+ * column read by sb_read_columns earlier in the interval, or ids the caller computed.  Row r belongs to group
+ * group_ids[r]; every group gets a record of its own in `groups` (HOST), filled at the synchronize.
+ *
+ * Everything not said here is sb_aggregate_columns' word for word: live rows, NaNs, the order of min / max with
+ * -0.0 < +0.0, 128-bit integer sums, float sums in double, the bytes of min / max, fields written as 0 where `ops` lacks
+ * their bit, the accepted types, what a count-only column looks at.
+ *   membership    a selected row whose id is >= n_groups is aggregated nowhere and counted in `out_of_range`; no error is
+ *                 raised (0xFF.. can mark a null key).  Ids of unselected rows are never interpreted.
+ *   counts        groups[g].selected: the selected rows of the group, null or not (count(*)); groups[g].count: the live
+ *                 ones (count(y)).  The sum of groups[g].selected over g, plus out_of_range, is `selected`.
+ *   empty groups  all counts 0, min / max all zero bytes, sum 0.
+ *   float sums    no floating-point atomics, neither in LDS nor in HBM: the order of the double additions of a group's
+ *                 sum is a function of the column's shape and data alone, so the same call gives the same bits every time
+ *                 it is issued, also in an interval that is issued again on another call's account: only a column that
+ *                 has a Freq page itself is decoded for the replay, and such a column is decoded in every interval.
+ *
+ * Refused at the call, nothing enqueued, no result field and no byte of `groups` touched: n_groups 0 or above
+ * SB_AGG_MAX_GROUPS, group_id_width not 1 / 2 / 4, `group_ids` null with rows > 0 or not aligned to its width or shorter
+ * than rows * group_id_width, `groups` null, and every refusal of sb_aggregate_columns with its code.
+ *
+ * Enqueued like sb_aggregate_columns and part of its synchronize interval in the same way: on a replay it is issued again
+ * in its place, behind the filter calls that write its bitmap and the read calls that write its ids.  `selection` and
+ * `group_ids` are INPUTS: they stay unmodified until the synchronize.  `rows` and `selected` are delivered even when the
+ * interval failed; `groups` and `out_of_range` are unspecified then.
+ *
+ * Layout (pinned by tests/test_aggregate_grouped_host.py): sb_agg_group 64 bytes; selected 0, count 8, nans 16, min 24,
+ * max 32, sum_lo 40, sum_hi 48, reserved 56.  sb_column_aggregate_grouped 128 bytes; physical_type 0, is_nullable 4,
+ * pages 8, pages_len 16, metas 24, n_pages 32, page_offsets 40, selection 48, selection_capacity 56, group_ids 64,
+ * group_ids_capacity 72, group_id_width 80, n_groups 84, ops 88, reserved 92, groups 96, rows 104, selected 112,
+ * out_of_range 120. */
+#define SB_AGG_MAX_GROUPS 256u
+
+typedef struct sb_agg_group {
+    uint64_t selected;       /* selected rows of this group, null or not */
+    uint64_t count;          /* of those, not null */
+    uint64_t nans;           /* of those, float NaNs */
+    uint8_t min[8], max[8];  /* as in sb_column_aggregate */
+    uint64_t sum_lo, sum_hi;
+    uint64_t reserved;       /* written as 0 */
+} sb_agg_group;              /* 64 bytes */
+
+typedef struct sb_column_aggregate_grouped {
+    int32_t physical_type;   /* SB_TYPE_* */
+    int32_t is_nullable;
+    const uint8_t* pages;    /* DEVICE, at any byte alignment */
+    uint64_t pages_len;
+    const sb_page_meta* metas; /* HOST */
+    uint64_t n_pages;
+    const uint64_t* page_offsets; /* optional (HOST), as in sb_column_read */
+    const uint8_t* selection;     /* DEVICE, input: as in sb_column_aggregate; NULL = every row */
+    uint64_t selection_capacity;
+    const void* group_ids;        /* DEVICE, input: one unsigned id per row of the column, aligned to its width */
+    uint64_t group_ids_capacity;  /* >= rows * group_id_width bytes */
+    uint32_t group_id_width;      /* 1, 2 or 4 */
+    uint32_t n_groups;            /* 1 .. SB_AGG_MAX_GROUPS */
+    uint32_t ops;            /* SB_AGG_* bits */
+    uint32_t reserved;       /* must be 0 */
+    sb_agg_group* groups;    /* HOST, n_groups entries, filled at the synchronize; must live until then */
+    /* results (HOST, valid after sb_ctx_synchronize) */
+    uint64_t rows;           /* sum of num_values */
+    uint64_t selected;       /* bits set in `selection` below `rows` (== rows without a selection) */
+    uint64_t out_of_range;   /* selected rows whose id is >= n_groups */
+} sb_column_aggregate_grouped;   /* 128 bytes */
+
+int32_t sb_aggregate_grouped(sb_ctx* ctx, sb_column_aggregate_grouped* cols, uint64_t n, int32_t mem);
+
 /* ------------------------------------------------------------------ encode
  * Replaces, per leaf column, the page loop of NativeWriter::encode_chunk
  * (src/write/common.rs:54-109): page slicing, then per page write::write -> write_simple

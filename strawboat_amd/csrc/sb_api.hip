@@ -1,6 +1,7 @@
 // strawboat-hip: C ABI (include/strawboat_hip.h) — context management and the decode entry
 // points.  Host logic only: page bookkeeping (the arithmetic of read_integer & co: running row
 // offset per page, src/read/array/integer.rs:210-238), table upload, kernel launches.
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 
@@ -10,7 +11,11 @@
 namespace sb {
 
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
-                   const SelLaunch* rsel, const AggLaunch* agg);
+                   const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp = nullptr);
+void launch_grp_zero(sb_ctx* ctx, const GrpLaunch& gl, uint32_t n_cols);
+void launch_grp_finish(sb_ctx* ctx, const GrpLaunch& gl, uint64_t* results, uint32_t n_cols);
+void launch_grp_plain(sb_ctx* ctx, const GrpLaunch& gl, uint32_t n_cols, const uint64_t* rows, const uint8_t* const* values,
+                      const uint8_t* const* validity);
 void launch_agg_finish(sb_ctx* ctx, const AggCol* acols, const AggPart* parts, uint64_t* results, uint32_t n_cols);
 void launch_agg_plain(sb_ctx* ctx, const AggCol* acols, uint32_t n_cols, AggPart* parts, const uint64_t* rows, const uint8_t* const* values,
                       const uint8_t* const* validity);
@@ -92,7 +97,7 @@ StageSlot* acquire_slot(sb_ctx* ctx, size_t need) {
     if (s.host)
         for (auto& p : ctx->iv.pending) {
             if (p.host < s.host || p.host >= s.host + s.cap) continue;
-            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::AGG_COL ? AGG_RESULT_WORDS * 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R) ? (size_t)p.bytes
+            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::AGG_COL ? AGG_RESULT_WORDS * 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R || p.kind == Pending::AGG_GRP_COL) ? (size_t)p.bytes
                                                                                                    : (size_t)(2 * p.n + 1) * 8;
             ctx->iv.rescued.emplace_back(p.host, p.host + nb);
             p.host = ctx->iv.rescued.back().data();
@@ -225,7 +230,8 @@ struct ReadMode {
     // synchronize / sb_filter_columns[_var], whose columns end in the filter kernels / sb_read_selected, whose columns end
     // in the selected-read kernels / sb_read_selected_var, whose binary columns end in those of sb_read_sel_bin.h /
     // sb_aggregate_columns, whose columns end in the aggregate kernels
-    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR, AGGREGATE } kind;
+    // / sb_aggregate_grouped, an aggregate call whose columns end in the grouped aggregate kernels
+    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR, AGGREGATE, AGG_GROUPED } kind;
     const FilterCol* filt = nullptr;             // FILTER: one per column
     uint64_t* const* sel_out = nullptr;          // ... sel_out[i]: the caller's `selected`
     const std::vector<uint8_t>* lits = nullptr;  // ... the literals of the FK_BYTES columns, FilterCol.lit being the offset of each
@@ -237,7 +243,11 @@ struct ReadMode {
     sb_column_read_selected_var* const* selv_users = nullptr;   // ... the callers' structs
     const AggCol* aggc = nullptr;                // AGGREGATE: one per column (the slots: filled in with the call's tables)
     sb_column_aggregate* const* agg_users = nullptr;   // ... the callers' structs
-    bool aggregate() const { return kind == AGGREGATE; }
+    const GrpCol* grpc = nullptr;                // AGG_GROUPED: one per column beside aggc
+    sb_column_aggregate_grouped* const* grp_users = nullptr;   // ... the callers' structs (agg_users is null)
+    uint32_t grp_gmax = 0;                       // ... the largest n_groups of the call: records per slot
+    bool aggregate() const { return kind == AGGREGATE || kind == AGG_GROUPED; }   // an AggCol per column, slots per page part and tile
+    bool grouped() const { return kind == AGG_GROUPED; }
     bool filter() const { return kind == FILTER; }
     bool selected() const { return kind == SELECTED; }
     bool selected_var() const { return kind == SELECTED_VAR; }
@@ -246,10 +256,10 @@ struct ReadMode {
     bool bin_staged() const { return kind == FILTER || kind == SELECTED_VAR; }
     // the columns end in a sink of their own: `values` is a share of the staging area, there is no validity buffer, and
     // the call neither consults nor feeds the launch hints of the read path
-    bool sink() const { return kind == FILTER || kind == SELECTED || kind == SELECTED_VAR || kind == AGGREGATE; }
+    bool sink() const { return kind == FILTER || kind == SELECTED || kind == SELECTED_VAR || kind == AGGREGATE || kind == AGG_GROUPED; }
     // words of 8 bytes that come back per column: { selected, values_len } for a SELECTED_VAR call, the result record of
-    // an AGGREGATE call
-    uint64_t result_words() const { return kind == SELECTED_VAR ? 2 : kind == AGGREGATE ? AGG_RESULT_WORDS : 1; }
+    // an AGGREGATE call, the header and the gmax group records of an AGG_GROUPED call
+    uint64_t result_words() const { return kind == SELECTED_VAR ? 2 : kind == AGGREGATE ? AGG_RESULT_WORDS : kind == AGG_GROUPED ? grp_result_words(grp_gmax) : 1; }
 };
 static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, const ReadMode& mode);
 static void update_read_hints(sb_ctx* ctx, uint32_t kinds);   // (next to read_hints, its reader)
@@ -404,6 +414,15 @@ static int32_t replay_interval(sb_ctx* ctx) {
     if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);   // (copies of groups that ran: overwritten by the replay's)
     std::vector<sb_ctx::Call> calls;
     calls.swap(ctx->iv.calls);
+    // the grouped aggregate columns that met a Freq page say so in their result header (k_grp_finish): they alone take the
+    // decoded route below, so that a column's route does not depend on what else the interval holds
+    ctx->grp_freq_users.clear();
+    for (const auto& p : ctx->iv.pending)
+        if (p.kind == Pending::AGG_GRP_COL) {
+            uint64_t met = 0;
+            memcpy(&met, p.host + 2 * sizeof(uint64_t), sizeof met);
+            if (met) ctx->grp_freq_users.push_back(p.user);
+        }
     release_interval(ctx, sb_ctx::Interval::REPLAY);
     clear_freq_logs(ctx);
     ctx->filter_freq = (ctx->h_status->kinds & KIND_FILTER_FREQ) != 0;
@@ -417,6 +436,7 @@ static int32_t replay_interval(sb_ctx* ctx) {
         if ((rc = reissue(ctx, cl)) != SB_OK) break;
     ctx->no_hints = saved;
     ctx->filter_freq = false;
+    ctx->grp_freq_users.clear();
     if (rc != SB_OK) ctx->iv.sticky = rc;
     rc = sb_ctx_synchronize(ctx);   // (in_replay: this one ends the interval whatever the device says)
     ctx->in_replay = false;
@@ -456,6 +476,16 @@ static void deliver_agg_col(const Pending& p) {   // (k_agg_finish's record: sb_
     c->sum_lo = v[5];
     c->sum_hi = v[6];
 }
+// k_grp_finish's header and group records (sb_aggregate_grouped.h); `ok` false: the interval failed, selected alone
+static void deliver_agg_grp_col(const Pending& p, bool ok) {
+    uint64_t head[8];
+    memcpy(head, p.host, sizeof head);
+    sb_column_aggregate_grouped* c = (sb_column_aggregate_grouped*)p.user;
+    c->selected = head[0];
+    if (!ok) return;
+    c->out_of_range = head[1];
+    memcpy(c->groups, p.host + sizeof head, (size_t)p.bytes - sizeof head);
+}
 static void deliver_write_col(const Pending& p) {
     sb_column_write* c = (sb_column_write*)p.user;
     const uint64_t* lens = (const uint64_t*)p.host;  // [n_pages lengths][n_pages num_values][total]
@@ -484,6 +514,7 @@ static void deliver_pending(sb_ctx* ctx, const Pending& p, int32_t rc) {
         case Pending::RSEL_COL: deliver_rsel_col(p); break;
         case Pending::RSEL_VAR_COL: deliver_rsel_var_col(p); break;
         case Pending::AGG_COL: deliver_agg_col(p); break;
+        case Pending::AGG_GRP_COL: deliver_agg_grp_col(p, rc == SB_OK); break;
         case Pending::WRITE_COL: deliver_write_col(p); break;
         case Pending::ENC_HINT:
             if (rc == SB_OK) apply_enc_hint(ctx, p);
@@ -732,7 +763,7 @@ static ReadHints read_hints(sb_ctx* ctx, const ReadMode& mode, const ReadShape& 
 // Where the call's tables sit, on the device (ctx->tables) and — up to `upload` — in the staging slot, whose next n words
 // receive the results.  A pure function of shape, hints and mode.
 struct ReadLayout {
-    size_t cols, tasks, fcols, bcols, lits, upload, descs, tiles, jobs_a, jobs_b, jobs_z, counts, vlen, zb_counts, zb_frames, zs, rle, bpg, aggp, total;
+    size_t cols, tasks, fcols, bcols, lits, upload, descs, tiles, jobs_a, jobs_b, jobs_z, counts, vlen, zb_counts, zb_frames, zs, rle, bpg, aggp, grp_recs, total;
     size_t job_cap;        // queue entries: 2 per page + room for the frames of Zstd buffers that are several frames (one entry per frame)
     bool want_z;           // queue Z (calls with binary columns that produce values): Zstd payloads known to k_parse, entropy stages with queue A's
     uint64_t zs_seg_cap;
@@ -753,6 +784,7 @@ static ReadLayout read_layout(uint64_t n, const ReadShape& sh, const ReadHints& 
     if (mode.aggregate()) off = align_up(off + n * sizeof(AggCol), 64);   // (likewise)
     L.bcols = off;
     if (mode.selected_var()) off = align_up(off + n * sizeof(SelBin), 64);
+    if (mode.grouped()) off = align_up(off + n * sizeof(GrpCol), 64);   // (in the SelBins' place)
     L.lits = off;
     if (mode.lits) off = align_up(off + mode.lits->size(), 64);
     L.upload = off;
@@ -786,7 +818,10 @@ static ReadLayout read_layout(uint64_t n, const ReadShape& sh, const ReadHints& 
     L.bpg = off;
     if (L.rle_parts > 1) off = align_up(off + P * sizeof(uint32_t), 64);
     L.aggp = off;   // an AGGREGATE call's partial records: a slot per (page, RLE part), then a slot per tile
-    if (mode.aggregate()) off = align_up(off + (P * L.rle_parts + sh.T) * sizeof(AggPart), 64);
+    if (mode.aggregate() && !mode.grouped()) off = align_up(off + (P * L.rle_parts + sh.T) * sizeof(AggPart), 64);
+    // an AGG_GROUPED call: a flag word per slot, a counter and a Freq mark per column (zeroed), then gmax records per slot (not zeroed)
+    L.grp_recs = align_up(off + (P * L.rle_parts + sh.T + 2 * n) * sizeof(uint64_t), 64);
+    if (mode.grouped()) off = align_up(L.grp_recs + (P * L.rle_parts + sh.T) * mode.grp_gmax * sizeof(GrpPart), 64);
     L.total = off;
     return L;
 }
@@ -915,6 +950,7 @@ static int32_t fill_read_tables(sb_ctx* ctx, uint8_t* host, const ReadLayout& L,
             hac[i].tile_slots = ntiles;
             tile0 += ntiles;
         }
+        if (mode.grouped()) memcpy(host + L.bcols, mode.grpc, n * sizeof(GrpCol));
     }
     SelCol* hsc = mode.ranked() ? (SelCol*)(host + L.fcols) : nullptr;
     for (uint64_t i = 0; hsc && i < n; i++) {   // the rank tables: behind the pages' areas, sized by the rows
@@ -1137,6 +1173,15 @@ static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, 
         // a call without a page still has a result: offsets[0] = 0, selected = values_len = 0
         if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, &sl, nullptr);
         else launch_rsel_bin(ctx, a, sl);
+    } else if (mode.grouped()) {
+        const uint64_t slots = sh.P * L.rle_parts + sh.T;
+        GrpLaunch gl{(const AggCol*)(ctx->tables.p + L.fcols), (const GrpCol*)(ctx->tables.p + L.bcols), (uint64_t*)(ctx->tables.p + L.aggp),
+                     (GrpPart*)(ctx->tables.p + L.grp_recs), slots, sh.P * L.rle_parts, mode.grp_gmax, false, false, (uint32_t)n, ctx->in_replay};
+        for (uint64_t i = 0; i < n; i++) ((mode.aggc[i].ops & AGG_VALUE_OPS) ? gl.any_val : gl.any_null) = true;
+        launch_grp_zero(ctx, gl, (uint32_t)n);
+        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, nullptr, nullptr, &gl);
+        // (a call without a page still has a result: selected, and empty groups)
+        launch_grp_finish(ctx, gl, d_vlen, (uint32_t)n);
     } else if (mode.aggregate()) {
         AggLaunch al{(const AggCol*)(ctx->tables.p + L.fcols), (AggPart*)(ctx->tables.p + L.aggp), sh.P * L.rle_parts, false, false};
         for (uint64_t i = 0; i < n; i++) ((mode.aggc[i].ops & AGG_VALUE_OPS) ? al.any_val : al.any_null) = true;
@@ -1166,7 +1211,7 @@ static int32_t queue_read_results(sb_ctx* ctx, StageSlot* slot, const ReadLayout
     const ColDesc* hc = (const ColDesc*)(slot->host + L.cols);
     uint8_t* hv = slot->host + L.upload;
     if (mode.aggregate()) {   // the result records, also of a call without a page
-        hipError_t e = hipMemcpyAsync(hv, ctx->tables.p + L.vlen, n * AGG_RESULT_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+        hipError_t e = hipMemcpyAsync(hv, ctx->tables.p + L.vlen, n * mode.result_words() * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
         if (e != hipSuccess) return check_hip(ctx, e, "aggregate readback");
     } else if (mode.selected_var()) {   // { selected, values_len } per column, behind the n bit counts; also of a call without a page
         hipError_t e = hipMemcpyAsync(hv, ctx->tables.p + L.vlen + n * sizeof(uint64_t), 2 * n * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
@@ -1184,10 +1229,11 @@ static int32_t queue_read_results(sb_ctx* ctx, StageSlot* slot, const ReadLayout
     slot->in_flight = true;
     for (uint64_t i = 0; i < n; i++) {
         Pending pd;
-        pd.kind = mode.filter() ? Pending::FILTER_COL : mode.selected() ? Pending::RSEL_COL : mode.selected_var() ? Pending::RSEL_VAR_COL : mode.aggregate() ? Pending::AGG_COL : Pending::READ_COL;
-        pd.user = mode.filter() ? (void*)mode.sel_out[i] : mode.selected() ? (void*)mode.sel_users[i] : mode.selected_var() ? (void*)mode.selv_users[i] : mode.aggregate() ? (void*)mode.agg_users[i] : (void*)&cols[i];
+        pd.kind = mode.filter() ? Pending::FILTER_COL : mode.selected() ? Pending::RSEL_COL : mode.selected_var() ? Pending::RSEL_VAR_COL : mode.grouped() ? Pending::AGG_GRP_COL : mode.aggregate() ? Pending::AGG_COL : Pending::READ_COL;
+        pd.user = mode.filter() ? (void*)mode.sel_out[i] : mode.selected() ? (void*)mode.sel_users[i] : mode.selected_var() ? (void*)mode.selv_users[i] : mode.grouped() ? (void*)mode.grp_users[i] : mode.aggregate() ? (void*)mode.agg_users[i] : (void*)&cols[i];
         pd.host = hv + i * sizeof(uint64_t) * mode.result_words();
         pd.n = 0;
+        if (mode.grouped()) pd.bytes = sizeof(uint64_t) * grp_result_words(mode.grp_users[i]->n_groups);   // (the header and the column's own groups)
         ctx->iv.pending.push_back(pd);
     }
     return SB_OK;
@@ -1969,6 +2015,201 @@ int32_t sb_aggregate_columns(sb_ctx* ctx, sb_column_aggregate* cols, uint64_t n,
         memset(c.max, 0, sizeof c.max);
     }
     if (!ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::AGGREGATE, cols, n, sb_write_options{}, mem});
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------ aggregate, grouped
+static sb_column_read read_col_of(const sb_column_aggregate_grouped& u) {
+    sb_column_read r;
+    memset(&r, 0, sizeof r);
+    r.physical_type = u.physical_type;
+    r.is_nullable = u.is_nullable;
+    r.pages = u.pages;
+    r.pages_len = u.pages_len;
+    r.metas = u.metas;
+    r.n_pages = u.n_pages;
+    r.page_offsets = u.page_offsets;
+    return r;
+}
+
+// The sibling of agg_columns_decoded: the columns with a value op decoded like a read into the staging area, reduced from
+// there by k_grp_plain into a slot per TILE_ROWS rows, combined by k_grp_finish.
+static int32_t grp_columns_decoded(sb_ctx* ctx, sb_column_aggregate_grouped* const* users, std::vector<AggCol>& hs, const std::vector<GrpCol>& hg,
+                                   uint64_t n) {
+    hipStream_t s = ctx->stream;
+    ctx->iv.filter_tmp.emplace_back(n);
+    std::vector<sb_column_read>& rr = ctx->iv.filter_tmp.back();
+    size_t total = 0;
+    std::vector<size_t> o_val(n), o_bits(n);
+    for (uint64_t i = 0; i < n; i++) {
+        o_val[i] = total;
+        total += align_up(hs[i].rows * hs[i].w, 64);
+        o_bits[i] = total;
+        total += align_up((hs[i].rows + 31) / 32 * 4, 64);
+    }
+    if (!ensure(ctx, ctx->filter_stage, total + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
+    for (uint64_t i = 0; i < n; i++) {
+        sb_column_read& r = rr[i] = read_col_of(*users[i]);
+        r.values = ctx->filter_stage.p + o_val[i];
+        r.values_capacity = hs[i].rows * hs[i].w;
+        r.validity = ctx->filter_stage.p + o_bits[i];
+        r.validity_capacity = (hs[i].rows + 31) / 32 * 4;
+    }
+    int32_t rc = read_columns_impl(ctx, rr.data(), n, SB_MEM_DEVICE, ReadMode{ReadMode::READ});
+    if (rc != SB_OK) return rc;
+    if (hipStreamSynchronize(s) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "grouped aggregate replay: synchronize failed");
+    rc = freq_second_pass(ctx);
+    if (rc != SB_OK) return rc;
+    uint32_t gmax = 1;
+    uint64_t slots = 0;
+    std::vector<uint64_t> rows(n);
+    std::vector<const uint8_t*> vals(n), bits(n);
+    for (uint64_t i = 0; i < n; i++) {
+        gmax = std::max(gmax, hg[i].n_groups);
+        rows[i] = hs[i].rows;
+        vals[i] = (const uint8_t*)rr[i].values;
+        bits[i] = users[i]->is_nullable ? rr[i].validity : nullptr;
+        hs[i].page_slot0 = hs[i].page_slots = 0;
+        hs[i].tile_slot0 = slots;
+        hs[i].tile_slots = (rows[i] + TILE_ROWS - 1) / TILE_ROWS;
+        slots += hs[i].tile_slots;
+    }
+    // [AggCol per column][GrpCol per column][the results][the slots' flags, the columns' counters and Freq marks][the slots' records]
+    const size_t res_bytes = n * grp_result_words(gmax) * sizeof(uint64_t);
+    size_t off = align_up(n * sizeof(AggCol), 64);
+    const size_t o_gc = off;
+    off = align_up(off + n * sizeof(GrpCol), 64);
+    const size_t o_res = off;
+    off = align_up(off + res_bytes, 64);
+    const size_t o_flags = off;
+    off = align_up(off + (size_t)(slots + 2 * n) * sizeof(uint64_t), 64);
+    const size_t o_recs = off;
+    off += (size_t)slots * gmax * sizeof(GrpPart);
+    uint8_t* dev = nullptr;
+    if (hipMalloc((void**)&dev, off + 64) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(grouped aggregate replay) failed");
+    ctx->iv.temp_dev.push_back(dev);
+    if (hipMemcpy(dev, hs.data(), n * sizeof(AggCol), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dev + o_gc, hg.data(), n * sizeof(GrpCol), hipMemcpyHostToDevice) != hipSuccess)
+        return ctx->fail(SB_ERR_EXTERNAL, "grouped aggregate replay: upload failed");
+    StageSlot* slot = acquire_slot(ctx, res_bytes);
+    if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
+    uint64_t* d_res = (uint64_t*)(dev + o_res);
+    GrpLaunch gl{(const AggCol*)dev, (const GrpCol*)(dev + o_gc), (uint64_t*)(dev + o_flags), (GrpPart*)(dev + o_recs), slots, 0, gmax, true, false, (uint32_t)n, true};
+    launch_grp_zero(ctx, gl, (uint32_t)n);
+    launch_grp_plain(ctx, gl, (uint32_t)n, rows.data(), vals.data(), bits.data());
+    launch_grp_finish(ctx, gl, d_res, (uint32_t)n);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(slot->host, d_res, res_bytes, hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return check_hip(ctx, e, "grouped aggregate replay");
+    (void)hipEventRecord(slot->done, s);
+    slot->in_flight = true;
+    for (uint64_t i = 0; i < n; i++) {
+        Pending pd;
+        pd.kind = Pending::AGG_GRP_COL;
+        pd.user = users[i];
+        pd.host = slot->host + i * grp_result_words(gmax) * sizeof(uint64_t);
+        pd.n = 0;
+        pd.bytes = sizeof(uint64_t) * grp_result_words(hg[i].n_groups);
+        ctx->iv.pending.push_back(pd);
+    }
+    return SB_OK;
+}
+
+int32_t sb_aggregate_grouped(sb_ctx* ctx, sb_column_aggregate_grouped* cols, uint64_t n, int32_t mem) {
+    if (!ctx || (!cols && n)) return SB_ERR_INVALID;
+    if (n == 0) return SB_OK;
+    // what is refused here is refused before anything is enqueued or written, and does not show again at the synchronize
+    auto refuse = [&](int32_t code, const char* msg) {
+        ctx->last_error = msg;
+        return code;
+    };
+    if (mem != SB_MEM_DEVICE) return refuse(SB_ERR_NYI, "sb_aggregate_grouped: SB_MEM_HOST is not implemented");
+    std::vector<AggCol> hs(n);
+    std::vector<GrpCol> hg(n);
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_column_aggregate_grouped& c = cols[i];
+        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(SB_ERR_INVALID, "bad physical_type");
+        if (c.ops & ~(SB_AGG_COUNT | SB_AGG_MIN | SB_AGG_MAX | SB_AGG_SUM)) return refuse(SB_ERR_INVALID, "unknown ops bits");
+        if (c.reserved) return refuse(SB_ERR_INVALID, "reserved is not 0");
+        if (c.n_groups == 0 || c.n_groups > SB_AGG_MAX_GROUPS) return refuse(SB_ERR_INVALID, "n_groups is not in 1 .. SB_AGG_MAX_GROUPS");
+        if (c.group_id_width != 1 && c.group_id_width != 2 && c.group_id_width != 4) return refuse(SB_ERR_INVALID, "group_id_width is not 1, 2 or 4");
+        if (!c.groups) return refuse(SB_ERR_INVALID, "groups is null");
+        if ((c.ops & AGG_VALUE_OPS) && !filter_comparable(c.physical_type))
+            return refuse(SB_ERR_NYI, "min / max / sum are implemented for 8- to 64-bit integers and floats");
+        if (c.n_pages && !c.metas) return refuse(SB_ERR_INVALID, "metas is null");
+        uint64_t rows = 0;
+        for (uint64_t p = 0; p < c.n_pages; p++) rows += c.metas[p].num_values;
+        if (c.selection && (((uintptr_t)c.selection & 3) || c.selection_capacity < (rows + 31) / 32 * 4))
+            return refuse(SB_ERR_INVALID, "selection not 4-byte aligned or smaller than 4*ceil(rows/32) bytes");
+        if (rows && !c.group_ids) return refuse(SB_ERR_INVALID, "group_ids is null");
+        if (c.group_ids && (((uintptr_t)c.group_ids & (c.group_id_width - 1)) || c.group_ids_capacity < rows * c.group_id_width))
+            return refuse(SB_ERR_INVALID, "group_ids not aligned to group_id_width or smaller than rows * group_id_width bytes");
+        AggCol& g = hs[i];
+        memset(&g, 0, sizeof g);
+        g.sel = (const uint32_t*)c.selection;
+        g.rows = rows;
+        g.ops = c.ops;
+        g.ptype = c.physical_type;
+        g.w = type_width(c.physical_type);
+        g.kind = c.physical_type == SB_TYPE_FLOAT32 ? FK_F32 : c.physical_type == SB_TYPE_FLOAT64 ? FK_F64 : c.physical_type <= SB_TYPE_INT64 ? FK_SIGNED : FK_UNSIGNED;
+        hg[i] = GrpCol{(const uint8_t*)c.group_ids, c.group_id_width, c.n_groups};
+    }
+    (void)hipSetDevice(ctx->device);
+    std::vector<sb_column_aggregate_grouped*> users(n);
+    for (uint64_t i = 0; i < n; i++) users[i] = &cols[i];
+    int32_t rc = SB_OK;
+    if (ctx->in_replay && ctx->filter_freq) {
+        // The columns that met a Freq page in the first pass (and so asked for this replay, or would have) through a full
+        // decode; the others as ever, on the page route, whose slots -- and float bits -- are those of an interval that is
+        // not replayed.
+        std::vector<sb_column_aggregate_grouped*> u_val, u_rest;
+        std::vector<AggCol> g_val, g_rest;
+        std::vector<GrpCol> c_val, c_rest;
+        for (uint64_t i = 0; i < n; i++) {
+            const bool dec = (hs[i].ops & AGG_VALUE_OPS) != 0 &&
+                             std::find(ctx->grp_freq_users.begin(), ctx->grp_freq_users.end(), (const void*)users[i]) != ctx->grp_freq_users.end();
+            (dec ? u_val : u_rest).push_back(users[i]);
+            (dec ? g_val : g_rest).push_back(hs[i]);
+            (dec ? c_val : c_rest).push_back(hg[i]);
+        }
+        if (!u_val.empty()) rc = grp_columns_decoded(ctx, u_val.data(), g_val, c_val, u_val.size());
+        users.swap(u_rest);
+        hs.swap(g_rest);
+        hg.swap(c_rest);
+    }
+    if (rc == SB_OK && !users.empty()) {
+        const uint64_t m = users.size();
+        size_t stage = 0;
+        for (uint64_t i = 0; i < m; i++)
+            if (hs[i].ops & AGG_VALUE_OPS) stage += align_up(hs[i].rows * hs[i].w, 64);
+        if (!ensure(ctx, ctx->filter_stage, stage + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
+        std::vector<sb_column_read> rc_cols(m);
+        size_t so = 0;
+        ReadMode mode{ReadMode::AGG_GROUPED};
+        for (uint64_t i = 0; i < m; i++) {
+            mode.grp_gmax = std::max(mode.grp_gmax, hg[i].n_groups);
+            sb_column_read& r = rc_cols[i] = read_col_of(*users[i]);
+            if (!(hs[i].ops & AGG_VALUE_OPS)) {
+                r.physical_type = SB_TYPE_NULL;   // (no page body is parsed, queued or planned for a count)
+                continue;
+            }
+            r.values = ctx->filter_stage.p + so;
+            r.values_capacity = hs[i].rows * hs[i].w;
+            so += align_up(r.values_capacity, 64);
+        }
+        mode.aggc = hs.data();
+        mode.grpc = hg.data();
+        mode.grp_users = users.data();
+        rc = read_columns_impl(ctx, rc_cols.data(), m, SB_MEM_DEVICE, mode);
+    }
+    if (rc != SB_OK) return rc;
+    for (uint64_t i = 0; i < n; i++) {   // (after the last thing that can refuse the call: a page outside pages_len)
+        sb_column_aggregate_grouped& c = cols[i];
+        c.rows = 0;
+        for (uint64_t p = 0; p < c.n_pages; p++) c.rows += c.metas[p].num_values;
+        c.selected = c.out_of_range = 0;
+    }
+    if (!ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::AGG_GROUPED, cols, n, sb_write_options{}, mem});
     return rc;
 }
 

@@ -353,6 +353,38 @@ struct AggLaunch {   // what launch_decode needs to end a call with the aggregat
     uint64_t tile_base;    // the slot of the call's first tile (the page slots come first)
     bool any_val, any_null;
 };
+// one column of a grouped aggregate call (sb_aggregate_grouped, sb_aggregate_grouped.h), next to its AggCol.  The slots are
+// the AggCol's; a slot holds `gmax` records (the call's largest n_groups), record g of slot s at index s * gmax + g, and a
+// flag word says whether the slot was written: the records themselves are never zeroed.
+constexpr uint32_t GRP_MAX_GROUPS = 256;           // SB_AGG_MAX_GROUPS
+struct GrpCol {
+    const uint8_t* ids;    // one unsigned id of `idw` bytes per row of the column (input)
+    uint32_t idw;          // 1, 2 or 4
+    uint32_t n_groups;     // 1 .. GRP_MAX_GROUPS
+};
+struct GrpPart {           // 64 bytes: a group's share of a slot
+    uint64_t sel;          // selected rows of the group, null or not
+    uint64_t cnt, nans;    // as in AggPart
+    uint64_t kmin, kmax;
+    uint64_t s0, s1;
+    uint64_t pad;
+};
+// the result of a column: a header { selected, out_of_range, met a Freq page, 0... } of 8 words, then a record per group in the layout of
+// sb_agg_group, `gmax` of them reserved
+__host__ __device__ inline uint64_t grp_result_words(uint32_t gmax) { return 8ull * (1 + gmax); }
+struct GrpLaunch {   // what launch_decode needs to end a call with the grouped aggregate kernels
+    const AggCol* acols;
+    const GrpCol* gcols;
+    uint64_t* flags;       // [slots]: 1 = the slot's records were written; behind them [n_cols]: rows with an id >= n_groups;
+                           // behind those [n_cols]: 1 = the column met a primitive Freq page under a value op
+    GrpPart* recs;         // [slots * gmax]
+    uint64_t slots;
+    uint64_t tile_base;    // the slot of the call's first tile (the page slots come first)
+    uint32_t gmax;
+    bool any_val, any_null;
+    uint32_t n_cols;
+    bool replayed;         // the call is issued again: its columns with a Freq page are not on this route (an error if one is)
+};
 constexpr uint32_t FK_UNSIGNED = 0, FK_SIGNED = 1, FK_F32 = 2, FK_F64 = 3, FK_BYTES = 4;
 constexpr uint32_t FILTER_MASK_PREFIX = 16u;   // FilterCol.mask of SB_PRED_STARTS_WITH (the four relation bits are clear)
 // words of the bit table (a bit per dictionary entry) that a filter call reserves at the END of the aux area of every page
