@@ -789,7 +789,9 @@ uint64_t sb_ctx_side_forks(sb_ctx* ctx);
  * previous calls of the same shape did not need (long-page Dict / Freq writers, the block-parallel LZ4 reader, emitters of
  * codecs no page chose); when a page needs one after all it is left undone, and sb_ctx_synchronize re-issues the
  * interval's sb_write_columns / sb_read_columns calls with everything launched before it returns.  Results are the same
- * either way; the counter lets tests show which path ran.  Does not synchronise. */
+ * either way; the counter lets tests show which path ran.  Does not synchronise.  A sb_read_columns_sizes call made
+ * inside an open interval closes it with its own synchronize: it is issued again with the interval's other calls, and
+ * both its values_len and theirs are delivered before it returns. */
 uint64_t sb_ctx_replays(sb_ctx* ctx);
 
 /* version / build info string ("strawboat-hip <ver> gfx950") */

@@ -364,8 +364,14 @@ static int32_t freq_second_pass(sb_ctx* ctx) {
     rc = read_columns_impl(ctx, ctx->iv.freq_cols.data(), ctx->iv.freq_cols.size(), SB_MEM_DEVICE, ReadMode{ReadMode::FREQ_PASS});
     if (rc != SB_OK) return rc;
     for (const FreqBatch& b : batches) launch_freq_scatter(ctx, b.d_entries, b.n, b.d_off, b.ex_base);
-    const hipError_t e = read_status(ctx, false);   // (KIND_REPLAY bits of the pass are cleared with the rest and not acted on)
+    const hipError_t e = read_status(ctx, false);
     if (e != hipSuccess) return check_hip(ctx, e, "freq second pass");
+    // The pass goes by no launch hint (read_hints), so nothing of it may have been left undone: there is no call to issue
+    // again from inside a synchronize, and the scatter above has read the exceptions already.  Never SB_OK over that.
+    if (ctx->h_status->kinds & KIND_REPLAY) {
+        (void)take_device_error(ctx, SB_ERR_EXTERNAL);   // (clears the device's word)
+        return ctx->fail(SB_ERR_EXTERNAL, "freq second pass: an exceptions block was left undone on a launch hint");
+    }
     return take_device_error(ctx, SB_OK);
 }
 
@@ -725,16 +731,18 @@ static void update_read_hints(sb_ctx* ctx, uint32_t kinds) {
 }
 
 // The consumer.  Only a READ call consults every hint and counts as a call of its interval: a sizes call launches what
-// values_len depends on, the Freq second pass runs inside a synchronize (not a call of the next interval), a filter call
-// consults no launch hint and leaves the read calls' hint state alone.
+// values_len depends on, a filter call consults no launch hint and leaves the read calls' hint state alone.  The Freq
+// second pass runs inside a synchronize, where nothing can be issued again: it goes by no hint at all (as if no_hints
+// were set), and it is not a call of the next interval, whose state it leaves alone.
 static ReadHints read_hints(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh) {
     ReadHints h;
+    const bool no_hints = ctx->no_hints || mode.freq_pass();
     // the block-parallel Zstd pipeline: in a context whose last read intervals met Zstd buffers
-    h.zb_on = ctx->zb_mode == 1 || (ctx->zb_mode == 2 && (ctx->zstd_recent || ctx->no_hints || mode.sink()));
+    h.zb_on = ctx->zb_mode == 1 || (ctx->zb_mode == 2 && (ctx->zstd_recent || no_hints || mode.sink()));
     if (!mode.freq_pass() && !mode.sink()) ctx->read_calls++;
     // long multi-frame Zstd buffers (a one-page column written by this library): frames found by a scan (sb_decode.hip)
-    h.zs_on = h.zb_on && !mode.sizes() && sh.max_page_len >= (1u << 20);
-    h.zb_skipped = (!h.zb_on && ctx->zb_mode == 2 && !mode.sizes() && sh.max_page_len >= (1u << 20)) ? 1u : 0u;
+    h.zs_on = h.zb_on && !mode.sizes() && sh.max_page_len >= ZSTD_LONG_MIN;
+    h.zb_skipped = (!h.zb_on && ctx->zb_mode == 2 && !mode.sizes() && sh.max_page_len >= ZSTD_LONG_MIN) ? 1u : 0u;
     // (the lane-per-frame record arena only for calls that can hold >= 4 x INFLATE_POOL frames of 16 KiB, and only in a
     // context that has met Zstd pages: LZ4 / plain / Dict-only readers never pay for it)
     h.zrec_wanted = sh.pages_bytes >= (48ull << 20) && (ctx->zb_mode == 1 || ctx->zstd_recent);
@@ -746,7 +754,7 @@ static ReadHints read_hints(sb_ctx* ctx, const ReadMode& mode, const ReadShape& 
     }
     // LZ4 blocks of megabytes (a one-page column): block-parallel (sb_lz4_giant.h) — tables and entries in a pool of their own
     if (!mode.sizes() && sh.max_page_len >= LZG_MIN) {
-        const bool none_met = ctx->lzg_state == 2 && !ctx->no_hints;   // the context's last intervals met no LZ4 block of megabytes
+        const bool none_met = ctx->lzg_state == 2 && !no_hints;   // the context's last intervals met no LZ4 block of megabytes
         // none met: no pool, no launches; k_inflate_lz4_big leaves such a block alone and asks for the replay (it used to
         // walk it with one workgroup: 0.8 s for 68 MB)
         h.lzg = none_met && !mode.sink() ? ReadHints::LZG_SKIPPED : ReadHints::LZG_POOL;
@@ -755,7 +763,7 @@ static ReadHints read_hints(sb_ctx* ctx, const ReadMode& mode, const ReadShape& 
         h.lzg_launch = h.lzg == ReadHints::LZG_POOL && !none_met;
         // (noted here, before anything of the call can fail: a call that fails later — tables, staging, page_offsets, pools,
         // upload, or the giant-LZ4 pool itself — has still shown its long pages; it used to be noted after all of those)
-        if (!mode.sink()) ctx->lzg_long_pages = true;
+        if (!mode.sink() && !mode.freq_pass()) ctx->lzg_long_pages = true;
     }
     return h;
 }
@@ -2213,10 +2221,18 @@ int32_t sb_aggregate_grouped(sb_ctx* ctx, sb_column_aggregate_grouped* cols, uin
     return rc;
 }
 
+// The call synchronizes, and the interval it closes may hold earlier calls of which one asks for a replay: the replay
+// drops every pending result and issues the recorded calls again, so the sizes call is recorded with them (its
+// values_len would stay unwritten otherwise).  By itself a sizes call never asks for one: it goes by no launch hint.
 int32_t sb_read_columns_sizes(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem) {
-    int32_t rc = read_columns_impl(ctx, cols, n, mem, ReadMode{ReadMode::SIZES});
+    int32_t rc = enqueue_read_sizes(ctx, cols, n, mem);
     if (rc != SB_OK) return rc;
+    if (ctx && n && !ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::SIZES, cols, n, sb_write_options{}, mem});
     return sb_ctx_synchronize(ctx);
 }
 
 }  // extern "C"
+
+int32_t enqueue_read_sizes(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem) {
+    return read_columns_impl(ctx, cols, n, mem, ReadMode{ReadMode::SIZES});
+}

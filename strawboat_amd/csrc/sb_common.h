@@ -192,6 +192,9 @@ struct ZbPools {             // (the defaults: the pipeline is not launched)
 // the pool of inflate waves (k_inflate) and its per-wave areas
 constexpr uint32_t INFLATE_POOL = 2048;          // waves
 constexpr uint32_t ZREC_PER_WAVE = 128 * 1024;   // pre-decoded Zstd sequence records (8 bytes each) per pool wave
+// a LONG Zstd buffer (compressed bytes): the host launches the frame scan for calls with a page this long, or marks the call
+// zb_skipped when the block pipeline is left out on a hint; k_zstd_split then leaves such a buffer undone and asks for the replay
+constexpr uint32_t ZSTD_LONG_MIN = 1u << 20;
 
 // one LZ4 block of megabytes decoded by the whole chip (sb_lz4_giant.h)
 constexpr uint32_t LZG_MIN = 2u << 20;     // compressed bytes

@@ -218,7 +218,7 @@ __device__ void zstd_split_walk(InflateJob* q, uint32_t* cnt, uint32_t cap, uint
 // at its end by binary search, and ONE lane follows the links from position 0 through LDS (30 ns per frame).  A magic
 // inside compressed data is just a candidate off the chain.  Anything unexpected (a segment with > 7 hits, > 4096
 // candidates, a broken chain) falls back to zstd_split_walk for that buffer.
-constexpr uint32_t ZS_BIG = 1u << 20, ZS_SEG = 16384, ZS_SLOTS = 7, ZS_LIST = 16, ZS_MAXC = 4096;
+constexpr uint32_t ZS_BIG = ZSTD_LONG_MIN, ZS_SEG = 16384, ZS_SLOTS = 7, ZS_LIST = 16, ZS_MAXC = 4096;
 __global__ void __launch_bounds__(WG) k_zsplit_scan(const InflateJob* q, DecodeArgs a) {
     const uint32_t e = blockIdx.y;
     if (e >= min(a.zs_hdr[0], ZS_LIST)) return;
@@ -434,7 +434,7 @@ __global__ void __launch_bounds__(WG) k_zstd_split(InflateJob* q, uint32_t* cnt,
         if (job.codec == SB_CODEC_LZ4 && job.csize >= (2u << 20) && !(st->kinds & KIND_LZ4_GIANT)) atomicOr(&st->kinds, KIND_LZ4_GIANT);
         if ((job.codec & ~JOB_REL) != SB_CODEC_ZSTD) return;
         if (!(st->kinds & KIND_ZSTD)) atomicOr(&st->kinds, KIND_ZSTD);   // (the host sizes the block pipeline's pools for later calls)
-        if (a.zb_skipped && job.csize >= (1u << 20)) {   // a long buffer and no pipeline: not decoded now, the interval is replayed with it
+        if (a.zb_skipped && job.csize >= ZSTD_LONG_MIN) {   // a long buffer and no pipeline: not decoded now, the interval is replayed with it
             atomicOr(&st->kinds, KIND_REPLAY);
             q[j].codec = CODEC_SPLIT;
             return;

@@ -235,7 +235,7 @@ struct sb_ctx {
     // never a one-workgroup walk over a million-row page.  (The callers' column arrays and buffers live until the
     // synchronize anyway: the results are written into them there.)
     struct Call {
-        enum Kind { READ, WRITE, FILTER, FILTER_VAR, READ_SEL, READ_SEL_VAR, AGGREGATE, AGG_GROUPED } kind;   // sb_read_columns, sb_write_columns, sb_filter_columns, sb_filter_columns_var, sb_read_selected, sb_read_selected_var, sb_aggregate_columns, sb_aggregate_grouped
+        enum Kind { READ, WRITE, FILTER, FILTER_VAR, READ_SEL, READ_SEL_VAR, AGGREGATE, AGG_GROUPED, SIZES } kind;   // sb_read_columns, sb_write_columns, sb_filter_columns, sb_filter_columns_var, sb_read_selected, sb_read_selected_var, sb_aggregate_columns, sb_aggregate_grouped, sb_read_columns_sizes (its enqueue: the call's own synchronize may be the one that replays)
         void* cols;
         uint64_t n;
         sb_write_options opts;
@@ -331,9 +331,13 @@ struct sb_ctx {
     }
 };
 
+// the enqueue of sb_read_columns_sizes without its synchronize (sb_api.hip)
+int32_t enqueue_read_sizes(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem);
+
 // issues a call of the interval again (a replay: sb_api.hip, replay_interval)
 inline int32_t reissue(sb_ctx* ctx, sb_ctx::Call& cl) {
     switch (cl.kind) {
+        case sb_ctx::Call::SIZES: return enqueue_read_sizes(ctx, (sb_column_read*)cl.cols, cl.n, cl.mem);
         case sb_ctx::Call::READ: return sb_read_columns(ctx, (sb_column_read*)cl.cols, cl.n, cl.mem);
         case sb_ctx::Call::WRITE: return sb_write_columns(ctx, (sb_column_write*)cl.cols, cl.n, &cl.opts, cl.mem);
         case sb_ctx::Call::FILTER: return sb_filter_columns(ctx, (sb_column_filter*)cl.cols, cl.n, cl.mem);
