@@ -233,19 +233,19 @@ struct ReadMode {
     // / sb_aggregate_grouped, an aggregate call whose columns end in the grouped aggregate kernels
     enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR, AGGREGATE, AGG_GROUPED } kind;
     const FilterCol* filt = nullptr;             // FILTER: one per column
-    uint64_t* const* sel_out = nullptr;          // ... sel_out[i]: the caller's `selected`
     const std::vector<uint8_t>* lits = nullptr;  // ... the literals of the FK_BYTES columns, FilterCol.lit being the offset of each
     bool sizes() const { return kind == SIZES; }
     bool freq_pass() const { return kind == FREQ_PASS; }
     const SelCol* selc = nullptr;                // SELECTED: one per column (rank: filled in with the call's tables)
-    sb_column_read_selected* const* sel_users = nullptr;   // ... the callers' structs
     const SelBin* selb = nullptr;                // SELECTED_VAR: one per column beside selc (sums: filled in with the call's tables)
-    sb_column_read_selected_var* const* selv_users = nullptr;   // ... the callers' structs
     const AggCol* aggc = nullptr;                // AGGREGATE: one per column (the slots: filled in with the call's tables)
-    sb_column_aggregate* const* agg_users = nullptr;   // ... the callers' structs
     const GrpCol* grpc = nullptr;                // AGG_GROUPED: one per column beside aggc
-    sb_column_aggregate_grouped* const* grp_users = nullptr;   // ... the callers' structs (agg_users is null)
     uint32_t grp_gmax = 0;                       // ... the largest n_groups of the call: records per slot
+    // Where a column's result goes at the synchronize, as Pending has it (sb_host.h): users[i] beside pending_kind.  Set by
+    // the entry points of the sinks: the callers' structs, for a filter call the caller's `selected` (results[i] + 1).
+    // Null for the other kinds of call, whose results go to the sb_column_read structs of the call itself.
+    void* const* users = nullptr;
+    Pending::Kind pending_kind = Pending::READ_COL;
     bool aggregate() const { return kind == AGGREGATE || kind == AGG_GROUPED; }   // an AggCol per column, slots per page part and tile
     bool grouped() const { return kind == AGG_GROUPED; }
     bool filter() const { return kind == FILTER; }
@@ -1211,6 +1211,21 @@ static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, 
     }
 }
 
+// One Pending per column of a call whose results are on their way to `host`, `stride` bytes apart.  grpc: the columns of a
+// grouped aggregate, of whose record the header and the column's own groups are handed over.
+static void push_pending(sb_ctx* ctx, Pending::Kind kind, void* const* users, const uint8_t* host, size_t stride, uint64_t n,
+                         const GrpCol* grpc = nullptr) {
+    for (uint64_t i = 0; i < n; i++) {
+        Pending pd;
+        pd.kind = kind;
+        pd.user = users[i];
+        pd.host = host + i * stride;
+        pd.n = 0;
+        if (grpc) pd.bytes = sizeof(uint64_t) * grp_result_words(grpc[i].n_groups);
+        ctx->iv.pending.push_back(pd);
+    }
+}
+
 // Results: values_len per column (a filter call: the bits set per column) into the slot's n words behind the upload;
 // sb_ctx_synchronize hands them to the callers' structs
 static int32_t queue_read_results(sb_ctx* ctx, StageSlot* slot, const ReadLayout& L, const ReadMode& mode, const ReadShape& sh,
@@ -1235,15 +1250,13 @@ static int32_t queue_read_results(sb_ctx* ctx, StageSlot* slot, const ReadLayout
     }
     (void)hipEventRecord(slot->done, s);
     slot->in_flight = true;
-    for (uint64_t i = 0; i < n; i++) {
-        Pending pd;
-        pd.kind = mode.filter() ? Pending::FILTER_COL : mode.selected() ? Pending::RSEL_COL : mode.selected_var() ? Pending::RSEL_VAR_COL : mode.grouped() ? Pending::AGG_GRP_COL : mode.aggregate() ? Pending::AGG_COL : Pending::READ_COL;
-        pd.user = mode.filter() ? (void*)mode.sel_out[i] : mode.selected() ? (void*)mode.sel_users[i] : mode.selected_var() ? (void*)mode.selv_users[i] : mode.grouped() ? (void*)mode.grp_users[i] : mode.aggregate() ? (void*)mode.agg_users[i] : (void*)&cols[i];
-        pd.host = hv + i * sizeof(uint64_t) * mode.result_words();
-        pd.n = 0;
-        if (mode.grouped()) pd.bytes = sizeof(uint64_t) * grp_result_words(mode.grp_users[i]->n_groups);   // (the header and the column's own groups)
-        ctx->iv.pending.push_back(pd);
+    std::vector<void*> own;   // (the results of a call that is no sink go to its own columns)
+    if (!mode.users) {
+        own.resize(n);
+        for (uint64_t i = 0; i < n; i++) own[i] = &cols[i];
     }
+    push_pending(ctx, mode.pending_kind, mode.users ? mode.users : own.data(), hv, sizeof(uint64_t) * mode.result_words(), n,
+                 mode.grouped() ? mode.grpc : nullptr);
     return SB_OK;
 }
 
@@ -1319,16 +1332,51 @@ int32_t sb_read_columns(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t m
     return rc;
 }
 
-// ------------------------------------------------------------------------------------ filter
+// ------------------------------------------------------------------------------------ sinks: the steps their entry points share
 static bool filter_comparable(int32_t t) {
     return (t >= SB_TYPE_INT8 && t <= SB_TYPE_UINT64) || t == SB_TYPE_FLOAT32 || t == SB_TYPE_FLOAT64;
 }
 
-// The replay of an interval in which a filter call met a primitive Freq page (KIND_FILTER_FREQ): the numeric comparison
-// columns are decoded like a read — values and validity into the staging area, the exceptions of Freq pages by the second
-// pass, which needs the host and so cannot run inside the enqueue-only call — and compared from there.
-// The pages of a filter column as a read column (outputs: none yet)
-static sb_column_read read_col_of(const sb_column_filter_var& u) {
+// how the sink kernels compare, order and add the values of a numeric type
+static uint32_t value_kind(int32_t t) {
+    return t == SB_TYPE_FLOAT32 ? FK_F32 : t == SB_TYPE_FLOAT64 ? FK_F64 : t <= SB_TYPE_INT64 ? FK_SIGNED : FK_UNSIGNED;
+}
+
+// what an entry point refuses itself is refused before anything is enqueued or written, and does not show again at the synchronize
+static int32_t refuse(sb_ctx* ctx, int32_t code, const char* msg) {
+    ctx->last_error = msg;
+    return code;
+}
+
+// How every sink entry point begins.  False: the call ends here, with *rc.
+static bool sink_entry(sb_ctx* ctx, const void* cols, uint64_t n, int32_t mem, const char* name, int32_t* rc) {
+    *rc = SB_OK;
+    if (!ctx || (!cols && n)) {
+        *rc = SB_ERR_INVALID;
+    } else if (n && mem != SB_MEM_DEVICE) {
+        ctx->last_error = std::string(name) + ": SB_MEM_HOST is not implemented";
+        *rc = SB_ERR_NYI;
+    }
+    return *rc == SB_OK && n;
+}
+
+extern "C++" {   // (templates: not inside the C linkage of the entry points)
+// The column structs of the sinks begin alike, with the pages of the column as sb_column_filter has them
+template <class Col>
+constexpr bool has_pages_prefix() {
+    return offsetof(Col, physical_type) == offsetof(sb_column_filter, physical_type) && offsetof(Col, is_nullable) == offsetof(sb_column_filter, is_nullable) &&
+           offsetof(Col, pages) == offsetof(sb_column_filter, pages) && offsetof(Col, pages_len) == offsetof(sb_column_filter, pages_len) &&
+           offsetof(Col, metas) == offsetof(sb_column_filter, metas) && offsetof(Col, n_pages) == offsetof(sb_column_filter, n_pages) &&
+           offsetof(Col, page_offsets) == offsetof(sb_column_filter, page_offsets);
+}
+static_assert(offsetof(sb_column_filter, page_offsets) == 40, "the pages of a sink column: 48 bytes");
+static_assert(has_pages_prefix<sb_column_filter_var>() && has_pages_prefix<sb_column_read_selected>() && has_pages_prefix<sb_column_read_selected_var>() &&
+                  has_pages_prefix<sb_column_aggregate>() && has_pages_prefix<sb_column_aggregate_grouped>(),
+              "every sink column begins with the seven fields of sb_column_filter, at its offsets");
+
+// The pages of a sink column as a read column (outputs: none yet)
+template <class Col>
+static sb_column_read read_col_of(const Col& u) {
     sb_column_read r;
     memset(&r, 0, sizeof r);
     r.physical_type = u.physical_type;
@@ -1341,31 +1389,99 @@ static sb_column_read read_col_of(const sb_column_filter_var& u) {
     return r;
 }
 
-static int32_t filter_columns_decoded(sb_ctx* ctx, sb_column_filter_var* const* users, const FilterCol* hf, uint64_t* const* sel_out, uint64_t m) {
-    hipStream_t s = ctx->stream;
-    ctx->iv.filter_tmp.emplace_back(m);
+// The rows of a column: what its pages' metas say.  False: it has pages and no metas ("metas is null").
+template <class Col>
+static bool column_rows(const Col& c, uint64_t* rows) {
+    if (c.n_pages && !c.metas) return false;
+    uint64_t r = 0;
+    for (uint64_t p = 0; p < c.n_pages; p++) r += c.metas[p].num_values;
+    *rows = r;
+    return true;
+}
+
+// The elements of v whose dec[i] is set, taken out of v; both parts keep their order.  (A replayed call splits its columns'
+// parallel vectors with it: those that go through a full decode, and the rest.)
+template <class T>
+static std::vector<T> take_if(std::vector<T>& v, const std::vector<bool>& dec) {
+    std::vector<T> taken, rest;
+    for (size_t i = 0; i < v.size(); i++) (dec[i] ? taken : rest).push_back(v[i]);
+    v.swap(rest);
+    return taken;
+}
+}   // extern "C++"
+
+// The normal route: column i's share of the staging area, cap[i] bytes at a multiple of 64, as the `values` of its read
+// column.  NO_SHARE: no page body of the column is parsed, queued or planned (a null test, a count) -- it is read as SB_TYPE_NULL.
+static const uint64_t NO_SHARE = ~0ull;
+static int32_t stage_shares(sb_ctx* ctx, sb_column_read* rc_cols, const uint64_t* cap, uint64_t n) {
+    size_t stage = 0;
+    for (uint64_t i = 0; i < n; i++)
+        if (cap[i] != NO_SHARE) stage += align_up(cap[i], 64);
+    if (!ensure(ctx, ctx->filter_stage, stage + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
+    size_t so = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        sb_column_read& r = rc_cols[i];
+        if (cap[i] == NO_SHARE) {
+            r.physical_type = SB_TYPE_NULL;
+            continue;
+        }
+        r.values = ctx->filter_stage.p + so;
+        r.values_capacity = cap[i];
+        so += align_up(cap[i], 64);
+    }
+    return SB_OK;
+}
+
+// The replay of an interval in which a sink call met a primitive Freq page (KIND_FILTER_FREQ), first half: the columns are
+// decoded like a read -- values and validity into the staging area, the exceptions of Freq pages by the second pass, which
+// needs the host and so cannot run inside the enqueue-only call -- and the sink's plain kernels take them from there.
+// pages: the columns as read_col_of gives them; they live in iv.filter_tmp until the interval ends, and *out is where.
+// what: the sink, for the error texts.
+static int32_t decode_for_replay(sb_ctx* ctx, std::vector<sb_column_read>&& pages, const uint64_t* rows, const char* what, const sb_column_read** out) {
+    ctx->iv.filter_tmp.push_back(std::move(pages));
     std::vector<sb_column_read>& rr = ctx->iv.filter_tmp.back();
+    const uint64_t n = rr.size();
     size_t total = 0;
-    std::vector<size_t> o_val(m), o_bits(m);
-    for (uint64_t i = 0; i < m; i++) {
-        o_val[i] = total;
-        total += align_up(users[i]->rows * type_width(users[i]->physical_type), 64);
-        o_bits[i] = total;
-        total += align_up((users[i]->rows + 31) / 32 * 4, 64);
-    }
+    for (uint64_t i = 0; i < n; i++)
+        total += align_up(rows[i] * type_width(rr[i].physical_type), 64) + align_up((rows[i] + 31) / 32 * 4, 64);
     if (!ensure(ctx, ctx->filter_stage, total + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
-    for (uint64_t i = 0; i < m; i++) {
-        const sb_column_filter_var& u = *users[i];
-        sb_column_read& r = rr[i] = read_col_of(u);
-        r.values = ctx->filter_stage.p + o_val[i];
-        r.values_capacity = u.rows * type_width(u.physical_type);
-        r.validity = ctx->filter_stage.p + o_bits[i];
-        r.validity_capacity = (u.rows + 31) / 32 * 4;
+    size_t so = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        sb_column_read& r = rr[i];
+        r.values = ctx->filter_stage.p + so;
+        r.values_capacity = rows[i] * type_width(r.physical_type);
+        so += align_up(r.values_capacity, 64);
+        r.validity = ctx->filter_stage.p + so;
+        r.validity_capacity = (rows[i] + 31) / 32 * 4;
+        so += align_up(r.validity_capacity, 64);
     }
-    int32_t rc = read_columns_impl(ctx, rr.data(), m, SB_MEM_DEVICE, ReadMode{ReadMode::READ});
+    int32_t rc = read_columns_impl(ctx, rr.data(), n, SB_MEM_DEVICE, ReadMode{ReadMode::READ});
     if (rc != SB_OK) return rc;
-    if (hipStreamSynchronize(s) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "filter replay: synchronize failed");
-    rc = freq_second_pass(ctx);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, std::string(what) + " replay: synchronize failed");
+    *out = rr.data();
+    return freq_second_pass(ctx);
+}
+
+// ... second half: the plain kernels are launched, and their results -- `stride` bytes per column at d_res -- travel to
+// the slot, which was acquired before the launches, and from there to the callers at the synchronize.
+static int32_t queue_sink_results(sb_ctx* ctx, StageSlot* slot, const void* d_res, size_t stride, uint64_t n, Pending::Kind kind, void* const* users,
+                                  const GrpCol* grpc, const char* what) {
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(slot->host, d_res, n * stride, hipMemcpyDeviceToHost, ctx->stream);
+    if (e != hipSuccess) return check_hip(ctx, e, (std::string(what) + " replay").c_str());
+    (void)hipEventRecord(slot->done, ctx->stream);
+    slot->in_flight = true;
+    push_pending(ctx, kind, users, slot->host, stride, n, grpc);
+    return SB_OK;
+}
+
+// ------------------------------------------------------------------------------------ filter
+// The numeric comparison columns of a replayed filter call: decoded, and compared from the staging area.
+static int32_t filter_columns_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pages, const uint64_t* rows, const FilterCol* hf, void* const* sel_out) {
+    hipStream_t s = ctx->stream;
+    const uint64_t m = pages.size();
+    const sb_column_read* rr = nullptr;
+    int32_t rc = decode_for_replay(ctx, std::move(pages), rows, "filter", &rr);
     if (rc != SB_OK) return rc;
     uint64_t* d_counts = nullptr;
     if (hipMalloc((void**)&d_counts, m * sizeof(uint64_t)) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter counts) failed");
@@ -1373,73 +1489,56 @@ static int32_t filter_columns_decoded(sb_ctx* ctx, sb_column_filter_var* const* 
     StageSlot* slot = acquire_slot(ctx, m * sizeof(uint64_t));
     if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
     for (uint64_t i = 0; i < m; i++) {
-        const uint64_t rows = users[i]->rows;
-        if (hf[i].combine == SB_SEL_SET && rows) (void)hipMemsetAsync(hf[i].sel, 0, (rows + 31) / 32 * 4, s);
-        launch_filter_plain(ctx, hf[i], (const uint8_t*)rr[i].values, users[i]->is_nullable ? rr[i].validity : nullptr, rows,
-                            type_width(users[i]->physical_type), d_counts + i);
+        if (hf[i].combine == SB_SEL_SET && rows[i]) (void)hipMemsetAsync(hf[i].sel, 0, (rows[i] + 31) / 32 * 4, s);
+        launch_filter_plain(ctx, hf[i], (const uint8_t*)rr[i].values, rr[i].is_nullable ? rr[i].validity : nullptr, rows[i],
+                            type_width(rr[i].physical_type), d_counts + i);
     }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(slot->host, d_counts, m * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return check_hip(ctx, e, "filter replay");
-    (void)hipEventRecord(slot->done, s);
-    slot->in_flight = true;
-    for (uint64_t i = 0; i < m; i++) {
-        Pending pd;
-        pd.kind = Pending::FILTER_COL;
-        pd.user = sel_out[i];
-        pd.host = slot->host + i * sizeof(uint64_t);
-        pd.n = 0;
-        ctx->iv.pending.push_back(pd);
-    }
-    return SB_OK;
+    return queue_sink_results(ctx, slot, d_counts, sizeof(uint64_t), m, Pending::FILTER_COL, sel_out, nullptr, "filter");
 }
 
 // Both entry points end here.  `cols` is the call in the var layout (sb_filter_columns copies its columns into one that
 // lives for the call); results[i] are the caller's own { rows, selected } words, which outlive the call.
 static int32_t filter_impl(sb_ctx* ctx, const sb_column_filter_var* cols, uint64_t* const* results, uint64_t n) {
-    // what is refused here is refused before anything is enqueued, and does not show again at the synchronize
-    auto refuse = [&](int32_t code, const char* msg) {
-        ctx->last_error = msg;
-        return code;
-    };
     std::vector<FilterCol> hf(n);
-    std::vector<sb_column_read> rc_cols(n);
     std::vector<sb_column_filter_var> work(cols, cols + n);   // (with rows and the default stage_capacity filled in)
-    std::vector<sb_column_filter_var*> users(n);
     std::vector<uint8_t> lits;   // the binary literals, each at a multiple of 8 and followed by 8 zero bytes
     for (uint64_t i = 0; i < n; i++) {
         sb_column_filter_var& c = work[i];
-        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(SB_ERR_INVALID, "bad physical_type");
-        if (c.op < SB_PRED_EQ || c.op > SB_PRED_STARTS_WITH) return refuse(SB_ERR_INVALID, "bad op");
-        if (c.combine < SB_SEL_SET || c.combine > SB_SEL_OR) return refuse(SB_ERR_INVALID, "bad combine");
+        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(ctx, SB_ERR_INVALID, "bad physical_type");
+        if (c.op < SB_PRED_EQ || c.op > SB_PRED_STARTS_WITH) return refuse(ctx, SB_ERR_INVALID, "bad op");
+        if (c.combine < SB_SEL_SET || c.combine > SB_SEL_OR) return refuse(ctx, SB_ERR_INVALID, "bad combine");
         const bool null_op = c.op == SB_PRED_IS_NULL || c.op == SB_PRED_IS_NOT_NULL;
         const bool bin = is_binary_t(c.physical_type);
-        if (c.op == SB_PRED_STARTS_WITH && !bin) return refuse(SB_ERR_INVALID, "STARTS_WITH needs a Binary / LargeBinary column");
+        if (c.op == SB_PRED_STARTS_WITH && !bin) return refuse(ctx, SB_ERR_INVALID, "STARTS_WITH needs a Binary / LargeBinary column");
         if (!null_op && !bin && !filter_comparable(c.physical_type))
-            return refuse(SB_ERR_NYI, "comparison predicates are implemented for 8- to 64-bit integers, floats and binary types");
+            return refuse(ctx, SB_ERR_NYI, "comparison predicates are implemented for 8- to 64-bit integers, floats and binary types");
         if (!null_op) {
-            if (!bin && c.literal_len != type_width(c.physical_type)) return refuse(SB_ERR_INVALID, "literal_len is not the width of the column's type");
-            if (bin && c.literal_len > (1ull << 30)) return refuse(SB_ERR_INVALID, "a binary literal has at most 2^30 bytes");
-            if (c.literal_len && !c.literal) return refuse(SB_ERR_INVALID, "literal is null");
+            if (!bin && c.literal_len != type_width(c.physical_type)) return refuse(ctx, SB_ERR_INVALID, "literal_len is not the width of the column's type");
+            if (bin && c.literal_len > (1ull << 30)) return refuse(ctx, SB_ERR_INVALID, "a binary literal has at most 2^30 bytes");
+            if (c.literal_len && !c.literal) return refuse(ctx, SB_ERR_INVALID, "literal is null");
         }
-        if (c.n_pages && !c.metas) return refuse(SB_ERR_INVALID, "metas is null");
         uint64_t rows = 0;
-        for (uint64_t p = 0; p < c.n_pages; p++) rows += c.metas[p].num_values;
+        if (!column_rows(c, &rows)) return refuse(ctx, SB_ERR_INVALID, "metas is null");
         const uint64_t sel_bytes = (rows + 31) / 32 * 4;
         if (rows && (!c.selection || ((uintptr_t)c.selection & 3) || c.selection_capacity < sel_bytes))
-            return refuse(SB_ERR_INVALID, "selection missing, not 4-byte aligned or smaller than 4*ceil(rows/32) bytes");
+            return refuse(ctx, SB_ERR_INVALID, "selection missing, not 4-byte aligned or smaller than 4*ceil(rows/32) bytes");
         for (uint64_t j = 0; j < i && rows; j++)
             if (work[j].rows && c.selection < work[j].selection + (work[j].rows + 31) / 32 * 4 && work[j].selection < c.selection + sel_bytes)
-                return refuse(SB_ERR_INVALID, "two columns of one call share a selection buffer: chain them with two calls");
+                return refuse(ctx, SB_ERR_INVALID, "two columns of one call share a selection buffer: chain them with two calls");
         c.rows = rows;
     }
-    size_t stage = 0;
+    std::vector<sb_column_read> rc_cols(n);
+    std::vector<uint64_t> rows(n), cap(n);   // (cap: the column's share of the staging area)
+    std::vector<void*> sel_out(n);           // the callers' `selected`
     for (uint64_t i = 0; i < n; i++) {
         sb_column_filter_var& c = work[i];
         const bool null_op = c.op == SB_PRED_IS_NULL || c.op == SB_PRED_IS_NOT_NULL;
         results[i][0] = c.rows;
         results[i][1] = 0;
-        users[i] = &c;
+        sel_out[i] = results[i] + 1;
+        rc_cols[i] = read_col_of(c);
+        rows[i] = c.rows;
+        cap[i] = NO_SHARE;
         FilterCol& f = hf[i];
         memset(&f, 0, sizeof f);
         f.sel = (uint32_t*)c.selection;
@@ -1457,103 +1556,71 @@ static int32_t filter_impl(sb_ctx* ctx, const sb_column_filter_var* cols, uint64
             if (c.literal_len) lits.insert(lits.end(), c.literal, c.literal + c.literal_len);
             lits.insert(lits.end(), 8, (uint8_t)0);
             if (!c.stage_capacity) c.stage_capacity = 4 * c.pages_len;
-            stage += align_up(c.stage_capacity, 64);
+            cap[i] = c.stage_capacity;
             continue;
         }
+        // the literal widened to the 8 bytes the kernels compare: floats as doubles, signed integers sign-extended
         const uint32_t w = type_width(c.physical_type);
         uint64_t raw = 0;
         memcpy(&raw, c.literal, w);
-        if (c.physical_type == SB_TYPE_FLOAT32) {
+        f.kind = value_kind(c.physical_type);
+        f.lit = raw;
+        if (f.kind == FK_F32) {
             float v;
             memcpy(&v, c.literal, 4);
             const double dv = (double)v;
             memcpy(&f.lit, &dv, 8);
-            f.kind = FK_F32;
-        } else if (c.physical_type == SB_TYPE_FLOAT64) {
-            f.lit = raw;
-            f.kind = FK_F64;
-        } else if (c.physical_type <= SB_TYPE_INT64) {
+        } else if (f.kind == FK_SIGNED) {
             const uint32_t sh = 64 - 8 * w;
             f.lit = (uint64_t)((int64_t)(raw << sh) >> sh);
-            f.kind = FK_SIGNED;
-        } else {
-            f.lit = raw;
-            f.kind = FK_UNSIGNED;
         }
-        stage += align_up(c.rows * w, 64);
+        cap[i] = c.rows * w;
     }
     (void)hipSetDevice(ctx->device);
     int32_t rc = SB_OK;
-    std::vector<uint64_t*> sel_out(n);
-    for (uint64_t i = 0; i < n; i++) sel_out[i] = results[i] + 1;
     if (ctx->in_replay && ctx->filter_freq) {
         // IS_[NOT_]NULL and binary columns as ever; the numeric comparison columns through a full decode
-        std::vector<sb_column_filter_var*> u_cmp, u_rest;
-        std::vector<FilterCol> f_cmp, f_rest;
-        std::vector<uint64_t*> s_cmp, s_rest;
-        for (uint64_t i = 0; i < n; i++) {
-            const bool dec = hf[i].op < SB_PRED_IS_NULL && hf[i].kind != FK_BYTES;
-            (dec ? u_cmp : u_rest).push_back(users[i]);
-            (dec ? f_cmp : f_rest).push_back(hf[i]);
-            (dec ? s_cmp : s_rest).push_back(sel_out[i]);
-        }
-        if (!u_cmp.empty()) rc = filter_columns_decoded(ctx, u_cmp.data(), f_cmp.data(), s_cmp.data(), u_cmp.size());
-        if (rc != SB_OK || u_rest.empty()) return rc;
-        users.swap(u_rest);
-        hf.swap(f_rest);
-        sel_out.swap(s_rest);
-        n = users.size();
-        stage = 0;
-        for (uint64_t i = 0; i < n; i++)
-            if (hf[i].kind == FK_BYTES) stage += align_up(users[i]->stage_capacity, 64);
+        std::vector<bool> dec(n);
+        for (uint64_t i = 0; i < n; i++) dec[i] = hf[i].op < SB_PRED_IS_NULL && hf[i].kind != FK_BYTES;
+        std::vector<sb_column_read> r_cmp = take_if(rc_cols, dec);
+        const std::vector<uint64_t> n_cmp = take_if(rows, dec);
+        const std::vector<FilterCol> f_cmp = take_if(hf, dec);
+        const std::vector<void*> s_cmp = take_if(sel_out, dec);
+        take_if(cap, dec);
+        if (!r_cmp.empty()) rc = filter_columns_decoded(ctx, std::move(r_cmp), n_cmp.data(), f_cmp.data(), s_cmp.data());
+        if (rc != SB_OK || rc_cols.empty()) return rc;
     }
-    if (!ensure(ctx, ctx->filter_stage, stage + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
-    size_t so = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        const sb_column_filter_var& c = *users[i];
-        const bool null_op = c.op == SB_PRED_IS_NULL || c.op == SB_PRED_IS_NOT_NULL;
-        sb_column_read& r = rc_cols[i] = read_col_of(c);
-        if (null_op) r.physical_type = SB_TYPE_NULL;   // (no page body is parsed, queued or planned for a null test)
-        if (!null_op) {
-            r.values = ctx->filter_stage.p + so;
-            r.values_capacity = is_binary_t(c.physical_type) ? c.stage_capacity : c.rows * type_width(c.physical_type);
-            so += align_up(r.values_capacity, 64);
-        }
-    }
-    return read_columns_impl(ctx, rc_cols.data(), n, SB_MEM_DEVICE, ReadMode{ReadMode::FILTER, hf.data(), sel_out.data(), &lits});
+    if ((rc = stage_shares(ctx, rc_cols.data(), cap.data(), rc_cols.size())) != SB_OK) return rc;
+    ReadMode mode{ReadMode::FILTER};
+    mode.filt = hf.data();
+    mode.lits = &lits;
+    mode.users = sel_out.data();
+    mode.pending_kind = Pending::FILTER_COL;
+    return read_columns_impl(ctx, rc_cols.data(), rc_cols.size(), SB_MEM_DEVICE, mode);
 }
 
 int32_t sb_filter_columns_var(sb_ctx* ctx, sb_column_filter_var* cols, uint64_t n, int32_t mem) {
-    if (!ctx || (!cols && n)) return SB_ERR_INVALID;
-    if (n == 0) return SB_OK;
-    if (mem != SB_MEM_DEVICE) {
-        ctx->last_error = "sb_filter_columns_var: SB_MEM_HOST is not implemented";
-        return SB_ERR_NYI;
-    }
+    int32_t rc;
+    if (!sink_entry(ctx, cols, n, mem, "sb_filter_columns_var", &rc)) return rc;
     std::vector<uint64_t*> results(n);
     for (uint64_t i = 0; i < n; i++) results[i] = &cols[i].rows;   // { rows, selected }
-    const int32_t rc = filter_impl(ctx, cols, results.data(), n);
+    rc = filter_impl(ctx, cols, results.data(), n);
     if (rc == SB_OK && !ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::FILTER_VAR, cols, n, sb_write_options{}, mem});
     return rc;
 }
 
 int32_t sb_filter_columns(sb_ctx* ctx, sb_column_filter* cols, uint64_t n, int32_t mem) {
-    if (!ctx || (!cols && n)) return SB_ERR_INVALID;
-    if (n == 0) return SB_OK;
-    auto refuse = [&](int32_t code, const char* msg) {
-        ctx->last_error = msg;
-        return code;
-    };
-    if (mem != SB_MEM_DEVICE) return refuse(SB_ERR_NYI, "sb_filter_columns: SB_MEM_HOST is not implemented");
+    int32_t rc;
+    if (!sink_entry(ctx, cols, n, mem, "sb_filter_columns", &rc)) return rc;
     // the eight inline literal bytes hold numbers only: everything else this entry point refused before stays refused
     std::vector<sb_column_filter_var> v(n);
     std::vector<uint64_t*> results(n);
     for (uint64_t i = 0; i < n; i++) {
         sb_column_filter& c = cols[i];
-        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(SB_ERR_INVALID, "bad physical_type");
-        if (c.op < SB_PRED_EQ || c.op > SB_PRED_IS_NOT_NULL) return refuse(SB_ERR_INVALID, "bad op");
+        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(ctx, SB_ERR_INVALID, "bad physical_type");
+        if (c.op < SB_PRED_EQ || c.op > SB_PRED_IS_NOT_NULL) return refuse(ctx, SB_ERR_INVALID, "bad op");
         if (c.op < SB_PRED_IS_NULL && !filter_comparable(c.physical_type))
-            return refuse(SB_ERR_NYI, "comparison predicates are implemented for 8- to 64-bit integers and floats");
+            return refuse(ctx, SB_ERR_NYI, "comparison predicates are implemented for 8- to 64-bit integers and floats");
         sb_column_filter_var& d = v[i];
         memset(&d, 0, sizeof d);
         d.physical_type = c.physical_type;
@@ -1572,52 +1639,17 @@ int32_t sb_filter_columns(sb_ctx* ctx, sb_column_filter* cols, uint64_t n, int32
         static_assert(offsetof(sb_column_filter, selected) == offsetof(sb_column_filter, rows) + 8, "{ rows, selected }");
         results[i] = &c.rows;
     }
-    const int32_t rc = filter_impl(ctx, v.data(), results.data(), n);
+    rc = filter_impl(ctx, v.data(), results.data(), n);
     if (rc == SB_OK && !ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::FILTER, cols, n, sb_write_options{}, mem});
     return rc;
 }
 
 // ------------------------------------------------------------------------------------ selected read
-static sb_column_read read_col_of(const sb_column_read_selected& u) {
-    sb_column_read r;
-    memset(&r, 0, sizeof r);
-    r.physical_type = u.physical_type;
-    r.is_nullable = u.is_nullable;
-    r.pages = u.pages;
-    r.pages_len = u.pages_len;
-    r.metas = u.metas;
-    r.n_pages = u.n_pages;
-    r.page_offsets = u.page_offsets;
-    return r;
-}
-
-// The replay of an interval in which a Freq page was met by a call that ends in a sink (KIND_FILTER_FREQ): like
-// filter_columns_decoded, the columns are decoded like a read into the staging area — values, validity, the Freq second
-// pass — and k_rsel_plain compacts them from there with the same sink.
-static int32_t rsel_columns_decoded(sb_ctx* ctx, sb_column_read_selected* cols, std::vector<SelCol>& hs, uint64_t n) {
-    hipStream_t s = ctx->stream;
-    ctx->iv.filter_tmp.emplace_back(n);
-    std::vector<sb_column_read>& rr = ctx->iv.filter_tmp.back();
-    size_t total = 0;
-    std::vector<size_t> o_val(n), o_bits(n);
-    for (uint64_t i = 0; i < n; i++) {
-        o_val[i] = total;
-        total += align_up(cols[i].rows * hs[i].w, 64);
-        o_bits[i] = total;
-        total += align_up((cols[i].rows + 31) / 32 * 4, 64);
-    }
-    if (!ensure(ctx, ctx->filter_stage, total + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
-    for (uint64_t i = 0; i < n; i++) {
-        sb_column_read& r = rr[i] = read_col_of(cols[i]);
-        r.values = ctx->filter_stage.p + o_val[i];
-        r.values_capacity = cols[i].rows * hs[i].w;
-        r.validity = ctx->filter_stage.p + o_bits[i];
-        r.validity_capacity = (cols[i].rows + 31) / 32 * 4;
-    }
-    int32_t rc = read_columns_impl(ctx, rr.data(), n, SB_MEM_DEVICE, ReadMode{ReadMode::READ});
-    if (rc != SB_OK) return rc;
-    if (hipStreamSynchronize(s) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "selected-read replay: synchronize failed");
-    rc = freq_second_pass(ctx);
+// The columns of a replayed call: decoded, and compacted from the staging area by k_rsel_plain with the same sink.
+static int32_t rsel_columns_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pages, const uint64_t* rows, std::vector<SelCol>& hs, void* const* users) {
+    const uint64_t n = pages.size();
+    const sb_column_read* rr = nullptr;
+    int32_t rc = decode_for_replay(ctx, std::move(pages), rows, "selected-read", &rr);
     if (rc != SB_OK) return rc;
     // [SelCol per column][bits set per column][the rank tables]
     size_t off = align_up(n * sizeof(SelCol), 64);
@@ -1626,19 +1658,17 @@ static int32_t rsel_columns_decoded(sb_ctx* ctx, sb_column_read_selected* cols, 
     std::vector<size_t> o_rank(n);
     for (uint64_t i = 0; i < n; i++) {
         o_rank[i] = off;
-        off += align_up(rsel_rank_words(cols[i].rows) * 8, 16);
+        off += align_up(rsel_rank_words(rows[i]) * 8, 16);
     }
     uint8_t* dev = nullptr;
     if (hipMalloc((void**)&dev, off) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(selected-read replay) failed");
     ctx->iv.temp_dev.push_back(dev);
-    std::vector<uint64_t> rows(n);
     std::vector<const uint8_t*> vals(n), bits(n);
     bool any_nullable = false;
     for (uint64_t i = 0; i < n; i++) {
         hs[i].rank = (uint64_t*)(dev + o_rank[i]);
-        rows[i] = cols[i].rows;
         vals[i] = (const uint8_t*)rr[i].values;
-        bits[i] = cols[i].is_nullable ? rr[i].validity : nullptr;
+        bits[i] = rr[i].is_nullable ? rr[i].validity : nullptr;
         if (hs[i].validity) any_nullable = true;
     }
     if (hipMemcpy(dev, hs.data(), n * sizeof(SelCol), hipMemcpyHostToDevice) != hipSuccess)
@@ -1646,21 +1676,8 @@ static int32_t rsel_columns_decoded(sb_ctx* ctx, sb_column_read_selected* cols, 
     StageSlot* slot = acquire_slot(ctx, n * sizeof(uint64_t));
     if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
     uint64_t* d_counts = (uint64_t*)(dev + o_counts);
-    launch_rsel_plain(ctx, (const SelCol*)dev, (uint32_t)n, d_counts, any_nullable, rows.data(), vals.data(), bits.data());
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(slot->host, d_counts, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return check_hip(ctx, e, "selected-read replay");
-    (void)hipEventRecord(slot->done, s);
-    slot->in_flight = true;
-    for (uint64_t i = 0; i < n; i++) {
-        Pending pd;
-        pd.kind = Pending::RSEL_COL;
-        pd.user = &cols[i];
-        pd.host = slot->host + i * sizeof(uint64_t);
-        pd.n = 0;
-        ctx->iv.pending.push_back(pd);
-    }
-    return SB_OK;
+    launch_rsel_plain(ctx, (const SelCol*)dev, (uint32_t)n, d_counts, any_nullable, rows, vals.data(), bits.data());
+    return queue_sink_results(ctx, slot, d_counts, sizeof(uint64_t), n, Pending::RSEL_COL, users, nullptr, "selected-read");
 }
 
 // What sb_read_selected and sb_read_selected_var check of a column's arguments behind their own type checks, and of
@@ -1676,10 +1693,8 @@ struct SelSpans {
 };
 template <class Col>
 static const char* sel_check_column(const Col& c, SelSpans& sp, uint64_t* rows) {
-    if (c.n_pages && !c.metas) return "metas is null";
-    uint64_t r = 0;
-    for (uint64_t p = 0; p < c.n_pages; p++) r += c.metas[p].num_values;
-    *rows = r;
+    if (!column_rows(c, rows)) return "metas is null";
+    const uint64_t r = *rows;
     const uint64_t sel_bytes = (r + 31) / 32 * 4;
     if (r && (!c.selection || ((uintptr_t)c.selection & 3) || c.selection_capacity < sel_bytes))
         return "selection missing, not 4-byte aligned or smaller than 4*ceil(rows/32) bytes";
@@ -1703,33 +1718,29 @@ static const char* sel_check_overlaps(const SelSpans& sp) {
 }   // extern "C++"
 
 int32_t sb_read_selected(sb_ctx* ctx, sb_column_read_selected* cols, uint64_t n, int32_t mem) {
-    if (!ctx || (!cols && n)) return SB_ERR_INVALID;
-    if (n == 0) return SB_OK;
-    // what is refused here is refused before anything is enqueued or written, and does not show again at the synchronize
-    auto refuse = [&](int32_t code, const char* msg) {
-        ctx->last_error = msg;
-        return code;
-    };
-    if (mem != SB_MEM_DEVICE) return refuse(SB_ERR_NYI, "sb_read_selected: SB_MEM_HOST is not implemented");
+    int32_t rc;
+    if (!sink_entry(ctx, cols, n, mem, "sb_read_selected", &rc)) return rc;
     std::vector<uint64_t> rows(n);
     SelSpans sp;
     for (uint64_t i = 0; i < n; i++) {
         const sb_column_read_selected& c = cols[i];
-        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(SB_ERR_INVALID, "bad physical_type");
+        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(ctx, SB_ERR_INVALID, "bad physical_type");
         if (!filter_comparable(c.physical_type))
-            return refuse(SB_ERR_NYI, "sb_read_selected is implemented for 8- to 64-bit integers and floats");
-        if (const char* msg = sel_check_column(c, sp, &rows[i])) return refuse(SB_ERR_INVALID, msg);
+            return refuse(ctx, SB_ERR_NYI, "sb_read_selected is implemented for 8- to 64-bit integers and floats");
+        if (const char* msg = sel_check_column(c, sp, &rows[i])) return refuse(ctx, SB_ERR_INVALID, msg);
     }
-    if (const char* msg = sel_check_overlaps(sp)) return refuse(SB_ERR_INVALID, msg);
+    if (const char* msg = sel_check_overlaps(sp)) return refuse(ctx, SB_ERR_INVALID, msg);
     std::vector<SelCol> hs(n);
-    std::vector<sb_column_read_selected*> users(n);
-    size_t stage = 0;
+    std::vector<sb_column_read> rc_cols(n);
+    std::vector<void*> users(n);
+    std::vector<uint64_t> cap(n);
     for (uint64_t i = 0; i < n; i++) {
         sb_column_read_selected& c = cols[i];
         c.rows = rows[i];
         c.selected = 0;
         c.values_len = 0;
         users[i] = &c;
+        rc_cols[i] = read_col_of(c);
         SelCol& sc = hs[i];
         memset(&sc, 0, sizeof sc);
         sc.w = type_width(c.physical_type);
@@ -1739,26 +1750,17 @@ int32_t sb_read_selected(sb_ctx* ctx, sb_column_read_selected* cols, uint64_t n,
         sc.rows = rows[i];
         sc.cap_rows = c.values ? c.values_capacity / sc.w : 0;
         sc.cap_words = sc.validity ? c.validity_capacity / 4 : 0;
-        stage += align_up(rows[i] * sc.w, 64);
+        cap[i] = rows[i] * sc.w;   // (the share of the staging area a filter comparison column has)
     }
     (void)hipSetDevice(ctx->device);
-    int32_t rc;
     if (ctx->in_replay && ctx->filter_freq) {
-        rc = rsel_columns_decoded(ctx, cols, hs, n);
+        rc = rsel_columns_decoded(ctx, std::move(rc_cols), rows.data(), hs, users.data());
     } else {
-        if (!ensure(ctx, ctx->filter_stage, stage + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
-        // the columns' shares of the staging area, as a filter comparison column has them
-        std::vector<sb_column_read> rc_cols(n);
-        size_t so = 0;
-        for (uint64_t i = 0; i < n; i++) {
-            sb_column_read& r = rc_cols[i] = read_col_of(cols[i]);
-            r.values = ctx->filter_stage.p + so;
-            r.values_capacity = rows[i] * hs[i].w;
-            so += align_up(r.values_capacity, 64);
-        }
+        if ((rc = stage_shares(ctx, rc_cols.data(), cap.data(), n)) != SB_OK) return rc;
         ReadMode mode{ReadMode::SELECTED};
         mode.selc = hs.data();
-        mode.sel_users = users.data();
+        mode.users = users.data();
+        mode.pending_kind = Pending::RSEL_COL;
         rc = read_columns_impl(ctx, rc_cols.data(), n, SB_MEM_DEVICE, mode);
     }
     if (rc == SB_OK && !ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::READ_SEL, cols, n, sb_write_options{}, mem});
@@ -1766,58 +1768,40 @@ int32_t sb_read_selected(sb_ctx* ctx, sb_column_read_selected* cols, uint64_t n,
 }
 
 // ------------------------------------------------------------------------------------ selected read, binary columns
-static sb_column_read read_col_of(const sb_column_read_selected_var& u) {
-    sb_column_read r;
-    memset(&r, 0, sizeof r);
-    r.physical_type = u.physical_type;
-    r.is_nullable = u.is_nullable;
-    r.pages = u.pages;
-    r.pages_len = u.pages_len;
-    r.metas = u.metas;
-    r.n_pages = u.n_pages;
-    r.page_offsets = u.page_offsets;
-    return r;
-}
-
 // The binary columns of a selected read are what the binary columns of a filter call are up to k_plan: a share of the
 // staging area for the inflated value blocks, Freq pages as virtual Dict pages.  So the call never asks for the Freq
 // replay, and in an interval that is replayed for someone else's primitive Freq page (ctx->filter_freq) it takes this
 // same path, as filter_impl does for its binary columns.
 int32_t sb_read_selected_var(sb_ctx* ctx, sb_column_read_selected_var* cols, uint64_t n, int32_t mem) {
-    if (!ctx || (!cols && n)) return SB_ERR_INVALID;
-    if (n == 0) return SB_OK;
-    // what is refused here is refused before anything is enqueued or written, and does not show again at the synchronize
-    auto refuse = [&](int32_t code, const char* msg) {
-        ctx->last_error = msg;
-        return code;
-    };
-    if (mem != SB_MEM_DEVICE) return refuse(SB_ERR_NYI, "sb_read_selected_var: SB_MEM_HOST is not implemented");
+    int32_t rc;
+    if (!sink_entry(ctx, cols, n, mem, "sb_read_selected_var", &rc)) return rc;
     std::vector<uint64_t> rows(n);
     SelSpans sp;
     for (uint64_t i = 0; i < n; i++) {
         const sb_column_read_selected_var& c = cols[i];
-        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(SB_ERR_INVALID, "bad physical_type");
+        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(ctx, SB_ERR_INVALID, "bad physical_type");
         if (!is_binary_t(c.physical_type))
-            return refuse(SB_ERR_NYI, "sb_read_selected_var is implemented for Binary and LargeBinary: numbers go through sb_read_selected");
-        if (const char* msg = sel_check_column(c, sp, &rows[i])) return refuse(SB_ERR_INVALID, msg);
+            return refuse(ctx, SB_ERR_NYI, "sb_read_selected_var is implemented for Binary and LargeBinary: numbers go through sb_read_selected");
+        if (const char* msg = sel_check_column(c, sp, &rows[i])) return refuse(ctx, SB_ERR_INVALID, msg);
         const uint32_t osize = type_width(c.physical_type);
         // (offsets[0] is written by every accepted call, so a buffer without room for it counts as missing)
         if (!c.offsets || ((uintptr_t)c.offsets & (osize - 1)) || c.offsets_capacity < osize)
-            return refuse(SB_ERR_INVALID, "offsets missing, not aligned to its entries or smaller than one entry");
+            return refuse(ctx, SB_ERR_INVALID, "offsets missing, not aligned to its entries or smaller than one entry");
         sp.outs.push_back({(const uint8_t*)c.offsets, c.offsets_capacity});
     }
-    if (const char* msg = sel_check_overlaps(sp)) return refuse(SB_ERR_INVALID, msg);
+    if (const char* msg = sel_check_overlaps(sp)) return refuse(ctx, SB_ERR_INVALID, msg);
     std::vector<SelCol> hs(n);
     std::vector<SelBin> hb(n);
-    std::vector<sb_column_read_selected_var*> users(n);
-    std::vector<uint64_t> stage_cap(n);
-    size_t stage = 0;
+    std::vector<sb_column_read> rc_cols(n);
+    std::vector<void*> users(n);
+    std::vector<uint64_t> cap(n);
     for (uint64_t i = 0; i < n; i++) {
         sb_column_read_selected_var& c = cols[i];
         c.rows = rows[i];
         c.selected = 0;
         c.values_len = 0;
         users[i] = &c;
+        rc_cols[i] = read_col_of(c);
         SelCol& sc = hs[i];
         memset(&sc, 0, sizeof sc);
         sc.w = type_width(c.physical_type);
@@ -1832,70 +1816,66 @@ int32_t sb_read_selected_var(sb_ctx* ctx, sb_column_read_selected_var* cols, uin
         bc.offsets = (uint8_t*)c.offsets;
         bc.values_cap = c.values ? c.values_capacity : 0;
         bc.osize = sc.w;
-        stage_cap[i] = c.stage_capacity ? c.stage_capacity : 4 * c.pages_len;   // (the caller's field stays as given: a replay reads it again)
-        stage += align_up(stage_cap[i], 64);
+        // the share of the staging area a binary filter column has (the caller's field stays as given: a replay reads it again)
+        cap[i] = c.stage_capacity ? c.stage_capacity : 4 * c.pages_len;
     }
     (void)hipSetDevice(ctx->device);
-    if (!ensure(ctx, ctx->filter_stage, stage + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
-    // the columns' shares of the staging area, as a binary filter column has them
-    std::vector<sb_column_read> rc_cols(n);
-    size_t so = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        sb_column_read& r = rc_cols[i] = read_col_of(cols[i]);
-        r.values = ctx->filter_stage.p + so;
-        r.values_capacity = stage_cap[i];
-        so += align_up(stage_cap[i], 64);
-    }
+    if ((rc = stage_shares(ctx, rc_cols.data(), cap.data(), n)) != SB_OK) return rc;
     ReadMode mode{ReadMode::SELECTED_VAR};
     mode.selc = hs.data();
     mode.selb = hb.data();
-    mode.selv_users = users.data();
-    const int32_t rc = read_columns_impl(ctx, rc_cols.data(), n, SB_MEM_DEVICE, mode);
+    mode.users = users.data();
+    mode.pending_kind = Pending::RSEL_VAR_COL;
+    rc = read_columns_impl(ctx, rc_cols.data(), n, SB_MEM_DEVICE, mode);
     if (rc == SB_OK && !ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::READ_SEL_VAR, cols, n, sb_write_options{}, mem});
     return rc;
 }
 
 // ------------------------------------------------------------------------------------ aggregate
-static sb_column_read read_col_of(const sb_column_aggregate& u) {
-    sb_column_read r;
-    memset(&r, 0, sizeof r);
-    r.physical_type = u.physical_type;
-    r.is_nullable = u.is_nullable;
-    r.pages = u.pages;
-    r.pages_len = u.pages_len;
-    r.metas = u.metas;
-    r.n_pages = u.n_pages;
-    r.page_offsets = u.page_offsets;
-    return r;
+extern "C++" {
+// What both aggregate entry points check of a column, in two steps (sb_aggregate_grouped checks its group fields behind
+// each), and the column's AggCol
+template <class Col>
+static int32_t agg_check_ops(sb_ctx* ctx, const Col& c) {
+    if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(ctx, SB_ERR_INVALID, "bad physical_type");
+    if (c.ops & ~(SB_AGG_COUNT | SB_AGG_MIN | SB_AGG_MAX | SB_AGG_SUM)) return refuse(ctx, SB_ERR_INVALID, "unknown ops bits");
+    if (c.reserved) return refuse(ctx, SB_ERR_INVALID, "reserved is not 0");
+    return SB_OK;
+}
+template <class Col>
+static int32_t agg_check_fill(sb_ctx* ctx, const Col& c, AggCol& g) {
+    if ((c.ops & AGG_VALUE_OPS) && !filter_comparable(c.physical_type))
+        return refuse(ctx, SB_ERR_NYI, "min / max / sum are implemented for 8- to 64-bit integers and floats");
+    uint64_t rows = 0;
+    if (!column_rows(c, &rows)) return refuse(ctx, SB_ERR_INVALID, "metas is null");
+    if (c.selection && (((uintptr_t)c.selection & 3) || c.selection_capacity < (rows + 31) / 32 * 4))
+        return refuse(ctx, SB_ERR_INVALID, "selection not 4-byte aligned or smaller than 4*ceil(rows/32) bytes");
+    memset(&g, 0, sizeof g);
+    g.sel = (const uint32_t*)c.selection;
+    g.rows = rows;
+    g.ops = c.ops;
+    g.ptype = c.physical_type;
+    g.w = type_width(c.physical_type);
+    g.kind = value_kind(c.physical_type);
+    return SB_OK;
+}
+}   // extern "C++"
+
+// the share of the staging area a filter comparison column has; none for a column without a value op
+static std::vector<uint64_t> agg_stage_caps(const std::vector<AggCol>& hs) {
+    std::vector<uint64_t> cap(hs.size());
+    for (size_t i = 0; i < hs.size(); i++) cap[i] = (hs[i].ops & AGG_VALUE_OPS) ? hs[i].rows * hs[i].w : NO_SHARE;
+    return cap;
 }
 
-// The replay of an interval in which a Freq page was met by a call that ends in a sink (KIND_FILTER_FREQ): the sibling of
-// rsel_columns_decoded.  The columns with a value op are decoded like a read into the staging area — values, validity, the
-// Freq second pass — and k_agg_plain reduces them from there with the same sink: a slot per TILE_ROWS rows.
-static int32_t agg_columns_decoded(sb_ctx* ctx, sb_column_aggregate* const* users, std::vector<AggCol>& hs, uint64_t n) {
-    hipStream_t s = ctx->stream;
-    ctx->iv.filter_tmp.emplace_back(n);
-    std::vector<sb_column_read>& rr = ctx->iv.filter_tmp.back();
-    size_t total = 0;
-    std::vector<size_t> o_val(n), o_bits(n);
-    for (uint64_t i = 0; i < n; i++) {
-        o_val[i] = total;
-        total += align_up(hs[i].rows * hs[i].w, 64);
-        o_bits[i] = total;
-        total += align_up((hs[i].rows + 31) / 32 * 4, 64);
-    }
-    if (!ensure(ctx, ctx->filter_stage, total + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
-    for (uint64_t i = 0; i < n; i++) {
-        sb_column_read& r = rr[i] = read_col_of(*users[i]);
-        r.values = ctx->filter_stage.p + o_val[i];
-        r.values_capacity = hs[i].rows * hs[i].w;
-        r.validity = ctx->filter_stage.p + o_bits[i];
-        r.validity_capacity = (hs[i].rows + 31) / 32 * 4;
-    }
-    int32_t rc = read_columns_impl(ctx, rr.data(), n, SB_MEM_DEVICE, ReadMode{ReadMode::READ});
-    if (rc != SB_OK) return rc;
-    if (hipStreamSynchronize(s) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "aggregate replay: synchronize failed");
-    rc = freq_second_pass(ctx);
+// The columns with a value op of a replayed call: decoded, and reduced from the staging area by k_agg_plain with the same
+// sink: a slot per TILE_ROWS rows.
+static int32_t agg_columns_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pages, std::vector<AggCol>& hs, void* const* users) {
+    const uint64_t n = pages.size();
+    std::vector<uint64_t> rows(n);
+    for (uint64_t i = 0; i < n; i++) rows[i] = hs[i].rows;
+    const sb_column_read* rr = nullptr;
+    int32_t rc = decode_for_replay(ctx, std::move(pages), rows.data(), "aggregate", &rr);
     if (rc != SB_OK) return rc;
     // [AggCol per column][the result records][the partial records: a slot per TILE_ROWS rows]
     size_t off = align_up(n * sizeof(AggCol), 64);
@@ -1903,12 +1883,10 @@ static int32_t agg_columns_decoded(sb_ctx* ctx, sb_column_aggregate* const* user
     off = align_up(off + n * AGG_RESULT_WORDS * sizeof(uint64_t), 64);
     const size_t o_parts = off;
     uint64_t slots = 0;
-    std::vector<uint64_t> rows(n);
     std::vector<const uint8_t*> vals(n), bits(n);
     for (uint64_t i = 0; i < n; i++) {
-        rows[i] = hs[i].rows;
         vals[i] = (const uint8_t*)rr[i].values;
-        bits[i] = users[i]->is_nullable ? rr[i].validity : nullptr;
+        bits[i] = rr[i].is_nullable ? rr[i].validity : nullptr;
         hs[i].page_slot0 = hs[i].page_slots = 0;
         hs[i].tile_slot0 = slots;
         hs[i].tile_slots = (rows[i] + TILE_ROWS - 1) / TILE_ROWS;
@@ -1925,99 +1903,43 @@ static int32_t agg_columns_decoded(sb_ctx* ctx, sb_column_aggregate* const* user
     uint64_t* d_res = (uint64_t*)(dev + o_res);
     launch_agg_plain(ctx, (const AggCol*)dev, (uint32_t)n, (AggPart*)(dev + o_parts), rows.data(), vals.data(), bits.data());
     launch_agg_finish(ctx, (const AggCol*)dev, (const AggPart*)(dev + o_parts), d_res, (uint32_t)n);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(slot->host, d_res, n * AGG_RESULT_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return check_hip(ctx, e, "aggregate replay");
-    (void)hipEventRecord(slot->done, s);
-    slot->in_flight = true;
-    for (uint64_t i = 0; i < n; i++) {
-        Pending pd;
-        pd.kind = Pending::AGG_COL;
-        pd.user = users[i];
-        pd.host = slot->host + i * AGG_RESULT_WORDS * sizeof(uint64_t);
-        pd.n = 0;
-        ctx->iv.pending.push_back(pd);
-    }
-    return SB_OK;
+    return queue_sink_results(ctx, slot, d_res, AGG_RESULT_WORDS * sizeof(uint64_t), n, Pending::AGG_COL, users, nullptr, "aggregate");
 }
 
 int32_t sb_aggregate_columns(sb_ctx* ctx, sb_column_aggregate* cols, uint64_t n, int32_t mem) {
-    if (!ctx || (!cols && n)) return SB_ERR_INVALID;
-    if (n == 0) return SB_OK;
-    // what is refused here is refused before anything is enqueued or written, and does not show again at the synchronize
-    auto refuse = [&](int32_t code, const char* msg) {
-        ctx->last_error = msg;
-        return code;
-    };
-    if (mem != SB_MEM_DEVICE) return refuse(SB_ERR_NYI, "sb_aggregate_columns: SB_MEM_HOST is not implemented");
+    int32_t rc;
+    if (!sink_entry(ctx, cols, n, mem, "sb_aggregate_columns", &rc)) return rc;
     std::vector<AggCol> hs(n);
-    for (uint64_t i = 0; i < n; i++) {
-        const sb_column_aggregate& c = cols[i];
-        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(SB_ERR_INVALID, "bad physical_type");
-        if (c.ops & ~(SB_AGG_COUNT | SB_AGG_MIN | SB_AGG_MAX | SB_AGG_SUM)) return refuse(SB_ERR_INVALID, "unknown ops bits");
-        if (c.reserved) return refuse(SB_ERR_INVALID, "reserved is not 0");
-        if ((c.ops & AGG_VALUE_OPS) && !filter_comparable(c.physical_type))
-            return refuse(SB_ERR_NYI, "min / max / sum are implemented for 8- to 64-bit integers and floats");
-        if (c.n_pages && !c.metas) return refuse(SB_ERR_INVALID, "metas is null");
-        uint64_t rows = 0;
-        for (uint64_t p = 0; p < c.n_pages; p++) rows += c.metas[p].num_values;
-        if (c.selection && (((uintptr_t)c.selection & 3) || c.selection_capacity < (rows + 31) / 32 * 4))
-            return refuse(SB_ERR_INVALID, "selection not 4-byte aligned or smaller than 4*ceil(rows/32) bytes");
-        AggCol& g = hs[i];
-        memset(&g, 0, sizeof g);
-        g.sel = (const uint32_t*)c.selection;
-        g.rows = rows;
-        g.ops = c.ops;
-        g.ptype = c.physical_type;
-        g.w = type_width(c.physical_type);
-        g.kind = c.physical_type == SB_TYPE_FLOAT32 ? FK_F32 : c.physical_type == SB_TYPE_FLOAT64 ? FK_F64 : c.physical_type <= SB_TYPE_INT64 ? FK_SIGNED : FK_UNSIGNED;
-    }
+    for (uint64_t i = 0; i < n; i++)
+        if ((rc = agg_check_ops(ctx, cols[i])) != SB_OK || (rc = agg_check_fill(ctx, cols[i], hs[i])) != SB_OK) return rc;
     (void)hipSetDevice(ctx->device);
-    std::vector<sb_column_aggregate*> users(n);
-    for (uint64_t i = 0; i < n; i++) users[i] = &cols[i];
-    int32_t rc = SB_OK;
+    std::vector<sb_column_read> rc_cols(n);
+    std::vector<void*> users(n);
+    for (uint64_t i = 0; i < n; i++) {
+        rc_cols[i] = read_col_of(cols[i]);
+        users[i] = &cols[i];
+    }
     if (ctx->in_replay && ctx->filter_freq) {
         // the columns without a value op as ever (no page body is looked at); the others through a full decode
-        std::vector<sb_column_aggregate*> u_val, u_rest;
-        std::vector<AggCol> g_val, g_rest;
-        for (uint64_t i = 0; i < n; i++) {
-            const bool dec = (hs[i].ops & AGG_VALUE_OPS) != 0;
-            (dec ? u_val : u_rest).push_back(users[i]);
-            (dec ? g_val : g_rest).push_back(hs[i]);
-        }
-        if (!u_val.empty()) rc = agg_columns_decoded(ctx, u_val.data(), g_val, u_val.size());
-        users.swap(u_rest);
-        hs.swap(g_rest);
+        std::vector<bool> dec(n);
+        for (uint64_t i = 0; i < n; i++) dec[i] = (hs[i].ops & AGG_VALUE_OPS) != 0;
+        std::vector<sb_column_read> r_val = take_if(rc_cols, dec);
+        std::vector<AggCol> g_val = take_if(hs, dec);
+        const std::vector<void*> u_val = take_if(users, dec);
+        if (!r_val.empty()) rc = agg_columns_decoded(ctx, std::move(r_val), g_val, u_val.data());
     }
-    if (rc == SB_OK && !users.empty()) {
-        const uint64_t m = users.size();
-        size_t stage = 0;
-        for (uint64_t i = 0; i < m; i++)
-            if (hs[i].ops & AGG_VALUE_OPS) stage += align_up(hs[i].rows * hs[i].w, 64);
-        if (!ensure(ctx, ctx->filter_stage, stage + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
-        // the columns' shares of the staging area, as a filter comparison column has them
-        std::vector<sb_column_read> rc_cols(m);
-        size_t so = 0;
-        for (uint64_t i = 0; i < m; i++) {
-            sb_column_read& r = rc_cols[i] = read_col_of(*users[i]);
-            if (!(hs[i].ops & AGG_VALUE_OPS)) {
-                r.physical_type = SB_TYPE_NULL;   // (no page body is parsed, queued or planned for a count)
-                continue;
-            }
-            r.values = ctx->filter_stage.p + so;
-            r.values_capacity = hs[i].rows * hs[i].w;
-            so += align_up(r.values_capacity, 64);
-        }
+    if (rc == SB_OK && !rc_cols.empty()) {
+        if ((rc = stage_shares(ctx, rc_cols.data(), agg_stage_caps(hs).data(), rc_cols.size())) != SB_OK) return rc;
         ReadMode mode{ReadMode::AGGREGATE};
         mode.aggc = hs.data();
-        mode.agg_users = users.data();
-        rc = read_columns_impl(ctx, rc_cols.data(), m, SB_MEM_DEVICE, mode);
+        mode.users = users.data();
+        mode.pending_kind = Pending::AGG_COL;
+        rc = read_columns_impl(ctx, rc_cols.data(), rc_cols.size(), SB_MEM_DEVICE, mode);
     }
     if (rc != SB_OK) return rc;
     for (uint64_t i = 0; i < n; i++) {   // (after the last thing that can refuse the call: a page outside pages_len)
         sb_column_aggregate& c = cols[i];
-        c.rows = 0;
-        for (uint64_t p = 0; p < c.n_pages; p++) c.rows += c.metas[p].num_values;
+        column_rows(c, &c.rows);
         c.selected = c.count = c.nans = c.sum_lo = c.sum_hi = 0;
         memset(c.min, 0, sizeof c.min);
         memset(c.max, 0, sizeof c.max);
@@ -2027,68 +1949,35 @@ int32_t sb_aggregate_columns(sb_ctx* ctx, sb_column_aggregate* cols, uint64_t n,
 }
 
 // ------------------------------------------------------------------------------------ aggregate, grouped
-static sb_column_read read_col_of(const sb_column_aggregate_grouped& u) {
-    sb_column_read r;
-    memset(&r, 0, sizeof r);
-    r.physical_type = u.physical_type;
-    r.is_nullable = u.is_nullable;
-    r.pages = u.pages;
-    r.pages_len = u.pages_len;
-    r.metas = u.metas;
-    r.n_pages = u.n_pages;
-    r.page_offsets = u.page_offsets;
-    return r;
-}
-
-// The sibling of agg_columns_decoded: the columns with a value op decoded like a read into the staging area, reduced from
-// there by k_grp_plain into a slot per TILE_ROWS rows, combined by k_grp_finish.
-static int32_t grp_columns_decoded(sb_ctx* ctx, sb_column_aggregate_grouped* const* users, std::vector<AggCol>& hs, const std::vector<GrpCol>& hg,
-                                   uint64_t n) {
-    hipStream_t s = ctx->stream;
-    ctx->iv.filter_tmp.emplace_back(n);
-    std::vector<sb_column_read>& rr = ctx->iv.filter_tmp.back();
-    size_t total = 0;
-    std::vector<size_t> o_val(n), o_bits(n);
-    for (uint64_t i = 0; i < n; i++) {
-        o_val[i] = total;
-        total += align_up(hs[i].rows * hs[i].w, 64);
-        o_bits[i] = total;
-        total += align_up((hs[i].rows + 31) / 32 * 4, 64);
-    }
-    if (!ensure(ctx, ctx->filter_stage, total + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
-    for (uint64_t i = 0; i < n; i++) {
-        sb_column_read& r = rr[i] = read_col_of(*users[i]);
-        r.values = ctx->filter_stage.p + o_val[i];
-        r.values_capacity = hs[i].rows * hs[i].w;
-        r.validity = ctx->filter_stage.p + o_bits[i];
-        r.validity_capacity = (hs[i].rows + 31) / 32 * 4;
-    }
-    int32_t rc = read_columns_impl(ctx, rr.data(), n, SB_MEM_DEVICE, ReadMode{ReadMode::READ});
-    if (rc != SB_OK) return rc;
-    if (hipStreamSynchronize(s) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "grouped aggregate replay: synchronize failed");
-    rc = freq_second_pass(ctx);
+// The sibling of agg_columns_decoded: reduced from the staging area by k_grp_plain into a slot per TILE_ROWS rows, combined
+// by k_grp_finish.
+static int32_t grp_columns_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pages, std::vector<AggCol>& hs, const std::vector<GrpCol>& hg,
+                                   void* const* users) {
+    const uint64_t n = pages.size();
+    std::vector<uint64_t> rows(n);
+    for (uint64_t i = 0; i < n; i++) rows[i] = hs[i].rows;
+    const sb_column_read* rr = nullptr;
+    int32_t rc = decode_for_replay(ctx, std::move(pages), rows.data(), "grouped aggregate", &rr);
     if (rc != SB_OK) return rc;
     uint32_t gmax = 1;
     uint64_t slots = 0;
-    std::vector<uint64_t> rows(n);
     std::vector<const uint8_t*> vals(n), bits(n);
     for (uint64_t i = 0; i < n; i++) {
         gmax = std::max(gmax, hg[i].n_groups);
-        rows[i] = hs[i].rows;
         vals[i] = (const uint8_t*)rr[i].values;
-        bits[i] = users[i]->is_nullable ? rr[i].validity : nullptr;
+        bits[i] = rr[i].is_nullable ? rr[i].validity : nullptr;
         hs[i].page_slot0 = hs[i].page_slots = 0;
         hs[i].tile_slot0 = slots;
         hs[i].tile_slots = (rows[i] + TILE_ROWS - 1) / TILE_ROWS;
         slots += hs[i].tile_slots;
     }
     // [AggCol per column][GrpCol per column][the results][the slots' flags, the columns' counters and Freq marks][the slots' records]
-    const size_t res_bytes = n * grp_result_words(gmax) * sizeof(uint64_t);
+    const size_t res_stride = grp_result_words(gmax) * sizeof(uint64_t);
     size_t off = align_up(n * sizeof(AggCol), 64);
     const size_t o_gc = off;
     off = align_up(off + n * sizeof(GrpCol), 64);
     const size_t o_res = off;
-    off = align_up(off + res_bytes, 64);
+    off = align_up(off + n * res_stride, 64);
     const size_t o_flags = off;
     off = align_up(off + (size_t)(slots + 2 * n) * sizeof(uint64_t), 64);
     const size_t o_recs = off;
@@ -2099,127 +1988,75 @@ static int32_t grp_columns_decoded(sb_ctx* ctx, sb_column_aggregate_grouped* con
     if (hipMemcpy(dev, hs.data(), n * sizeof(AggCol), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(dev + o_gc, hg.data(), n * sizeof(GrpCol), hipMemcpyHostToDevice) != hipSuccess)
         return ctx->fail(SB_ERR_EXTERNAL, "grouped aggregate replay: upload failed");
-    StageSlot* slot = acquire_slot(ctx, res_bytes);
+    StageSlot* slot = acquire_slot(ctx, n * res_stride);
     if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
     uint64_t* d_res = (uint64_t*)(dev + o_res);
     GrpLaunch gl{(const AggCol*)dev, (const GrpCol*)(dev + o_gc), (uint64_t*)(dev + o_flags), (GrpPart*)(dev + o_recs), slots, 0, gmax, true, false, (uint32_t)n, true};
     launch_grp_zero(ctx, gl, (uint32_t)n);
     launch_grp_plain(ctx, gl, (uint32_t)n, rows.data(), vals.data(), bits.data());
     launch_grp_finish(ctx, gl, d_res, (uint32_t)n);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(slot->host, d_res, res_bytes, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return check_hip(ctx, e, "grouped aggregate replay");
-    (void)hipEventRecord(slot->done, s);
-    slot->in_flight = true;
-    for (uint64_t i = 0; i < n; i++) {
-        Pending pd;
-        pd.kind = Pending::AGG_GRP_COL;
-        pd.user = users[i];
-        pd.host = slot->host + i * grp_result_words(gmax) * sizeof(uint64_t);
-        pd.n = 0;
-        pd.bytes = sizeof(uint64_t) * grp_result_words(hg[i].n_groups);
-        ctx->iv.pending.push_back(pd);
-    }
-    return SB_OK;
+    return queue_sink_results(ctx, slot, d_res, res_stride, n, Pending::AGG_GRP_COL, users, hg.data(), "grouped aggregate");
 }
 
 int32_t sb_aggregate_grouped(sb_ctx* ctx, sb_column_aggregate_grouped* cols, uint64_t n, int32_t mem) {
-    if (!ctx || (!cols && n)) return SB_ERR_INVALID;
-    if (n == 0) return SB_OK;
-    // what is refused here is refused before anything is enqueued or written, and does not show again at the synchronize
-    auto refuse = [&](int32_t code, const char* msg) {
-        ctx->last_error = msg;
-        return code;
-    };
-    if (mem != SB_MEM_DEVICE) return refuse(SB_ERR_NYI, "sb_aggregate_grouped: SB_MEM_HOST is not implemented");
+    int32_t rc;
+    if (!sink_entry(ctx, cols, n, mem, "sb_aggregate_grouped", &rc)) return rc;
     std::vector<AggCol> hs(n);
     std::vector<GrpCol> hg(n);
     for (uint64_t i = 0; i < n; i++) {
         const sb_column_aggregate_grouped& c = cols[i];
-        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(SB_ERR_INVALID, "bad physical_type");
-        if (c.ops & ~(SB_AGG_COUNT | SB_AGG_MIN | SB_AGG_MAX | SB_AGG_SUM)) return refuse(SB_ERR_INVALID, "unknown ops bits");
-        if (c.reserved) return refuse(SB_ERR_INVALID, "reserved is not 0");
-        if (c.n_groups == 0 || c.n_groups > SB_AGG_MAX_GROUPS) return refuse(SB_ERR_INVALID, "n_groups is not in 1 .. SB_AGG_MAX_GROUPS");
-        if (c.group_id_width != 1 && c.group_id_width != 2 && c.group_id_width != 4) return refuse(SB_ERR_INVALID, "group_id_width is not 1, 2 or 4");
-        if (!c.groups) return refuse(SB_ERR_INVALID, "groups is null");
-        if ((c.ops & AGG_VALUE_OPS) && !filter_comparable(c.physical_type))
-            return refuse(SB_ERR_NYI, "min / max / sum are implemented for 8- to 64-bit integers and floats");
-        if (c.n_pages && !c.metas) return refuse(SB_ERR_INVALID, "metas is null");
-        uint64_t rows = 0;
-        for (uint64_t p = 0; p < c.n_pages; p++) rows += c.metas[p].num_values;
-        if (c.selection && (((uintptr_t)c.selection & 3) || c.selection_capacity < (rows + 31) / 32 * 4))
-            return refuse(SB_ERR_INVALID, "selection not 4-byte aligned or smaller than 4*ceil(rows/32) bytes");
-        if (rows && !c.group_ids) return refuse(SB_ERR_INVALID, "group_ids is null");
+        if ((rc = agg_check_ops(ctx, c)) != SB_OK) return rc;
+        if (c.n_groups == 0 || c.n_groups > SB_AGG_MAX_GROUPS) return refuse(ctx, SB_ERR_INVALID, "n_groups is not in 1 .. SB_AGG_MAX_GROUPS");
+        if (c.group_id_width != 1 && c.group_id_width != 2 && c.group_id_width != 4) return refuse(ctx, SB_ERR_INVALID, "group_id_width is not 1, 2 or 4");
+        if (!c.groups) return refuse(ctx, SB_ERR_INVALID, "groups is null");
+        if ((rc = agg_check_fill(ctx, c, hs[i])) != SB_OK) return rc;
+        const uint64_t rows = hs[i].rows;
+        if (rows && !c.group_ids) return refuse(ctx, SB_ERR_INVALID, "group_ids is null");
         if (c.group_ids && (((uintptr_t)c.group_ids & (c.group_id_width - 1)) || c.group_ids_capacity < rows * c.group_id_width))
-            return refuse(SB_ERR_INVALID, "group_ids not aligned to group_id_width or smaller than rows * group_id_width bytes");
-        AggCol& g = hs[i];
-        memset(&g, 0, sizeof g);
-        g.sel = (const uint32_t*)c.selection;
-        g.rows = rows;
-        g.ops = c.ops;
-        g.ptype = c.physical_type;
-        g.w = type_width(c.physical_type);
-        g.kind = c.physical_type == SB_TYPE_FLOAT32 ? FK_F32 : c.physical_type == SB_TYPE_FLOAT64 ? FK_F64 : c.physical_type <= SB_TYPE_INT64 ? FK_SIGNED : FK_UNSIGNED;
+            return refuse(ctx, SB_ERR_INVALID, "group_ids not aligned to group_id_width or smaller than rows * group_id_width bytes");
         hg[i] = GrpCol{(const uint8_t*)c.group_ids, c.group_id_width, c.n_groups};
     }
     (void)hipSetDevice(ctx->device);
-    std::vector<sb_column_aggregate_grouped*> users(n);
-    for (uint64_t i = 0; i < n; i++) users[i] = &cols[i];
-    int32_t rc = SB_OK;
+    std::vector<sb_column_read> rc_cols(n);
+    std::vector<void*> users(n);
+    for (uint64_t i = 0; i < n; i++) {
+        rc_cols[i] = read_col_of(cols[i]);
+        users[i] = &cols[i];
+    }
     if (ctx->in_replay && ctx->filter_freq) {
         // The columns that met a Freq page in the first pass (and so asked for this replay, or would have) through a full
         // decode; the others as ever, on the page route, whose slots -- and float bits -- are those of an interval that is
         // not replayed.
-        std::vector<sb_column_aggregate_grouped*> u_val, u_rest;
-        std::vector<AggCol> g_val, g_rest;
-        std::vector<GrpCol> c_val, c_rest;
-        for (uint64_t i = 0; i < n; i++) {
-            const bool dec = (hs[i].ops & AGG_VALUE_OPS) != 0 &&
-                             std::find(ctx->grp_freq_users.begin(), ctx->grp_freq_users.end(), (const void*)users[i]) != ctx->grp_freq_users.end();
-            (dec ? u_val : u_rest).push_back(users[i]);
-            (dec ? g_val : g_rest).push_back(hs[i]);
-            (dec ? c_val : c_rest).push_back(hg[i]);
-        }
-        if (!u_val.empty()) rc = grp_columns_decoded(ctx, u_val.data(), g_val, c_val, u_val.size());
-        users.swap(u_rest);
-        hs.swap(g_rest);
-        hg.swap(c_rest);
+        std::vector<bool> dec(n);
+        for (uint64_t i = 0; i < n; i++)
+            dec[i] = (hs[i].ops & AGG_VALUE_OPS) != 0 &&
+                     std::find(ctx->grp_freq_users.begin(), ctx->grp_freq_users.end(), (const void*)users[i]) != ctx->grp_freq_users.end();
+        std::vector<sb_column_read> r_val = take_if(rc_cols, dec);
+        std::vector<AggCol> g_val = take_if(hs, dec);
+        const std::vector<GrpCol> c_val = take_if(hg, dec);
+        const std::vector<void*> u_val = take_if(users, dec);
+        if (!r_val.empty()) rc = grp_columns_decoded(ctx, std::move(r_val), g_val, c_val, u_val.data());
     }
-    if (rc == SB_OK && !users.empty()) {
-        const uint64_t m = users.size();
-        size_t stage = 0;
-        for (uint64_t i = 0; i < m; i++)
-            if (hs[i].ops & AGG_VALUE_OPS) stage += align_up(hs[i].rows * hs[i].w, 64);
-        if (!ensure(ctx, ctx->filter_stage, stage + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter staging) failed");
-        std::vector<sb_column_read> rc_cols(m);
-        size_t so = 0;
+    if (rc == SB_OK && !rc_cols.empty()) {
+        if ((rc = stage_shares(ctx, rc_cols.data(), agg_stage_caps(hs).data(), rc_cols.size())) != SB_OK) return rc;
         ReadMode mode{ReadMode::AGG_GROUPED};
-        for (uint64_t i = 0; i < m; i++) {
-            mode.grp_gmax = std::max(mode.grp_gmax, hg[i].n_groups);
-            sb_column_read& r = rc_cols[i] = read_col_of(*users[i]);
-            if (!(hs[i].ops & AGG_VALUE_OPS)) {
-                r.physical_type = SB_TYPE_NULL;   // (no page body is parsed, queued or planned for a count)
-                continue;
-            }
-            r.values = ctx->filter_stage.p + so;
-            r.values_capacity = hs[i].rows * hs[i].w;
-            so += align_up(r.values_capacity, 64);
-        }
+        for (const GrpCol& g : hg) mode.grp_gmax = std::max(mode.grp_gmax, g.n_groups);
         mode.aggc = hs.data();
         mode.grpc = hg.data();
-        mode.grp_users = users.data();
-        rc = read_columns_impl(ctx, rc_cols.data(), m, SB_MEM_DEVICE, mode);
+        mode.users = users.data();
+        mode.pending_kind = Pending::AGG_GRP_COL;
+        rc = read_columns_impl(ctx, rc_cols.data(), rc_cols.size(), SB_MEM_DEVICE, mode);
     }
     if (rc != SB_OK) return rc;
     for (uint64_t i = 0; i < n; i++) {   // (after the last thing that can refuse the call: a page outside pages_len)
         sb_column_aggregate_grouped& c = cols[i];
-        c.rows = 0;
-        for (uint64_t p = 0; p < c.n_pages; p++) c.rows += c.metas[p].num_values;
+        column_rows(c, &c.rows);
         c.selected = c.out_of_range = 0;
     }
     if (!ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::AGG_GROUPED, cols, n, sb_write_options{}, mem});
     return rc;
 }
+
 
 // The call synchronizes, and the interval it closes may hold earlier calls of which one asks for a replay: the replay
 // drops every pending result and issues the recorded calls again, so the sizes call is recorded with them (its
