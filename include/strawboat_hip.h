@@ -254,6 +254,60 @@ typedef struct sb_column_filter_var {
 
 int32_t sb_filter_columns_var(sb_ctx* ctx, sb_column_filter_var* cols, uint64_t n, int32_t mem);
 
+/* Set membership: `WHERE c IN (v0, v1, ...)` / `NOT IN` with up to SB_IN_MAX_VALUES literals per column, evaluated on the
+ * pages in ONE walk of them (n chained EQ / OR calls walk and inflate them n times).  A non-null row satisfies IN when
+ * its value equals at least one literal and NOT_IN when it equals none; a null row satisfies neither.
+ *
+ * Numbers (INT8..INT64, UINT8..UINT64, FLOAT32, FLOAT64) compare as SB_PRED_EQ does: signedness from the physical type,
+ * floats as IEEE 754 (-0.0 matches 0.0 either way round; a NaN row is in no list and so satisfies NOT_IN; a NaN literal
+ * is accepted and matches nothing).  Binary / LargeBinary values compare as byte strings, as SB_PRED_EQ of
+ * sb_filter_columns_var; the empty string is a literal like any other.  The literals may come in any order and repeat.
+ * n_values == 0: IN selects nothing, NOT_IN every non-null row; `values` may be null then.
+ * The list is searched once per run of an RLE page, per entry of a Dict page (strings included), per OneValue page and
+ * per row of every other page.
+ *
+ * combine, `rows` / `selected`, the zero bits behind `rows` after SET, page errors (the decoder's codes, at the
+ * synchronize), page_offsets, stage_capacity, replays and the rule that two columns of one call may not share a selection
+ * are those of sb_filter_columns_var.  Numeric and binary columns may share a call.  `values` and `value_offsets` must
+ * stay valid and unmodified until sb_ctx_synchronize: a replay reads them again.
+ *
+ * Refused at the call (nothing enqueued, no selection touched): Boolean / Int128 / Int256 / Null columns, SB_MEM_HOST
+ * (SB_ERR_NYI); an op other than IN / NOT_IN, n_values > SB_IN_MAX_VALUES, `values` null with literal bytes to read,
+ * value_offsets on a numeric column, no value_offsets on a binary column with n_values > 0, offsets that do not start
+ * at 0 or that descend, more than 2^30 literal bytes, the selection refusals of sb_filter_columns (SB_ERR_INVALID); a
+ * page outside [0, pages_len) (SB_ERR_IO).
+ *
+ * Offsets: physical_type 0, is_nullable 4, pages 8, pages_len 16, metas 24, n_pages 32, page_offsets 40, op 48,
+ * combine 52, values 56, value_offsets 64, n_values 72, selection 80, selection_capacity 88, stage_capacity 96, rows 104,
+ * selected 112. */
+#define SB_PRED_IN 9
+#define SB_PRED_NOT_IN 10
+#define SB_IN_MAX_VALUES 1024u
+
+typedef struct sb_column_filter_in {
+    int32_t physical_type;   /* SB_TYPE_* */
+    int32_t is_nullable;
+    const uint8_t* pages;    /* DEVICE, at any byte alignment */
+    uint64_t pages_len;
+    const sb_page_meta* metas; /* HOST */
+    uint64_t n_pages;
+    const uint64_t* page_offsets; /* optional (HOST) */
+    int32_t op;              /* SB_PRED_IN | SB_PRED_NOT_IN */
+    int32_t combine;         /* SB_SEL_* */
+    const uint8_t* values;   /* HOST: numbers: n_values values of the column's type, little endian, back to back;
+                                binary: the literals' bytes back to back */
+    const uint64_t* value_offsets; /* HOST: binary: n_values + 1 ascending offsets into `values`, [0] == 0; numbers: NULL */
+    uint64_t n_values;       /* 0 .. SB_IN_MAX_VALUES */
+    uint8_t* selection;      /* DEVICE: LSB-first bitmap, 4-byte aligned */
+    uint64_t selection_capacity; /* >= 4*ceil(rows/32) bytes */
+    uint64_t stage_capacity; /* binary columns: as in sb_column_filter_var; 0 = 4 * pages_len */
+    /* results (HOST, valid after sb_ctx_synchronize) */
+    uint64_t rows;
+    uint64_t selected;
+} sb_column_filter_in;       /* 120 bytes */
+
+int32_t sb_filter_columns_in(sb_ctx* ctx, sb_column_filter_in* cols, uint64_t n, int32_t mem);
+
 /* ------------------------------------------------------------------ selected read
  * The second half of the filter: the pages of a payload column and a selection bitmap go in, the selected rows come
  * out packed.  Output row k is the column's row at the k-th set bit of `selection` below `rows`: its `values` are the

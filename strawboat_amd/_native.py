@@ -23,10 +23,12 @@ EXPORTS = ("sb_version", "sb_ctx_create", "sb_ctx_destroy", "sb_ctx_synchronize"
            "sb_file_reader_n_columns", "sb_file_reader_column", "sb_file_reader_schema", "sb_file_reader_read_pages",
            "sb_file_reader_close", "sb_stat_page", "sb_schema_last_error", "sb_schema_to_bytes", "sb_schema_from_bytes",
            "sb_schema_metadata_from_bytes", "sb_filter_columns", "sb_filter_columns_var", "sb_read_selected",
-           "sb_read_selected_var", "sb_aggregate_columns", "sb_aggregate_grouped")
+           "sb_read_selected_var", "sb_aggregate_columns", "sb_aggregate_grouped", "sb_filter_columns_in")
 
 SB_PRED_EQ, SB_PRED_NE, SB_PRED_LT, SB_PRED_LE, SB_PRED_GT, SB_PRED_GE, SB_PRED_IS_NULL, SB_PRED_IS_NOT_NULL = range(8)
 SB_PRED_STARTS_WITH = 8   # binary types only (sb_filter_columns_var)
+SB_PRED_IN, SB_PRED_NOT_IN = 9, 10   # sb_filter_columns_in
+SB_IN_MAX_VALUES = 1024
 SB_SEL_SET, SB_SEL_AND, SB_SEL_OR = range(3)
 SB_AGG_COUNT, SB_AGG_MIN, SB_AGG_MAX, SB_AGG_SUM = 1, 2, 4, 8
 SB_AGG_MAX_GROUPS = 256
@@ -65,6 +67,15 @@ class ColumnFilterVarC(C.Structure):
                 ("page_offsets", C.c_void_p), ("op", C.c_int32), ("combine", C.c_int32),
                 ("literal", C.c_void_p), ("literal_len", C.c_uint64), ("selection", C.c_void_p),
                 ("selection_capacity", C.c_uint64), ("stage_capacity", C.c_uint64),
+                ("rows", C.c_uint64), ("selected", C.c_uint64)]
+
+
+class ColumnFilterInC(C.Structure):
+    _fields_ = [("physical_type", C.c_int32), ("is_nullable", C.c_int32), ("pages", C.c_void_p),
+                ("pages_len", C.c_uint64), ("metas", C.POINTER(PageMetaC)), ("n_pages", C.c_uint64),
+                ("page_offsets", C.c_void_p), ("op", C.c_int32), ("combine", C.c_int32),
+                ("values", C.c_void_p), ("value_offsets", C.c_void_p), ("n_values", C.c_uint64),
+                ("selection", C.c_void_p), ("selection_capacity", C.c_uint64), ("stage_capacity", C.c_uint64),
                 ("rows", C.c_uint64), ("selected", C.c_uint64)]
 
 
@@ -202,6 +213,8 @@ def load():
     L.sb_filter_columns.argtypes = [C.c_void_p, C.POINTER(ColumnFilterC), C.c_uint64, C.c_int32]
     L.sb_filter_columns_var.restype = C.c_int32
     L.sb_filter_columns_var.argtypes = [C.c_void_p, C.POINTER(ColumnFilterVarC), C.c_uint64, C.c_int32]
+    L.sb_filter_columns_in.restype = C.c_int32
+    L.sb_filter_columns_in.argtypes = [C.c_void_p, C.POINTER(ColumnFilterInC), C.c_uint64, C.c_int32]
     L.sb_read_selected.restype = C.c_int32
     L.sb_read_selected.argtypes = [C.c_void_p, C.POINTER(ColumnReadSelectedC), C.c_uint64, C.c_int32]
     L.sb_read_selected_var.restype = C.c_int32

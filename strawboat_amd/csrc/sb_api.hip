@@ -11,7 +11,7 @@
 namespace sb {
 
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
-                   const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp = nullptr);
+                   const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp = nullptr, const InCol* icols = nullptr);
 void launch_grp_zero(sb_ctx* ctx, const GrpLaunch& gl, uint32_t n_cols);
 void launch_grp_finish(sb_ctx* ctx, const GrpLaunch& gl, uint64_t* results, uint32_t n_cols);
 void launch_grp_plain(sb_ctx* ctx, const GrpLaunch& gl, uint32_t n_cols, const uint64_t* rows, const uint8_t* const* values,
@@ -23,6 +23,8 @@ void launch_rsel_plain(sb_ctx* ctx, const SelCol* scols, uint32_t n_cols, uint64
                        const uint8_t* const* values, const uint8_t* const* validity);
 void launch_rsel_bin(sb_ctx* ctx, const DecodeArgs& a, const SelLaunch& sl);
 void launch_filter_plain(sb_ctx* ctx, const FilterCol& f, const uint8_t* values, const uint8_t* validity, uint64_t rows, uint32_t w, uint64_t* count);
+void launch_filter_in_plain(sb_ctx* ctx, const FilterCol& f, const InCol& ic, const uint8_t* values, const uint8_t* validity, uint64_t rows, uint32_t w,
+                            uint64_t* count);
 void launch_parse_sizes(sb_ctx* ctx, const DecodeArgs& a, uint64_t* col_values_len);
 void launch_freq_scatter(sb_ctx* ctx, const FreqEntry* entries, uint32_t n, const uint64_t* ex_off, const uint8_t* ex_base);
 
@@ -234,6 +236,7 @@ struct ReadMode {
     enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR, AGGREGATE, AGG_GROUPED } kind;
     const FilterCol* filt = nullptr;             // FILTER: one per column
     const std::vector<uint8_t>* lits = nullptr;  // ... the literals of the FK_BYTES columns, FilterCol.lit being the offset of each
+    bool in_list = false;                        // ... sb_filter_columns_in: `lits` begins with an InCol per column, whose pointers are offsets in `lits`
     bool sizes() const { return kind == SIZES; }
     bool freq_pass() const { return kind == FREQ_PASS; }
     const SelCol* selc = nullptr;                // SELECTED: one per column (rank: filled in with the call's tables)
@@ -944,6 +947,11 @@ static int32_t fill_read_tables(sb_ctx* ctx, uint8_t* host, const ReadLayout& L,
         if (mode.lits && !mode.lits->empty()) memcpy(host + L.lits, mode.lits->data(), mode.lits->size());
         for (uint64_t i = 0; i < n; i++)
             if (hfc[i].kind == FK_BYTES) hfc[i].lit += (uint64_t)(uintptr_t)(ctx->tables.p + L.lits);
+        InCol* hic = mode.in_list ? (InCol*)(host + L.lits) : nullptr;
+        for (uint64_t i = 0; hic && i < n; i++) {
+            hic[i].keys = (const uint64_t*)(ctx->tables.p + L.lits + (size_t)(uintptr_t)hic[i].keys);
+            hic[i].bytes = ctx->tables.p + L.lits + (size_t)(uintptr_t)hic[i].bytes;
+        }
     }
     if (mode.aggregate()) {   // the columns' slots among the call's partial records (read_layout: L.aggp)
         AggCol* hac = (AggCol*)(host + L.fcols);
@@ -1162,11 +1170,12 @@ static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, 
     } else if (mode.filter()) {
         FilterLaunch fl{(const FilterCol*)(ctx->tables.p + L.fcols), d_vlen, false, false, false, false};
         for (uint64_t i = 0; i < n; i++) {
-            const bool null_op = mode.filt[i].op >= SB_PRED_IS_NULL;
+            const bool null_op = !mode.in_list && mode.filt[i].op >= SB_PRED_IS_NULL;   // (IN / NOT_IN: searched, sb_filter_in.h)
             (null_op ? fl.any_null : mode.filt[i].kind == FK_BYTES ? fl.any_bin : fl.any_cmp) = true;
             if (mode.filt[i].combine == SB_SEL_SET) fl.any_set = true;
         }
-        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, &fl, nullptr, nullptr);
+        const InCol* icols = mode.in_list ? (const InCol*)(ctx->tables.p + L.lits) : nullptr;
+        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, &fl, nullptr, nullptr, nullptr, icols);
     } else if (mode.selected()) {
         SelLaunch sl{(const SelCol*)(ctx->tables.p + L.fcols), d_vlen, false};
         for (uint64_t i = 0; i < n; i++)
@@ -1641,6 +1650,179 @@ int32_t sb_filter_columns(sb_ctx* ctx, sb_column_filter* cols, uint64_t n, int32
     }
     rc = filter_impl(ctx, v.data(), results.data(), n);
     if (rc == SB_OK && !ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::FILTER, cols, n, sb_write_options{}, mem});
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------ IN / NOT IN
+// The list of a column as the kernels search it (sb_filter_in.h), appended to `blob` at a multiple of 8; ic's pointers are
+// offsets in `blob` until the tables have their place.  Numbers: order keys, sorted, without duplicates and without NaNs.
+// Binary: the literals sorted as byte strings, without duplicates, as [n + 1 offsets | bytes | 8 zero bytes].
+static void in_set_append(const sb_column_filter_in& c, uint32_t kind, std::vector<uint8_t>& blob, InCol* ic) {
+    blob.resize(align_up(blob.size(), 8));
+    memset(ic, 0, sizeof *ic);
+    ic->negate = c.op == SB_PRED_NOT_IN;
+    std::vector<uint64_t> words;   // the keys, or the offsets
+    std::vector<uint8_t> bytes;
+    if (kind == FK_BYTES) {
+        struct Lit {
+            const uint8_t* p;
+            uint64_t len;
+        };
+        std::vector<Lit> lits(c.n_values);
+        for (uint64_t j = 0; j < c.n_values; j++) lits[j] = Lit{c.values + c.value_offsets[j], c.value_offsets[j + 1] - c.value_offsets[j]};
+        auto cmp3 = [](const Lit& a, const Lit& b) {
+            const uint64_t m = std::min(a.len, b.len);
+            const int r = m ? memcmp(a.p, b.p, m) : 0;
+            return r ? r : a.len < b.len ? -1 : a.len > b.len ? 1 : 0;
+        };
+        std::sort(lits.begin(), lits.end(), [&](const Lit& a, const Lit& b) { return cmp3(a, b) < 0; });
+        lits.erase(std::unique(lits.begin(), lits.end(), [&](const Lit& a, const Lit& b) { return cmp3(a, b) == 0; }), lits.end());
+        words.push_back(0);
+        for (const Lit& l : lits) {
+            if (l.len) bytes.insert(bytes.end(), l.p, l.p + l.len);
+            words.push_back(bytes.size());
+        }
+        bytes.insert(bytes.end(), 8, (uint8_t)0);
+        ic->n = (uint32_t)lits.size();
+    } else {
+        const uint32_t w = type_width(c.physical_type);
+        for (uint64_t j = 0; j < c.n_values; j++) {
+            uint64_t raw = 0;
+            memcpy(&raw, c.values + j * w, w);
+            if (kind == FK_F32 && (raw & 0x7FFFFFFFull) > 0x7F800000ull) continue;   // NaN: matches nothing
+            if (kind == FK_F64 && (raw & ~(1ull << 63)) > 0x7FF0000000000000ull) continue;
+            words.push_back(in_key(kind, w, raw));
+        }
+        std::sort(words.begin(), words.end());
+        words.erase(std::unique(words.begin(), words.end()), words.end());
+        ic->n = (uint32_t)words.size();
+    }
+    while ((1ull << ic->steps) < (uint64_t)ic->n + 1) ic->steps++;
+    ic->keys = (const uint64_t*)(uintptr_t)blob.size();
+    blob.insert(blob.end(), (const uint8_t*)words.data(), (const uint8_t*)(words.data() + words.size()));
+    ic->bytes = (const uint8_t*)(uintptr_t)blob.size();
+    blob.insert(blob.end(), bytes.begin(), bytes.end());
+}
+
+// The numeric columns of a replayed IN call: decoded, and searched from the staging area (filter_columns_decoded with the
+// sets, which go to the device in a buffer of the interval's)
+static int32_t filter_in_columns_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pages, const uint64_t* rows, const FilterCol* hf,
+                                         const InCol* hic, const std::vector<uint8_t>& blob, void* const* sel_out) {
+    hipStream_t s = ctx->stream;
+    const uint64_t m = pages.size();
+    const sb_column_read* rr = nullptr;
+    int32_t rc = decode_for_replay(ctx, std::move(pages), rows, "filter", &rr);
+    if (rc != SB_OK) return rc;
+    uint8_t* d_buf = nullptr;
+    const size_t o_sets = align_up(m * sizeof(uint64_t), 64);
+    if (hipMalloc((void**)&d_buf, o_sets + blob.size() + 8) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter counts) failed");
+    ctx->iv.temp_dev.push_back(d_buf);
+    // (a copy that has ended when it returns: `blob` does not outlive the call)
+    if (!blob.empty() && hipMemcpy(d_buf + o_sets, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess)
+        return ctx->fail(SB_ERR_EXTERNAL, "H2D of the lists failed");
+    uint64_t* d_counts = (uint64_t*)d_buf;
+    StageSlot* slot = acquire_slot(ctx, m * sizeof(uint64_t));
+    if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
+    for (uint64_t i = 0; i < m; i++) {
+        if (hf[i].combine == SB_SEL_SET && rows[i]) (void)hipMemsetAsync(hf[i].sel, 0, (rows[i] + 31) / 32 * 4, s);
+        InCol ic = hic[i];
+        ic.keys = (const uint64_t*)(d_buf + o_sets + (size_t)(uintptr_t)ic.keys);
+        ic.bytes = d_buf + o_sets + (size_t)(uintptr_t)ic.bytes;
+        launch_filter_in_plain(ctx, hf[i], ic, (const uint8_t*)rr[i].values, rr[i].is_nullable ? rr[i].validity : nullptr, rows[i],
+                               type_width(rr[i].physical_type), d_counts + i);
+    }
+    return queue_sink_results(ctx, slot, d_counts, sizeof(uint64_t), m, Pending::FILTER_COL, sel_out, nullptr, "filter");
+}
+
+static_assert(sizeof(sb_column_filter_in) == 120 && offsetof(sb_column_filter_in, op) == 48 && offsetof(sb_column_filter_in, values) == 56 &&
+                  offsetof(sb_column_filter_in, value_offsets) == 64 && offsetof(sb_column_filter_in, n_values) == 72 &&
+                  offsetof(sb_column_filter_in, selection) == 80 && offsetof(sb_column_filter_in, stage_capacity) == 96 &&
+                  offsetof(sb_column_filter_in, rows) == 104 && offsetof(sb_column_filter_in, selected) == 112 && has_pages_prefix<sb_column_filter_in>(),
+              "sb_column_filter_in: the offsets the header states");
+
+int32_t sb_filter_columns_in(sb_ctx* ctx, sb_column_filter_in* cols, uint64_t n, int32_t mem) {
+    int32_t rc;
+    if (!sink_entry(ctx, cols, n, mem, "sb_filter_columns_in", &rc)) return rc;
+    std::vector<uint64_t> rows(n), cap(n);
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_column_filter_in& c = cols[i];
+        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(ctx, SB_ERR_INVALID, "bad physical_type");
+        if (c.op != SB_PRED_IN && c.op != SB_PRED_NOT_IN) return refuse(ctx, SB_ERR_INVALID, "bad op: SB_PRED_IN or SB_PRED_NOT_IN");
+        if (c.combine < SB_SEL_SET || c.combine > SB_SEL_OR) return refuse(ctx, SB_ERR_INVALID, "bad combine");
+        const bool bin = is_binary_t(c.physical_type);
+        if (!bin && !filter_comparable(c.physical_type))
+            return refuse(ctx, SB_ERR_NYI, "IN lists are implemented for 8- to 64-bit integers, floats and binary types");
+        if (c.n_values > SB_IN_MAX_VALUES) return refuse(ctx, SB_ERR_INVALID, "n_values exceeds SB_IN_MAX_VALUES");
+        if (!bin) {
+            if (c.value_offsets) return refuse(ctx, SB_ERR_INVALID, "value_offsets on a numeric column");
+            if (c.n_values && !c.values) return refuse(ctx, SB_ERR_INVALID, "values is null");
+        } else if (c.n_values) {
+            if (!c.value_offsets) return refuse(ctx, SB_ERR_INVALID, "value_offsets is null");
+            if (c.value_offsets[0] != 0) return refuse(ctx, SB_ERR_INVALID, "value_offsets[0] is not 0");
+            for (uint64_t j = 0; j < c.n_values; j++)
+                if (c.value_offsets[j + 1] < c.value_offsets[j]) return refuse(ctx, SB_ERR_INVALID, "value_offsets descend");
+            if (c.value_offsets[c.n_values] > (1ull << 30)) return refuse(ctx, SB_ERR_INVALID, "the literals of a column have at most 2^30 bytes");
+            if (c.value_offsets[c.n_values] && !c.values) return refuse(ctx, SB_ERR_INVALID, "values is null");
+        }
+        if (!column_rows(c, &rows[i])) return refuse(ctx, SB_ERR_INVALID, "metas is null");
+        const uint64_t sel_bytes = (rows[i] + 31) / 32 * 4;
+        if (rows[i] && (!c.selection || ((uintptr_t)c.selection & 3) || c.selection_capacity < sel_bytes))
+            return refuse(ctx, SB_ERR_INVALID, "selection missing, not 4-byte aligned or smaller than 4*ceil(rows/32) bytes");
+        for (uint64_t j = 0; j < i && rows[i]; j++)
+            if (rows[j] && c.selection < cols[j].selection + (rows[j] + 31) / 32 * 4 && cols[j].selection < c.selection + sel_bytes)
+                return refuse(ctx, SB_ERR_INVALID, "two columns of one call share a selection buffer: chain them with two calls");
+    }
+    // [InCol per column | the sets], FilterCol per column beside
+    std::vector<uint8_t> blob(align_up(n * sizeof(InCol), 64));
+    std::vector<InCol> hic(n);
+    std::vector<FilterCol> hf(n);
+    std::vector<sb_column_read> rc_cols(n);
+    std::vector<void*> sel_out(n);
+    for (uint64_t i = 0; i < n; i++) {
+        sb_column_filter_in& c = cols[i];
+        c.rows = rows[i];
+        c.selected = 0;
+        static_assert(offsetof(sb_column_filter_in, selected) == offsetof(sb_column_filter_in, rows) + 8, "{ rows, selected }");
+        sel_out[i] = &c.selected;
+        rc_cols[i] = read_col_of(c);
+        const bool bin = is_binary_t(c.physical_type);
+        FilterCol& f = hf[i];
+        memset(&f, 0, sizeof f);
+        f.sel = (uint32_t*)c.selection;
+        f.op = (uint32_t)c.op;
+        f.combine = (uint32_t)c.combine;
+        f.ptype = c.physical_type;
+        f.kind = bin ? FK_BYTES : value_kind(c.physical_type);
+        in_set_append(c, f.kind, blob, &hic[i]);
+        // the share of the staging area a comparison column has (the caller's stage_capacity stays as given: a replay reads it again)
+        cap[i] = bin ? (c.stage_capacity ? c.stage_capacity : 4 * c.pages_len) : rows[i] * type_width(c.physical_type);
+    }
+    (void)hipSetDevice(ctx->device);
+    const bool first_issue = !ctx->in_replay;
+    if (ctx->in_replay && ctx->filter_freq) {
+        // binary columns as ever; the numeric columns through a full decode
+        std::vector<bool> dec(n);
+        for (uint64_t i = 0; i < n; i++) dec[i] = hf[i].kind != FK_BYTES;
+        std::vector<sb_column_read> r_cmp = take_if(rc_cols, dec);
+        const std::vector<uint64_t> n_cmp = take_if(rows, dec);
+        const std::vector<FilterCol> f_cmp = take_if(hf, dec);
+        const std::vector<InCol> i_cmp = take_if(hic, dec);
+        const std::vector<void*> s_cmp = take_if(sel_out, dec);
+        take_if(cap, dec);
+        if (!r_cmp.empty()) rc = filter_in_columns_decoded(ctx, std::move(r_cmp), n_cmp.data(), f_cmp.data(), i_cmp.data(), blob, s_cmp.data());
+        if (rc != SB_OK || rc_cols.empty()) return rc;
+    }
+    const uint64_t m = rc_cols.size();
+    memcpy(blob.data(), hic.data(), m * sizeof(InCol));
+    if ((rc = stage_shares(ctx, rc_cols.data(), cap.data(), m)) != SB_OK) return rc;
+    ReadMode mode{ReadMode::FILTER};
+    mode.filt = hf.data();
+    mode.lits = &blob;
+    mode.in_list = true;
+    mode.users = sel_out.data();
+    mode.pending_kind = Pending::FILTER_COL;
+    rc = read_columns_impl(ctx, rc_cols.data(), m, SB_MEM_DEVICE, mode);
+    if (rc == SB_OK && first_issue) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::FILTER_IN, cols, n, sb_write_options{}, mem});
     return rc;
 }
 

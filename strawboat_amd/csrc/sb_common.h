@@ -295,6 +295,34 @@ struct FilterLaunch {   // what launch_decode needs to end a call with the filte
     bool any_cmp, any_null, any_set;
     bool any_bin;          // comparison columns of a binary type: k_filter_bin_base / _entries / k_filter_bin (sb_filter_bin.h)
 };
+// one column of an IN / NOT IN call (sb_filter_columns_in, sb_filter_in.h), next to its FilterCol: the literals as a sorted
+// set without duplicates, in the call's tables.  FilterCol.op is SB_PRED_IN / SB_PRED_NOT_IN, FilterCol.kind as ever.
+constexpr uint32_t IN_MAX_VALUES = 1024;   // SB_IN_MAX_VALUES
+struct InCol {
+    const uint64_t* keys;   // numeric: n order keys (in_key), ascending; FK_BYTES: n + 1 ascending offsets into `bytes`
+    const uint8_t* bytes;   // FK_BYTES: the literals back to back in byte-string order, followed by 8 zero bytes
+    uint32_t n;             // 0 .. IN_MAX_VALUES
+    uint32_t steps;         // ceil(log2(n + 1)): the trip count of the search
+    uint32_t negate;        // NOT IN
+    uint32_t pad;
+};
+// The order key of a numeric value (agg_key's mapping, sb_aggregate.h: unsigned as is, signed with the sign bit flipped,
+// floats in the total order), with -0.0 folded onto +0.0: equal keys <=> values that compare equal, for everything that
+// is not a NaN.  A NaN's key is no other value's, and the host keeps NaN literals out of the set.
+__host__ __device__ inline uint64_t in_key(uint32_t kind, uint32_t w, uint64_t raw) {
+    if (kind == 0u /* FK_UNSIGNED */) return raw;
+    if (kind == 1u /* FK_SIGNED */) {
+        const uint32_t sh = 64 - 8 * w;
+        return (uint64_t)((int64_t)(raw << sh) >> sh) ^ (1ull << 63);
+    }
+    if (kind == 2u /* FK_F32 */) {
+        uint32_t b = (uint32_t)raw;
+        if ((b << 1) == 0) b = 0;
+        return (b >> 31) ? (uint32_t)~b : (b | 0x80000000u);
+    }
+    if ((raw << 1) == 0) raw = 0;
+    return (raw >> 63) ? ~raw : (raw | (1ull << 63));
+}
 // one column of a selected read (sb_read_selected, sb_read_sel.h), next to its ColDesc
 constexpr uint32_t RSEL_RANK_BLOCKS = 64;   // workgroups per column of the rank scan (k_rsel_sums / k_rsel_rank)
 struct SelCol {

@@ -3121,6 +3121,7 @@ static void launch_lzg(sb_ctx* ctx, const DecodeArgs& a, bool lzg_on, InflateJob
 }  // namespace sb
 #include "sb_filter.h"
 #include "sb_filter_bin.h"
+#include "sb_filter_in.h"
 #include "sb_read_sel.h"
 #include "sb_read_sel_bin.h"
 #include "sb_aggregate.h"
@@ -3128,7 +3129,7 @@ static void launch_lzg(sb_ctx* ctx, const DecodeArgs& a, bool lzg_on, InflateJob
 namespace sb {
 
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
-                   const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp) {
+                   const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp, const InCol* icols) {
     hipStream_t s = ctx->stream;
     (void)hipMemsetAsync(a.job_counts, 0, 16 * sizeof(uint32_t), s);
     const bool qa = !(a.read_skips & RSKIP_QUEUE_A);
@@ -3194,6 +3195,10 @@ void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_p
     if (any_binary && a.lz4_big_min != 0xFFFFFFFFu) {
         KScope k(ctx, "k_inflate_lz4_big(values)");
         k_inflate_lz4_big<<<min(a.zs_segs ? a.job_cap_a : 2 * a.n_pages, LZ4_BIG_POOL), LB_T, 0, s>>>(a.jobs_b, a.job_counts + 1, a.status, a.lz4_big_min, a.job_cap_a, a.lzg_skipped);
+    }
+    if (flt && icols) {   // sb_filter_columns_in: ... searched in the columns' lists (sb_filter_in.h)
+        launch_filter_in(ctx, a, *flt, icols);
+        return;
     }
     if (flt) {   // sb_filter_columns: the same pages, compared instead of stored
         launch_filter(ctx, a, *flt);

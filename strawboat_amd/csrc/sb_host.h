@@ -235,7 +235,7 @@ struct sb_ctx {
     // never a one-workgroup walk over a million-row page.  (The callers' column arrays and buffers live until the
     // synchronize anyway: the results are written into them there.)
     struct Call {
-        enum Kind { READ, WRITE, FILTER, FILTER_VAR, READ_SEL, READ_SEL_VAR, AGGREGATE, AGG_GROUPED, SIZES } kind;   // sb_read_columns, sb_write_columns, sb_filter_columns, sb_filter_columns_var, sb_read_selected, sb_read_selected_var, sb_aggregate_columns, sb_aggregate_grouped, sb_read_columns_sizes (its enqueue: the call's own synchronize may be the one that replays)
+        enum Kind { READ, WRITE, FILTER, FILTER_VAR, FILTER_IN, READ_SEL, READ_SEL_VAR, AGGREGATE, AGG_GROUPED, SIZES } kind;   // sb_read_columns, sb_write_columns, sb_filter_columns, sb_filter_columns_var, sb_filter_columns_in, sb_read_selected, sb_read_selected_var, sb_aggregate_columns, sb_aggregate_grouped, sb_read_columns_sizes (its enqueue: the call's own synchronize may be the one that replays)
         void* cols;
         uint64_t n;
         sb_write_options opts;
@@ -342,6 +342,7 @@ inline int32_t reissue(sb_ctx* ctx, sb_ctx::Call& cl) {
         case sb_ctx::Call::WRITE: return sb_write_columns(ctx, (sb_column_write*)cl.cols, cl.n, &cl.opts, cl.mem);
         case sb_ctx::Call::FILTER: return sb_filter_columns(ctx, (sb_column_filter*)cl.cols, cl.n, cl.mem);
         case sb_ctx::Call::FILTER_VAR: return sb_filter_columns_var(ctx, (sb_column_filter_var*)cl.cols, cl.n, cl.mem);
+        case sb_ctx::Call::FILTER_IN: return sb_filter_columns_in(ctx, (sb_column_filter_in*)cl.cols, cl.n, cl.mem);
         case sb_ctx::Call::READ_SEL: return sb_read_selected(ctx, (sb_column_read_selected*)cl.cols, cl.n, cl.mem);
         case sb_ctx::Call::READ_SEL_VAR: return sb_read_selected_var(ctx, (sb_column_read_selected_var*)cl.cols, cl.n, cl.mem);
         case sb_ctx::Call::AGGREGATE: return sb_aggregate_columns(ctx, (sb_column_aggregate*)cl.cols, cl.n, cl.mem);
