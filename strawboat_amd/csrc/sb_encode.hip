@@ -3780,15 +3780,10 @@ __global__ void __launch_bounds__(WG, (emit_pages_occupancy<KIND, CODEC>()))
         // already emitted: by the fused select + RLE pass / by the section-parallel writers of long pages (sb_dict_big.h)
         if (a.outs[page].pad == 1 && a.outs[page].length != 0) return;
     }
-    if constexpr (CODEC == SB_CODEC_RLE) {
-        if (threadIdx.x == 0 && a.use_counts) atomicAdd(&a.codec_counts[HINT_RLE_EMIT], 1u);   // (RLE pages the fused selectors did not write: the hint for the next call)
-    }
     if constexpr (CODEC == SB_CODEC_DICT) {
         // a long page whose section-parallel writers were skipped on a hint: not one workgroup's walk over millions of rows —
         // the page stays unwritten and the call is replayed (k_enc_layout)
         if ((a.skips & SKIP_DICT_BIG) && p.bigx_off && page < a.n_pages) return;
-        // (binary Dict pages k_enc_bin_page did not finish itself: the hint for the next call)
-        if (KIND < 0 && threadIdx.x == 0 && a.use_counts) atomicAdd(&a.codec_counts[HINT_BIN_DICT_EMIT], 1u);
     }
     const EncCol c = get_col(a, p.col);
     if (c.ptype == SB_TYPE_NULL) return;
@@ -3802,6 +3797,15 @@ __global__ void __launch_bounds__(WG, (emit_pages_occupancy<KIND, CODEC>()))
         if (c.ptype != SB_TYPE_LARGE_BINARY) return;
     } else {
         if (is_bool || is_bin || c.width != (uint32_t)KIND) return;
+    }
+    // The hints for the next call with this plan, counted for pages of this instance's own kind only.  (Counted before the
+    // kind check, a Dict page of an integer column made the binary instance count slot 30 — or not, when the integer
+    // kind's selector on the other stream of a mixed call had not chosen yet — and every instance counted slot 29.)
+    if constexpr (CODEC == SB_CODEC_RLE && (KIND == 4 || KIND == 8)) {
+        if (threadIdx.x == 0 && a.use_counts) atomicAdd(&a.codec_counts[HINT_RLE_EMIT], 1u);   // (RLE pages the fused selectors did not write)
+    }
+    if constexpr (CODEC == SB_CODEC_DICT && KIND < 0) {
+        if (threadIdx.x == 0 && a.use_counts) atomicAdd(&a.codec_counts[HINT_BIN_DICT_EMIT], 1u);   // (binary Dict pages k_enc_bin_page did not finish itself)
     }
     uint8_t* slot = page_slot(a, c, p);
     const uint64_t N = p.rows;
