@@ -556,6 +556,71 @@ typedef struct sb_column_aggregate_grouped {
 
 int32_t sb_aggregate_grouped(sb_ctx* ctx, sb_column_aggregate_grouped* cols, uint64_t n, int32_t mem);
 
+/* ------------------------------------------------------------------ top-k
+ * SELECT ... WHERE x < 5 ORDER BY y [DESC] LIMIT k.  The pages of a column and (optionally) a selection bitmap go in; the
+ * k best of the selected rows come back in `out` (HOST) with their row numbers, with which sb_read_selected fetches the
+ * other columns of the winners.  No selected value is stored on the way.
+ *
+ *   live rows     a row is live if its selection bit is set and it is not null, exactly as for sb_aggregate_columns;
+ *                 rows / selected / count / nans mean what they mean there.
+ *   candidates    the live rows that are not NaN.  found = min(k, count - nans).
+ *   order         by value in the aggregate's order: integers by the physical type's signedness; floats numerically with
+ *                 -0.0 < +0.0, +-inf included.  Ascending for SB_TOPK_SMALLEST, descending for SB_TOPK_LARGEST.  TIES ARE
+ *                 BROKEN BY THE LOWER ROW NUMBER, IN BOTH ORDERS.  That is a total order on (value, row), so the result
+ *                 is unique: the same bytes every time the call is issued, a replayed interval included, whatever the
+ *                 schedule.
+ *   out           out[0 .. found) holds the winners in that order: `row` is the row's number in the column, `value` the
+ *                 bytes of that row's value, little endian, in the first `width` bytes, and 0 behind them.
+ *                 out[found .. k) is written as all zero.  No byte behind out[k) is touched.
+ *
+ * Types: INT8..INT64, UINT8..UINT64, FLOAT32, FLOAT64.
+ *
+ * Refused at the call, nothing enqueued and no result field or byte of `out` touched: another physical type and
+ * SB_MEM_HOST (SB_ERR_NYI); k of 0 or above SB_TOPK_MAX_K, an unknown `order`, `reserved` != 0, `out` null, and every
+ * argument refusal of sb_aggregate_columns, with its code.
+ *
+ * Enqueued like sb_aggregate_columns and part of its synchronize interval in the same way: on a replay it is issued again
+ * in its place, behind the filter calls that write its bitmap.  A column with a primitive Freq page asks for that replay
+ * itself.  `selection` is an INPUT: it stays unmodified until the synchronize.  `rows` and `selected` are delivered even
+ * when the interval failed; the other results and `out` are unspecified then.  The call consults no launch hint of the read
+ * path and leaves its counters alone.
+ *
+ * Layout (pinned by tests/test_topk_host.py): sb_topk_row 16 bytes; row 0, value 8.  sb_column_topk 128 bytes;
+ * physical_type 0, is_nullable 4, pages 8, pages_len 16, metas 24, n_pages 32, page_offsets 40, selection 48,
+ * selection_capacity 56, k 64, order 68, out 72, reserved 80, rows 88, selected 96, count 104, nans 112, found 120. */
+#define SB_TOPK_MAX_K 256u
+#define SB_TOPK_SMALLEST 0u
+#define SB_TOPK_LARGEST  1u
+
+typedef struct sb_topk_row {
+    uint64_t row;            /* the row's number in the column */
+    uint8_t value[8];        /* as min / max in sb_column_aggregate */
+} sb_topk_row;               /* 16 bytes */
+
+typedef struct sb_column_topk {
+    int32_t physical_type;   /* SB_TYPE_* */
+    int32_t is_nullable;
+    const uint8_t* pages;    /* DEVICE, at any byte alignment */
+    uint64_t pages_len;
+    const sb_page_meta* metas; /* HOST */
+    uint64_t n_pages;
+    const uint64_t* page_offsets; /* optional (HOST), as in sb_column_read */
+    const uint8_t* selection;     /* DEVICE, input: as in sb_column_aggregate; NULL = every row */
+    uint64_t selection_capacity;
+    uint32_t k;              /* 1 .. SB_TOPK_MAX_K */
+    uint32_t order;          /* SB_TOPK_SMALLEST / SB_TOPK_LARGEST */
+    sb_topk_row* out;        /* HOST, k entries, filled at the synchronize; must live until then */
+    uint64_t reserved;       /* must be 0 */
+    /* results (HOST, valid after sb_ctx_synchronize) */
+    uint64_t rows;           /* sum of num_values */
+    uint64_t selected;       /* bits set in `selection` below `rows` (== rows without a selection) */
+    uint64_t count;          /* selected rows that are not null */
+    uint64_t nans;           /* of those, float NaNs */
+    uint64_t found;          /* min(k, count - nans): the entries of `out` that hold a row */
+} sb_column_topk;            /* 128 bytes */
+
+int32_t sb_topk_columns(sb_ctx* ctx, sb_column_topk* cols, uint64_t n, int32_t mem);
+
 /* ------------------------------------------------------------------ encode
  * Replaces, per leaf column, the page loop of NativeWriter::encode_chunk
  * (src/write/common.rs:54-109): page slicing, then per page write::write -> write_simple

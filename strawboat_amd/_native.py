@@ -23,7 +23,8 @@ EXPORTS = ("sb_version", "sb_ctx_create", "sb_ctx_destroy", "sb_ctx_synchronize"
            "sb_file_reader_n_columns", "sb_file_reader_column", "sb_file_reader_schema", "sb_file_reader_read_pages",
            "sb_file_reader_close", "sb_stat_page", "sb_schema_last_error", "sb_schema_to_bytes", "sb_schema_from_bytes",
            "sb_schema_metadata_from_bytes", "sb_filter_columns", "sb_filter_columns_var", "sb_read_selected",
-           "sb_read_selected_var", "sb_aggregate_columns", "sb_aggregate_grouped", "sb_filter_columns_in")
+           "sb_read_selected_var", "sb_aggregate_columns", "sb_aggregate_grouped", "sb_filter_columns_in",
+           "sb_topk_columns")
 
 SB_PRED_EQ, SB_PRED_NE, SB_PRED_LT, SB_PRED_LE, SB_PRED_GT, SB_PRED_GE, SB_PRED_IS_NULL, SB_PRED_IS_NOT_NULL = range(8)
 SB_PRED_STARTS_WITH = 8   # binary types only (sb_filter_columns_var)
@@ -32,6 +33,8 @@ SB_IN_MAX_VALUES = 1024
 SB_SEL_SET, SB_SEL_AND, SB_SEL_OR = range(3)
 SB_AGG_COUNT, SB_AGG_MIN, SB_AGG_MAX, SB_AGG_SUM = 1, 2, 4, 8
 SB_AGG_MAX_GROUPS = 256
+SB_TOPK_MAX_K = 256
+SB_TOPK_SMALLEST, SB_TOPK_LARGEST = 0, 1
 
 
 class PageMetaC(C.Structure):
@@ -120,6 +123,19 @@ class ColumnAggregateGroupedC(C.Structure):
                 ("n_groups", C.c_uint32), ("ops", C.c_uint32), ("reserved", C.c_uint32),
                 ("groups", C.POINTER(AggGroupC)), ("rows", C.c_uint64), ("selected", C.c_uint64),
                 ("out_of_range", C.c_uint64)]
+
+
+class TopKRowC(C.Structure):
+    _fields_ = [("row", C.c_uint64), ("value", C.c_uint8 * 8)]
+
+
+class ColumnTopKC(C.Structure):
+    _fields_ = [("physical_type", C.c_int32), ("is_nullable", C.c_int32), ("pages", C.c_void_p),
+                ("pages_len", C.c_uint64), ("metas", C.POINTER(PageMetaC)), ("n_pages", C.c_uint64),
+                ("page_offsets", C.c_void_p), ("selection", C.c_void_p), ("selection_capacity", C.c_uint64),
+                ("k", C.c_uint32), ("order", C.c_uint32), ("out", C.POINTER(TopKRowC)), ("reserved", C.c_uint64),
+                ("rows", C.c_uint64), ("selected", C.c_uint64), ("count", C.c_uint64), ("nans", C.c_uint64),
+                ("found", C.c_uint64)]
 
 
 class ColumnWriteC(C.Structure):
@@ -223,6 +239,8 @@ def load():
     L.sb_aggregate_columns.argtypes = [C.c_void_p, C.POINTER(ColumnAggregateC), C.c_uint64, C.c_int32]
     L.sb_aggregate_grouped.restype = C.c_int32
     L.sb_aggregate_grouped.argtypes = [C.c_void_p, C.POINTER(ColumnAggregateGroupedC), C.c_uint64, C.c_int32]
+    L.sb_topk_columns.restype = C.c_int32
+    L.sb_topk_columns.argtypes = [C.c_void_p, C.POINTER(ColumnTopKC), C.c_uint64, C.c_int32]
     L.sb_read_columns_sizes.restype = C.c_int32
     L.sb_read_columns_sizes.argtypes = [C.c_void_p, C.POINTER(ColumnReadC), C.c_uint64, C.c_int32]
     L.sb_write_bound.restype = C.c_uint64

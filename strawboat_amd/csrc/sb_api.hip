@@ -11,7 +11,12 @@
 namespace sb {
 
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
-                   const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp = nullptr, const InCol* icols = nullptr);
+                   const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp = nullptr, const InCol* icols = nullptr,
+                   const TopkLaunch* topk = nullptr);
+void launch_topk_zero(sb_ctx* ctx, const TopkLaunch& tl);
+void launch_topk_finish(sb_ctx* ctx, const TopkLaunch& tl, uint64_t* results, uint32_t n_cols);
+void launch_topk_plain(sb_ctx* ctx, const TopkLaunch& tl, uint32_t n_cols, const uint64_t* rows, const uint8_t* const* values,
+                       const uint8_t* const* validity);
 void launch_grp_zero(sb_ctx* ctx, const GrpLaunch& gl, uint32_t n_cols);
 void launch_grp_finish(sb_ctx* ctx, const GrpLaunch& gl, uint64_t* results, uint32_t n_cols);
 void launch_grp_plain(sb_ctx* ctx, const GrpLaunch& gl, uint32_t n_cols, const uint64_t* rows, const uint8_t* const* values,
@@ -99,7 +104,7 @@ StageSlot* acquire_slot(sb_ctx* ctx, size_t need) {
     if (s.host)
         for (auto& p : ctx->iv.pending) {
             if (p.host < s.host || p.host >= s.host + s.cap) continue;
-            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::AGG_COL ? AGG_RESULT_WORDS * 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R || p.kind == Pending::AGG_GRP_COL) ? (size_t)p.bytes
+            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::AGG_COL ? AGG_RESULT_WORDS * 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R || p.kind == Pending::AGG_GRP_COL || p.kind == Pending::TOPK_COL) ? (size_t)p.bytes
                                                                                                    : (size_t)(2 * p.n + 1) * 8;
             ctx->iv.rescued.emplace_back(p.host, p.host + nb);
             p.host = ctx->iv.rescued.back().data();
@@ -233,7 +238,8 @@ struct ReadMode {
     // in the selected-read kernels / sb_read_selected_var, whose binary columns end in those of sb_read_sel_bin.h /
     // sb_aggregate_columns, whose columns end in the aggregate kernels
     // / sb_aggregate_grouped, an aggregate call whose columns end in the grouped aggregate kernels
-    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR, AGGREGATE, AGG_GROUPED } kind;
+    // / sb_topk_columns, an aggregate call whose columns end in the top-k kernels
+    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR, AGGREGATE, AGG_GROUPED, TOPK } kind;
     const FilterCol* filt = nullptr;             // FILTER: one per column
     const std::vector<uint8_t>* lits = nullptr;  // ... the literals of the FK_BYTES columns, FilterCol.lit being the offset of each
     bool in_list = false;                        // ... sb_filter_columns_in: `lits` begins with an InCol per column, whose pointers are offsets in `lits`
@@ -244,13 +250,16 @@ struct ReadMode {
     const AggCol* aggc = nullptr;                // AGGREGATE: one per column (the slots: filled in with the call's tables)
     const GrpCol* grpc = nullptr;                // AGG_GROUPED: one per column beside aggc
     uint32_t grp_gmax = 0;                       // ... the largest n_groups of the call: records per slot
+    const TopkCol* topkc = nullptr;              // TOPK: one per column beside aggc
+    uint32_t topk_kmax = 0;                      // ... the largest k of the call: records per slot
     // Where a column's result goes at the synchronize, as Pending has it (sb_host.h): users[i] beside pending_kind.  Set by
     // the entry points of the sinks: the callers' structs, for a filter call the caller's `selected` (results[i] + 1).
     // Null for the other kinds of call, whose results go to the sb_column_read structs of the call itself.
     void* const* users = nullptr;
     Pending::Kind pending_kind = Pending::READ_COL;
-    bool aggregate() const { return kind == AGGREGATE || kind == AGG_GROUPED; }   // an AggCol per column, slots per page part and tile
+    bool aggregate() const { return kind == AGGREGATE || kind == AGG_GROUPED || kind == TOPK; }   // an AggCol per column, slots per page part and tile
     bool grouped() const { return kind == AGG_GROUPED; }
+    bool topk() const { return kind == TOPK; }
     bool filter() const { return kind == FILTER; }
     bool selected() const { return kind == SELECTED; }
     bool selected_var() const { return kind == SELECTED_VAR; }
@@ -259,10 +268,13 @@ struct ReadMode {
     bool bin_staged() const { return kind == FILTER || kind == SELECTED_VAR; }
     // the columns end in a sink of their own: `values` is a share of the staging area, there is no validity buffer, and
     // the call neither consults nor feeds the launch hints of the read path
-    bool sink() const { return kind == FILTER || kind == SELECTED || kind == SELECTED_VAR || kind == AGGREGATE || kind == AGG_GROUPED; }
+    bool sink() const { return kind == FILTER || kind == SELECTED || kind == SELECTED_VAR || aggregate(); }
     // words of 8 bytes that come back per column: { selected, values_len } for a SELECTED_VAR call, the result record of
-    // an AGGREGATE call, the header and the gmax group records of an AGG_GROUPED call
-    uint64_t result_words() const { return kind == SELECTED_VAR ? 2 : kind == AGGREGATE ? AGG_RESULT_WORDS : kind == AGG_GROUPED ? grp_result_words(grp_gmax) : 1; }
+    // an AGGREGATE call, the header and the gmax group records of an AGG_GROUPED call, the header and the kmax entries of
+    // a TOPK call
+    uint64_t result_words() const {
+        return kind == SELECTED_VAR ? 2 : kind == AGGREGATE ? AGG_RESULT_WORDS : kind == AGG_GROUPED ? grp_result_words(grp_gmax) : kind == TOPK ? topk_result_words(topk_kmax) : 1;
+    }
 };
 static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, const ReadMode& mode);
 static void update_read_hints(sb_ctx* ctx, uint32_t kinds);   // (next to read_hints, its reader)
@@ -495,6 +507,19 @@ static void deliver_agg_grp_col(const Pending& p, bool ok) {
     c->out_of_range = head[1];
     memcpy(c->groups, p.host + sizeof head, (size_t)p.bytes - sizeof head);
 }
+// k_topk_finish's header and entries (sb_topk.h); `ok` false: the interval failed, selected alone
+static void deliver_topk_col(const Pending& p, bool ok) {
+    uint64_t head[8];
+    memcpy(head, p.host, sizeof head);
+    sb_column_topk* c = (sb_column_topk*)p.user;
+    c->selected = head[0];
+    if (!ok) return;
+    c->count = head[1];
+    c->nans = head[2];
+    c->found = head[3];
+    // (k as the struct has it now, but never more than the record that was enqueued holds: header + kmax entries)
+    memcpy(c->out, p.host + sizeof head, std::min<size_t>((size_t)c->k * sizeof(sb_topk_row), (size_t)p.bytes - sizeof head));
+}
 static void deliver_write_col(const Pending& p) {
     sb_column_write* c = (sb_column_write*)p.user;
     const uint64_t* lens = (const uint64_t*)p.host;  // [n_pages lengths][n_pages num_values][total]
@@ -524,6 +549,7 @@ static void deliver_pending(sb_ctx* ctx, const Pending& p, int32_t rc) {
         case Pending::RSEL_VAR_COL: deliver_rsel_var_col(p); break;
         case Pending::AGG_COL: deliver_agg_col(p); break;
         case Pending::AGG_GRP_COL: deliver_agg_grp_col(p, rc == SB_OK); break;
+        case Pending::TOPK_COL: deliver_topk_col(p, rc == SB_OK); break;
         case Pending::WRITE_COL: deliver_write_col(p); break;
         case Pending::ENC_HINT:
             if (rc == SB_OK) apply_enc_hint(ctx, p);
@@ -774,7 +800,7 @@ static ReadHints read_hints(sb_ctx* ctx, const ReadMode& mode, const ReadShape& 
 // Where the call's tables sit, on the device (ctx->tables) and — up to `upload` — in the staging slot, whose next n words
 // receive the results.  A pure function of shape, hints and mode.
 struct ReadLayout {
-    size_t cols, tasks, fcols, bcols, lits, upload, descs, tiles, jobs_a, jobs_b, jobs_z, counts, vlen, zb_counts, zb_frames, zs, rle, bpg, aggp, grp_recs, total;
+    size_t cols, tasks, fcols, bcols, lits, upload, descs, tiles, jobs_a, jobs_b, jobs_z, counts, vlen, zb_counts, zb_frames, zs, rle, bpg, aggp, grp_recs, topk_recs, total;
     size_t job_cap;        // queue entries: 2 per page + room for the frames of Zstd buffers that are several frames (one entry per frame)
     bool want_z;           // queue Z (calls with binary columns that produce values): Zstd payloads known to k_parse, entropy stages with queue A's
     uint64_t zs_seg_cap;
@@ -796,6 +822,7 @@ static ReadLayout read_layout(uint64_t n, const ReadShape& sh, const ReadHints& 
     L.bcols = off;
     if (mode.selected_var()) off = align_up(off + n * sizeof(SelBin), 64);
     if (mode.grouped()) off = align_up(off + n * sizeof(GrpCol), 64);   // (in the SelBins' place)
+    if (mode.topk()) off = align_up(off + n * sizeof(TopkCol), 64);     // (likewise)
     L.lits = off;
     if (mode.lits) off = align_up(off + mode.lits->size(), 64);
     L.upload = off;
@@ -829,10 +856,13 @@ static ReadLayout read_layout(uint64_t n, const ReadShape& sh, const ReadHints& 
     L.bpg = off;
     if (L.rle_parts > 1) off = align_up(off + P * sizeof(uint32_t), 64);
     L.aggp = off;   // an AGGREGATE call's partial records: a slot per (page, RLE part), then a slot per tile
-    if (mode.aggregate() && !mode.grouped()) off = align_up(off + (P * L.rle_parts + sh.T) * sizeof(AggPart), 64);
+    if (mode.kind == ReadMode::AGGREGATE) off = align_up(off + (P * L.rle_parts + sh.T) * sizeof(AggPart), 64);
     // an AGG_GROUPED call: a flag word per slot, a counter and a Freq mark per column (zeroed), then gmax records per slot (not zeroed)
     L.grp_recs = align_up(off + (P * L.rle_parts + sh.T + 2 * n) * sizeof(uint64_t), 64);
     if (mode.grouped()) off = align_up(L.grp_recs + (P * L.rle_parts + sh.T) * mode.grp_gmax * sizeof(GrpPart), 64);
+    // a TOPK call: a header per slot (zeroed), then kmax records per slot (not zeroed)
+    L.topk_recs = align_up(off + (P * L.rle_parts + sh.T) * sizeof(TopkHead), 64);
+    if (mode.topk()) off = align_up(L.topk_recs + (P * L.rle_parts + sh.T) * mode.topk_kmax * sizeof(TopkRec), 64);
     L.total = off;
     return L;
 }
@@ -967,6 +997,7 @@ static int32_t fill_read_tables(sb_ctx* ctx, uint8_t* host, const ReadLayout& L,
             tile0 += ntiles;
         }
         if (mode.grouped()) memcpy(host + L.bcols, mode.grpc, n * sizeof(GrpCol));
+        if (mode.topk()) memcpy(host + L.bcols, mode.topkc, n * sizeof(TopkCol));
     }
     SelCol* hsc = mode.ranked() ? (SelCol*)(host + L.fcols) : nullptr;
     for (uint64_t i = 0; hsc && i < n; i++) {   // the rank tables: behind the pages' areas, sized by the rows
@@ -1199,6 +1230,13 @@ static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, 
         if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, nullptr, nullptr, &gl);
         // (a call without a page still has a result: selected, and empty groups)
         launch_grp_finish(ctx, gl, d_vlen, (uint32_t)n);
+    } else if (mode.topk()) {
+        TopkLaunch tl{(const AggCol*)(ctx->tables.p + L.fcols), (const TopkCol*)(ctx->tables.p + L.bcols), (TopkHead*)(ctx->tables.p + L.aggp),
+                      (TopkRec*)(ctx->tables.p + L.topk_recs), sh.P * L.rle_parts + sh.T, sh.P * L.rle_parts, mode.topk_kmax};
+        launch_topk_zero(ctx, tl);
+        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, nullptr, nullptr, nullptr, nullptr, &tl);
+        // (a call without a page still has a result: selected, and an `out` of zeros)
+        launch_topk_finish(ctx, tl, d_vlen, (uint32_t)n);
     } else if (mode.aggregate()) {
         AggLaunch al{(const AggCol*)(ctx->tables.p + L.fcols), (AggPart*)(ctx->tables.p + L.aggp), sh.P * L.rle_parts, false, false};
         for (uint64_t i = 0; i < n; i++) ((mode.aggc[i].ops & AGG_VALUE_OPS) ? al.any_val : al.any_null) = true;
@@ -1231,6 +1269,7 @@ static void push_pending(sb_ctx* ctx, Pending::Kind kind, void* const* users, co
         pd.host = host + i * stride;
         pd.n = 0;
         if (grpc) pd.bytes = sizeof(uint64_t) * grp_result_words(grpc[i].n_groups);
+        if (kind == Pending::TOPK_COL) pd.bytes = stride;   // (the header and kmax entries: the column's own k is in its struct)
         ctx->iv.pending.push_back(pd);
     }
 }
@@ -1380,7 +1419,7 @@ constexpr bool has_pages_prefix() {
 }
 static_assert(offsetof(sb_column_filter, page_offsets) == 40, "the pages of a sink column: 48 bytes");
 static_assert(has_pages_prefix<sb_column_filter_var>() && has_pages_prefix<sb_column_read_selected>() && has_pages_prefix<sb_column_read_selected_var>() &&
-                  has_pages_prefix<sb_column_aggregate>() && has_pages_prefix<sb_column_aggregate_grouped>(),
+                  has_pages_prefix<sb_column_aggregate>() && has_pages_prefix<sb_column_aggregate_grouped>() && has_pages_prefix<sb_column_topk>(),
               "every sink column begins with the seven fields of sb_column_filter, at its offsets");
 
 // The pages of a sink column as a read column (outputs: none yet)
@@ -2025,9 +2064,9 @@ static int32_t agg_check_ops(sb_ctx* ctx, const Col& c) {
     return SB_OK;
 }
 template <class Col>
-static int32_t agg_check_fill(sb_ctx* ctx, const Col& c, AggCol& g) {
-    if ((c.ops & AGG_VALUE_OPS) && !filter_comparable(c.physical_type))
-        return refuse(ctx, SB_ERR_NYI, "min / max / sum are implemented for 8- to 64-bit integers and floats");
+static int32_t agg_check_fill(sb_ctx* ctx, const Col& c, uint32_t ops, AggCol& g,   // (ops: the column's, or a top-k column's SB_AGG_MIN)
+                              const char* nyi = "min / max / sum are implemented for 8- to 64-bit integers and floats") {
+    if ((ops & AGG_VALUE_OPS) && !filter_comparable(c.physical_type)) return refuse(ctx, SB_ERR_NYI, nyi);
     uint64_t rows = 0;
     if (!column_rows(c, &rows)) return refuse(ctx, SB_ERR_INVALID, "metas is null");
     if (c.selection && (((uintptr_t)c.selection & 3) || c.selection_capacity < (rows + 31) / 32 * 4))
@@ -2035,7 +2074,7 @@ static int32_t agg_check_fill(sb_ctx* ctx, const Col& c, AggCol& g) {
     memset(&g, 0, sizeof g);
     g.sel = (const uint32_t*)c.selection;
     g.rows = rows;
-    g.ops = c.ops;
+    g.ops = ops;
     g.ptype = c.physical_type;
     g.w = type_width(c.physical_type);
     g.kind = value_kind(c.physical_type);
@@ -2048,6 +2087,22 @@ static std::vector<uint64_t> agg_stage_caps(const std::vector<AggCol>& hs) {
     std::vector<uint64_t> cap(hs.size());
     for (size_t i = 0; i < hs.size(); i++) cap[i] = (hs[i].ops & AGG_VALUE_OPS) ? hs[i].rows * hs[i].w : NO_SHARE;
     return cap;
+}
+
+// The decoded columns of a replay as the plain kernels of the aggregate, grouped and top-k sinks take them: values and
+// validity of each, and its slots in its AggCol -- one per TILE_ROWS rows, the columns' back to back.  Returns the slots.
+static uint64_t replay_slots(const sb_column_read* rr, const std::vector<uint64_t>& rows, std::vector<AggCol>& hs, std::vector<const uint8_t*>& vals,
+                             std::vector<const uint8_t*>& bits) {
+    uint64_t slots = 0;
+    for (size_t i = 0; i < hs.size(); i++) {
+        vals[i] = (const uint8_t*)rr[i].values;
+        bits[i] = rr[i].is_nullable ? rr[i].validity : nullptr;
+        hs[i].page_slot0 = hs[i].page_slots = 0;
+        hs[i].tile_slot0 = slots;
+        hs[i].tile_slots = (rows[i] + TILE_ROWS - 1) / TILE_ROWS;
+        slots += hs[i].tile_slots;
+    }
+    return slots;
 }
 
 // The columns with a value op of a replayed call: decoded, and reduced from the staging area by k_agg_plain with the same
@@ -2064,16 +2119,8 @@ static int32_t agg_columns_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pa
     const size_t o_res = off;
     off = align_up(off + n * AGG_RESULT_WORDS * sizeof(uint64_t), 64);
     const size_t o_parts = off;
-    uint64_t slots = 0;
     std::vector<const uint8_t*> vals(n), bits(n);
-    for (uint64_t i = 0; i < n; i++) {
-        vals[i] = (const uint8_t*)rr[i].values;
-        bits[i] = rr[i].is_nullable ? rr[i].validity : nullptr;
-        hs[i].page_slot0 = hs[i].page_slots = 0;
-        hs[i].tile_slot0 = slots;
-        hs[i].tile_slots = (rows[i] + TILE_ROWS - 1) / TILE_ROWS;
-        slots += hs[i].tile_slots;
-    }
+    const uint64_t slots = replay_slots(rr, rows, hs, vals, bits);
     off += (size_t)slots * sizeof(AggPart);
     uint8_t* dev = nullptr;
     if (hipMalloc((void**)&dev, off + 64) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(aggregate replay) failed");
@@ -2093,7 +2140,7 @@ int32_t sb_aggregate_columns(sb_ctx* ctx, sb_column_aggregate* cols, uint64_t n,
     if (!sink_entry(ctx, cols, n, mem, "sb_aggregate_columns", &rc)) return rc;
     std::vector<AggCol> hs(n);
     for (uint64_t i = 0; i < n; i++)
-        if ((rc = agg_check_ops(ctx, cols[i])) != SB_OK || (rc = agg_check_fill(ctx, cols[i], hs[i])) != SB_OK) return rc;
+        if ((rc = agg_check_ops(ctx, cols[i])) != SB_OK || (rc = agg_check_fill(ctx, cols[i], cols[i].ops, hs[i])) != SB_OK) return rc;
     (void)hipSetDevice(ctx->device);
     std::vector<sb_column_read> rc_cols(n);
     std::vector<void*> users(n);
@@ -2142,17 +2189,9 @@ static int32_t grp_columns_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pa
     int32_t rc = decode_for_replay(ctx, std::move(pages), rows.data(), "grouped aggregate", &rr);
     if (rc != SB_OK) return rc;
     uint32_t gmax = 1;
-    uint64_t slots = 0;
+    for (const GrpCol& g : hg) gmax = std::max(gmax, g.n_groups);
     std::vector<const uint8_t*> vals(n), bits(n);
-    for (uint64_t i = 0; i < n; i++) {
-        gmax = std::max(gmax, hg[i].n_groups);
-        vals[i] = (const uint8_t*)rr[i].values;
-        bits[i] = rr[i].is_nullable ? rr[i].validity : nullptr;
-        hs[i].page_slot0 = hs[i].page_slots = 0;
-        hs[i].tile_slot0 = slots;
-        hs[i].tile_slots = (rows[i] + TILE_ROWS - 1) / TILE_ROWS;
-        slots += hs[i].tile_slots;
-    }
+    const uint64_t slots = replay_slots(rr, rows, hs, vals, bits);
     // [AggCol per column][GrpCol per column][the results][the slots' flags, the columns' counters and Freq marks][the slots' records]
     const size_t res_stride = grp_result_words(gmax) * sizeof(uint64_t);
     size_t off = align_up(n * sizeof(AggCol), 64);
@@ -2191,7 +2230,7 @@ int32_t sb_aggregate_grouped(sb_ctx* ctx, sb_column_aggregate_grouped* cols, uin
         if (c.n_groups == 0 || c.n_groups > SB_AGG_MAX_GROUPS) return refuse(ctx, SB_ERR_INVALID, "n_groups is not in 1 .. SB_AGG_MAX_GROUPS");
         if (c.group_id_width != 1 && c.group_id_width != 2 && c.group_id_width != 4) return refuse(ctx, SB_ERR_INVALID, "group_id_width is not 1, 2 or 4");
         if (!c.groups) return refuse(ctx, SB_ERR_INVALID, "groups is null");
-        if ((rc = agg_check_fill(ctx, c, hs[i])) != SB_OK) return rc;
+        if ((rc = agg_check_fill(ctx, c, c.ops, hs[i])) != SB_OK) return rc;
         const uint64_t rows = hs[i].rows;
         if (rows && !c.group_ids) return refuse(ctx, SB_ERR_INVALID, "group_ids is null");
         if (c.group_ids && (((uintptr_t)c.group_ids & (c.group_id_width - 1)) || c.group_ids_capacity < rows * c.group_id_width))
@@ -2236,6 +2275,95 @@ int32_t sb_aggregate_grouped(sb_ctx* ctx, sb_column_aggregate_grouped* cols, uin
         c.selected = c.out_of_range = 0;
     }
     if (!ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::AGG_GROUPED, cols, n, sb_write_options{}, mem});
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------ top-k
+// The sibling of agg_columns_decoded: ordered from the staging area by k_topk_plain into a slot per TILE_ROWS rows, combined
+// by k_topk_finish.
+static int32_t topk_columns_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pages, std::vector<AggCol>& hs, const std::vector<TopkCol>& ht,
+                                    void* const* users) {
+    const uint64_t n = pages.size();
+    std::vector<uint64_t> rows(n);
+    for (uint64_t i = 0; i < n; i++) rows[i] = hs[i].rows;
+    const sb_column_read* rr = nullptr;
+    int32_t rc = decode_for_replay(ctx, std::move(pages), rows.data(), "top-k", &rr);
+    if (rc != SB_OK) return rc;
+    uint32_t kmax = 1;
+    for (const TopkCol& t : ht) kmax = std::max(kmax, t.k);
+    std::vector<const uint8_t*> vals(n), bits(n);
+    const uint64_t slots = replay_slots(rr, rows, hs, vals, bits);
+    // [AggCol per column][TopkCol per column][the results][the slots' headers][the slots' records]
+    const size_t res_stride = topk_result_words(kmax) * sizeof(uint64_t);
+    size_t off = align_up(n * sizeof(AggCol), 64);
+    const size_t o_tc = off;
+    off = align_up(off + n * sizeof(TopkCol), 64);
+    const size_t o_res = off;
+    off = align_up(off + n * res_stride, 64);
+    const size_t o_heads = off;
+    off = align_up(off + (size_t)slots * sizeof(TopkHead), 64);
+    const size_t o_recs = off;
+    off += (size_t)slots * kmax * sizeof(TopkRec);
+    uint8_t* dev = nullptr;
+    if (hipMalloc((void**)&dev, off + 64) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(top-k replay) failed");
+    ctx->iv.temp_dev.push_back(dev);
+    if (hipMemcpy(dev, hs.data(), n * sizeof(AggCol), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dev + o_tc, ht.data(), n * sizeof(TopkCol), hipMemcpyHostToDevice) != hipSuccess)
+        return ctx->fail(SB_ERR_EXTERNAL, "top-k replay: upload failed");
+    StageSlot* slot = acquire_slot(ctx, n * res_stride);
+    if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
+    uint64_t* d_res = (uint64_t*)(dev + o_res);
+    TopkLaunch tl{(const AggCol*)dev, (const TopkCol*)(dev + o_tc), (TopkHead*)(dev + o_heads), (TopkRec*)(dev + o_recs), slots, 0, kmax};
+    launch_topk_zero(ctx, tl);
+    launch_topk_plain(ctx, tl, (uint32_t)n, rows.data(), vals.data(), bits.data());
+    launch_topk_finish(ctx, tl, d_res, (uint32_t)n);
+    return queue_sink_results(ctx, slot, d_res, res_stride, n, Pending::TOPK_COL, users, nullptr, "top-k");
+}
+
+int32_t sb_topk_columns(sb_ctx* ctx, sb_column_topk* cols, uint64_t n, int32_t mem) {
+    int32_t rc;
+    if (!sink_entry(ctx, cols, n, mem, "sb_topk_columns", &rc)) return rc;
+    std::vector<AggCol> hs(n);
+    std::vector<TopkCol> ht(n);
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_column_topk& c = cols[i];
+        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(ctx, SB_ERR_INVALID, "bad physical_type");
+        if (c.k == 0 || c.k > SB_TOPK_MAX_K) return refuse(ctx, SB_ERR_INVALID, "k is not in 1 .. SB_TOPK_MAX_K");
+        if (c.order != SB_TOPK_SMALLEST && c.order != SB_TOPK_LARGEST) return refuse(ctx, SB_ERR_INVALID, "unknown order");
+        if (c.reserved) return refuse(ctx, SB_ERR_INVALID, "reserved is not 0");
+        if (!c.out) return refuse(ctx, SB_ERR_INVALID, "out is null");
+        // (ordered like a minimum: every value is looked at)
+        if ((rc = agg_check_fill(ctx, c, SB_AGG_MIN, hs[i], "top-k is implemented for 8- to 64-bit integers and floats")) != SB_OK) return rc;
+        ht[i] = TopkCol{c.k, c.order == SB_TOPK_LARGEST ? 1u : 0u};
+    }
+    (void)hipSetDevice(ctx->device);
+    std::vector<sb_column_read> rc_cols(n);
+    std::vector<void*> users(n);
+    for (uint64_t i = 0; i < n; i++) {
+        rc_cols[i] = read_col_of(cols[i]);
+        users[i] = &cols[i];
+    }
+    if (ctx->in_replay && ctx->filter_freq) {
+        // Every column through a full decode, as sb_aggregate_columns has it.  The result is one set in one sequence on
+        // either route, so which interval a column is decoded in does not show in its bytes.
+        rc = topk_columns_decoded(ctx, std::move(rc_cols), hs, ht, users.data());
+    } else {
+        if ((rc = stage_shares(ctx, rc_cols.data(), agg_stage_caps(hs).data(), n)) != SB_OK) return rc;
+        ReadMode mode{ReadMode::TOPK};
+        for (const TopkCol& t : ht) mode.topk_kmax = std::max(mode.topk_kmax, t.k);
+        mode.aggc = hs.data();
+        mode.topkc = ht.data();
+        mode.users = users.data();
+        mode.pending_kind = Pending::TOPK_COL;
+        rc = read_columns_impl(ctx, rc_cols.data(), n, SB_MEM_DEVICE, mode);
+    }
+    if (rc != SB_OK) return rc;
+    for (uint64_t i = 0; i < n; i++) {   // (after the last thing that can refuse the call: a page outside pages_len)
+        sb_column_topk& c = cols[i];
+        column_rows(c, &c.rows);
+        c.selected = c.count = c.nans = c.found = 0;
+    }
+    if (!ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::TOPK, cols, n, sb_write_options{}, mem});
     return rc;
 }
 

@@ -416,6 +416,35 @@ struct GrpLaunch {   // what launch_decode needs to end a call with the grouped 
     uint32_t n_cols;
     bool replayed;         // the call is issued again: its columns with a Freq page are not on this route (an error if one is)
 };
+// one column of a top-k call (sb_topk_columns, sb_topk.h), next to its AggCol, whose slots it uses.  A slot is a header and
+// `kmax` records (the call's largest k), record i of slot s at index s * kmax + i; the headers are zeroed, the records
+// are not, and a record is read only below its header's n.
+constexpr uint32_t TOPK_MAX_K = 256;               // SB_TOPK_MAX_K
+struct TopkCol {
+    uint32_t k;            // 1 .. TOPK_MAX_K
+    uint32_t largest;      // SB_TOPK_LARGEST: descending by value
+};
+struct TopkRec {           // smaller (key, row) wins
+    uint64_t key;          // the value's order key (agg_key), complemented for `largest`
+    uint64_t row;          // the row's number in the column
+};
+struct TopkHead {          // all zero: the slot was not written
+    uint64_t written;
+    uint64_t cnt, nans;    // as in AggPart
+    uint64_t n;            // records of the slot: its best min(k, cnt - nans)
+};
+// the result of a column: { selected, count, nans, found, 0, 0, 0, 0 }, then kmax entries in the layout of sb_topk_row,
+// of which the column's own k are written
+__host__ __device__ inline uint64_t topk_result_words(uint32_t kmax) { return 8 + 2ull * kmax; }
+struct TopkLaunch {   // what launch_decode needs to end a call with the top-k kernels
+    const AggCol* acols;
+    const TopkCol* tcols;
+    TopkHead* heads;       // [slots]
+    TopkRec* recs;         // [slots * kmax]
+    uint64_t slots;
+    uint64_t tile_base;    // the slot of the call's first tile (the page slots come first)
+    uint32_t kmax;
+};
 constexpr uint32_t FK_UNSIGNED = 0, FK_SIGNED = 1, FK_F32 = 2, FK_F64 = 3, FK_BYTES = 4;
 constexpr uint32_t FILTER_MASK_PREFIX = 16u;   // FilterCol.mask of SB_PRED_STARTS_WITH (the four relation bits are clear)
 // words of the bit table (a bit per dictionary entry) that a filter call reserves at the END of the aux area of every page

@@ -3126,10 +3126,11 @@ static void launch_lzg(sb_ctx* ctx, const DecodeArgs& a, bool lzg_on, InflateJob
 #include "sb_read_sel_bin.h"
 #include "sb_aggregate.h"
 #include "sb_aggregate_grouped.h"
+#include "sb_topk.h"
 namespace sb {
 
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
-                   const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp, const InCol* icols) {
+                   const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp, const InCol* icols, const TopkLaunch* topk) {
     hipStream_t s = ctx->stream;
     (void)hipMemsetAsync(a.job_counts, 0, 16 * sizeof(uint32_t), s);
     const bool qa = !(a.read_skips & RSKIP_QUEUE_A);
@@ -3218,6 +3219,10 @@ void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_p
     }
     if (grp) {   // sb_aggregate_grouped: ... to a record per column and group
         launch_grp(ctx, a, *grp);
+        return;
+    }
+    if (topk) {   // sb_topk_columns: ... to the k best rows per column
+        launch_topk(ctx, a, *topk);
         return;
     }
     // the three expand kernels work on disjoint pages (page-level RLE, tiles of primitives, tiles of binary columns): side
