@@ -227,10 +227,27 @@ int32_t sb_filter_columns(sb_ctx* ctx, sb_column_filter* cols, uint64_t n, int32
  * guess for a binary read, src/read/array/binary.rs:241).  A column that needs more raises SB_ERR_INVALID at the
  * synchronize, as sb_read_columns does for a `values` buffer that is too small.
  *
- * Refused at the call (nothing enqueued, no selection touched): STARTS_WITH on a type that is not binary, a numeric
- * literal_len that is not the type's width, a binary literal of more than 2^30 bytes, a null literal with
- * literal_len > 0 (SB_ERR_INVALID); comparisons on Boolean / Int128 / Int256 / Null, SB_MEM_HOST (SB_ERR_NYI). */
+ * Binary columns, ENDS_WITH / CONTAINS / NOT_STARTS_WITH / NOT_ENDS_WITH / NOT_CONTAINS (`LIKE '%lit'`, `LIKE '%lit%'`,
+ * `NOT LIKE ...`): everything works on bytes, which for valid UTF-8 equals a search by characters.  CONTAINS: there is
+ * an i with value[i .. i + literal_len) equal to the literal.  ENDS_WITH: the value has at least literal_len bytes and
+ * its last literal_len bytes equal the literal.  A NOT_ op selects exactly the non-null rows whose positive form is
+ * false (SET / AND / OR have no complement, and a null row must satisfy neither form, so these are ops of their own).
+ * A null row satisfies none of the five, whatever bytes its slot holds.  An empty literal: the positive forms select
+ * every non-null row, the negated forms none.  Once per Dict / Freq entry as above; on a plain page CONTAINS scans the
+ * value bytes of 4096 rows at a time, so its cost follows the bytes and not the rows.  Struct, combine modes, the zero
+ * bits behind `rows` after SET, page_offsets, stage_capacity, page errors and replays are those of STARTS_WITH.
+ *
+ * Refused at the call (nothing enqueued, no selection touched): STARTS_WITH or one of ops 11 .. 15 on a type that is
+ * not binary, ops 9 and 10 (sb_filter_columns_in) and every op above 15, a numeric literal_len that is not the type's
+ * width, a binary literal of more than 2^30 bytes, a null literal with literal_len > 0 (SB_ERR_INVALID); comparisons
+ * on Boolean / Int128 / Int256 / Null, SB_MEM_HOST (SB_ERR_NYI).  sb_filter_columns refuses ops 8 and above, and
+ * sb_filter_columns_in everything but 9 and 10. */
 #define SB_PRED_STARTS_WITH 8
+#define SB_PRED_ENDS_WITH 11          /* (9 and 10: SB_PRED_IN / SB_PRED_NOT_IN below) */
+#define SB_PRED_CONTAINS 12
+#define SB_PRED_NOT_STARTS_WITH 13
+#define SB_PRED_NOT_ENDS_WITH 14
+#define SB_PRED_NOT_CONTAINS 15
 
 typedef struct sb_column_filter_var {
     int32_t physical_type;   /* SB_TYPE_* */

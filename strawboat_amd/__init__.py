@@ -8,7 +8,7 @@ from .types import (ColumnMeta, CommonCompression, Compression, PageMeta, Physic
                     WriteOptions)
 from .context import Context  # noqa: F401
 from . import filter, read, shard, write  # noqa: F401
-from .filter import Predicate, Selection, filter_columns  # noqa: F401
+from .filter import Predicate, Selection, filter_columns, like_predicate  # noqa: F401
 from .filter_in import FilterInBatch, InList, filter_in  # noqa: F401
 from .read_selected import ReadSelectedBatch, SelectedArray, read_selected  # noqa: F401
 from .read_selected_var import ReadSelectedVarBatch, SelectedBinaryArray, read_selected_var  # noqa: F401
@@ -16,7 +16,7 @@ from .aggregate import Aggregate, AggregateBatch, aggregate_columns  # noqa: F40
 from .aggregate_grouped import GroupedAggregate, GroupedAggregateBatch, aggregate_grouped  # noqa: F401
 from .topk import TopK, TopKBatch, selection_of_rows, topk_columns  # noqa: F401
 
-__all__ = ["Context", "read", "write", "filter", "Predicate", "Selection", "filter_columns", "InList", "FilterInBatch", "filter_in", "read_selected", "ReadSelectedBatch", "SelectedArray",
+__all__ = ["Context", "read", "write", "filter", "Predicate", "Selection", "filter_columns", "like_predicate", "InList", "FilterInBatch", "filter_in", "read_selected", "ReadSelectedBatch", "SelectedArray",
            "read_selected_var", "ReadSelectedVarBatch", "SelectedBinaryArray", "aggregate_columns", "AggregateBatch", "Aggregate",
            "aggregate_grouped", "GroupedAggregateBatch", "GroupedAggregate", "topk_columns", "TopKBatch", "TopK", "selection_of_rows", "WriteOptions", "PageMeta", "ColumnMeta", "Compression",
            "CommonCompression", "PhysicalType"]

@@ -29,6 +29,8 @@ EXPORTS = ("sb_version", "sb_ctx_create", "sb_ctx_destroy", "sb_ctx_synchronize"
 SB_PRED_EQ, SB_PRED_NE, SB_PRED_LT, SB_PRED_LE, SB_PRED_GT, SB_PRED_GE, SB_PRED_IS_NULL, SB_PRED_IS_NOT_NULL = range(8)
 SB_PRED_STARTS_WITH = 8   # binary types only (sb_filter_columns_var)
 SB_PRED_IN, SB_PRED_NOT_IN = 9, 10   # sb_filter_columns_in
+# binary types only (sb_filter_columns_var)
+SB_PRED_ENDS_WITH, SB_PRED_CONTAINS, SB_PRED_NOT_STARTS_WITH, SB_PRED_NOT_ENDS_WITH, SB_PRED_NOT_CONTAINS = range(11, 16)
 SB_IN_MAX_VALUES = 1024
 SB_SEL_SET, SB_SEL_AND, SB_SEL_OR = range(3)
 SB_AGG_COUNT, SB_AGG_MIN, SB_AGG_MAX, SB_AGG_SUM = 1, 2, 4, 8

@@ -1203,6 +1203,7 @@ static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, 
         for (uint64_t i = 0; i < n; i++) {
             const bool null_op = !mode.in_list && mode.filt[i].op >= SB_PRED_IS_NULL;   // (IN / NOT_IN: searched, sb_filter_in.h)
             (null_op ? fl.any_null : mode.filt[i].kind == FK_BYTES ? fl.any_bin : fl.any_cmp) = true;
+            if (!null_op && !mode.in_list && mode.filt[i].kind == FK_BYTES && (mode.filt[i].mask & FILTER_MASK_SUB)) fl.any_sub = true;
             if (mode.filt[i].combine == SB_SEL_SET) fl.any_set = true;
         }
         const InCol* icols = mode.in_list ? (const InCol*)(ctx->tables.p + L.lits) : nullptr;
@@ -1544,6 +1545,26 @@ static int32_t filter_columns_decoded(sb_ctx* ctx, std::vector<sb_column_read>&&
     return queue_sink_results(ctx, slot, d_counts, sizeof(uint64_t), m, Pending::FILTER_COL, sel_out, nullptr, "filter");
 }
 
+// FilterCol.mask of the string ops (sb_filter_bin.h, sb_filter_sub.h); 0: not one of them
+static uint32_t filter_str_mask(int32_t op) {
+    switch (op) {
+        case SB_PRED_STARTS_WITH:
+            return FILTER_MASK_PREFIX;
+        case SB_PRED_ENDS_WITH:
+            return FILTER_MASK_SUFFIX;
+        case SB_PRED_CONTAINS:
+            return FILTER_MASK_SUBSTR;
+        case SB_PRED_NOT_STARTS_WITH:
+            return FILTER_MASK_PREFIX | FILTER_MASK_NOT;
+        case SB_PRED_NOT_ENDS_WITH:
+            return FILTER_MASK_SUFFIX | FILTER_MASK_NOT;
+        case SB_PRED_NOT_CONTAINS:
+            return FILTER_MASK_SUBSTR | FILTER_MASK_NOT;
+        default:
+            return 0;
+    }
+}
+
 // Both entry points end here.  `cols` is the call in the var layout (sb_filter_columns copies its columns into one that
 // lives for the call); results[i] are the caller's own { rows, selected } words, which outlive the call.
 static int32_t filter_impl(sb_ctx* ctx, const sb_column_filter_var* cols, uint64_t* const* results, uint64_t n) {
@@ -1553,11 +1574,12 @@ static int32_t filter_impl(sb_ctx* ctx, const sb_column_filter_var* cols, uint64
     for (uint64_t i = 0; i < n; i++) {
         sb_column_filter_var& c = work[i];
         if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(ctx, SB_ERR_INVALID, "bad physical_type");
-        if (c.op < SB_PRED_EQ || c.op > SB_PRED_STARTS_WITH) return refuse(ctx, SB_ERR_INVALID, "bad op");
+        const bool str_op = c.op == SB_PRED_STARTS_WITH || (c.op >= SB_PRED_ENDS_WITH && c.op <= SB_PRED_NOT_CONTAINS);
+        if (c.op < SB_PRED_EQ || (c.op > SB_PRED_IS_NOT_NULL && !str_op)) return refuse(ctx, SB_ERR_INVALID, "bad op");
         if (c.combine < SB_SEL_SET || c.combine > SB_SEL_OR) return refuse(ctx, SB_ERR_INVALID, "bad combine");
         const bool null_op = c.op == SB_PRED_IS_NULL || c.op == SB_PRED_IS_NOT_NULL;
         const bool bin = is_binary_t(c.physical_type);
-        if (c.op == SB_PRED_STARTS_WITH && !bin) return refuse(ctx, SB_ERR_INVALID, "STARTS_WITH needs a Binary / LargeBinary column");
+        if (str_op && !bin) return refuse(ctx, SB_ERR_INVALID, "STARTS_WITH / ENDS_WITH / CONTAINS and their NOT_ forms need a Binary / LargeBinary column");
         if (!null_op && !bin && !filter_comparable(c.physical_type))
             return refuse(ctx, SB_ERR_NYI, "comparison predicates are implemented for 8- to 64-bit integers, floats and binary types");
         if (!null_op) {
@@ -1590,12 +1612,13 @@ static int32_t filter_impl(sb_ctx* ctx, const sb_column_filter_var* cols, uint64
         FilterCol& f = hf[i];
         memset(&f, 0, sizeof f);
         f.sel = (uint32_t*)c.selection;
-        f.op = c.op == SB_PRED_STARTS_WITH ? (uint32_t)SB_PRED_EQ : (uint32_t)c.op;   // (the kernels tell null tests by op >= IS_NULL; a prefix test by its mask)
+        const uint32_t str_mask = filter_str_mask(c.op);
+        f.op = str_mask ? (uint32_t)SB_PRED_EQ : (uint32_t)c.op;   // (the kernels tell null tests by op >= IS_NULL; a prefix / suffix / substring test by its mask)
         f.combine = (uint32_t)c.combine;
         f.ptype = c.physical_type;
         if (null_op) continue;
         static const uint32_t MASKS[6] = {2u, 13u, 1u, 3u, 4u, 6u};   // EQ NE LT LE GT GE over (less, equal, greater, unordered)
-        f.mask = c.op == SB_PRED_STARTS_WITH ? FILTER_MASK_PREFIX : MASKS[c.op];
+        f.mask = str_mask ? str_mask : MASKS[c.op];
         if (is_binary_t(c.physical_type)) {
             f.kind = FK_BYTES;
             f.lit_len = (uint32_t)c.literal_len;

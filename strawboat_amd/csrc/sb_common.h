@@ -294,6 +294,7 @@ struct FilterLaunch {   // what launch_decode needs to end a call with the filte
     uint64_t* counts;      // [n_cols]: bits set per column
     bool any_cmp, any_null, any_set;
     bool any_bin;          // comparison columns of a binary type: k_filter_bin_base / _entries / k_filter_bin (sb_filter_bin.h)
+    bool any_sub = false;  // ... with a FILTER_MASK_SUB bit among them: k_filter_sub_entries / k_filter_sub as well (sb_filter_sub.h)
 };
 // one column of an IN / NOT IN call (sb_filter_columns_in, sb_filter_in.h), next to its FilterCol: the literals as a sorted
 // set without duplicates, in the call's tables.  FilterCol.op is SB_PRED_IN / SB_PRED_NOT_IN, FilterCol.kind as ever.
@@ -447,6 +448,9 @@ struct TopkLaunch {   // what launch_decode needs to end a call with the top-k k
 };
 constexpr uint32_t FK_UNSIGNED = 0, FK_SIGNED = 1, FK_F32 = 2, FK_F64 = 3, FK_BYTES = 4;
 constexpr uint32_t FILTER_MASK_PREFIX = 16u;   // FilterCol.mask of SB_PRED_STARTS_WITH (the four relation bits are clear)
+// ... of SB_PRED_ENDS_WITH, SB_PRED_CONTAINS and, ORed onto one of the three, of the NOT_ forms (sb_filter_sub.h)
+constexpr uint32_t FILTER_MASK_SUFFIX = 32u, FILTER_MASK_SUBSTR = 64u, FILTER_MASK_NOT = 128u;
+constexpr uint32_t FILTER_MASK_SUB = FILTER_MASK_SUFFIX | FILTER_MASK_SUBSTR | FILTER_MASK_NOT;   // a column of sb_filter_sub.h
 // words of the bit table (a bit per dictionary entry) that a filter call reserves at the END of the aux area of every page
 // of a binary comparison column: an entry is a u64 length and its bytes, so a page of L bytes has at most L / 8 of them
 __host__ __device__ inline uint64_t filter_bin_table_words(uint64_t page_len) { return (page_len / 256 + 4) & ~3ull; }

@@ -3121,6 +3121,7 @@ static void launch_lzg(sb_ctx* ctx, const DecodeArgs& a, bool lzg_on, InflateJob
 }  // namespace sb
 #include "sb_filter.h"
 #include "sb_filter_bin.h"
+#include "sb_filter_sub.h"
 #include "sb_filter_in.h"
 #include "sb_read_sel.h"
 #include "sb_read_sel_bin.h"

@@ -321,6 +321,8 @@ __global__ void __launch_bounds__(WG) k_filter_clear(const ColDesc* cols, const 
 }
 
 void launch_filter_bin(sb_ctx* ctx, const DecodeArgs& a, const FilterCol* fcols);   // sb_filter_bin.h
+void launch_filter_sub_entries(sb_ctx* ctx, const DecodeArgs& a, const FilterCol* fcols);   // sb_filter_sub.h
+void launch_filter_sub(sb_ctx* ctx, const DecodeArgs& a, const FilterCol* fcols);
 void launch_filter(sb_ctx* ctx, const DecodeArgs& a, const FilterLaunch& fl) {
     hipStream_t s = ctx->stream;
     const FilterCol* fcols = fl.fcols;
@@ -343,7 +345,9 @@ void launch_filter(sb_ctx* ctx, const DecodeArgs& a, const FilterLaunch& fl) {
         KScope k(ctx, "k_filter");
         k_filter<<<min(a.n_tiles, TILE_GRID), WG, 0, s>>>(a, fcols);
     }
+    if (fl.any_sub) launch_filter_sub_entries(ctx, a, fcols);   // (the bit tables k_filter_bin reads)
     if (fl.any_bin) launch_filter_bin(ctx, a, fcols);
+    if (fl.any_sub) launch_filter_sub(ctx, a, fcols);
     KScope k(ctx, "k_filter_count");
     k_filter_count<<<a.n_cols, WG, 0, s>>>(a.cols, fcols, counts);
 }

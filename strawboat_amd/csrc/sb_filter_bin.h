@@ -2,7 +2,9 @@
 // whose sink — filter_span / sel_put — every kernel here ends in).
 //
 // Values compare with the column's literal as byte strings: bytes unsigned, lexicographic, a proper prefix less than the
-// longer string; STARTS_WITH beside the six orderings (FilterCol.mask == FILTER_MASK_PREFIX).
+// longer string; STARTS_WITH beside the six orderings (FilterCol.mask == FILTER_MASK_PREFIX).  ENDS_WITH, CONTAINS and the
+// NOT_ forms (a FILTER_MASK_SUB bit in the mask) have kernels of their own, sb_filter_sub.h: only the row lookups of their
+// Dict / Freq pages are done here.
 //   Dict, Freq (a virtual Dict page,  k_filter_bin_entries evaluates the predicate ONCE PER ENTRY of every such page of the
 //   k_plan)                           call (a lane per entry, the entry found through k_plan's offset table) into a bit table
 //                                     at the end of the page's aux area; k_filter_bin then looks a bit up per row: the tile's
@@ -123,6 +125,7 @@ __global__ void __launch_bounds__(WG) k_filter_bin_entries(DecodeArgs a, const F
     if (!is_binary(a.cols[t.col].ptype)) return;
     const FilterCol f = fcols[t.col];
     if (f.kind != FK_BYTES) return;
+    if (f.mask & FILTER_MASK_SUB) return;   // (k_filter_sub_entries)
     BinDict bd;
     if (!bin_dict(a, t, d, &bd)) {
         if (threadIdx.x == 0 && blockIdx.y == 0) raise(a.status, SB_ERR_INVALID, p, 220);
@@ -178,10 +181,12 @@ __device__ void filter_bin_tile(const DecodeArgs& a, const FilterCol* fcols, uin
     const FilterSink k{f.sel, d.def_bits, t.out_row, t.num_values, f.combine};
     const BinLit lit = bin_lit(f);
     if (is_basic(d.codec)) {
+        if (lit.mask & FILTER_MASK_SUB) return;   // (k_filter_sub)
         const uint8_t* vals = d.codec == SB_CODEC_NONE ? d.vbody : c.values + d.val_base;
         if (c.ptype == SB_TYPE_BINARY) filter_bin_basic<int32_t>(k, lo, hi, d.src, vals, d.vusize, lit);
         else filter_bin_basic<int64_t>(k, lo, hi, d.src, vals, d.vusize, lit);
     } else if (d.codec == SB_CODEC_ONEVALUE) {
+        if (lit.mask & FILTER_MASK_SUB) return;   // (k_filter_sub)
         const bool v = bin_eval(d.dict, d.dict_n, lit);
         filter_span(k, lo, hi, [&](uint64_t) { return v; });
     } else if (d.codec == SB_CODEC_DICT || d.codec == SB_CODEC_FREQ) {

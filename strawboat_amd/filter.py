@@ -5,7 +5,8 @@ the pages of `x` and `s` gives one bit per row (LSB-first, like an Arrow validit
 number of bits set, without the decoded values ever being written to memory
 (sb_filter_columns_var in include/strawboat_hip.h).  Null rows satisfy no comparison; floats
 compare as IEEE 754; Binary / Utf8 values compare as byte strings (bytes unsigned, a proper
-prefix is less), and have "starts_with" beside the six orderings.
+prefix is less), and have "starts_with", "ends_with", "contains" and their "not_" forms beside
+the six orderings (like_predicate maps the LIKE patterns these serve onto them).
 """
 import ctypes as C
 import math
@@ -20,7 +21,10 @@ from .types import PhysicalType
 
 OPS = {"eq": N.SB_PRED_EQ, "ne": N.SB_PRED_NE, "lt": N.SB_PRED_LT, "le": N.SB_PRED_LE, "gt": N.SB_PRED_GT,
        "ge": N.SB_PRED_GE, "is_null": N.SB_PRED_IS_NULL, "is_not_null": N.SB_PRED_IS_NOT_NULL,
-       "starts_with": N.SB_PRED_STARTS_WITH}
+       "starts_with": N.SB_PRED_STARTS_WITH, "ends_with": N.SB_PRED_ENDS_WITH, "contains": N.SB_PRED_CONTAINS,
+       "not_starts_with": N.SB_PRED_NOT_STARTS_WITH, "not_ends_with": N.SB_PRED_NOT_ENDS_WITH,
+       "not_contains": N.SB_PRED_NOT_CONTAINS}
+STRING_OPS = ("starts_with", "ends_with", "contains", "not_starts_with", "not_ends_with", "not_contains")
 COMBINE = {"set": N.SB_SEL_SET, "and": N.SB_SEL_AND, "or": N.SB_SEL_OR}
 
 _P = PhysicalType
@@ -73,8 +77,9 @@ _WIDTH = {_P.INT8: 1, _P.UINT8: 1, _P.INT16: 2, _P.UINT16: 2, _P.INT32: 4, _P.UI
 def literal_bytes(physical_type, op, value) -> bytes:
     """The literal of sb_column_filter_var: exactly the type's width for a number (pack_literal's
     rules), the bytes themselves for a Binary / LargeBinary column (`str` is encoded as UTF-8).
-    A bytes / str literal on a numeric column, a number on a binary column and "starts_with" on
-    a numeric column raise ValueError."""
+    A bytes / str literal on a numeric column, a number on a binary column and a string op
+    ("starts_with", "ends_with", "contains" and their "not_" forms) on a numeric column raise
+    ValueError."""
     if op in ("is_null", "is_not_null"):
         return b""
     if physical_type in _BINARY:
@@ -83,16 +88,18 @@ def literal_bytes(physical_type, op, value) -> bytes:
         if isinstance(value, (bytes, bytearray, memoryview)):
             return bytes(value)
         raise ValueError("literal %r is not bytes or str, the column is a binary column" % (value,))
-    if op == "starts_with":
-        raise ValueError("starts_with needs a Binary / LargeBinary column, not physical type %d" % physical_type)
+    if op in STRING_OPS:
+        raise ValueError("%s needs a Binary / LargeBinary column, not physical type %d" % (op, physical_type))
     if isinstance(value, (str, bytes, bytearray, memoryview)):
         raise ValueError("literal %r is not a number" % (value,))
     return pack_literal(physical_type, value)[:_WIDTH[physical_type]]
 
 
 class Predicate:
-    """op: "eq" "ne" "lt" "le" "gt" "ge" (with a literal), "starts_with" (binary columns, with a
-    bytes / str literal) or "is_null" "is_not_null" (without)."""
+    """op: "eq" "ne" "lt" "le" "gt" "ge" (with a literal), "starts_with" "ends_with" "contains"
+    "not_starts_with" "not_ends_with" "not_contains" (binary columns, with a bytes / str literal;
+    a "not_" op selects the non-null rows whose positive form is false) or "is_null"
+    "is_not_null" (without)."""
 
     def __init__(self, op, literal=None):
         if op not in OPS:
@@ -107,6 +114,56 @@ class Predicate:
 
     def __repr__(self):
         return "Predicate(%r, %r)" % (self.op, self.literal)
+
+
+def like_predicate(pattern, negate=False, escape="\\") -> Predicate:
+    """The Predicate of SQL's `col LIKE pattern` (`NOT LIKE` with negate) for the patterns the
+    device serves: 'lit' -> eq (ne), 'lit%' -> starts_with, '%lit' -> ends_with, '%lit%' ->
+    contains (the "not_" ops when negated), '%' / '%%' -> starts_with b"" (every non-null row).
+    `escape` + '%', '_' or the escape character itself is that character, literally.  Every other
+    pattern, which means a '%' inside the literal or an unescaped '_', raises NotImplementedError.
+    Runs on the host only; `pattern` is str or bytes, and so is the literal."""
+    is_str = isinstance(pattern, str)
+    if not is_str and not isinstance(pattern, (bytes, bytearray, memoryview)):
+        raise ValueError("pattern %r is not str or bytes" % (pattern,))
+    text = pattern if is_str else bytes(pattern).decode("latin-1")   # (one character per byte, mapped back below)
+    esc = escape if isinstance(escape, str) else bytes(escape).decode("latin-1")
+    if len(esc) != 1:
+        raise ValueError("escape must be one character")
+    lit, wild = [], []   # the literal's characters; positions in `lit` where a '%' stands in front
+    i = 0
+    while i < len(text):
+        ch = text[i]
+        if ch == esc:
+            if i + 1 >= len(text) or text[i + 1] not in ("%", "_", esc):
+                raise ValueError("pattern %r: the escape character must be followed by %%, _ or itself" % (pattern,))
+            lit.append(text[i + 1])
+            i += 2
+            continue
+        if ch == "_":
+            raise NotImplementedError("LIKE pattern %r: '_' is not served on the device" % (pattern,))
+        if ch == "%":
+            wild.append(len(lit))
+        else:
+            lit.append(ch)
+        i += 1
+    if any(0 < w < len(lit) for w in wild):
+        raise NotImplementedError("LIKE pattern %r: a '%%' inside the literal is not served on the device" % (pattern,))
+    literal = "".join(lit)
+    literal = literal if is_str else literal.encode("latin-1")
+    head = bool(wild) and wild[0] == 0
+    tail = bool(wild) and wild[-1] == len(lit)
+    if not lit and wild:
+        op = "starts_with"   # matches every non-null row
+    elif head and tail:
+        op = "contains"
+    elif head:
+        op = "ends_with"
+    elif tail:
+        op = "starts_with"
+    else:
+        return Predicate("ne" if negate else "eq", literal)
+    return Predicate("not_" + op if negate else op, literal)
 
 
 class Selection:
