@@ -638,6 +638,75 @@ typedef struct sb_column_topk {
 
 int32_t sb_topk_columns(sb_ctx* ctx, sb_column_topk* cols, uint64_t n, int32_t mem);
 
+/* ------------------------------------------------------------------ key ids
+ * SELECT ... GROUP BY k / SELECT DISTINCT k WHERE ...  The pages of an INTEGER key column and (optionally) a selection
+ * bitmap go in; the distinct values of the live rows come back in `keys` (HOST), and every row of the column gets a dense
+ * id in `ids` (DEVICE): the link between sb_filter_columns* and sb_aggregate_grouped, whose group ids these are.
+ *
+ *   live rows     a row is live if its selection bit is set and it is not null, exactly as for sb_aggregate_columns;
+ *                 rows / selected / count mean what they mean there.
+ *   keys          the distinct values of the live rows, ascending by the physical type's signedness; n_keys of them.  Key i
+ *                 is written like sb_topk_row.value: the value's bytes, little endian, in the first `width` bytes of the
+ *                 8-byte slot keys[8 * i ..], and 0 behind them.  keys[n_keys .. max_keys) is written as zero.
+ *   ids           one unsigned integer of id_width bytes per row of the column, all `rows` of them written: the position
+ *                 of the row's value in `keys`, or all ones (SB_KEY_ID_NONE truncated to id_width) for a row that is not
+ *                 live.  The sorted order makes the ids a function of the data alone: the same bytes every time the call
+ *                 is issued, a replayed interval included, whatever the schedule.  Handed to sb_aggregate_grouped
+ *                 unchanged (group_id_width = id_width, n_groups >= n_keys), its out_of_range counts the selected rows
+ *                 that are null.
+ *   max_keys      1 .. min(SB_KEY_MAX_KEYS, 2^(8 * id_width) - 1): with id_width 1 at most 255, so that all ones is no id.
+ *   overflow      the live rows have more than max_keys distinct values: overflow = 1 and the synchronize still returns
+ *                 SB_OK (an engine probes a column's cardinality this way and falls back); n_keys, `keys` and `ids` are
+ *                 unspecified then.  Otherwise 0.  Either way no byte behind keys[max_keys) or behind ids_capacity is
+ *                 touched.
+ *
+ * Types: INT8..INT64, UINT8..UINT64.
+ *
+ * Refused at the call, nothing enqueued and no result field, byte of `keys` or byte of `ids` touched: Float32 / Float64
+ * (NaN and +-0 need a grouping rule of their own), Boolean, Int128 / Int256, Binary / LargeBinary, Null and SB_MEM_HOST
+ * (SB_ERR_NYI); id_width not 1 / 2 / 4, max_keys 0 or above its limit, `ids` null with rows > 0, misaligned or smaller
+ * than rows * id_width, `keys` null, `reserved` != 0, two columns of one call whose `ids` overlap (SB_ERR_INVALID), and
+ * every argument refusal of sb_aggregate_columns, with its code.
+ *
+ * Enqueued like sb_aggregate_columns and part of its synchronize interval in the same way: on a replay it is issued again
+ * in its place, behind the filter calls that write its bitmap and in front of the sb_aggregate_grouped calls that read its
+ * ids.  A column with a primitive Freq page asks for that replay itself.  `selection` is an INPUT: it stays unmodified
+ * until the synchronize.  Page errors are the decoder's, with its codes, at the synchronize; `rows` and `selected` are
+ * delivered even when the interval failed, the other results, `keys` and `ids` are unspecified then.  The call consults no
+ * launch hint of the read path and leaves its counters alone.
+ *
+ * Layout (pinned by tests/test_key_ids_host.py): sb_column_key_ids 144 bytes; physical_type 0, is_nullable 4, pages 8,
+ * pages_len 16, metas 24, n_pages 32, page_offsets 40, selection 48, selection_capacity 56, ids 64, ids_capacity 72,
+ * id_width 80, max_keys 84, keys 88, reserved 96, rows 104, selected 112, count 120, n_keys 128, overflow 136. */
+#define SB_KEY_MAX_KEYS 1024u
+#define SB_KEY_ID_NONE 0xFFFFFFFFu
+
+typedef struct sb_column_key_ids {
+    int32_t physical_type;   /* SB_TYPE_* */
+    int32_t is_nullable;
+    const uint8_t* pages;    /* DEVICE, at any byte alignment */
+    uint64_t pages_len;
+    const sb_page_meta* metas; /* HOST */
+    uint64_t n_pages;
+    const uint64_t* page_offsets; /* optional (HOST), as in sb_column_read */
+    const uint8_t* selection;     /* DEVICE, input: as in sb_column_aggregate; NULL = every row */
+    uint64_t selection_capacity;
+    void* ids;               /* DEVICE, output: one id per row, aligned to id_width */
+    uint64_t ids_capacity;   /* >= rows * id_width bytes */
+    uint32_t id_width;       /* 1, 2 or 4 */
+    uint32_t max_keys;       /* 1 .. min(SB_KEY_MAX_KEYS, 2^(8 * id_width) - 1) */
+    uint8_t* keys;           /* HOST, 8 * max_keys bytes, filled at the synchronize; must live until then */
+    uint64_t reserved;       /* must be 0 */
+    /* results (HOST, valid after sb_ctx_synchronize) */
+    uint64_t rows;           /* sum of num_values */
+    uint64_t selected;       /* bits set in `selection` below `rows` (== rows without a selection) */
+    uint64_t count;          /* selected rows that are not null */
+    uint64_t n_keys;         /* distinct values among them */
+    uint64_t overflow;       /* 1: more than max_keys of them; n_keys, keys and ids are unspecified */
+} sb_column_key_ids;         /* 144 bytes */
+
+int32_t sb_key_ids(sb_ctx* ctx, sb_column_key_ids* cols, uint64_t n, int32_t mem);
+
 /* ------------------------------------------------------------------ encode
  * Replaces, per leaf column, the page loop of NativeWriter::encode_chunk
  * (src/write/common.rs:54-109): page slicing, then per page write::write -> write_simple

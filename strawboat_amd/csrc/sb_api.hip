@@ -12,7 +12,12 @@ namespace sb {
 
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
                    const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp = nullptr, const InCol* icols = nullptr,
-                   const TopkLaunch* topk = nullptr);
+                   const TopkLaunch* topk = nullptr, const KeyLaunch* keys = nullptr);
+void launch_key_zero(sb_ctx* ctx, const KeyLaunch& kl);
+void launch_key_finish(sb_ctx* ctx, const KeyLaunch& kl, uint64_t* results);
+void launch_key_assign(sb_ctx* ctx, const DecodeArgs& a, const KeyLaunch& kl);
+void launch_key_collect_plain(sb_ctx* ctx, const KeyLaunch& kl, const uint64_t* rows, const uint8_t* const* values, const uint8_t* const* validity);
+void launch_key_assign_plain(sb_ctx* ctx, const KeyLaunch& kl, const uint64_t* rows, const uint8_t* const* values, const uint8_t* const* validity);
 void launch_topk_zero(sb_ctx* ctx, const TopkLaunch& tl);
 void launch_topk_finish(sb_ctx* ctx, const TopkLaunch& tl, uint64_t* results, uint32_t n_cols);
 void launch_topk_plain(sb_ctx* ctx, const TopkLaunch& tl, uint32_t n_cols, const uint64_t* rows, const uint8_t* const* values,
@@ -104,7 +109,7 @@ StageSlot* acquire_slot(sb_ctx* ctx, size_t need) {
     if (s.host)
         for (auto& p : ctx->iv.pending) {
             if (p.host < s.host || p.host >= s.host + s.cap) continue;
-            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::AGG_COL ? AGG_RESULT_WORDS * 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R || p.kind == Pending::AGG_GRP_COL || p.kind == Pending::TOPK_COL) ? (size_t)p.bytes
+            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::AGG_COL ? AGG_RESULT_WORDS * 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R || p.kind == Pending::AGG_GRP_COL || p.kind == Pending::TOPK_COL || p.kind == Pending::KEY_COL) ? (size_t)p.bytes
                                                                                                    : (size_t)(2 * p.n + 1) * 8;
             ctx->iv.rescued.emplace_back(p.host, p.host + nb);
             p.host = ctx->iv.rescued.back().data();
@@ -239,7 +244,8 @@ struct ReadMode {
     // sb_aggregate_columns, whose columns end in the aggregate kernels
     // / sb_aggregate_grouped, an aggregate call whose columns end in the grouped aggregate kernels
     // / sb_topk_columns, an aggregate call whose columns end in the top-k kernels
-    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR, AGGREGATE, AGG_GROUPED, TOPK } kind;
+    // / sb_key_ids, an aggregate call whose columns end in the key kernels: two walks, the finish between them
+    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR, AGGREGATE, AGG_GROUPED, TOPK, KEY_IDS } kind;
     const FilterCol* filt = nullptr;             // FILTER: one per column
     const std::vector<uint8_t>* lits = nullptr;  // ... the literals of the FK_BYTES columns, FilterCol.lit being the offset of each
     bool in_list = false;                        // ... sb_filter_columns_in: `lits` begins with an InCol per column, whose pointers are offsets in `lits`
@@ -252,14 +258,18 @@ struct ReadMode {
     uint32_t grp_gmax = 0;                       // ... the largest n_groups of the call: records per slot
     const TopkCol* topkc = nullptr;              // TOPK: one per column beside aggc
     uint32_t topk_kmax = 0;                      // ... the largest k of the call: records per slot
+    const KeyCol* keyc = nullptr;                // KEY_IDS: one per column beside aggc
+    uint32_t key_kmax = 0;                       // ... the largest max_keys of the call: key slots per result
+    uint64_t key_slots = 0;                      // ... the slots of the columns' tables together
     // Where a column's result goes at the synchronize, as Pending has it (sb_host.h): users[i] beside pending_kind.  Set by
     // the entry points of the sinks: the callers' structs, for a filter call the caller's `selected` (results[i] + 1).
     // Null for the other kinds of call, whose results go to the sb_column_read structs of the call itself.
     void* const* users = nullptr;
     Pending::Kind pending_kind = Pending::READ_COL;
-    bool aggregate() const { return kind == AGGREGATE || kind == AGG_GROUPED || kind == TOPK; }   // an AggCol per column, slots per page part and tile
+    bool aggregate() const { return kind == AGGREGATE || kind == AGG_GROUPED || kind == TOPK || kind == KEY_IDS; }   // an AggCol per column, slots per page part and tile
     bool grouped() const { return kind == AGG_GROUPED; }
     bool topk() const { return kind == TOPK; }
+    bool key_ids() const { return kind == KEY_IDS; }
     bool filter() const { return kind == FILTER; }
     bool selected() const { return kind == SELECTED; }
     bool selected_var() const { return kind == SELECTED_VAR; }
@@ -271,9 +281,9 @@ struct ReadMode {
     bool sink() const { return kind == FILTER || kind == SELECTED || kind == SELECTED_VAR || aggregate(); }
     // words of 8 bytes that come back per column: { selected, values_len } for a SELECTED_VAR call, the result record of
     // an AGGREGATE call, the header and the gmax group records of an AGG_GROUPED call, the header and the kmax entries of
-    // a TOPK call
+    // a TOPK call, the header and the kmax key slots of a KEY_IDS call
     uint64_t result_words() const {
-        return kind == SELECTED_VAR ? 2 : kind == AGGREGATE ? AGG_RESULT_WORDS : kind == AGG_GROUPED ? grp_result_words(grp_gmax) : kind == TOPK ? topk_result_words(topk_kmax) : 1;
+        return kind == SELECTED_VAR ? 2 : kind == AGGREGATE ? AGG_RESULT_WORDS : kind == AGG_GROUPED ? grp_result_words(grp_gmax) : kind == TOPK ? topk_result_words(topk_kmax) : kind == KEY_IDS ? key_result_words(key_kmax) : 1;
     }
 };
 static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, const ReadMode& mode);
@@ -520,6 +530,19 @@ static void deliver_topk_col(const Pending& p, bool ok) {
     // (k as the struct has it now, but never more than the record that was enqueued holds: header + kmax entries)
     memcpy(c->out, p.host + sizeof head, std::min<size_t>((size_t)c->k * sizeof(sb_topk_row), (size_t)p.bytes - sizeof head));
 }
+// k_key_finish's header and key slots (sb_key_ids.h); `ok` false: the interval failed, selected alone
+static void deliver_key_col(const Pending& p, bool ok) {
+    uint64_t head[8];
+    memcpy(head, p.host, sizeof head);
+    sb_column_key_ids* c = (sb_column_key_ids*)p.user;
+    c->selected = head[0];
+    if (!ok) return;
+    c->count = head[1];
+    c->n_keys = head[2];
+    c->overflow = head[3];
+    // (max_keys as the struct has it now, but never more than the record that was enqueued holds: header + kmax slots)
+    memcpy(c->keys, p.host + sizeof head, std::min<size_t>((size_t)c->max_keys * 8, (size_t)p.bytes - sizeof head));
+}
 static void deliver_write_col(const Pending& p) {
     sb_column_write* c = (sb_column_write*)p.user;
     const uint64_t* lens = (const uint64_t*)p.host;  // [n_pages lengths][n_pages num_values][total]
@@ -550,6 +573,7 @@ static void deliver_pending(sb_ctx* ctx, const Pending& p, int32_t rc) {
         case Pending::AGG_COL: deliver_agg_col(p); break;
         case Pending::AGG_GRP_COL: deliver_agg_grp_col(p, rc == SB_OK); break;
         case Pending::TOPK_COL: deliver_topk_col(p, rc == SB_OK); break;
+        case Pending::KEY_COL: deliver_key_col(p, rc == SB_OK); break;
         case Pending::WRITE_COL: deliver_write_col(p); break;
         case Pending::ENC_HINT:
             if (rc == SB_OK) apply_enc_hint(ctx, p);
@@ -800,7 +824,7 @@ static ReadHints read_hints(sb_ctx* ctx, const ReadMode& mode, const ReadShape& 
 // Where the call's tables sit, on the device (ctx->tables) and — up to `upload` — in the staging slot, whose next n words
 // receive the results.  A pure function of shape, hints and mode.
 struct ReadLayout {
-    size_t cols, tasks, fcols, bcols, lits, upload, descs, tiles, jobs_a, jobs_b, jobs_z, counts, vlen, zb_counts, zb_frames, zs, rle, bpg, aggp, grp_recs, topk_recs, total;
+    size_t cols, tasks, fcols, bcols, lits, upload, descs, tiles, jobs_a, jobs_b, jobs_z, counts, vlen, zb_counts, zb_frames, zs, rle, bpg, aggp, grp_recs, topk_recs, key_sorted, total;
     size_t job_cap;        // queue entries: 2 per page + room for the frames of Zstd buffers that are several frames (one entry per frame)
     bool want_z;           // queue Z (calls with binary columns that produce values): Zstd payloads known to k_parse, entropy stages with queue A's
     uint64_t zs_seg_cap;
@@ -823,6 +847,7 @@ static ReadLayout read_layout(uint64_t n, const ReadShape& sh, const ReadHints& 
     if (mode.selected_var()) off = align_up(off + n * sizeof(SelBin), 64);
     if (mode.grouped()) off = align_up(off + n * sizeof(GrpCol), 64);   // (in the SelBins' place)
     if (mode.topk()) off = align_up(off + n * sizeof(TopkCol), 64);     // (likewise)
+    if (mode.key_ids()) off = align_up(off + n * sizeof(KeyCol), 64);   // (likewise)
     L.lits = off;
     if (mode.lits) off = align_up(off + mode.lits->size(), 64);
     L.upload = off;
@@ -863,6 +888,9 @@ static ReadLayout read_layout(uint64_t n, const ReadShape& sh, const ReadHints& 
     // a TOPK call: a header per slot (zeroed), then kmax records per slot (not zeroed)
     L.topk_recs = align_up(off + (P * L.rle_parts + sh.T) * sizeof(TopkHead), 64);
     if (mode.topk()) off = align_up(L.topk_recs + (P * L.rle_parts + sh.T) * mode.topk_kmax * sizeof(TopkRec), 64);
+    // a KEY_IDS call: a state per column and the columns' tables (zeroed), then KEY_MAX_KEYS sorted keys per column (not zeroed)
+    L.key_sorted = align_up(off + n * sizeof(KeyState) + mode.key_slots * sizeof(uint64_t), 64);
+    if (mode.key_ids()) off = align_up(L.key_sorted + n * KEY_MAX_KEYS * sizeof(uint64_t), 64);
     L.total = off;
     return L;
 }
@@ -998,6 +1026,7 @@ static int32_t fill_read_tables(sb_ctx* ctx, uint8_t* host, const ReadLayout& L,
         }
         if (mode.grouped()) memcpy(host + L.bcols, mode.grpc, n * sizeof(GrpCol));
         if (mode.topk()) memcpy(host + L.bcols, mode.topkc, n * sizeof(TopkCol));
+        if (mode.key_ids()) memcpy(host + L.bcols, mode.keyc, n * sizeof(KeyCol));
     }
     SelCol* hsc = mode.ranked() ? (SelCol*)(host + L.fcols) : nullptr;
     for (uint64_t i = 0; hsc && i < n; i++) {   // the rank tables: behind the pages' areas, sized by the rows
@@ -1238,6 +1267,15 @@ static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, 
         if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, nullptr, nullptr, nullptr, nullptr, &tl);
         // (a call without a page still has a result: selected, and an `out` of zeros)
         launch_topk_finish(ctx, tl, d_vlen, (uint32_t)n);
+    } else if (mode.key_ids()) {
+        KeyLaunch kl{(const AggCol*)(ctx->tables.p + L.fcols), (const KeyCol*)(ctx->tables.p + L.bcols), (KeyState*)(ctx->tables.p + L.aggp),
+                     (uint64_t*)(ctx->tables.p + L.aggp + n * sizeof(KeyState)), (uint64_t*)(ctx->tables.p + L.key_sorted),
+                     n * sizeof(KeyState) + mode.key_slots * sizeof(uint64_t), mode.key_kmax, (uint32_t)n};
+        launch_key_zero(ctx, kl);
+        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &kl);
+        // (a call without a page still has a result: selected, and `keys` of zeros)
+        launch_key_finish(ctx, kl, d_vlen);
+        if (sh.P) launch_key_assign(ctx, a, kl);
     } else if (mode.aggregate()) {
         AggLaunch al{(const AggCol*)(ctx->tables.p + L.fcols), (AggPart*)(ctx->tables.p + L.aggp), sh.P * L.rle_parts, false, false};
         for (uint64_t i = 0; i < n; i++) ((mode.aggc[i].ops & AGG_VALUE_OPS) ? al.any_val : al.any_null) = true;
@@ -1271,6 +1309,7 @@ static void push_pending(sb_ctx* ctx, Pending::Kind kind, void* const* users, co
         pd.n = 0;
         if (grpc) pd.bytes = sizeof(uint64_t) * grp_result_words(grpc[i].n_groups);
         if (kind == Pending::TOPK_COL) pd.bytes = stride;   // (the header and kmax entries: the column's own k is in its struct)
+        if (kind == Pending::KEY_COL) pd.bytes = stride;    // (likewise: the header and kmax key slots)
         ctx->iv.pending.push_back(pd);
     }
 }
@@ -1420,7 +1459,8 @@ constexpr bool has_pages_prefix() {
 }
 static_assert(offsetof(sb_column_filter, page_offsets) == 40, "the pages of a sink column: 48 bytes");
 static_assert(has_pages_prefix<sb_column_filter_var>() && has_pages_prefix<sb_column_read_selected>() && has_pages_prefix<sb_column_read_selected_var>() &&
-                  has_pages_prefix<sb_column_aggregate>() && has_pages_prefix<sb_column_aggregate_grouped>() && has_pages_prefix<sb_column_topk>(),
+                  has_pages_prefix<sb_column_aggregate>() && has_pages_prefix<sb_column_aggregate_grouped>() && has_pages_prefix<sb_column_topk>() &&
+                  has_pages_prefix<sb_column_key_ids>(),
               "every sink column begins with the seven fields of sb_column_filter, at its offsets");
 
 // The pages of a sink column as a read column (outputs: none yet)
@@ -2387,6 +2427,117 @@ int32_t sb_topk_columns(sb_ctx* ctx, sb_column_topk* cols, uint64_t n, int32_t m
         c.selected = c.count = c.nans = c.found = 0;
     }
     if (!ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::TOPK, cols, n, sb_write_options{}, mem});
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------ key ids
+static KeyLaunch key_launch_at(uint8_t* acols, uint8_t* kcols, uint8_t* state, uint8_t* sorted, uint64_t n, uint64_t slots, uint32_t kmax) {
+    return KeyLaunch{(const AggCol*)acols, (const KeyCol*)kcols, (KeyState*)state, (uint64_t*)(state + n * sizeof(KeyState)), (uint64_t*)sorted,
+                     n * sizeof(KeyState) + slots * sizeof(uint64_t), kmax, (uint32_t)n};
+}
+
+// The sibling of topk_columns_decoded: the three phases from the staging area, k_key_collect_plain and k_key_assign_plain
+// around the same k_key_finish.
+static int32_t key_ids_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pages, std::vector<AggCol>& hs, const std::vector<KeyCol>& hk, uint64_t slots,
+                               uint32_t kmax, void* const* users) {
+    const uint64_t n = pages.size();
+    std::vector<uint64_t> rows(n);
+    for (uint64_t i = 0; i < n; i++) rows[i] = hs[i].rows;
+    const sb_column_read* rr = nullptr;
+    int32_t rc = decode_for_replay(ctx, std::move(pages), rows.data(), "key ids", &rr);
+    if (rc != SB_OK) return rc;
+    std::vector<const uint8_t*> vals(n), bits(n);
+    (void)replay_slots(rr, rows, hs, vals, bits);
+    // [AggCol per column][KeyCol per column][the results][the columns' states, their tables][the sorted keys]
+    const size_t res_stride = key_result_words(kmax) * sizeof(uint64_t);
+    size_t off = align_up(n * sizeof(AggCol), 64);
+    const size_t o_kc = off;
+    off = align_up(off + n * sizeof(KeyCol), 64);
+    const size_t o_res = off;
+    off = align_up(off + n * res_stride, 64);
+    const size_t o_state = off;
+    off = align_up(off + n * sizeof(KeyState) + (size_t)slots * sizeof(uint64_t), 64);
+    const size_t o_sorted = off;
+    off += n * KEY_MAX_KEYS * sizeof(uint64_t);
+    uint8_t* dev = nullptr;
+    if (hipMalloc((void**)&dev, off + 64) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(key ids replay) failed");
+    ctx->iv.temp_dev.push_back(dev);
+    if (hipMemcpy(dev, hs.data(), n * sizeof(AggCol), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dev + o_kc, hk.data(), n * sizeof(KeyCol), hipMemcpyHostToDevice) != hipSuccess)
+        return ctx->fail(SB_ERR_EXTERNAL, "key ids replay: upload failed");
+    StageSlot* slot = acquire_slot(ctx, n * res_stride);
+    if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
+    uint64_t* d_res = (uint64_t*)(dev + o_res);
+    const KeyLaunch kl = key_launch_at(dev, dev + o_kc, dev + o_state, dev + o_sorted, n, slots, kmax);
+    launch_key_zero(ctx, kl);
+    launch_key_collect_plain(ctx, kl, rows.data(), vals.data(), bits.data());
+    launch_key_finish(ctx, kl, d_res);
+    launch_key_assign_plain(ctx, kl, rows.data(), vals.data(), bits.data());
+    return queue_sink_results(ctx, slot, d_res, res_stride, n, Pending::KEY_COL, users, nullptr, "key ids");
+}
+
+int32_t sb_key_ids(sb_ctx* ctx, sb_column_key_ids* cols, uint64_t n, int32_t mem) {
+    int32_t rc;
+    if (!sink_entry(ctx, cols, n, mem, "sb_key_ids", &rc)) return rc;
+    std::vector<AggCol> hs(n);
+    std::vector<KeyCol> hk(n);
+    uint64_t slots = 0;
+    uint32_t kmax = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_column_key_ids& c = cols[i];
+        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(ctx, SB_ERR_INVALID, "bad physical_type");
+        if (c.physical_type < SB_TYPE_INT8 || c.physical_type > SB_TYPE_UINT64)
+            return refuse(ctx, SB_ERR_NYI, "key ids are implemented for 8- to 64-bit integers");
+        if (c.id_width != 1 && c.id_width != 2 && c.id_width != 4) return refuse(ctx, SB_ERR_INVALID, "id_width is not 1, 2 or 4");
+        const uint64_t limit = std::min<uint64_t>(SB_KEY_MAX_KEYS, (1ull << (8 * c.id_width)) - 1);
+        if (c.max_keys == 0 || c.max_keys > limit) return refuse(ctx, SB_ERR_INVALID, "max_keys is not in 1 .. min(SB_KEY_MAX_KEYS, 2^(8 * id_width) - 1)");
+        if (c.reserved) return refuse(ctx, SB_ERR_INVALID, "reserved is not 0");
+        if (!c.keys) return refuse(ctx, SB_ERR_INVALID, "keys is null");
+        // (collected like a minimum: every live value is looked at)
+        if ((rc = agg_check_fill(ctx, c, SB_AGG_MIN, hs[i], "key ids are implemented for 8- to 64-bit integers")) != SB_OK) return rc;
+        const uint64_t rows = hs[i].rows;
+        if (rows && !c.ids) return refuse(ctx, SB_ERR_INVALID, "ids is null");
+        if (c.ids && (((uintptr_t)c.ids & (c.id_width - 1)) || c.ids_capacity < rows * c.id_width))
+            return refuse(ctx, SB_ERR_INVALID, "ids not aligned to id_width or smaller than rows * id_width bytes");
+        hk[i] = KeyCol{(uint8_t*)c.ids, slots, key_table_slots(c.max_keys) - 1, c.max_keys, c.id_width, 0};
+        slots += key_table_slots(c.max_keys);
+        kmax = std::max(kmax, c.max_keys);
+    }
+    for (uint64_t i = 0; i < n; i++)   // (the bytes a column writes: rows * id_width)
+        for (uint64_t j = i + 1; j < n; j++) {
+            const uintptr_t a0 = (uintptr_t)cols[i].ids, a1 = a0 + hs[i].rows * cols[i].id_width;
+            const uintptr_t b0 = (uintptr_t)cols[j].ids, b1 = b0 + hs[j].rows * cols[j].id_width;
+            if (a0 < b1 && b0 < a1) return refuse(ctx, SB_ERR_INVALID, "ids of two columns of one call overlap");
+        }
+    (void)hipSetDevice(ctx->device);
+    std::vector<sb_column_read> rc_cols(n);
+    std::vector<void*> users(n);
+    for (uint64_t i = 0; i < n; i++) {
+        rc_cols[i] = read_col_of(cols[i]);
+        users[i] = &cols[i];
+    }
+    if (ctx->in_replay && ctx->filter_freq) {
+        // Every column through a full decode, as sb_aggregate_columns has it.  Keys and ids are functions of the data alone,
+        // so which interval a column is decoded in does not show in its bytes.
+        rc = key_ids_decoded(ctx, std::move(rc_cols), hs, hk, slots, kmax, users.data());
+    } else {
+        if ((rc = stage_shares(ctx, rc_cols.data(), agg_stage_caps(hs).data(), n)) != SB_OK) return rc;
+        ReadMode mode{ReadMode::KEY_IDS};
+        mode.aggc = hs.data();
+        mode.keyc = hk.data();
+        mode.key_kmax = kmax;
+        mode.key_slots = slots;
+        mode.users = users.data();
+        mode.pending_kind = Pending::KEY_COL;
+        rc = read_columns_impl(ctx, rc_cols.data(), n, SB_MEM_DEVICE, mode);
+    }
+    if (rc != SB_OK) return rc;
+    for (uint64_t i = 0; i < n; i++) {   // (after the last thing that can refuse the call: a page outside pages_len)
+        sb_column_key_ids& c = cols[i];
+        column_rows(c, &c.rows);
+        c.selected = c.count = c.n_keys = c.overflow = 0;
+    }
+    if (!ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::KEY_IDS, cols, n, sb_write_options{}, mem});
     return rc;
 }
 

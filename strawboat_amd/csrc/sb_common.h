@@ -324,6 +324,63 @@ __host__ __device__ inline uint64_t in_key(uint32_t kind, uint32_t w, uint64_t r
     if ((raw << 1) == 0) raw = 0;
     return (raw >> 63) ? ~raw : (raw | (1ull << 63));
 }
+// The keys below x among n ascending keys: in_member's loop (sb_filter_in.h) returning the position.  `steps` =
+// ceil(log2(n + 1)) probes whatever x is, and no branch; n = 0 has 0 steps and the position 0.  Where x is one of the keys
+// the position is its index.
+__host__ __device__ inline uint32_t key_steps(uint32_t n) {
+    uint32_t s = 0;
+    while ((1ull << s) < (uint64_t)n + 1) s++;
+    return s;
+}
+__host__ __device__ inline uint32_t key_lower_bound(const uint64_t* keys, uint32_t n, uint32_t steps, uint64_t x) {
+    uint32_t pos = 0;
+    for (uint32_t s = steps; s-- > 0;) {
+        const uint32_t p = pos + (1u << s);
+        const uint64_t k = keys[(p < n ? p : n) - 1];   // (steps > 0: n >= 1, and p >= 1)
+        pos = (p <= n && k < x) ? p : pos;
+    }
+    return pos;
+}
+// one column of a key-id call (sb_key_ids, sb_key_ids.h), next to its AggCol (of which sel, rows, kind and w are used).
+// The distinct set of a column is an open-addressing table of order keys (in_key) in the call's scratch: `tab_mask` + 1
+// slots, a power of two >= 4 * max_keys, 0 = empty; the key 0 itself is KeyState.has_zero.
+constexpr uint32_t KEY_MAX_KEYS = 1024;            // SB_KEY_MAX_KEYS (= IN_MAX_VALUES: 8 KiB of LDS, 11 probes)
+struct KeyCol {
+    uint8_t* ids;          // the caller's ids: one unsigned integer of `idw` bytes per row of the column (output)
+    uint64_t tab0;         // the column's first slot in KeyLaunch.tabs
+    uint32_t tab_mask;
+    uint32_t max_keys;     // 1 .. min(KEY_MAX_KEYS, 2^(8 * idw) - 1)
+    uint32_t idw;          // 1, 2 or 4
+    uint32_t pad;
+};
+struct KeyState {          // 32 bytes per column, zeroed with the tables before the collect walk
+    uint64_t count;        // live rows (one integer add per tile / page part)
+    uint32_t inserted;     // keys that won a slot of the table
+    uint32_t overflow;     // collect: more than max_keys keys are in, nothing more is inserted; k_key_finish: the verdict
+    uint32_t has_zero;     // the order key 0 is among the live rows
+    uint32_t n_keys;       // k_key_finish: the sorted keys of the column ...
+    uint32_t steps;        // ... and the trip count of the search over them
+    uint32_t pad;
+};
+// the result of a column: { selected, count, n_keys, overflow, 0, 0, 0, 0 }, then kmax key slots of 8 bytes (the call's
+// largest max_keys), of which the column's own max_keys are handed over
+__host__ __device__ inline uint64_t key_result_words(uint32_t kmax) { return 8 + (uint64_t)kmax; }
+__host__ __device__ inline uint32_t key_table_slots(uint32_t max_keys) {
+    uint32_t s = 64;
+    while (s < 4 * max_keys) s <<= 1;
+    return s;
+}
+struct AggCol;
+struct KeyLaunch {   // what launch_decode needs to end a call with the collect kernels; the finish and assign kernels take it too
+    const AggCol* acols;
+    const KeyCol* kcols;
+    KeyState* st;          // [n_cols], and behind them the tables: one area, zeroed by launch_key_zero
+    uint64_t* tabs;
+    uint64_t* sorted;      // [n_cols * KEY_MAX_KEYS]: k_key_finish's sorted order keys, for the assign walk
+    uint64_t zero_bytes;   // of the area at `st`
+    uint32_t kmax;
+    uint32_t n_cols;
+};
 // one column of a selected read (sb_read_selected, sb_read_sel.h), next to its ColDesc
 constexpr uint32_t RSEL_RANK_BLOCKS = 64;   // workgroups per column of the rank scan (k_rsel_sums / k_rsel_rank)
 struct SelCol {

@@ -3128,10 +3128,12 @@ static void launch_lzg(sb_ctx* ctx, const DecodeArgs& a, bool lzg_on, InflateJob
 #include "sb_aggregate.h"
 #include "sb_aggregate_grouped.h"
 #include "sb_topk.h"
+#include "sb_key_ids.h"
 namespace sb {
 
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
-                   const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp, const InCol* icols, const TopkLaunch* topk) {
+                   const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp, const InCol* icols, const TopkLaunch* topk,
+                   const KeyLaunch* keys) {
     hipStream_t s = ctx->stream;
     (void)hipMemsetAsync(a.job_counts, 0, 16 * sizeof(uint32_t), s);
     const bool qa = !(a.read_skips & RSKIP_QUEUE_A);
@@ -3224,6 +3226,10 @@ void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_p
     }
     if (topk) {   // sb_topk_columns: ... to the k best rows per column
         launch_topk(ctx, a, *topk);
+        return;
+    }
+    if (keys) {   // sb_key_ids: ... to the columns' tables of distinct keys (the first of the call's two walks)
+        launch_key_collect(ctx, a, *keys);
         return;
     }
     // the three expand kernels work on disjoint pages (page-level RLE, tiles of primitives, tiles of binary columns): side
