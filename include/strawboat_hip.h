@@ -707,6 +707,79 @@ typedef struct sb_column_key_ids {
 
 int32_t sb_key_ids(sb_ctx* ctx, sb_column_key_ids* cols, uint64_t n, int32_t mem);
 
+/* ------------------------------------------------------------------ key ids of Binary / Utf8 columns
+ * sb_key_ids for SB_TYPE_BINARY / SB_TYPE_LARGE_BINARY key columns: GROUP BY country / status / host, SELECT DISTINCT of
+ * a string column.  Live rows, rows / selected / count, `ids`, id_width, max_keys, the enqueueing, replays and page
+ * errors are those of sb_key_ids; what differs is how the keys come back.
+ *
+ *   keys          the distinct byte strings of the live rows, n_keys of them.  Distinct as byte strings, whatever their
+ *                 hashes; ascending in the order of SB_PRED_LT of sb_filter_columns_var: bytes compare unsigned, a proper
+ *                 prefix is less than the longer string.  The empty string is a key like any other; a null row gives no
+ *                 key, whatever bytes the writer left in it.
+ *   key_offsets   HOST, max_keys + 1 entries, filled at the synchronize: key_offsets[0] == 0, key i is
+ *                 keys[key_offsets[i] .. key_offsets[i + 1]), the entries behind n_keys repeat keys_len.
+ *   keys          HOST, keys_capacity bytes (at most SB_KEY_VAR_MAX_BYTES): the keys' bytes back to back, and zero in
+ *                 [keys_len, keys_capacity).  key_offsets / keys are the value_offsets / values of sb_column_filter_in:
+ *                 a semi-join hands both over unchanged.
+ *   overflow      a bit set; the synchronize returns SB_OK either way.
+ *                 SB_KEY_OVERFLOW_KEYS: more than max_keys distinct live strings; n_keys, keys_len, key_offsets, `keys`
+ *                 and `ids` are unspecified.
+ *                 SB_KEY_OVERFLOW_BYTES: the keys fit max_keys but their bytes exceed keys_capacity: n_keys, keys_len,
+ *                 key_offsets and `ids` are valid, only the bytes of `keys` are not delivered (they are written as
+ *                 zero); keys_len says what to allocate.
+ *                 In no case is a byte written outside ids_capacity, key_offsets[0 .. max_keys] and keys[0 .. keys_capacity).
+ *   stage_capacity  as in sb_column_filter_var: the column's share of the staging area for LZ4 / Zstd / Snappy value
+ *                 blocks; 0 = 4 * pages_len.
+ *
+ * A Dict / Freq page costs one insertion and one search per dictionary entry that a live row points at (an entry no
+ * live row points at is no key), a OneValue page one per tile, a Basic page one per live row.  A Dict index beyond the
+ * dictionary on a live row is SB_ERR_OUT_OF_SPEC; offsets that leave a values block are cut to it.  The call never asks
+ * for a replay itself (a Freq page of strings is a virtual Dict page) and consults no launch hint.
+ *
+ * Refused at the call, nothing enqueued and no result field or output byte touched: every refusal of sb_key_ids with
+ * its code (`keys` null is refused only with keys_capacity > 0); a type that is not Binary / LargeBinary and SB_MEM_HOST
+ * (SB_ERR_NYI); key_offsets null, keys_capacity above SB_KEY_VAR_MAX_BYTES (SB_ERR_INVALID); a call of 2^28 pages or
+ * more, a page of more than 2^26 rows or of 2^29 bytes or more (SB_ERR_NYI: page and row / entry number are fields of
+ * the 64-bit word a slot of the distinct set holds).
+ *
+ * Layout (pinned by tests/test_key_ids_var_host.py): sb_column_key_ids_var 176 bytes; physical_type 0, is_nullable 4,
+ * pages 8, pages_len 16, metas 24, n_pages 32, page_offsets 40, selection 48, selection_capacity 56, ids 64,
+ * ids_capacity 72, id_width 80, max_keys 84, key_offsets 88, keys 96, keys_capacity 104, stage_capacity 112,
+ * reserved 120, rows 128, selected 136, count 144, n_keys 152, keys_len 160, overflow 168. */
+#define SB_KEY_VAR_MAX_BYTES (1u << 20)
+#define SB_KEY_OVERFLOW_KEYS 1u
+#define SB_KEY_OVERFLOW_BYTES 2u
+
+typedef struct sb_column_key_ids_var {
+    int32_t physical_type;   /* SB_TYPE_BINARY | SB_TYPE_LARGE_BINARY */
+    int32_t is_nullable;
+    const uint8_t* pages;    /* DEVICE, at any byte alignment */
+    uint64_t pages_len;
+    const sb_page_meta* metas; /* HOST */
+    uint64_t n_pages;
+    const uint64_t* page_offsets; /* optional (HOST), as in sb_column_read */
+    const uint8_t* selection;     /* DEVICE, input: as in sb_column_aggregate; NULL = every row */
+    uint64_t selection_capacity;
+    void* ids;               /* DEVICE, output: one id per row, aligned to id_width */
+    uint64_t ids_capacity;   /* >= rows * id_width bytes */
+    uint32_t id_width;       /* 1, 2 or 4 */
+    uint32_t max_keys;       /* 1 .. min(SB_KEY_MAX_KEYS, 2^(8 * id_width) - 1) */
+    uint64_t* key_offsets;   /* HOST, max_keys + 1 entries, filled at the synchronize; must live until then */
+    uint8_t* keys;           /* HOST, keys_capacity bytes, likewise */
+    uint64_t keys_capacity;  /* 0 .. SB_KEY_VAR_MAX_BYTES */
+    uint64_t stage_capacity; /* see above; 0 = 4 * pages_len */
+    uint64_t reserved;       /* must be 0 */
+    /* results (HOST, valid after sb_ctx_synchronize) */
+    uint64_t rows;           /* sum of num_values */
+    uint64_t selected;       /* bits set in `selection` below `rows` (== rows without a selection) */
+    uint64_t count;          /* selected rows that are not null */
+    uint64_t n_keys;         /* distinct strings among them */
+    uint64_t keys_len;       /* their bytes together */
+    uint64_t overflow;       /* SB_KEY_OVERFLOW_* bits */
+} sb_column_key_ids_var;     /* 176 bytes */
+
+int32_t sb_key_ids_var(sb_ctx* ctx, sb_column_key_ids_var* cols, uint64_t n, int32_t mem);
+
 /* ------------------------------------------------------------------ encode
  * Replaces, per leaf column, the page loop of NativeWriter::encode_chunk
  * (src/write/common.rs:54-109): page slicing, then per page write::write -> write_simple

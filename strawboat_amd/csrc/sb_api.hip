@@ -12,12 +12,15 @@ namespace sb {
 
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
                    const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp = nullptr, const InCol* icols = nullptr,
-                   const TopkLaunch* topk = nullptr, const KeyLaunch* keys = nullptr);
+                   const TopkLaunch* topk = nullptr, const KeyLaunch* keys = nullptr, const KeyVarLaunch* keyv = nullptr);
 void launch_key_zero(sb_ctx* ctx, const KeyLaunch& kl);
 void launch_key_finish(sb_ctx* ctx, const KeyLaunch& kl, uint64_t* results);
 void launch_key_assign(sb_ctx* ctx, const DecodeArgs& a, const KeyLaunch& kl);
 void launch_key_collect_plain(sb_ctx* ctx, const KeyLaunch& kl, const uint64_t* rows, const uint8_t* const* values, const uint8_t* const* validity);
 void launch_key_assign_plain(sb_ctx* ctx, const KeyLaunch& kl, const uint64_t* rows, const uint8_t* const* values, const uint8_t* const* validity);
+void launch_keyv_zero(sb_ctx* ctx, const KeyVarLaunch& kl);
+void launch_keyv_finish(sb_ctx* ctx, const DecodeArgs& a, const KeyVarLaunch& kl, uint64_t* results);
+void launch_keyv_assign(sb_ctx* ctx, const DecodeArgs& a, const KeyVarLaunch& kl);
 void launch_topk_zero(sb_ctx* ctx, const TopkLaunch& tl);
 void launch_topk_finish(sb_ctx* ctx, const TopkLaunch& tl, uint64_t* results, uint32_t n_cols);
 void launch_topk_plain(sb_ctx* ctx, const TopkLaunch& tl, uint32_t n_cols, const uint64_t* rows, const uint8_t* const* values,
@@ -109,7 +112,7 @@ StageSlot* acquire_slot(sb_ctx* ctx, size_t need) {
     if (s.host)
         for (auto& p : ctx->iv.pending) {
             if (p.host < s.host || p.host >= s.host + s.cap) continue;
-            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::AGG_COL ? AGG_RESULT_WORDS * 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R || p.kind == Pending::AGG_GRP_COL || p.kind == Pending::TOPK_COL || p.kind == Pending::KEY_COL) ? (size_t)p.bytes
+            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::AGG_COL ? AGG_RESULT_WORDS * 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R || p.kind == Pending::AGG_GRP_COL || p.kind == Pending::TOPK_COL || p.kind == Pending::KEY_COL || p.kind == Pending::KEY_VAR_COL) ? (size_t)p.bytes
                                                                                                    : (size_t)(2 * p.n + 1) * 8;
             ctx->iv.rescued.emplace_back(p.host, p.host + nb);
             p.host = ctx->iv.rescued.back().data();
@@ -245,7 +248,8 @@ struct ReadMode {
     // / sb_aggregate_grouped, an aggregate call whose columns end in the grouped aggregate kernels
     // / sb_topk_columns, an aggregate call whose columns end in the top-k kernels
     // / sb_key_ids, an aggregate call whose columns end in the key kernels: two walks, the finish between them
-    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR, AGGREGATE, AGG_GROUPED, TOPK, KEY_IDS } kind;
+    // / sb_key_ids_var, the same for binary columns, whose value blocks are staged as a filter call stages them
+    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR, AGGREGATE, AGG_GROUPED, TOPK, KEY_IDS, KEY_IDS_VAR } kind;
     const FilterCol* filt = nullptr;             // FILTER: one per column
     const std::vector<uint8_t>* lits = nullptr;  // ... the literals of the FK_BYTES columns, FilterCol.lit being the offset of each
     bool in_list = false;                        // ... sb_filter_columns_in: `lits` begins with an InCol per column, whose pointers are offsets in `lits`
@@ -261,29 +265,32 @@ struct ReadMode {
     const KeyCol* keyc = nullptr;                // KEY_IDS: one per column beside aggc
     uint32_t key_kmax = 0;                       // ... the largest max_keys of the call: key slots per result
     uint64_t key_slots = 0;                      // ... the slots of the columns' tables together
+    const KeyVarCol* keyvc = nullptr;            // KEY_IDS_VAR: one per column beside aggc (key_kmax and key_slots as above)
+    uint64_t key_kbytes = 0;                     // ... the largest keys_capacity of the call: bytes per result
     // Where a column's result goes at the synchronize, as Pending has it (sb_host.h): users[i] beside pending_kind.  Set by
     // the entry points of the sinks: the callers' structs, for a filter call the caller's `selected` (results[i] + 1).
     // Null for the other kinds of call, whose results go to the sb_column_read structs of the call itself.
     void* const* users = nullptr;
     Pending::Kind pending_kind = Pending::READ_COL;
-    bool aggregate() const { return kind == AGGREGATE || kind == AGG_GROUPED || kind == TOPK || kind == KEY_IDS; }   // an AggCol per column, slots per page part and tile
+    bool aggregate() const { return kind == AGGREGATE || kind == AGG_GROUPED || kind == TOPK || kind == KEY_IDS || kind == KEY_IDS_VAR; }   // an AggCol per column, slots per page part and tile
     bool grouped() const { return kind == AGG_GROUPED; }
     bool topk() const { return kind == TOPK; }
     bool key_ids() const { return kind == KEY_IDS; }
+    bool key_var() const { return kind == KEY_IDS_VAR; }
     bool filter() const { return kind == FILTER; }
     bool selected() const { return kind == SELECTED; }
     bool selected_var() const { return kind == SELECTED_VAR; }
     bool ranked() const { return kind == SELECTED || kind == SELECTED_VAR; }   // a SelCol and a rank table per column
     // binary columns whose value blocks are staged and compared or gathered: no offsets are written by the read's kernels
-    bool bin_staged() const { return kind == FILTER || kind == SELECTED_VAR; }
+    bool bin_staged() const { return kind == FILTER || kind == SELECTED_VAR || kind == KEY_IDS_VAR; }
     // the columns end in a sink of their own: `values` is a share of the staging area, there is no validity buffer, and
     // the call neither consults nor feeds the launch hints of the read path
     bool sink() const { return kind == FILTER || kind == SELECTED || kind == SELECTED_VAR || aggregate(); }
     // words of 8 bytes that come back per column: { selected, values_len } for a SELECTED_VAR call, the result record of
     // an AGGREGATE call, the header and the gmax group records of an AGG_GROUPED call, the header and the kmax entries of
-    // a TOPK call, the header and the kmax key slots of a KEY_IDS call
+    // a TOPK call, the header and the kmax key slots of a KEY_IDS call, the header, offsets and bytes of a KEY_IDS_VAR call
     uint64_t result_words() const {
-        return kind == SELECTED_VAR ? 2 : kind == AGGREGATE ? AGG_RESULT_WORDS : kind == AGG_GROUPED ? grp_result_words(grp_gmax) : kind == TOPK ? topk_result_words(topk_kmax) : kind == KEY_IDS ? key_result_words(key_kmax) : 1;
+        return kind == SELECTED_VAR ? 2 : kind == AGGREGATE ? AGG_RESULT_WORDS : kind == AGG_GROUPED ? grp_result_words(grp_gmax) : kind == TOPK ? topk_result_words(topk_kmax) : kind == KEY_IDS ? key_result_words(key_kmax) : kind == KEY_IDS_VAR ? keyv_result_words(key_kmax, key_kbytes) : 1;
     }
 };
 static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, const ReadMode& mode);
@@ -543,6 +550,26 @@ static void deliver_key_col(const Pending& p, bool ok) {
     // (max_keys as the struct has it now, but never more than the record that was enqueued holds: header + kmax slots)
     memcpy(c->keys, p.host + sizeof head, std::min<size_t>((size_t)c->max_keys * 8, (size_t)p.bytes - sizeof head));
 }
+// k_keyv_finish's header, offsets and bytes (sb_key_ids_bin.h); `ok` false: the interval failed, selected alone.  The
+// record holds kmax + 1 offsets in front of the bytes, kmax being the largest max_keys of the call it was enqueued with.
+static void deliver_key_var_col(const Pending& p, bool ok) {
+    uint64_t head[8];
+    memcpy(head, p.host, sizeof head);
+    sb_column_key_ids_var* c = (sb_column_key_ids_var*)p.user;
+    c->selected = head[0];
+    if (!ok) return;
+    c->count = head[1];
+    c->n_keys = head[2];
+    c->overflow = head[3];
+    c->keys_len = head[4];
+    const size_t kmax = (size_t)p.n, room = (size_t)p.bytes - sizeof head;
+    const size_t n_off = std::min<size_t>((size_t)c->max_keys, kmax) + 1;
+    memcpy(c->key_offsets, p.host + sizeof head, n_off * 8);
+    const size_t cap = std::min<size_t>((size_t)c->keys_capacity, room - (kmax + 1) * 8);
+    const size_t len = head[3] == 0 ? std::min<size_t>((size_t)head[4], cap) : 0;   // (an overflow of either kind: no bytes)
+    if (len) memcpy(c->keys, p.host + sizeof head + (kmax + 1) * 8, len);
+    if (cap > len) memset(c->keys + len, 0, cap - len);
+}
 static void deliver_write_col(const Pending& p) {
     sb_column_write* c = (sb_column_write*)p.user;
     const uint64_t* lens = (const uint64_t*)p.host;  // [n_pages lengths][n_pages num_values][total]
@@ -574,6 +601,7 @@ static void deliver_pending(sb_ctx* ctx, const Pending& p, int32_t rc) {
         case Pending::AGG_GRP_COL: deliver_agg_grp_col(p, rc == SB_OK); break;
         case Pending::TOPK_COL: deliver_topk_col(p, rc == SB_OK); break;
         case Pending::KEY_COL: deliver_key_col(p, rc == SB_OK); break;
+        case Pending::KEY_VAR_COL: deliver_key_var_col(p, rc == SB_OK); break;
         case Pending::WRITE_COL: deliver_write_col(p); break;
         case Pending::ENC_HINT:
             if (rc == SB_OK) apply_enc_hint(ctx, p);
@@ -848,6 +876,7 @@ static ReadLayout read_layout(uint64_t n, const ReadShape& sh, const ReadHints& 
     if (mode.grouped()) off = align_up(off + n * sizeof(GrpCol), 64);   // (in the SelBins' place)
     if (mode.topk()) off = align_up(off + n * sizeof(TopkCol), 64);     // (likewise)
     if (mode.key_ids()) off = align_up(off + n * sizeof(KeyCol), 64);   // (likewise)
+    if (mode.key_var()) off = align_up(off + n * sizeof(KeyVarCol), 64);   // (likewise)
     L.lits = off;
     if (mode.lits) off = align_up(off + mode.lits->size(), 64);
     L.upload = off;
@@ -891,6 +920,8 @@ static ReadLayout read_layout(uint64_t n, const ReadShape& sh, const ReadHints& 
     // a KEY_IDS call: a state per column and the columns' tables (zeroed), then KEY_MAX_KEYS sorted keys per column (not zeroed)
     L.key_sorted = align_up(off + n * sizeof(KeyState) + mode.key_slots * sizeof(uint64_t), 64);
     if (mode.key_ids()) off = align_up(L.key_sorted + n * KEY_MAX_KEYS * sizeof(uint64_t), 64);
+    // a KEY_IDS_VAR call: the same area, of KeyVarStates and reference words; then the sorted keys of sb_key_ids_bin.h
+    if (mode.key_var()) off = align_up(L.key_sorted + n * KEYV_SORTED_BYTES, 64);
     L.total = off;
     return L;
 }
@@ -991,7 +1022,8 @@ static int32_t fill_read_tables(sb_ctx* ctx, uint8_t* host, const ReadLayout& L,
             t.first_tile = (uint32_t)tile_i;
             t.aux_off = scratch_off;
             scratch_off += align_up((len / 4 + N / 128 + 4 * ntiles + 16) * 4, 16);   // (4 * ntiles: tile_k0 / tile_base + tile_bytes, and the u64 tile totals of a long binary Dict page)
-            if (mode.filter() && is_binary_t(c.physical_type)) scratch_off += filter_bin_table_words(len) * 4;   // (a bit per dictionary entry: sb_filter_bin.h)
+            if (mode.key_var() && is_binary_t(c.physical_type)) scratch_off += keyv_id_table_words(len) * 4;    // (a 16-bit id per dictionary entry, in front of the bits: sb_key_ids_bin.h)
+            if ((mode.filter() || mode.key_var()) && is_binary_t(c.physical_type)) scratch_off += filter_bin_table_words(len) * 4;   // (a bit per dictionary entry: sb_filter_bin.h)
             t.infl_off = scratch_off;
             scratch_off += align_up((N + 1) * 8 + 16, 16);
             in_off += len;
@@ -1027,6 +1059,7 @@ static int32_t fill_read_tables(sb_ctx* ctx, uint8_t* host, const ReadLayout& L,
         if (mode.grouped()) memcpy(host + L.bcols, mode.grpc, n * sizeof(GrpCol));
         if (mode.topk()) memcpy(host + L.bcols, mode.topkc, n * sizeof(TopkCol));
         if (mode.key_ids()) memcpy(host + L.bcols, mode.keyc, n * sizeof(KeyCol));
+        if (mode.key_var()) memcpy(host + L.bcols, mode.keyvc, n * sizeof(KeyVarCol));
     }
     SelCol* hsc = mode.ranked() ? (SelCol*)(host + L.fcols) : nullptr;
     for (uint64_t i = 0; hsc && i < n; i++) {   // the rank tables: behind the pages' areas, sized by the rows
@@ -1276,6 +1309,15 @@ static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, 
         // (a call without a page still has a result: selected, and `keys` of zeros)
         launch_key_finish(ctx, kl, d_vlen);
         if (sh.P) launch_key_assign(ctx, a, kl);
+    } else if (mode.key_var()) {
+        KeyVarLaunch kl{(const AggCol*)(ctx->tables.p + L.fcols), (const KeyVarCol*)(ctx->tables.p + L.bcols), (KeyVarState*)(ctx->tables.p + L.aggp),
+                        (uint64_t*)(ctx->tables.p + L.aggp + n * sizeof(KeyVarState)), ctx->tables.p + L.key_sorted,
+                        n * sizeof(KeyVarState) + mode.key_slots * sizeof(uint64_t), mode.key_kbytes, mode.key_kmax, (uint32_t)n};
+        launch_keyv_zero(ctx, kl);
+        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &kl);
+        // (a call without a page still has a result: selected, offsets of zero)
+        launch_keyv_finish(ctx, a, kl, d_vlen);
+        if (sh.P) launch_keyv_assign(ctx, a, kl);
     } else if (mode.aggregate()) {
         AggLaunch al{(const AggCol*)(ctx->tables.p + L.fcols), (AggPart*)(ctx->tables.p + L.aggp), sh.P * L.rle_parts, false, false};
         for (uint64_t i = 0; i < n; i++) ((mode.aggc[i].ops & AGG_VALUE_OPS) ? al.any_val : al.any_null) = true;
@@ -1300,7 +1342,7 @@ static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, 
 // One Pending per column of a call whose results are on their way to `host`, `stride` bytes apart.  grpc: the columns of a
 // grouped aggregate, of whose record the header and the column's own groups are handed over.
 static void push_pending(sb_ctx* ctx, Pending::Kind kind, void* const* users, const uint8_t* host, size_t stride, uint64_t n,
-                         const GrpCol* grpc = nullptr) {
+                         const GrpCol* grpc = nullptr, uint32_t kmax = 0 /* KEY_VAR_COL: the call's largest max_keys */) {
     for (uint64_t i = 0; i < n; i++) {
         Pending pd;
         pd.kind = kind;
@@ -1310,6 +1352,7 @@ static void push_pending(sb_ctx* ctx, Pending::Kind kind, void* const* users, co
         if (grpc) pd.bytes = sizeof(uint64_t) * grp_result_words(grpc[i].n_groups);
         if (kind == Pending::TOPK_COL) pd.bytes = stride;   // (the header and kmax entries: the column's own k is in its struct)
         if (kind == Pending::KEY_COL) pd.bytes = stride;    // (likewise: the header and kmax key slots)
+        if (kind == Pending::KEY_VAR_COL) pd.bytes = stride, pd.n = kmax;   // (the header, kmax + 1 offsets, the bytes)
         ctx->iv.pending.push_back(pd);
     }
 }
@@ -1344,7 +1387,7 @@ static int32_t queue_read_results(sb_ctx* ctx, StageSlot* slot, const ReadLayout
         for (uint64_t i = 0; i < n; i++) own[i] = &cols[i];
     }
     push_pending(ctx, mode.pending_kind, mode.users ? mode.users : own.data(), hv, sizeof(uint64_t) * mode.result_words(), n,
-                 mode.grouped() ? mode.grpc : nullptr);
+                 mode.grouped() ? mode.grpc : nullptr, mode.key_kmax);
     return SB_OK;
 }
 
@@ -1460,7 +1503,7 @@ constexpr bool has_pages_prefix() {
 static_assert(offsetof(sb_column_filter, page_offsets) == 40, "the pages of a sink column: 48 bytes");
 static_assert(has_pages_prefix<sb_column_filter_var>() && has_pages_prefix<sb_column_read_selected>() && has_pages_prefix<sb_column_read_selected_var>() &&
                   has_pages_prefix<sb_column_aggregate>() && has_pages_prefix<sb_column_aggregate_grouped>() && has_pages_prefix<sb_column_topk>() &&
-                  has_pages_prefix<sb_column_key_ids>(),
+                  has_pages_prefix<sb_column_key_ids>() && has_pages_prefix<sb_column_key_ids_var>(),
               "every sink column begins with the seven fields of sb_column_filter, at its offsets");
 
 // The pages of a sink column as a read column (outputs: none yet)
@@ -2538,6 +2581,85 @@ int32_t sb_key_ids(sb_ctx* ctx, sb_column_key_ids* cols, uint64_t n, int32_t mem
         c.selected = c.count = c.n_keys = c.overflow = 0;
     }
     if (!ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::KEY_IDS, cols, n, sb_write_options{}, mem});
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------ key ids of binary columns
+static_assert(sizeof(sb_column_key_ids_var) == 176 && offsetof(sb_column_key_ids_var, selection) == 48 && offsetof(sb_column_key_ids_var, ids) == 64 &&
+                  offsetof(sb_column_key_ids_var, id_width) == 80 && offsetof(sb_column_key_ids_var, max_keys) == 84 &&
+                  offsetof(sb_column_key_ids_var, key_offsets) == 88 && offsetof(sb_column_key_ids_var, keys) == 96 &&
+                  offsetof(sb_column_key_ids_var, keys_capacity) == 104 && offsetof(sb_column_key_ids_var, stage_capacity) == 112 &&
+                  offsetof(sb_column_key_ids_var, reserved) == 120 && offsetof(sb_column_key_ids_var, rows) == 128 &&
+                  offsetof(sb_column_key_ids_var, keys_len) == 160 && offsetof(sb_column_key_ids_var, overflow) == 168,
+              "the layout the header pins");
+static_assert(SB_KEY_VAR_MAX_BYTES == KEYV_MAX_BYTES && KEYV_TAG_BITS + 2 + KEYV_INDEX_BITS + KEYV_PAGE_BITS == 64, "the header's limit; the slot's word");
+
+// One route, also on a replay: a Freq page of strings is a virtual Dict page, so no column is decoded first.
+int32_t sb_key_ids_var(sb_ctx* ctx, sb_column_key_ids_var* cols, uint64_t n, int32_t mem) {
+    int32_t rc;
+    if (!sink_entry(ctx, cols, n, mem, "sb_key_ids_var", &rc)) return rc;
+    std::vector<AggCol> hs(n);
+    std::vector<KeyVarCol> hk(n);
+    std::vector<uint64_t> cap(n);
+    uint64_t slots = 0, kbytes = 0, pages = 0;
+    uint32_t kmax = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_column_key_ids_var& c = cols[i];
+        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(ctx, SB_ERR_INVALID, "bad physical_type");
+        if (!is_binary_t(c.physical_type)) return refuse(ctx, SB_ERR_NYI, "sb_key_ids_var takes Binary / LargeBinary columns (integers: sb_key_ids)");
+        if (c.id_width != 1 && c.id_width != 2 && c.id_width != 4) return refuse(ctx, SB_ERR_INVALID, "id_width is not 1, 2 or 4");
+        const uint64_t limit = std::min<uint64_t>(SB_KEY_MAX_KEYS, (1ull << (8 * c.id_width)) - 1);
+        if (c.max_keys == 0 || c.max_keys > limit) return refuse(ctx, SB_ERR_INVALID, "max_keys is not in 1 .. min(SB_KEY_MAX_KEYS, 2^(8 * id_width) - 1)");
+        if (c.reserved) return refuse(ctx, SB_ERR_INVALID, "reserved is not 0");
+        if (!c.key_offsets) return refuse(ctx, SB_ERR_INVALID, "key_offsets is null");
+        if (c.keys_capacity > SB_KEY_VAR_MAX_BYTES) return refuse(ctx, SB_ERR_INVALID, "keys_capacity exceeds SB_KEY_VAR_MAX_BYTES");
+        if (!c.keys && c.keys_capacity) return refuse(ctx, SB_ERR_INVALID, "keys is null");
+        if ((rc = agg_check_fill(ctx, c, 0u, hs[i])) != SB_OK) return rc;
+        const uint64_t rows = hs[i].rows;
+        if (rows && !c.ids) return refuse(ctx, SB_ERR_INVALID, "ids is null");
+        if (c.ids && (((uintptr_t)c.ids & (c.id_width - 1)) || c.ids_capacity < rows * c.id_width))
+            return refuse(ctx, SB_ERR_INVALID, "ids not aligned to id_width or smaller than rows * id_width bytes");
+        // page and row / entry number are fields of the word a slot holds (kv_word, sb_common.h)
+        for (uint64_t p = 0; p < c.n_pages; p++)
+            if (c.metas[p].num_values > (1ull << KEYV_INDEX_BITS) || c.metas[p].length / 8 >= (1ull << KEYV_INDEX_BITS))
+                return refuse(ctx, SB_ERR_NYI, "sb_key_ids_var: a page of more than 2^26 rows or of 2^29 bytes or more");
+        pages += c.n_pages;
+        hk[i] = KeyVarCol{(uint8_t*)c.ids, slots, key_table_slots(c.max_keys) - 1, c.max_keys, c.id_width, 0, c.keys_capacity};
+        slots += key_table_slots(c.max_keys);
+        kmax = std::max(kmax, c.max_keys);
+        kbytes = std::max<uint64_t>(kbytes, c.keys_capacity);
+        cap[i] = c.stage_capacity ? c.stage_capacity : 4 * c.pages_len;   // (the caller's field stays as given: a replay reads it again)
+    }
+    if (pages >= (1ull << KEYV_PAGE_BITS)) return refuse(ctx, SB_ERR_NYI, "sb_key_ids_var: 2^28 pages or more in one call");
+    for (uint64_t i = 0; i < n; i++)   // (the bytes a column writes: rows * id_width)
+        for (uint64_t j = i + 1; j < n; j++) {
+            const uintptr_t a0 = (uintptr_t)cols[i].ids, a1 = a0 + hs[i].rows * cols[i].id_width;
+            const uintptr_t b0 = (uintptr_t)cols[j].ids, b1 = b0 + hs[j].rows * cols[j].id_width;
+            if (a0 < b1 && b0 < a1) return refuse(ctx, SB_ERR_INVALID, "ids of two columns of one call overlap");
+        }
+    (void)hipSetDevice(ctx->device);
+    std::vector<sb_column_read> rc_cols(n);
+    std::vector<void*> users(n);
+    for (uint64_t i = 0; i < n; i++) {
+        rc_cols[i] = read_col_of(cols[i]);
+        users[i] = &cols[i];
+    }
+    if ((rc = stage_shares(ctx, rc_cols.data(), cap.data(), n)) != SB_OK) return rc;
+    ReadMode mode{ReadMode::KEY_IDS_VAR};
+    mode.aggc = hs.data();
+    mode.keyvc = hk.data();
+    mode.key_kmax = kmax;
+    mode.key_slots = slots;
+    mode.key_kbytes = kbytes;
+    mode.users = users.data();
+    mode.pending_kind = Pending::KEY_VAR_COL;
+    if ((rc = read_columns_impl(ctx, rc_cols.data(), n, SB_MEM_DEVICE, mode)) != SB_OK) return rc;
+    for (uint64_t i = 0; i < n; i++) {   // (after the last thing that can refuse the call: a page outside pages_len)
+        sb_column_key_ids_var& c = cols[i];
+        column_rows(c, &c.rows);
+        c.selected = c.count = c.n_keys = c.keys_len = c.overflow = 0;
+    }
+    if (!ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::KEY_IDS_VAR, cols, n, sb_write_options{}, mem});
     return rc;
 }
 

@@ -381,6 +381,142 @@ struct KeyLaunch {   // what launch_decode needs to end a call with the collect 
     uint32_t kmax;
     uint32_t n_cols;
 };
+// ---- sb_key_ids_var (sb_key_ids_bin.h): the keys are byte strings.  The order is sb_filter_columns_var's (bin_rel_prefix):
+// bytes unsigned, a proper prefix less than the longer string.  The helpers below are the host's and the device's alike
+// (tests/test_key_ids_var_host.py runs them against std::lexicographical_compare / std::lower_bound); a load never touches
+// a byte before a string's first or behind its last (the rule at the head of sb_filter_bin.h).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SB_KV_PTR(T) __attribute__((address_space(1))) const T*   // strings live in HBM: global_load, not flat_load
+#else
+#define SB_KV_PTR(T) const T*
+#endif
+__host__ __device__ inline uint64_t kv_ld64(const uint8_t* p) {
+    uint64_t v;
+    __builtin_memcpy(&v, (SB_KV_PTR(uint8_t))p, 8);
+    return v;
+}
+// the n (0 .. 7) bytes at p as a little-endian number
+__host__ __device__ inline uint64_t kv_ld_short(const uint8_t* p, uint32_t n) {
+    SB_KV_PTR(uint8_t) g = (SB_KV_PTR(uint8_t))p;
+    if (n >= 4) {
+        uint32_t a, b;
+        __builtin_memcpy(&a, g, 4);
+        __builtin_memcpy(&b, g + n - 4, 4);
+        return (uint64_t)a | ((uint64_t)b << (8 * (n - 4)));
+    }
+    if (n >= 2) {
+        uint16_t a, b;
+        __builtin_memcpy(&a, g, 2);
+        __builtin_memcpy(&b, g + n - 2, 2);
+        return (uint64_t)a | ((uint64_t)b << (8 * (n - 2)));
+    }
+    return n ? (uint64_t)*g : 0ull;
+}
+#undef SB_KV_PTR
+// the first min(n, 8) bytes, zero padded, as a little-endian number / as a number that orders like the bytes.  Two strings
+// whose prefixes differ order as their prefixes do; equal prefixes decide nothing.
+__host__ __device__ inline uint64_t kv_first8(const uint8_t* p, uint32_t n) { return n >= 8 ? kv_ld64(p) : kv_ld_short(p, n); }
+__host__ __device__ inline uint64_t kv_prefix(const uint8_t* p, uint32_t n) { return __builtin_bswap64(kv_first8(p, n)); }
+// a against b: 0 less, 1 equal, 2 greater
+__host__ __device__ inline uint32_t kv_rel(const uint8_t* a, uint32_t n, const uint8_t* b, uint32_t m) {
+    const uint32_t k = n < m ? n : m;
+    if (k < 8) {
+        const uint64_t x = kv_ld_short(a, k), y = kv_ld_short(b, k);
+        if (x != y) return __builtin_bswap64(x) < __builtin_bswap64(y) ? 0u : 2u;
+    } else {
+        uint32_t i = 0;
+        for (; i + 8 <= k; i += 8) {
+            const uint64_t x = kv_ld64(a + i), y = kv_ld64(b + i);
+            if (x != y) return __builtin_bswap64(x) < __builtin_bswap64(y) ? 0u : 2u;
+        }
+        if (i < k) {   // the tail once more at its last 8 bytes: the bytes read twice are equal
+            const uint64_t x = kv_ld64(a + k - 8), y = kv_ld64(b + k - 8);
+            if (x != y) return __builtin_bswap64(x) < __builtin_bswap64(y) ? 0u : 2u;
+        }
+    }
+    return n < m ? 0u : n == m ? 1u : 2u;
+}
+__host__ __device__ inline bool kv_equal(const uint8_t* a, uint32_t n, const uint8_t* b, uint32_t m) { return n == m && kv_rel(a, n, b, m) == 1u; }
+// a function of the bytes alone; the low bits pick the slot, the top KEYV_TAG_BITS are the tag
+__host__ __device__ inline uint64_t kv_mix(uint64_t h, uint64_t w) {
+    h = (h ^ w) * 0x9E3779B97F4A7C15ull;
+    return h ^ (h >> 29);
+}
+__host__ __device__ inline uint64_t kv_hash(const uint8_t* p, uint32_t n) {
+    uint64_t h = ((uint64_t)n + 1) * 0xD6E8FEB86659FD93ull;
+    if (n < 8) {
+        h = kv_mix(h, kv_ld_short(p, n));
+    } else {
+        uint32_t i = 0;
+        for (; i + 8 <= n; i += 8) h = kv_mix(h, kv_ld64(p + i));
+        if (i < n) h = kv_mix(h, kv_ld64(p + n - 8));
+    }
+    h *= 0xFF51AFD7ED558CCDull;
+    return h ^ (h >> 32);
+}
+// The keys below x among n keys ascending by bytes: key_lower_bound's loop.  Key i is len[i] bytes at ptr[i] with the
+// prefix pre[i]; a probe whose prefix differs from x's loads no byte of the key.
+__host__ __device__ inline uint32_t kv_lower_bound(const uint64_t* pre, const uint64_t* ptr, const uint32_t* len, uint32_t n, uint32_t steps,
+                                                   const uint8_t* x, uint32_t xn) {
+    const uint64_t xpre = kv_prefix(x, xn);
+    uint32_t pos = 0;
+    for (uint32_t s = steps; s-- > 0;) {
+        const uint32_t p = pos + (1u << s);
+        const uint32_t i = (p < n ? p : n) - 1;   // (steps > 0: n >= 1, and p >= 1)
+        const uint64_t kp = pre[i];
+        const bool below = kp != xpre ? kp < xpre : kv_rel((const uint8_t*)(uintptr_t)ptr[i], len[i], x, xn) == 0u;
+        pos = (p <= n && below) ? p : pos;
+    }
+    return pos;
+}
+// The slot of a table or set is one 64-bit word, complete the moment a compare-and-swap makes it visible:
+//   bits 0 .. 7 the tag | 8 .. 9 the form (1 .. 3: never 0, the empty slot) | 10 .. 35 the index | 36 .. 63 the page
+// and names a string that memory no kernel of the call writes any more resolves to (pointer, length):
+//   KEYV_ENTRY  entry `index` of the Dict / Freq page   KEYV_ROW  row `index` of the Basic page   KEYV_ONE  the OneValue page's value
+constexpr uint32_t KEYV_TAG_BITS = 8, KEYV_INDEX_BITS = 26, KEYV_PAGE_BITS = 28;
+constexpr uint32_t KEYV_ENTRY = 1, KEYV_ROW = 2, KEYV_ONE = 3;
+__host__ __device__ inline uint64_t kv_word(uint32_t form, uint32_t page, uint32_t index, uint64_t hash) {
+    return ((uint64_t)page << 36) | ((uint64_t)index << 10) | ((uint64_t)form << 8) | (hash >> (64 - KEYV_TAG_BITS));
+}
+constexpr uint32_t KEYV_MAX_BYTES = 1u << 20;      // SB_KEY_VAR_MAX_BYTES
+// one column of the call, next to its AggCol (sel, rows); the table as KeyCol has it, of reference words
+struct KeyVarCol {
+    uint8_t* ids;          // as KeyCol.ids
+    uint64_t tab0;
+    uint32_t tab_mask;
+    uint32_t max_keys;
+    uint32_t idw;
+    uint32_t pad;
+    uint64_t keys_cap;     // keys_capacity
+};
+struct KeyVarState {       // 32 bytes per column, zeroed with the tables before the collect walk
+    uint64_t count;
+    uint32_t inserted;
+    uint32_t overflow;     // collect: the early flag; k_keyv_finish: the SB_KEY_OVERFLOW_* bits
+    uint32_t n_keys;
+    uint32_t steps;
+    uint64_t keys_len;
+};
+static_assert(sizeof(KeyVarState) == sizeof(KeyState), "read_layout places either behind the call's tables");
+// the result of a column: { selected, count, n_keys, overflow, keys_len, 0, 0, 0 }, then kmax + 1 offsets (behind n_keys:
+// keys_len), then the keys' bytes in kbytes (the call's largest keys_capacity) rounded up to words
+__host__ __device__ inline uint64_t keyv_result_words(uint32_t kmax, uint64_t kbytes) { return 8 + (uint64_t)kmax + 1 + (kbytes + 7) / 8; }
+// what k_keyv_finish leaves for the assign walk, per column: KEY_MAX_KEYS pointers, prefixes (8 bytes each) and lengths (4)
+constexpr uint64_t KEYV_SORTED_BYTES = (uint64_t)KEY_MAX_KEYS * 20;
+// words of the 16-bit id table (an id per dictionary entry) that the call reserves in front of the bit table of
+// filter_bin_table_words at the end of a page's aux area: at most L / 8 entries in a page of L bytes
+__host__ __device__ inline uint64_t keyv_id_table_words(uint64_t page_len) { return (page_len / 16 + 4) & ~3ull; }
+struct KeyVarLaunch {   // what launch_decode needs to end a call with the collect kernels; the finish and assign kernels take it too
+    const AggCol* acols;
+    const KeyVarCol* kcols;
+    KeyVarState* st;       // [n_cols], and behind them the tables: one area, zeroed by launch_keyv_zero
+    uint64_t* tabs;
+    uint8_t* sorted;       // [n_cols * KEYV_SORTED_BYTES]
+    uint64_t zero_bytes;
+    uint64_t kbytes;
+    uint32_t kmax;
+    uint32_t n_cols;
+};
 // one column of a selected read (sb_read_selected, sb_read_sel.h), next to its ColDesc
 constexpr uint32_t RSEL_RANK_BLOCKS = 64;   // workgroups per column of the rank scan (k_rsel_sums / k_rsel_rank)
 struct SelCol {
