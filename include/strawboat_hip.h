@@ -561,7 +561,7 @@ typedef struct sb_column_aggregate_grouped {
     const void* group_ids;        /* DEVICE, input: one unsigned id per row of the column, aligned to its width */
     uint64_t group_ids_capacity;  /* >= rows * group_id_width bytes */
     uint32_t group_id_width;      /* 1, 2 or 4 */
-    uint32_t n_groups;            /* 1 .. SB_AGG_MAX_GROUPS */
+    uint32_t n_groups;            /* 1 .. SB_AGG_MAX_GROUPS (sb_aggregate_grouped), 1 .. SB_AGG_LARGE_MAX_GROUPS (sb_aggregate_grouped_large) */
     uint32_t ops;            /* SB_AGG_* bits */
     uint32_t reserved;       /* must be 0 */
     sb_agg_group* groups;    /* HOST, n_groups entries, filled at the synchronize; must live until then */
@@ -572,6 +572,26 @@ typedef struct sb_column_aggregate_grouped {
 } sb_column_aggregate_grouped;   /* 128 bytes */
 
 int32_t sb_aggregate_grouped(sb_ctx* ctx, sb_column_aggregate_grouped* cols, uint64_t n, int32_t mem);
+
+/* ------------------------------------------------------------------ aggregate, grouped, up to 1024 groups
+ * sb_aggregate_grouped for key columns of 257 .. 1024 distinct values: every id sb_key_ids / sb_key_ids_var hands out
+ * (SB_KEY_MAX_KEYS) has a group here.  The same struct (sb_column_aggregate_grouped, layout unchanged), the same
+ * sb_agg_group records, n_groups 1 .. SB_AGG_LARGE_MAX_GROUPS.
+ *
+ * Everything said for sb_aggregate_grouped holds word for word with SB_AGG_LARGE_MAX_GROUPS in the limit's place: live rows,
+ * out_of_range, counts, empty groups, the order and bytes of min / max, 128-bit integer sums, float sums in double, the
+ * accepted types, the count-only route on every physical type, the refusals with their codes (nothing enqueued, no result
+ * field and no byte of `groups` touched), `rows` / `selected` delivered on a failed interval, membership in the
+ * synchronize interval and its replays.
+ *   float sums    one thing differs: the bits of a float sum are this call's own.  Its rows meet other tables in another
+ *                 order than sb_aggregate_grouped's (a table lives for 16 tiles of the column, not one), so the two calls
+ *                 need not give the same bits for the same input.  This call gives the same bits every time it is issued,
+ *                 a replayed interval included: no floating-point atomics, and the order of the double additions of a
+ *                 group's sum is a function of the column's own page layout and data alone, whatever other columns the
+ *                 call has. */
+#define SB_AGG_LARGE_MAX_GROUPS 1024u      /* == SB_KEY_MAX_KEYS */
+
+int32_t sb_aggregate_grouped_large(sb_ctx* ctx, sb_column_aggregate_grouped* cols, uint64_t n, int32_t mem);
 
 /* ------------------------------------------------------------------ top-k
  * SELECT ... WHERE x < 5 ORDER BY y [DESC] LIMIT k.  The pages of a column and (optionally) a selection bitmap go in; the

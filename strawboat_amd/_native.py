@@ -24,7 +24,7 @@ EXPORTS = ("sb_version", "sb_ctx_create", "sb_ctx_destroy", "sb_ctx_synchronize"
            "sb_file_reader_close", "sb_stat_page", "sb_schema_last_error", "sb_schema_to_bytes", "sb_schema_from_bytes",
            "sb_schema_metadata_from_bytes", "sb_filter_columns", "sb_filter_columns_var", "sb_read_selected",
            "sb_read_selected_var", "sb_aggregate_columns", "sb_aggregate_grouped", "sb_filter_columns_in",
-           "sb_topk_columns", "sb_key_ids", "sb_key_ids_var")
+           "sb_topk_columns", "sb_key_ids", "sb_key_ids_var", "sb_aggregate_grouped_large")
 
 SB_PRED_EQ, SB_PRED_NE, SB_PRED_LT, SB_PRED_LE, SB_PRED_GT, SB_PRED_GE, SB_PRED_IS_NULL, SB_PRED_IS_NOT_NULL = range(8)
 SB_PRED_STARTS_WITH = 8   # binary types only (sb_filter_columns_var)
@@ -35,6 +35,7 @@ SB_IN_MAX_VALUES = 1024
 SB_SEL_SET, SB_SEL_AND, SB_SEL_OR = range(3)
 SB_AGG_COUNT, SB_AGG_MIN, SB_AGG_MAX, SB_AGG_SUM = 1, 2, 4, 8
 SB_AGG_MAX_GROUPS = 256
+SB_AGG_LARGE_MAX_GROUPS = 1024   # == SB_KEY_MAX_KEYS
 SB_TOPK_MAX_K = 256
 SB_TOPK_SMALLEST, SB_TOPK_LARGEST = 0, 1
 SB_KEY_MAX_KEYS = 1024
@@ -266,6 +267,8 @@ def load():
     L.sb_aggregate_columns.argtypes = [C.c_void_p, C.POINTER(ColumnAggregateC), C.c_uint64, C.c_int32]
     L.sb_aggregate_grouped.restype = C.c_int32
     L.sb_aggregate_grouped.argtypes = [C.c_void_p, C.POINTER(ColumnAggregateGroupedC), C.c_uint64, C.c_int32]
+    L.sb_aggregate_grouped_large.restype = C.c_int32
+    L.sb_aggregate_grouped_large.argtypes = [C.c_void_p, C.POINTER(ColumnAggregateGroupedC), C.c_uint64, C.c_int32]
     L.sb_topk_columns.restype = C.c_int32
     L.sb_topk_columns.argtypes = [C.c_void_p, C.POINTER(ColumnTopKC), C.c_uint64, C.c_int32]
     L.sb_key_ids.restype = C.c_int32

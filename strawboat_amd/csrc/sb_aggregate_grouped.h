@@ -23,14 +23,16 @@
 namespace sb {
 
 typedef __attribute__((address_space(3))) uint64_t* l64p;
-// the table: field f of group g at s_g[f * GRP_MAX_GROUPS + g].  Fields 5.. are the two words of an integer sum, or the
+// the table: field f of group g at s_g[f * S + g], S the table's stride (GRP_MAX_GROUPS for this call's kernels).  Fields 5.. are the two words of an integer sum, or the
 // four waves' rows of a float sum
 constexpr uint32_t GF_SEL = 0, GF_CNT = 1, GF_NANS = 2, GF_KMIN = 3, GF_KMAX = 4, GF_SUM = 5;
 // distinct ids of a wave's step that get a shuffle tree each; the rest go by rank (grp_span).  A tree is six dependent
 // 64-bit shuffles, a rank round one LDS add for every id at once: past a handful of ids the rounds are cheaper
 constexpr uint32_t GRP_TREE_IDS = 4;
 constexpr uint32_t GRP_LDS_WORDS =(GF_SUM + WG / 64) * GRP_MAX_GROUPS;   // 18 KB
-__device__ __forceinline__ uint64_t* grp_field(uint64_t* s_g, uint32_t f) { return s_g + f * GRP_MAX_GROUPS; }
+// (S: the table's stride, the most groups it holds: GRP_MAX_GROUPS here, GRPL_MAX_GROUPS in sb_aggregate_grouped_large.h)
+template <uint32_t S = GRP_MAX_GROUPS>
+__device__ __forceinline__ uint64_t* grp_field(uint64_t* s_g, uint32_t f) { return s_g + f * S; }
 __device__ __forceinline__ void grp_lds_add(uint64_t* p, uint64_t v) {
     (void)__hip_atomic_fetch_add((l64p)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
@@ -48,10 +50,11 @@ __device__ __forceinline__ uint32_t grp_id(const uint8_t* ids, uint32_t w, uint6
     return w == 1 ? (uint32_t)ldu8(ids + c) : w == 2 ? (uint32_t)ldu16(ids + 2 * c) : ldu32(ids + 4 * c);
 }
 // by the whole workgroup, followed by a barrier
+template <uint32_t S = GRP_MAX_GROUPS>
 __device__ __forceinline__ void grp_table_clear(uint64_t* s_g, uint32_t G) {
     for (uint32_t i = threadIdx.x; i < G; i += WG) {
 #pragma unroll
-        for (uint32_t f = 0; f < GF_SUM + WG / 64; f++) grp_field(s_g, f)[i] = f == GF_KMIN ? ~0ull : 0ull;
+        for (uint32_t f = 0; f < GF_SUM + WG / 64; f++) grp_field<S>(s_g, f)[i] = f == GF_KMIN ? ~0ull : 0ull;
     }
     __syncthreads();
 }
@@ -60,7 +63,7 @@ __device__ __forceinline__ void grp_table_clear(uint64_t* s_g, uint32_t G) {
 // sum is a matter of the whole wave).  A selected row is counted in its group or, with an id >= n_groups, in `oor`; a live
 // one (VAL) is aggregated there: value_of(row, raw) gives its value, or false for a row that has none (a Dict index beyond
 // the dictionary: the caller raises).
-template <bool VAL, class V>
+template <bool VAL, uint32_t S = GRP_MAX_GROUPS, class V>
 __device__ __forceinline__ void grp_span(const GrpSink& k, uint64_t& oor, uint32_t kind, uint32_t w, uint64_t lo, uint64_t hi, V value_of) {
     const bool flt = VAL && agg_is_float(kind);
     uint64_t* const s_g = k.s_g;
@@ -75,21 +78,21 @@ __device__ __forceinline__ void grp_span(const GrpSink& k, uint64_t& oor, uint32
                 oor++;
                 on = false;
             } else {
-                grp_lds_add(grp_field(s_g, GF_SEL) + id, 1);
+                grp_lds_add(grp_field<S>(s_g, GF_SEL) + id, 1);
             }
         }
         if (on && k.all_null) on = false;
         if (on && k.def_bits) on = (ldu8(k.def_bits + (r >> 3)) >> (uint32_t)(r & 7)) & 1u;
         uint64_t raw = 0;
         if (VAL && on) on = value_of(r, raw);
-        if (on) grp_lds_add(grp_field(s_g, GF_CNT) + id, 1);
+        if (on) grp_lds_add(grp_field<S>(s_g, GF_CNT) + id, 1);
         if (!VAL) continue;
         double v = 0.0;
         if (flt) {
             if (on) v = kind == FK_F32 ? (double)__uint_as_float((uint32_t)raw) : agg_dbl(raw);
             // the wave's lanes by id: the lowest remaining lane names it, its lanes are added by a fixed tree (the other
             // lanes add 0.0), lane 0 adds the result into the wave's row
-            uint64_t* const row = grp_field(s_g, GF_SUM + (threadIdx.x >> 6));
+            uint64_t* const row = grp_field<S>(s_g, GF_SUM + (threadIdx.x >> 6));
             const uint32_t lane = threadIdx.x & 63;
             uint64_t left = __ballot(on);
             for (uint32_t it = 0; left && it < GRP_TREE_IDS; it++) {
@@ -136,45 +139,46 @@ __device__ __forceinline__ void grp_span(const GrpSink& k, uint64_t& oor, uint32
                 }
             }
             if (on && v != v) {
-                grp_lds_add(grp_field(s_g, GF_NANS) + id, 1);
+                grp_lds_add(grp_field<S>(s_g, GF_NANS) + id, 1);
                 on = false;   // a NaN has no place in min / max
             }
         } else if (on) {   // the 128-bit sum: the low word's old value tells the carry
             const uint64_t x = kind == FK_SIGNED ? agg_sext(raw, w) : raw;
-            const uint64_t old = __hip_atomic_fetch_add((l64p)(grp_field(s_g, GF_SUM) + id), x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            const uint64_t old = __hip_atomic_fetch_add((l64p)(grp_field<S>(s_g, GF_SUM) + id), x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             const uint64_t up = (old + x < x ? 1ull : 0ull) + (kind == FK_SIGNED ? (uint64_t)((int64_t)x >> 63) : 0ull);
-            if (up) grp_lds_add(grp_field(s_g, GF_SUM + 1) + id, up);
+            if (up) grp_lds_add(grp_field<S>(s_g, GF_SUM + 1) + id, up);
         }
         if (on) {
             const uint64_t key = agg_key(kind, w, raw);
-            (void)__hip_atomic_fetch_min((l64p)(grp_field(s_g, GF_KMIN) + id), key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            (void)__hip_atomic_fetch_max((l64p)(grp_field(s_g, GF_KMAX) + id), key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            (void)__hip_atomic_fetch_min((l64p)(grp_field<S>(s_g, GF_KMIN) + id), key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            (void)__hip_atomic_fetch_max((l64p)(grp_field<S>(s_g, GF_KMAX) + id), key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
     }
 }
 
 // The table into the records of `slot`, its flag set, and the workgroup's out-of-range rows added to the column's counter
 // (integers: exact in any order).  By the whole workgroup; barriers inside.
+template <uint32_t S = GRP_MAX_GROUPS>
 __device__ __forceinline__ void grp_store(const GrpLaunch& gl, uint32_t col, uint64_t slot, uint32_t G, bool flt, uint64_t* s_g, uint64_t oor,
                                           uint64_t* s_w64) {
     __syncthreads();
     GrpPart* out = gl.recs + slot * gl.gmax;
     for (uint32_t g = threadIdx.x; g < G; g += WG) {
         GrpPart p;
-        p.sel = grp_field(s_g, GF_SEL)[g];
-        p.cnt = grp_field(s_g, GF_CNT)[g];
-        p.nans = grp_field(s_g, GF_NANS)[g];
-        p.kmin = grp_field(s_g, GF_KMIN)[g];
-        p.kmax = grp_field(s_g, GF_KMAX)[g];
+        p.sel = grp_field<S>(s_g, GF_SEL)[g];
+        p.cnt = grp_field<S>(s_g, GF_CNT)[g];
+        p.nans = grp_field<S>(s_g, GF_NANS)[g];
+        p.kmin = grp_field<S>(s_g, GF_KMIN)[g];
+        p.kmax = grp_field<S>(s_g, GF_KMAX)[g];
         if (flt) {   // the waves' rows, in wave order
-            double s = agg_dbl(grp_field(s_g, GF_SUM)[g]);
+            double s = agg_dbl(grp_field<S>(s_g, GF_SUM)[g]);
 #pragma unroll
-            for (uint32_t wv = 1; wv < WG / 64; wv++) s += agg_dbl(grp_field(s_g, GF_SUM + wv)[g]);
+            for (uint32_t wv = 1; wv < WG / 64; wv++) s += agg_dbl(grp_field<S>(s_g, GF_SUM + wv)[g]);
             p.s0 = agg_bits(s);
             p.s1 = 0;
         } else {
-            p.s0 = grp_field(s_g, GF_SUM)[g];
-            p.s1 = grp_field(s_g, GF_SUM + 1)[g];
+            p.s0 = grp_field<S>(s_g, GF_SUM)[g];
+            p.s1 = grp_field<S>(s_g, GF_SUM + 1)[g];
         }
         p.pad = 0;
         out[g] = p;
@@ -187,6 +191,63 @@ __device__ __forceinline__ void grp_store(const GrpLaunch& gl, uint32_t col, uin
 }
 
 // ---- tiles of None / OneValue / Dict / bit-packed / inflated pages: agg_tile with the grouping sink
+// Rows [lo, hi) of tile `tile` of page `page` into the table of `k`, by the page's codec.  False: a page that has no tiles
+// (RLE pages of <= 8-byte values: k_grp_rle), nothing was looked at.
+template <uint32_t S = GRP_MAX_GROUPS>
+__device__ __forceinline__ bool grp_tile_rows(const DecodeArgs& a, const PageDesc& d, const PageTask& t, const ColDesc& c, const GrpSink& k, uint64_t& oor,
+                                              uint32_t kind, uint32_t page, uint32_t tile, uint64_t lo, uint64_t hi, uint32_t* s_a, uint32_t* s_w) {
+    const uint32_t w = c.width, rows = (uint32_t)(hi - lo);
+    switch (d.codec) {
+        case SB_CODEC_NONE: {
+            const uint8_t* src = d.src;
+            grp_span<true, S>(k, oor, kind, w, lo, hi, [&](uint64_t r, uint64_t& raw) { return raw = flt_load(src + r * w, w), true; });
+            break;
+        }
+        case SB_CODEC_LZ4:
+        case SB_CODEC_ZSTD:
+        case SB_CODEC_SNAPPY:
+        case SB_CODEC_PATAS: {   // inflated into the staging area
+            const uint8_t* src = c.values + t.out_row * w;
+            grp_span<true, S>(k, oor, kind, w, lo, hi, [&](uint64_t r, uint64_t& raw) { return raw = flt_load(src + r * w, w), true; });
+            break;
+        }
+        case SB_CODEC_ONEVALUE: {   // one load for the page: a row brings its id alone
+            const uint64_t one = flt_load(d.body, w);
+            grp_span<true, S>(k, oor, kind, w, lo, hi, [&](uint64_t, uint64_t& raw) { return raw = one, true; });
+            break;
+        }
+        case SB_CODEC_DICT: {
+            U32Stream is{d.isrc, (const uint32_t*)(a.scratch + t.aux_off), d.icodec, d.n_runs, t.num_values};
+            u32_tile_to_lds(is, tile, rows, s_a, s_w);
+            const uint8_t* dict = d.dict;
+            const uint32_t D = d.dict_n;
+            bool bad = false;
+            grp_span<true, S>(k, oor, kind, w, lo, hi, [&](uint64_t r, uint64_t& raw) {
+                const uint32_t e = s_a[sidx((int)(r - lo))];
+                if (e >= D) {
+                    bad = true;
+                    return false;
+                }
+                raw = flt_load(dict + (uint64_t)e * w, w);
+                return true;
+            });
+            if (bad) raise(a.status, SB_ERR_OUT_OF_SPEC, page, 400);
+            break;
+        }
+        case SB_CODEC_BITPACKING:
+        case SB_CODEC_DELTA_BITPACKING: {
+            if (w != 4) break;
+            U32Stream vs{d.body, (const uint32_t*)(a.scratch + t.aux_off), d.codec, 0, t.num_values};
+            u32_tile_to_lds(vs, tile, rows, s_a, s_w);
+            grp_span<true, S>(k, oor, kind, w, lo, hi, [&](uint64_t r, uint64_t& raw) { return raw = (uint64_t)s_a[sidx((int)(r - lo))], true; });
+            break;
+        }
+        default:   // (RLE pages of <= 8-byte values have no tiles: k_grp_rle)
+            return false;
+    }
+    return true;
+}
+
 __device__ void grp_tile(const DecodeArgs& a, const GrpLaunch& gl, uint32_t ti, uint32_t* s_a, uint32_t* s_w, uint64_t* s_g, uint64_t* s_w64) {
     const TileTask tt = a.tiles[ti];
     const PageDesc d = a.descs[tt.page];
@@ -196,7 +257,7 @@ __device__ void grp_tile(const DecodeArgs& a, const GrpLaunch& gl, uint32_t ti, 
     const AggCol g = gl.acols[tt.col];
     if (!(g.ops & AGG_VALUE_OPS)) return;   // (k_grp_null)
     const GrpCol gc = gl.gcols[tt.col];
-    const uint32_t w = c.width, kind = g.kind;
+    const uint32_t kind = g.kind;
     const uint64_t lo = (uint64_t)tt.tile * TILE_ROWS;
     const uint32_t rows = (uint32_t)min((uint64_t)TILE_ROWS, t.num_values - lo);
     const uint64_t hi = lo + rows;
@@ -217,54 +278,7 @@ __device__ void grp_tile(const DecodeArgs& a, const GrpLaunch& gl, uint32_t ti, 
     grp_table_clear(s_g, gc.n_groups);
     const GrpSink k{g.sel, d.def_bits, t.out_row, gc.ids, gc.idw, gc.n_groups, s_g, false};
     uint64_t oor = 0;
-    switch (d.codec) {
-        case SB_CODEC_NONE: {
-            const uint8_t* src = d.src;
-            grp_span<true>(k, oor, kind, w, lo, hi, [&](uint64_t r, uint64_t& raw) { return raw = flt_load(src + r * w, w), true; });
-            break;
-        }
-        case SB_CODEC_LZ4:
-        case SB_CODEC_ZSTD:
-        case SB_CODEC_SNAPPY:
-        case SB_CODEC_PATAS: {   // inflated into the staging area
-            const uint8_t* src = c.values + t.out_row * w;
-            grp_span<true>(k, oor, kind, w, lo, hi, [&](uint64_t r, uint64_t& raw) { return raw = flt_load(src + r * w, w), true; });
-            break;
-        }
-        case SB_CODEC_ONEVALUE: {   // one load for the page: a row brings its id alone
-            const uint64_t one = flt_load(d.body, w);
-            grp_span<true>(k, oor, kind, w, lo, hi, [&](uint64_t, uint64_t& raw) { return raw = one, true; });
-            break;
-        }
-        case SB_CODEC_DICT: {
-            U32Stream is{d.isrc, (const uint32_t*)(a.scratch + t.aux_off), d.icodec, d.n_runs, t.num_values};
-            u32_tile_to_lds(is, tt.tile, rows, s_a, s_w);
-            const uint8_t* dict = d.dict;
-            const uint32_t D = d.dict_n;
-            bool bad = false;
-            grp_span<true>(k, oor, kind, w, lo, hi, [&](uint64_t r, uint64_t& raw) {
-                const uint32_t e = s_a[sidx((int)(r - lo))];
-                if (e >= D) {
-                    bad = true;
-                    return false;
-                }
-                raw = flt_load(dict + (uint64_t)e * w, w);
-                return true;
-            });
-            if (bad) raise(a.status, SB_ERR_OUT_OF_SPEC, tt.page, 400);
-            break;
-        }
-        case SB_CODEC_BITPACKING:
-        case SB_CODEC_DELTA_BITPACKING: {
-            if (w != 4) break;
-            U32Stream vs{d.body, (const uint32_t*)(a.scratch + t.aux_off), d.codec, 0, t.num_values};
-            u32_tile_to_lds(vs, tt.tile, rows, s_a, s_w);
-            grp_span<true>(k, oor, kind, w, lo, hi, [&](uint64_t r, uint64_t& raw) { return raw = (uint64_t)s_a[sidx((int)(r - lo))], true; });
-            break;
-        }
-        default:   // (RLE pages of <= 8-byte values have no tiles: k_grp_rle)
-            return;
-    }
+    if (!grp_tile_rows(a, d, t, c, k, oor, kind, tt.page, tt.tile, lo, hi, s_a, s_w)) return;
     grp_store(gl, tt.col, gl.tile_base + t.first_tile + tt.tile, gc.n_groups, agg_is_float(kind), s_g, oor, s_w64);
 }
 

@@ -12,7 +12,8 @@ namespace sb {
 
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
                    const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp = nullptr, const InCol* icols = nullptr,
-                   const TopkLaunch* topk = nullptr, const KeyLaunch* keys = nullptr, const KeyVarLaunch* keyv = nullptr);
+                   const TopkLaunch* topk = nullptr, const KeyLaunch* keys = nullptr, const KeyVarLaunch* keyv = nullptr,
+                   const GrpLaunch* grpl = nullptr);
 void launch_key_zero(sb_ctx* ctx, const KeyLaunch& kl);
 void launch_key_finish(sb_ctx* ctx, const KeyLaunch& kl, uint64_t* results);
 void launch_key_assign(sb_ctx* ctx, const DecodeArgs& a, const KeyLaunch& kl);
@@ -29,6 +30,10 @@ void launch_grp_zero(sb_ctx* ctx, const GrpLaunch& gl, uint32_t n_cols);
 void launch_grp_finish(sb_ctx* ctx, const GrpLaunch& gl, uint64_t* results, uint32_t n_cols);
 void launch_grp_plain(sb_ctx* ctx, const GrpLaunch& gl, uint32_t n_cols, const uint64_t* rows, const uint8_t* const* values,
                       const uint8_t* const* validity);
+void launch_grpl_zero(sb_ctx* ctx, const GrpLaunch& gl, uint32_t n_cols);
+void launch_grpl_finish(sb_ctx* ctx, const GrpLaunch& gl, uint64_t* results, uint32_t n_cols);
+void launch_grpl_plain(sb_ctx* ctx, const GrpLaunch& gl, uint32_t n_cols, const uint64_t* rows, const uint8_t* const* values,
+                       const uint8_t* const* validity);
 void launch_agg_finish(sb_ctx* ctx, const AggCol* acols, const AggPart* parts, uint64_t* results, uint32_t n_cols);
 void launch_agg_plain(sb_ctx* ctx, const AggCol* acols, uint32_t n_cols, AggPart* parts, const uint64_t* rows, const uint8_t* const* values,
                       const uint8_t* const* validity);
@@ -112,7 +117,7 @@ StageSlot* acquire_slot(sb_ctx* ctx, size_t need) {
     if (s.host)
         for (auto& p : ctx->iv.pending) {
             if (p.host < s.host || p.host >= s.host + s.cap) continue;
-            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::AGG_COL ? AGG_RESULT_WORDS * 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R || p.kind == Pending::AGG_GRP_COL || p.kind == Pending::TOPK_COL || p.kind == Pending::KEY_COL || p.kind == Pending::KEY_VAR_COL) ? (size_t)p.bytes
+            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::AGG_COL ? AGG_RESULT_WORDS * 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R || p.kind == Pending::AGG_GRP_COL || p.kind == Pending::AGG_GRPL_COL || p.kind == Pending::TOPK_COL || p.kind == Pending::KEY_COL || p.kind == Pending::KEY_VAR_COL) ? (size_t)p.bytes
                                                                                                    : (size_t)(2 * p.n + 1) * 8;
             ctx->iv.rescued.emplace_back(p.host, p.host + nb);
             p.host = ctx->iv.rescued.back().data();
@@ -246,10 +251,11 @@ struct ReadMode {
     // in the selected-read kernels / sb_read_selected_var, whose binary columns end in those of sb_read_sel_bin.h /
     // sb_aggregate_columns, whose columns end in the aggregate kernels
     // / sb_aggregate_grouped, an aggregate call whose columns end in the grouped aggregate kernels
+    // / sb_aggregate_grouped_large, the same with up to 1024 groups: a slot per chunk of 16 tiles instead of a slot per tile
     // / sb_topk_columns, an aggregate call whose columns end in the top-k kernels
     // / sb_key_ids, an aggregate call whose columns end in the key kernels: two walks, the finish between them
     // / sb_key_ids_var, the same for binary columns, whose value blocks are staged as a filter call stages them
-    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR, AGGREGATE, AGG_GROUPED, TOPK, KEY_IDS, KEY_IDS_VAR } kind;
+    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR, AGGREGATE, AGG_GROUPED, AGG_GROUPED_LARGE, TOPK, KEY_IDS, KEY_IDS_VAR } kind;
     const FilterCol* filt = nullptr;             // FILTER: one per column
     const std::vector<uint8_t>* lits = nullptr;  // ... the literals of the FK_BYTES columns, FilterCol.lit being the offset of each
     bool in_list = false;                        // ... sb_filter_columns_in: `lits` begins with an InCol per column, whose pointers are offsets in `lits`
@@ -258,7 +264,7 @@ struct ReadMode {
     const SelCol* selc = nullptr;                // SELECTED: one per column (rank: filled in with the call's tables)
     const SelBin* selb = nullptr;                // SELECTED_VAR: one per column beside selc (sums: filled in with the call's tables)
     const AggCol* aggc = nullptr;                // AGGREGATE: one per column (the slots: filled in with the call's tables)
-    const GrpCol* grpc = nullptr;                // AGG_GROUPED: one per column beside aggc
+    const GrpCol* grpc = nullptr;                // AGG_GROUPED, AGG_GROUPED_LARGE: one per column beside aggc
     uint32_t grp_gmax = 0;                       // ... the largest n_groups of the call: records per slot
     const TopkCol* topkc = nullptr;              // TOPK: one per column beside aggc
     uint32_t topk_kmax = 0;                      // ... the largest k of the call: records per slot
@@ -272,8 +278,9 @@ struct ReadMode {
     // Null for the other kinds of call, whose results go to the sb_column_read structs of the call itself.
     void* const* users = nullptr;
     Pending::Kind pending_kind = Pending::READ_COL;
-    bool aggregate() const { return kind == AGGREGATE || kind == AGG_GROUPED || kind == TOPK || kind == KEY_IDS || kind == KEY_IDS_VAR; }   // an AggCol per column, slots per page part and tile
-    bool grouped() const { return kind == AGG_GROUPED; }
+    bool aggregate() const { return kind == AGGREGATE || kind == AGG_GROUPED || kind == AGG_GROUPED_LARGE || kind == TOPK || kind == KEY_IDS || kind == KEY_IDS_VAR; }   // an AggCol per column, slots per page part and tile
+    bool grouped() const { return kind == AGG_GROUPED || kind == AGG_GROUPED_LARGE; }   // a GrpCol per column, flags and gmax records per slot
+    bool grouped_large() const { return kind == AGG_GROUPED_LARGE; }                  // ... whose tile slots are a slot per chunk of GRPL_CHUNK_TILES tiles
     bool topk() const { return kind == TOPK; }
     bool key_ids() const { return kind == KEY_IDS; }
     bool key_var() const { return kind == KEY_IDS_VAR; }
@@ -290,7 +297,7 @@ struct ReadMode {
     // an AGGREGATE call, the header and the gmax group records of an AGG_GROUPED call, the header and the kmax entries of
     // a TOPK call, the header and the kmax key slots of a KEY_IDS call, the header, offsets and bytes of a KEY_IDS_VAR call
     uint64_t result_words() const {
-        return kind == SELECTED_VAR ? 2 : kind == AGGREGATE ? AGG_RESULT_WORDS : kind == AGG_GROUPED ? grp_result_words(grp_gmax) : kind == TOPK ? topk_result_words(topk_kmax) : kind == KEY_IDS ? key_result_words(key_kmax) : kind == KEY_IDS_VAR ? keyv_result_words(key_kmax, key_kbytes) : 1;
+        return kind == SELECTED_VAR ? 2 : kind == AGGREGATE ? AGG_RESULT_WORDS : grouped() ? grp_result_words(grp_gmax) : kind == TOPK ? topk_result_words(topk_kmax) : kind == KEY_IDS ? key_result_words(key_kmax) : kind == KEY_IDS_VAR ? keyv_result_words(key_kmax, key_kbytes) : 1;
     }
 };
 static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, const ReadMode& mode);
@@ -454,12 +461,14 @@ static int32_t replay_interval(sb_ctx* ctx) {
     calls.swap(ctx->iv.calls);
     // the grouped aggregate columns that met a Freq page say so in their result header (k_grp_finish): they alone take the
     // decoded route below, so that a column's route does not depend on what else the interval holds
+    // (the two grouped calls keep their marks apart: one struct may be handed to both in one interval)
     ctx->grp_freq_users.clear();
+    ctx->grpl_freq_users.clear();
     for (const auto& p : ctx->iv.pending)
-        if (p.kind == Pending::AGG_GRP_COL) {
+        if (p.kind == Pending::AGG_GRP_COL || p.kind == Pending::AGG_GRPL_COL) {
             uint64_t met = 0;
             memcpy(&met, p.host + 2 * sizeof(uint64_t), sizeof met);
-            if (met) ctx->grp_freq_users.push_back(p.user);
+            if (met) (p.kind == Pending::AGG_GRP_COL ? ctx->grp_freq_users : ctx->grpl_freq_users).push_back(p.user);
         }
     release_interval(ctx, sb_ctx::Interval::REPLAY);
     clear_freq_logs(ctx);
@@ -475,6 +484,7 @@ static int32_t replay_interval(sb_ctx* ctx) {
     ctx->no_hints = saved;
     ctx->filter_freq = false;
     ctx->grp_freq_users.clear();
+    ctx->grpl_freq_users.clear();
     if (rc != SB_OK) ctx->iv.sticky = rc;
     rc = sb_ctx_synchronize(ctx);   // (in_replay: this one ends the interval whatever the device says)
     ctx->in_replay = false;
@@ -598,7 +608,8 @@ static void deliver_pending(sb_ctx* ctx, const Pending& p, int32_t rc) {
         case Pending::RSEL_COL: deliver_rsel_col(p); break;
         case Pending::RSEL_VAR_COL: deliver_rsel_var_col(p); break;
         case Pending::AGG_COL: deliver_agg_col(p); break;
-        case Pending::AGG_GRP_COL: deliver_agg_grp_col(p, rc == SB_OK); break;
+        case Pending::AGG_GRP_COL:
+        case Pending::AGG_GRPL_COL: deliver_agg_grp_col(p, rc == SB_OK); break;
         case Pending::TOPK_COL: deliver_topk_col(p, rc == SB_OK); break;
         case Pending::KEY_COL: deliver_key_col(p, rc == SB_OK); break;
         case Pending::KEY_VAR_COL: deliver_key_var_col(p, rc == SB_OK); break;
@@ -714,6 +725,7 @@ uint32_t sb_ctx_profile_read(sb_ctx* ctx, sb_kernel_stat* out, uint32_t cap) {
 // What the columns and their page lists decide for the whole call
 struct ReadShape {
     uint64_t P = 0, T = 0;   // pages, tiles
+    uint64_t C = 0;          // chunks of GRPL_CHUNK_TILES tiles, column by column (the tile slots of an AGG_GROUPED_LARGE call)
     uint64_t max_page_len = 0, max_page_rows = 0, pages_bytes = 0;
     uint64_t lzg_pages = 0;  // blocks that may go block-parallel: sb_lz4_giant.h
     bool any_binary = false, any_prim = false;
@@ -728,6 +740,7 @@ static int32_t read_shape(sb_ctx* ctx, sb_column_read* cols, uint64_t n, const R
         if (c.n_pages && !c.metas) return ctx->fail(SB_ERR_INVALID, "metas is null");
         if (c.pages_len && !c.pages && c.physical_type != SB_TYPE_NULL) return ctx->fail(SB_ERR_INVALID, "pages is null");
         uint64_t rows = 0;
+        const uint64_t tiles0 = a.T;
         for (uint64_t p = 0; p < c.n_pages; p++) {
             rows += c.metas[p].num_values;
             a.T += (c.metas[p].num_values + TILE_ROWS - 1) / TILE_ROWS;
@@ -737,6 +750,7 @@ static int32_t read_shape(sb_ctx* ctx, sb_column_read* cols, uint64_t n, const R
         }
         c.rows = rows;
         c.values_len = 0;
+        a.C += grpl_chunks(a.T - tiles0);
         a.P += c.n_pages;
         a.pages_bytes += c.pages_len;
         if (is_binary_t(c.physical_type))
@@ -912,8 +926,10 @@ static ReadLayout read_layout(uint64_t n, const ReadShape& sh, const ReadHints& 
     L.aggp = off;   // an AGGREGATE call's partial records: a slot per (page, RLE part), then a slot per tile
     if (mode.kind == ReadMode::AGGREGATE) off = align_up(off + (P * L.rle_parts + sh.T) * sizeof(AggPart), 64);
     // an AGG_GROUPED call: a flag word per slot, a counter and a Freq mark per column (zeroed), then gmax records per slot (not zeroed)
-    L.grp_recs = align_up(off + (P * L.rle_parts + sh.T + 2 * n) * sizeof(uint64_t), 64);
-    if (mode.grouped()) off = align_up(L.grp_recs + (P * L.rle_parts + sh.T) * mode.grp_gmax * sizeof(GrpPart), 64);
+    // (an AGG_GROUPED_LARGE call: the same with a slot per chunk in the tile slots' place)
+    const uint64_t grp_tile_slots = mode.grouped_large() ? sh.C : sh.T;
+    L.grp_recs = align_up(off + (P * L.rle_parts + grp_tile_slots + 2 * n) * sizeof(uint64_t), 64);
+    if (mode.grouped()) off = align_up(L.grp_recs + (P * L.rle_parts + grp_tile_slots) * mode.grp_gmax * sizeof(GrpPart), 64);
     // a TOPK call: a header per slot (zeroed), then kmax records per slot (not zeroed)
     L.topk_recs = align_up(off + (P * L.rle_parts + sh.T) * sizeof(TopkHead), 64);
     if (mode.topk()) off = align_up(L.topk_recs + (P * L.rle_parts + sh.T) * mode.topk_kmax * sizeof(TopkRec), 64);
@@ -1052,6 +1068,7 @@ static int32_t fill_read_tables(sb_ctx* ctx, uint8_t* host, const ReadLayout& L,
             for (uint64_t p = 0; p < cols[i].n_pages; p++) ntiles += (cols[i].metas[p].num_values + TILE_ROWS - 1) / TILE_ROWS;
             hac[i].page_slot0 = (uint64_t)hc[i].first_page * L.rle_parts;
             hac[i].page_slots = cols[i].n_pages * L.rle_parts;
+            if (mode.grouped_large()) ntiles = grpl_chunks(ntiles);   // (a slot per chunk of the column's tiles)
             hac[i].tile_slot0 = page_i * L.rle_parts + tile0;
             hac[i].tile_slots = ntiles;
             tile0 += ntiles;
@@ -1285,14 +1302,19 @@ static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, 
         if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, &sl, nullptr);
         else launch_rsel_bin(ctx, a, sl);
     } else if (mode.grouped()) {
-        const uint64_t slots = sh.P * L.rle_parts + sh.T;
+        const bool large = mode.grouped_large();
+        const uint64_t slots = sh.P * L.rle_parts + (large ? sh.C : sh.T);
         GrpLaunch gl{(const AggCol*)(ctx->tables.p + L.fcols), (const GrpCol*)(ctx->tables.p + L.bcols), (uint64_t*)(ctx->tables.p + L.aggp),
                      (GrpPart*)(ctx->tables.p + L.grp_recs), slots, sh.P * L.rle_parts, mode.grp_gmax, false, false, (uint32_t)n, ctx->in_replay};
         for (uint64_t i = 0; i < n; i++) ((mode.aggc[i].ops & AGG_VALUE_OPS) ? gl.any_val : gl.any_null) = true;
-        launch_grp_zero(ctx, gl, (uint32_t)n);
-        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, nullptr, nullptr, &gl);
+        if (large) launch_grpl_zero(ctx, gl, (uint32_t)n);
+        else launch_grp_zero(ctx, gl, (uint32_t)n);
+        if (sh.P && large)
+            launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &gl);
+        else if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, nullptr, nullptr, &gl);
         // (a call without a page still has a result: selected, and empty groups)
-        launch_grp_finish(ctx, gl, d_vlen, (uint32_t)n);
+        if (large) launch_grpl_finish(ctx, gl, d_vlen, (uint32_t)n);
+        else launch_grp_finish(ctx, gl, d_vlen, (uint32_t)n);
     } else if (mode.topk()) {
         TopkLaunch tl{(const AggCol*)(ctx->tables.p + L.fcols), (const TopkCol*)(ctx->tables.p + L.bcols), (TopkHead*)(ctx->tables.p + L.aggp),
                       (TopkRec*)(ctx->tables.p + L.topk_recs), sh.P * L.rle_parts + sh.T, sh.P * L.rle_parts, mode.topk_kmax};
@@ -2285,9 +2307,10 @@ int32_t sb_aggregate_columns(sb_ctx* ctx, sb_column_aggregate* cols, uint64_t n,
 
 // ------------------------------------------------------------------------------------ aggregate, grouped
 // The sibling of agg_columns_decoded: reduced from the staging area by k_grp_plain into a slot per TILE_ROWS rows, combined
-// by k_grp_finish.
+// by k_grp_finish.  large (sb_aggregate_grouped_large): by k_grpl_plain into a slot per GRPL_CHUNK_TILES * TILE_ROWS rows,
+// combined by k_grpl_finish.
 static int32_t grp_columns_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pages, std::vector<AggCol>& hs, const std::vector<GrpCol>& hg,
-                                   void* const* users) {
+                                   void* const* users, bool large) {
     const uint64_t n = pages.size();
     std::vector<uint64_t> rows(n);
     for (uint64_t i = 0; i < n; i++) rows[i] = hs[i].rows;
@@ -2297,7 +2320,15 @@ static int32_t grp_columns_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pa
     uint32_t gmax = 1;
     for (const GrpCol& g : hg) gmax = std::max(gmax, g.n_groups);
     std::vector<const uint8_t*> vals(n), bits(n);
-    const uint64_t slots = replay_slots(rr, rows, hs, vals, bits);
+    uint64_t slots = replay_slots(rr, rows, hs, vals, bits);
+    if (large) {   // the columns' chunks back to back, in the tile slots' place
+        slots = 0;
+        for (AggCol& g : hs) {
+            g.tile_slot0 = slots;
+            g.tile_slots = grpl_chunks(g.tile_slots);
+            slots += g.tile_slots;
+        }
+    }
     // [AggCol per column][GrpCol per column][the results][the slots' flags, the columns' counters and Freq marks][the slots' records]
     const size_t res_stride = grp_result_words(gmax) * sizeof(uint64_t);
     size_t off = align_up(n * sizeof(AggCol), 64);
@@ -2319,21 +2350,32 @@ static int32_t grp_columns_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pa
     if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
     uint64_t* d_res = (uint64_t*)(dev + o_res);
     GrpLaunch gl{(const AggCol*)dev, (const GrpCol*)(dev + o_gc), (uint64_t*)(dev + o_flags), (GrpPart*)(dev + o_recs), slots, 0, gmax, true, false, (uint32_t)n, true};
-    launch_grp_zero(ctx, gl, (uint32_t)n);
-    launch_grp_plain(ctx, gl, (uint32_t)n, rows.data(), vals.data(), bits.data());
-    launch_grp_finish(ctx, gl, d_res, (uint32_t)n);
-    return queue_sink_results(ctx, slot, d_res, res_stride, n, Pending::AGG_GRP_COL, users, hg.data(), "grouped aggregate");
+    if (large) {
+        launch_grpl_zero(ctx, gl, (uint32_t)n);
+        launch_grpl_plain(ctx, gl, (uint32_t)n, rows.data(), vals.data(), bits.data());
+        launch_grpl_finish(ctx, gl, d_res, (uint32_t)n);
+    } else {
+        launch_grp_zero(ctx, gl, (uint32_t)n);
+        launch_grp_plain(ctx, gl, (uint32_t)n, rows.data(), vals.data(), bits.data());
+        launch_grp_finish(ctx, gl, d_res, (uint32_t)n);
+    }
+    return queue_sink_results(ctx, slot, d_res, res_stride, n, large ? Pending::AGG_GRPL_COL : Pending::AGG_GRP_COL, users, hg.data(), "grouped aggregate");
 }
 
-int32_t sb_aggregate_grouped(sb_ctx* ctx, sb_column_aggregate_grouped* cols, uint64_t n, int32_t mem) {
+// sb_aggregate_grouped and, with `large`, sb_aggregate_grouped_large: the same checks with the call's own limit, the same
+// Freq rule with the call's own marks, the kernels of sb_aggregate_grouped.h or of sb_aggregate_grouped_large.h
+static int32_t aggregate_grouped_impl(sb_ctx* ctx, sb_column_aggregate_grouped* cols, uint64_t n, int32_t mem, bool large) {
     int32_t rc;
-    if (!sink_entry(ctx, cols, n, mem, "sb_aggregate_grouped", &rc)) return rc;
+    if (!sink_entry(ctx, cols, n, mem, large ? "sb_aggregate_grouped_large" : "sb_aggregate_grouped", &rc)) return rc;
+    const std::vector<const void*>& freq_users = large ? ctx->grpl_freq_users : ctx->grp_freq_users;
     std::vector<AggCol> hs(n);
     std::vector<GrpCol> hg(n);
     for (uint64_t i = 0; i < n; i++) {
         const sb_column_aggregate_grouped& c = cols[i];
         if ((rc = agg_check_ops(ctx, c)) != SB_OK) return rc;
-        if (c.n_groups == 0 || c.n_groups > SB_AGG_MAX_GROUPS) return refuse(ctx, SB_ERR_INVALID, "n_groups is not in 1 .. SB_AGG_MAX_GROUPS");
+        if (!large && (c.n_groups == 0 || c.n_groups > SB_AGG_MAX_GROUPS)) return refuse(ctx, SB_ERR_INVALID, "n_groups is not in 1 .. SB_AGG_MAX_GROUPS");
+        if (large && (c.n_groups == 0 || c.n_groups > SB_AGG_LARGE_MAX_GROUPS))
+            return refuse(ctx, SB_ERR_INVALID, "n_groups is not in 1 .. SB_AGG_LARGE_MAX_GROUPS");
         if (c.group_id_width != 1 && c.group_id_width != 2 && c.group_id_width != 4) return refuse(ctx, SB_ERR_INVALID, "group_id_width is not 1, 2 or 4");
         if (!c.groups) return refuse(ctx, SB_ERR_INVALID, "groups is null");
         if ((rc = agg_check_fill(ctx, c, c.ops, hs[i])) != SB_OK) return rc;
@@ -2357,21 +2399,21 @@ int32_t sb_aggregate_grouped(sb_ctx* ctx, sb_column_aggregate_grouped* cols, uin
         std::vector<bool> dec(n);
         for (uint64_t i = 0; i < n; i++)
             dec[i] = (hs[i].ops & AGG_VALUE_OPS) != 0 &&
-                     std::find(ctx->grp_freq_users.begin(), ctx->grp_freq_users.end(), (const void*)users[i]) != ctx->grp_freq_users.end();
+                     std::find(freq_users.begin(), freq_users.end(), (const void*)users[i]) != freq_users.end();
         std::vector<sb_column_read> r_val = take_if(rc_cols, dec);
         std::vector<AggCol> g_val = take_if(hs, dec);
         const std::vector<GrpCol> c_val = take_if(hg, dec);
         const std::vector<void*> u_val = take_if(users, dec);
-        if (!r_val.empty()) rc = grp_columns_decoded(ctx, std::move(r_val), g_val, c_val, u_val.data());
+        if (!r_val.empty()) rc = grp_columns_decoded(ctx, std::move(r_val), g_val, c_val, u_val.data(), large);
     }
     if (rc == SB_OK && !rc_cols.empty()) {
         if ((rc = stage_shares(ctx, rc_cols.data(), agg_stage_caps(hs).data(), rc_cols.size())) != SB_OK) return rc;
-        ReadMode mode{ReadMode::AGG_GROUPED};
+        ReadMode mode{large ? ReadMode::AGG_GROUPED_LARGE : ReadMode::AGG_GROUPED};
         for (const GrpCol& g : hg) mode.grp_gmax = std::max(mode.grp_gmax, g.n_groups);
         mode.aggc = hs.data();
         mode.grpc = hg.data();
         mode.users = users.data();
-        mode.pending_kind = Pending::AGG_GRP_COL;
+        mode.pending_kind = large ? Pending::AGG_GRPL_COL : Pending::AGG_GRP_COL;
         rc = read_columns_impl(ctx, rc_cols.data(), rc_cols.size(), SB_MEM_DEVICE, mode);
     }
     if (rc != SB_OK) return rc;
@@ -2380,8 +2422,16 @@ int32_t sb_aggregate_grouped(sb_ctx* ctx, sb_column_aggregate_grouped* cols, uin
         column_rows(c, &c.rows);
         c.selected = c.out_of_range = 0;
     }
-    if (!ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::AGG_GROUPED, cols, n, sb_write_options{}, mem});
+    if (!ctx->in_replay)
+        ctx->iv.calls.push_back(sb_ctx::Call{large ? sb_ctx::Call::AGG_GROUPED_LARGE : sb_ctx::Call::AGG_GROUPED, cols, n, sb_write_options{}, mem});
     return rc;
+}
+
+int32_t sb_aggregate_grouped(sb_ctx* ctx, sb_column_aggregate_grouped* cols, uint64_t n, int32_t mem) {
+    return aggregate_grouped_impl(ctx, cols, n, mem, false);
+}
+int32_t sb_aggregate_grouped_large(sb_ctx* ctx, sb_column_aggregate_grouped* cols, uint64_t n, int32_t mem) {
+    return aggregate_grouped_impl(ctx, cols, n, mem, true);
 }
 
 // ------------------------------------------------------------------------------------ top-k

@@ -585,7 +585,7 @@ constexpr uint32_t GRP_MAX_GROUPS = 256;           // SB_AGG_MAX_GROUPS
 struct GrpCol {
     const uint8_t* ids;    // one unsigned id of `idw` bytes per row of the column (input)
     uint32_t idw;          // 1, 2 or 4
-    uint32_t n_groups;     // 1 .. GRP_MAX_GROUPS
+    uint32_t n_groups;     // 1 .. GRP_MAX_GROUPS (sb_aggregate_grouped_large: 1 .. GRPL_MAX_GROUPS)
 };
 struct GrpPart {           // 64 bytes: a group's share of a slot
     uint64_t sel;          // selected rows of the group, null or not
@@ -610,6 +610,25 @@ struct GrpLaunch {   // what launch_decode needs to end a call with the grouped 
     uint32_t n_cols;
     bool replayed;         // the call is issued again: its columns with a Freq page are not on this route (an error if one is)
 };
+// sb_aggregate_grouped_large (sb_aggregate_grouped_large.h): the same structs with up to GRPL_MAX_GROUPS groups.  Its
+// AggCol's tile_slot0 / tile_slots are not a slot per tile but one per CHUNK of GRPL_CHUNK_TILES tiles of the column:
+// tile j of the column (its tiles numbered from 0 through its pages, in page order) belongs to chunk j / GRPL_CHUNK_TILES.
+constexpr uint32_t GRPL_MAX_GROUPS = 1024;         // SB_AGG_LARGE_MAX_GROUPS (== KEY_MAX_KEYS)
+constexpr uint32_t GRPL_CHUNK_TILES = 16;          // 65 536 rows at the most share a table
+__host__ __device__ inline uint64_t grpl_chunks(uint64_t tiles) { return (tiles + GRPL_CHUNK_TILES - 1) / GRPL_CHUNK_TILES; }
+// The page that holds tile `gt` (numbered through the call, as PageTask::first_tile is) among pages [p0, p0 + n) of one
+// column, n > 0, whose first_tile values ascend: the LAST page whose first_tile is <= gt, so that a page without rows,
+// which shares its first_tile with the page behind it, is never the answer for a tile that exists.  gt is at least the
+// first page's first_tile.  A binary search of ceil(log2(n)) steps.
+__host__ __device__ inline uint32_t grpl_page_of(const PageTask* tasks, uint32_t p0, uint32_t n, uint32_t gt) {
+    uint32_t lo = 0, hi = n;   // tasks[p0 + lo].first_tile <= gt; hi == n or tasks[p0 + hi].first_tile > gt
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (tasks[p0 + mid].first_tile <= gt) lo = mid;
+        else hi = mid;
+    }
+    return p0 + lo;
+}
 // one column of a top-k call (sb_topk_columns, sb_topk.h), next to its AggCol, whose slots it uses.  A slot is a header and
 // `kmax` records (the call's largest k), record i of slot s at index s * kmax + i; the headers are zeroed, the records
 // are not, and a record is read only below its header's n.

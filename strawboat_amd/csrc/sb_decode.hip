@@ -3127,6 +3127,7 @@ static void launch_lzg(sb_ctx* ctx, const DecodeArgs& a, bool lzg_on, InflateJob
 #include "sb_read_sel_bin.h"
 #include "sb_aggregate.h"
 #include "sb_aggregate_grouped.h"
+#include "sb_aggregate_grouped_large.h"
 #include "sb_topk.h"
 #include "sb_key_ids.h"
 #include "sb_key_ids_bin.h"
@@ -3134,7 +3135,7 @@ namespace sb {
 
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
                    const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp, const InCol* icols, const TopkLaunch* topk,
-                   const KeyLaunch* keys, const KeyVarLaunch* keyv) {
+                   const KeyLaunch* keys, const KeyVarLaunch* keyv, const GrpLaunch* grpl) {
     hipStream_t s = ctx->stream;
     (void)hipMemsetAsync(a.job_counts, 0, 16 * sizeof(uint32_t), s);
     const bool qa = !(a.read_skips & RSKIP_QUEUE_A);
@@ -3227,6 +3228,10 @@ void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_p
     }
     if (grp) {   // sb_aggregate_grouped: ... to a record per column and group
         launch_grp(ctx, a, *grp);
+        return;
+    }
+    if (grpl) {   // sb_aggregate_grouped_large: ... with a table per chunk of 16 tiles
+        launch_grpl(ctx, a, *grpl);
         return;
     }
     if (topk) {   // sb_topk_columns: ... to the k best rows per column

@@ -1,0 +1,54 @@
+"""group_by:: — SELECT k, count(*), count(y), min(y), max(y), sum(y) ... WHERE ... GROUP BY k in one call.
+
+The whole chain on the device, in one synchronize interval: `key_ids` (integer keys) or `key_ids_var` (Binary /
+Utf8 keys) turns the key column into dense ids, `aggregate_grouped` (max_keys <= 256) or
+`aggregate_grouped_large` (up to 1024) reduces the value columns per id.  The number of distinct keys is not
+known before the synchronize, so every value column gets `max_keys` groups; the groups behind `n_keys` are
+empty, and `trim` cuts them off afterwards.  The selected rows whose key is null arrive in `out_of_range`.  More
+than `max_keys` distinct keys set the keys result's `overflow`, which is passed through, not raised: the groups
+mean nothing then.
+"""
+from typing import List, Sequence, Tuple
+
+import numpy as np
+
+from . import _native as N
+from .aggregate_grouped import MAX_GROUPS, Group, GroupedAggregate, aggregate_grouped
+from .aggregate_grouped_large import MAX_GROUPS_LARGE, aggregate_grouped_large
+from .key_ids import INTEGER_TYPES, key_ids
+from .key_ids_var import BINARY_TYPES, key_ids_var
+from .read import ColumnPages
+
+
+def check_group_by(key_type, max_keys):
+    """The refusals that need no device: the key's type and max_keys."""
+    if key_type not in INTEGER_TYPES and key_type not in BINARY_TYPES:
+        raise ValueError("group_by keys are 8- to 64-bit integers or Binary / LargeBinary, not physical type %d" % key_type)
+    if isinstance(max_keys, bool) or not isinstance(max_keys, (int, np.integer)) or not 1 <= max_keys <= MAX_GROUPS_LARGE:
+        raise ValueError("max_keys is %r, not an int in 1 .. %d" % (max_keys, MAX_GROUPS_LARGE))
+
+
+def group_by(ctx, key: ColumnPages, values: List[ColumnPages], selection=None,
+             ops: Sequence[str] = ("count", "min", "max", "sum"), max_keys: int = N.SB_KEY_MAX_KEYS) -> Tuple[object, List[GroupedAggregate]]:
+    """Enqueue the keys and ids of `key` and the per-key aggregates of every column of `values` under `selection`
+    (one for all, or None: every row) on ctx's stream.  Returns (keys_result, [GroupedAggregate per value column]):
+    a KeyIds or KeyIdsVar, and results of max_keys groups each; all valid after ctx.synchronize()."""
+    check_group_by(key.physical_type, max_keys)
+    max_keys = int(max_keys)
+    if key.physical_type in INTEGER_TYPES:
+        kres = key_ids(ctx, [key], selection, max_keys=max_keys)[0]
+    else:
+        kres = key_ids_var(ctx, [key], selection, max_keys=max_keys)[0]
+    if not values:
+        return kres, []
+    call = aggregate_grouped if max_keys <= MAX_GROUPS else aggregate_grouped_large
+    return kres, call(ctx, list(values), kres.ids, max_keys, selection, ops)
+
+
+def trim(keys_result, aggregates: List[GroupedAggregate]) -> List[List[Group]]:
+    """After the synchronize: the groups of every value column that have a key, groups[i][g] belonging to key g of
+    keys_result.  Raises on an overflow of the keys: the ids, and with them the groups, mean nothing then."""
+    if keys_result.overflow:
+        raise ValueError("the key column has more distinct keys than max_keys (overflow %d)" % int(keys_result.overflow))
+    n = keys_result.n_keys
+    return [list(a.groups[:n]) for a in aggregates]
