@@ -800,6 +800,75 @@ typedef struct sb_column_key_ids_var {
 
 int32_t sb_key_ids_var(sb_ctx* ctx, sb_column_key_ids_var* cols, uint64_t n, int32_t mem);
 
+/* ------------------------------------------------------------------ ids of composite keys
+ * SELECT ... GROUP BY a, b / SELECT DISTINCT a, b.  Every key column goes through sb_key_ids / sb_key_ids_var first; the
+ * 2 .. 4 id arrays they wrote (DEVICE) go in here, and one call turns them into the sorted distinct tuples of part ids
+ * (`tuples`, HOST) and a dense tuple id per row (`ids`, DEVICE), which sb_aggregate_grouped / _large take as group ids.
+ * No page is read and the call takes no selection: the part ids carry it.
+ *
+ *   parts         part p is part_ids[p]: `rows` unsigned integers of part_width[p] bytes, inside part_capacity[p] bytes.
+ *                 part_keys[p] (1 .. SB_KEY_MAX_KEYS) is the exclusive bound of a valid id of that part: the max_keys of
+ *                 the call that wrote it, since its n_keys is not known before the synchronize.  The fields of the parts
+ *                 at and behind n_parts are ignored.
+ *   live rows     a row is live if every part id is below its part's bound.  All ones — what sb_key_ids* write for a row
+ *                 that is not selected or null — is therefore not live, and neither is any other id at or above the bound;
+ *                 no error is raised for one.  `live` counts the live rows.  A row with a null in any key column has no
+ *                 tuple: under sb_aggregate_grouped it ends in out_of_range, as with a single key.
+ *   tuples        the distinct tuples of the live rows, n_keys of them, ascending lexicographically by part id with part 0
+ *                 most significant; the part ids of sb_key_ids* preserve the order of the key values, so this is the order
+ *                 of the key values too.  Tuple i is tuples[4 * i .. 4 * i + 4), the parts at and behind n_parts written
+ *                 as 0; tuples[4 * n_keys .. 4 * max_keys) is written as 0.
+ *   ids           one unsigned integer of id_width bytes per row, all `rows` of them written: the position of the row's
+ *                 tuple in `tuples`, or all ones (SB_KEY_ID_NONE truncated to id_width) for a row that is not live.  A
+ *                 function of the data alone: the same bytes whatever the schedule, a replayed interval included.
+ *   max_keys      1 .. min(SB_KEY_MAX_KEYS, 2^(8 * id_width) - 1), as in sb_key_ids.
+ *   overflow      more than max_keys distinct tuples: overflow = 1 and the synchronize still returns SB_OK; n_keys,
+ *                 `tuples` and `ids` are unspecified then.  Otherwise 0.  Either way nothing is written outside
+ *                 tuples[0 .. 4 * max_keys) and ids_capacity.
+ *   rows == 0     is valid: live and n_keys are 0.
+ *
+ * Whatever bits the part arrays hold (the ids of a part that itself overflowed are unspecified), no access leaves
+ * rows * part_width[p] bytes of a part, rows * id_width bytes of `ids` or the call's workspace: an id is compared with its
+ * bound before anything else is done with it, and it is never an index.
+ *
+ * Refused at the call, nothing enqueued and no result field or output byte touched: SB_MEM_HOST and more than 65535 items
+ * (SB_ERR_NYI); n_parts outside 2 .. 4, a part_width or id_width that is not 1 / 2 / 4, part_keys[p] 0 or above
+ * SB_KEY_MAX_KEYS, a part pointer or `ids` that is null with rows > 0, misaligned to its width or shorter than
+ * rows * width bytes, max_keys 0 or above its limit, `tuples` null, `reserved` != 0, `ids` overlapping any part of any
+ * item of the call, the `ids` of two items overlapping (SB_ERR_INVALID).  The part arrays are INPUTS: they stay
+ * unmodified until the synchronize.
+ *
+ * Part of the synchronize interval like sb_key_ids: on a replay it is issued again in its place, behind the sb_key_ids*
+ * calls that write its parts and in front of the grouped aggregates that read its ids.  It never asks for a replay itself,
+ * consults no launch hint of the read path and leaves its counters alone.  On a failed interval its results are
+ * unspecified.
+ *
+ * Layout (pinned by tests/test_key_combine_host.py): sb_key_combine_item 168 bytes; rows 0, n_parts 8, id_width 12,
+ * part_ids 16, part_capacity 48, part_width 80, part_keys 96, ids 112, ids_capacity 120, max_keys 128, reserved 132,
+ * tuples 136, live 144, n_keys 152, overflow 160. */
+#define SB_KEY_COMBINE_MAX_PARTS 4u
+
+typedef struct sb_key_combine_item {
+    uint64_t rows;
+    uint32_t n_parts;        /* 2 .. SB_KEY_COMBINE_MAX_PARTS */
+    uint32_t id_width;       /* of `ids`: 1, 2 or 4 */
+    const void* part_ids[SB_KEY_COMBINE_MAX_PARTS];   /* DEVICE, input: one id per row, aligned to part_width[p] */
+    uint64_t part_capacity[SB_KEY_COMBINE_MAX_PARTS]; /* >= rows * part_width[p] bytes */
+    uint32_t part_width[SB_KEY_COMBINE_MAX_PARTS];    /* 1, 2 or 4 */
+    uint32_t part_keys[SB_KEY_COMBINE_MAX_PARTS];     /* 1 .. SB_KEY_MAX_KEYS: ids at or above it are not live */
+    void* ids;               /* DEVICE, output: one id per row, aligned to id_width */
+    uint64_t ids_capacity;   /* >= rows * id_width bytes */
+    uint32_t max_keys;       /* 1 .. min(SB_KEY_MAX_KEYS, 2^(8 * id_width) - 1) */
+    uint32_t reserved;       /* must be 0 */
+    uint32_t* tuples;        /* HOST, 4 * max_keys entries, filled at the synchronize; must live until then */
+    /* results (HOST, valid after sb_ctx_synchronize) */
+    uint64_t live;           /* rows whose part ids are all below their bounds */
+    uint64_t n_keys;         /* distinct tuples among them */
+    uint64_t overflow;       /* 1: more than max_keys of them; n_keys, tuples and ids are unspecified */
+} sb_key_combine_item;       /* 168 bytes */
+
+int32_t sb_key_combine(sb_ctx* ctx, sb_key_combine_item* items, uint64_t n, int32_t mem);
+
 /* ------------------------------------------------------------------ encode
  * Replaces, per leaf column, the page loop of NativeWriter::encode_chunk
  * (src/write/common.rs:54-109): page slicing, then per page write::write -> write_simple

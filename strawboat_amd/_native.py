@@ -24,7 +24,8 @@ EXPORTS = ("sb_version", "sb_ctx_create", "sb_ctx_destroy", "sb_ctx_synchronize"
            "sb_file_reader_close", "sb_stat_page", "sb_schema_last_error", "sb_schema_to_bytes", "sb_schema_from_bytes",
            "sb_schema_metadata_from_bytes", "sb_filter_columns", "sb_filter_columns_var", "sb_read_selected",
            "sb_read_selected_var", "sb_aggregate_columns", "sb_aggregate_grouped", "sb_filter_columns_in",
-           "sb_topk_columns", "sb_key_ids", "sb_key_ids_var", "sb_aggregate_grouped_large")
+           "sb_topk_columns", "sb_key_ids", "sb_key_ids_var", "sb_aggregate_grouped_large",
+           "sb_key_combine")
 
 SB_PRED_EQ, SB_PRED_NE, SB_PRED_LT, SB_PRED_LE, SB_PRED_GT, SB_PRED_GE, SB_PRED_IS_NULL, SB_PRED_IS_NOT_NULL = range(8)
 SB_PRED_STARTS_WITH = 8   # binary types only (sb_filter_columns_var)
@@ -42,6 +43,7 @@ SB_KEY_MAX_KEYS = 1024
 SB_KEY_ID_NONE = 0xFFFFFFFF
 SB_KEY_VAR_MAX_BYTES = 1 << 20
 SB_KEY_OVERFLOW_KEYS, SB_KEY_OVERFLOW_BYTES = 1, 2
+SB_KEY_COMBINE_MAX_PARTS = 4
 
 
 class PageMetaC(C.Structure):
@@ -166,6 +168,14 @@ class ColumnKeyIdsVarC(C.Structure):
                 ("keys_len", C.c_uint64), ("overflow", C.c_uint64)]
 
 
+class KeyCombineItemC(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("n_parts", C.c_uint32), ("id_width", C.c_uint32),
+                ("part_ids", C.c_void_p * 4), ("part_capacity", C.c_uint64 * 4), ("part_width", C.c_uint32 * 4),
+                ("part_keys", C.c_uint32 * 4), ("ids", C.c_void_p), ("ids_capacity", C.c_uint64),
+                ("max_keys", C.c_uint32), ("reserved", C.c_uint32), ("tuples", C.c_void_p),
+                ("live", C.c_uint64), ("n_keys", C.c_uint64), ("overflow", C.c_uint64)]
+
+
 class ColumnWriteC(C.Structure):
     _fields_ = [("physical_type", C.c_int32), ("is_nullable", C.c_int32), ("rows", C.c_uint64),
                 ("values", C.c_void_p), ("values_bit_offset", C.c_uint64), ("values_len", C.c_uint64),
@@ -275,6 +285,8 @@ def load():
     L.sb_key_ids.argtypes = [C.c_void_p, C.POINTER(ColumnKeyIdsC), C.c_uint64, C.c_int32]
     L.sb_key_ids_var.restype = C.c_int32
     L.sb_key_ids_var.argtypes = [C.c_void_p, C.POINTER(ColumnKeyIdsVarC), C.c_uint64, C.c_int32]
+    L.sb_key_combine.restype = C.c_int32
+    L.sb_key_combine.argtypes = [C.c_void_p, C.POINTER(KeyCombineItemC), C.c_uint64, C.c_int32]
     L.sb_read_columns_sizes.restype = C.c_int32
     L.sb_read_columns_sizes.argtypes = [C.c_void_p, C.POINTER(ColumnReadC), C.c_uint64, C.c_int32]
     L.sb_write_bound.restype = C.c_uint64

@@ -22,6 +22,7 @@ void launch_key_assign_plain(sb_ctx* ctx, const KeyLaunch& kl, const uint64_t* r
 void launch_keyv_zero(sb_ctx* ctx, const KeyVarLaunch& kl);
 void launch_keyv_finish(sb_ctx* ctx, const DecodeArgs& a, const KeyVarLaunch& kl, uint64_t* results);
 void launch_keyv_assign(sb_ctx* ctx, const DecodeArgs& a, const KeyVarLaunch& kl);
+void launch_key_combine(sb_ctx* ctx, const CombLaunch& cl, uint64_t* results);
 void launch_topk_zero(sb_ctx* ctx, const TopkLaunch& tl);
 void launch_topk_finish(sb_ctx* ctx, const TopkLaunch& tl, uint64_t* results, uint32_t n_cols);
 void launch_topk_plain(sb_ctx* ctx, const TopkLaunch& tl, uint32_t n_cols, const uint64_t* rows, const uint8_t* const* values,
@@ -117,7 +118,7 @@ StageSlot* acquire_slot(sb_ctx* ctx, size_t need) {
     if (s.host)
         for (auto& p : ctx->iv.pending) {
             if (p.host < s.host || p.host >= s.host + s.cap) continue;
-            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::AGG_COL ? AGG_RESULT_WORDS * 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R || p.kind == Pending::AGG_GRP_COL || p.kind == Pending::AGG_GRPL_COL || p.kind == Pending::TOPK_COL || p.kind == Pending::KEY_COL || p.kind == Pending::KEY_VAR_COL) ? (size_t)p.bytes
+            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::AGG_COL ? AGG_RESULT_WORDS * 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R || p.kind == Pending::AGG_GRP_COL || p.kind == Pending::AGG_GRPL_COL || p.kind == Pending::TOPK_COL || p.kind == Pending::KEY_COL || p.kind == Pending::KEY_VAR_COL || p.kind == Pending::COMB_ITEM) ? (size_t)p.bytes
                                                                                                    : (size_t)(2 * p.n + 1) * 8;
             ctx->iv.rescued.emplace_back(p.host, p.host + nb);
             p.host = ctx->iv.rescued.back().data();
@@ -220,6 +221,7 @@ void sb_ctx_destroy(sb_ctx* ctx) {
     if (ctx->scratch.p) (void)hipFree(ctx->scratch.p);
     if (ctx->staging.p) (void)hipFree(ctx->staging.p);
     if (ctx->filter_stage.p) (void)hipFree(ctx->filter_stage.p);
+    if (ctx->combine.p) (void)hipFree(ctx->combine.p);
     if (ctx->zlit.p) (void)hipFree(ctx->zlit.p);
     if (ctx->zrec.p) (void)hipFree(ctx->zrec.p);
     if (ctx->zb_stats) (void)hipFree(ctx->zb_stats);
@@ -580,6 +582,27 @@ static void deliver_key_var_col(const Pending& p, bool ok) {
     if (len) memcpy(c->keys, p.host + sizeof head + (kmax + 1) * 8, len);
     if (cap > len) memset(c->keys + len, 0, cap - len);
 }
+// k_key_finish's header and sorted codes of a key-combine item (sb_key_combine.h): { rows, live, n_keys, overflow, 0 .. },
+// then kmax codes, of which the first n_keys are unpacked into `tuples`; a failed interval delivers nothing
+static void deliver_comb_item(const Pending& p, bool ok) {
+    if (!ok) return;
+    uint64_t head[8];
+    memcpy(head, p.host, sizeof head);
+    sb_key_combine_item* c = (sb_key_combine_item*)p.user;
+    c->live = head[1];
+    c->n_keys = head[2];
+    c->overflow = head[3];
+    // (max_keys and n_parts as the struct has them now, but never more codes than the record that was enqueued holds)
+    const size_t room = ((size_t)p.bytes - sizeof head) / 8, cap = std::min<size_t>((size_t)c->max_keys, room);
+    const size_t nk = head[3] ? 0 : std::min<size_t>((size_t)head[2], cap);
+    const uint32_t parts = std::min<uint32_t>(c->n_parts, COMB_MAX_PARTS);
+    for (size_t i = 0; i < nk; i++) {
+        uint64_t code;
+        memcpy(&code, p.host + sizeof head + i * 8, 8);
+        comb_unpack(code, parts, c->tuples + COMB_MAX_PARTS * i);
+    }
+    memset(c->tuples + COMB_MAX_PARTS * nk, 0, ((size_t)c->max_keys - nk) * COMB_MAX_PARTS * sizeof(uint32_t));
+}
 static void deliver_write_col(const Pending& p) {
     sb_column_write* c = (sb_column_write*)p.user;
     const uint64_t* lens = (const uint64_t*)p.host;  // [n_pages lengths][n_pages num_values][total]
@@ -613,6 +636,7 @@ static void deliver_pending(sb_ctx* ctx, const Pending& p, int32_t rc) {
         case Pending::TOPK_COL: deliver_topk_col(p, rc == SB_OK); break;
         case Pending::KEY_COL: deliver_key_col(p, rc == SB_OK); break;
         case Pending::KEY_VAR_COL: deliver_key_var_col(p, rc == SB_OK); break;
+        case Pending::COMB_ITEM: deliver_comb_item(p, rc == SB_OK); break;
         case Pending::WRITE_COL: deliver_write_col(p); break;
         case Pending::ENC_HINT:
             if (rc == SB_OK) apply_enc_hint(ctx, p);
@@ -1373,7 +1397,7 @@ static void push_pending(sb_ctx* ctx, Pending::Kind kind, void* const* users, co
         pd.n = 0;
         if (grpc) pd.bytes = sizeof(uint64_t) * grp_result_words(grpc[i].n_groups);
         if (kind == Pending::TOPK_COL) pd.bytes = stride;   // (the header and kmax entries: the column's own k is in its struct)
-        if (kind == Pending::KEY_COL) pd.bytes = stride;    // (likewise: the header and kmax key slots)
+        if (kind == Pending::KEY_COL || kind == Pending::COMB_ITEM) pd.bytes = stride;    // (likewise: the header and kmax key slots / codes)
         if (kind == Pending::KEY_VAR_COL) pd.bytes = stride, pd.n = kmax;   // (the header, kmax + 1 offsets, the bytes)
         ctx->iv.pending.push_back(pd);
     }
@@ -2711,6 +2735,122 @@ int32_t sb_key_ids_var(sb_ctx* ctx, sb_column_key_ids_var* cols, uint64_t n, int
     }
     if (!ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::KEY_IDS_VAR, cols, n, sb_write_options{}, mem});
     return rc;
+}
+
+// ------------------------------------------------------------------------------------ ids of composite keys
+static_assert(sizeof(sb_key_combine_item) == 168 && offsetof(sb_key_combine_item, n_parts) == 8 && offsetof(sb_key_combine_item, id_width) == 12 &&
+                  offsetof(sb_key_combine_item, part_ids) == 16 && offsetof(sb_key_combine_item, part_capacity) == 48 &&
+                  offsetof(sb_key_combine_item, part_width) == 80 && offsetof(sb_key_combine_item, part_keys) == 96 &&
+                  offsetof(sb_key_combine_item, ids) == 112 && offsetof(sb_key_combine_item, ids_capacity) == 120 &&
+                  offsetof(sb_key_combine_item, max_keys) == 128 && offsetof(sb_key_combine_item, reserved) == 132 &&
+                  offsetof(sb_key_combine_item, tuples) == 136 && offsetof(sb_key_combine_item, live) == 144 &&
+                  offsetof(sb_key_combine_item, n_keys) == 152 && offsetof(sb_key_combine_item, overflow) == 160,
+              "the layout the header pins");
+static_assert(SB_KEY_COMBINE_MAX_PARTS == COMB_MAX_PARTS, "the header's limit");
+
+// No page is read, so no read_columns_impl: the call's workspace is carved out of a buffer of the context's that grows
+// (ctx->combine), as read_columns_impl carves ctx->tables --
+//   [AggCol per item][KeyCol per item][CombItem per item]   uploaded from the staging slot
+//   [k_key_finish's records]                                read back into the slot, behind the upload
+//   [KeyState per item, the items' tables]                  zeroed
+//   [KEY_MAX_KEYS sorted codes per item]
+// -- and everything travels on the context's stream, behind the calls that write the parts.
+int32_t sb_key_combine(sb_ctx* ctx, sb_key_combine_item* items, uint64_t n, int32_t mem) {
+    int32_t rc;
+    if (!sink_entry(ctx, items, n, mem, "sb_key_combine", &rc)) return rc;
+    if (n > 65535) return refuse(ctx, SB_ERR_NYI, "sb_key_combine: more than 65535 items in one call");
+    std::vector<AggCol> hs(n);
+    std::vector<KeyCol> hk(n);
+    std::vector<CombItem> hc(n);
+    uint64_t slots = 0, max_rows = 0;
+    uint32_t kmax = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_key_combine_item& c = items[i];
+        if (c.n_parts < 2 || c.n_parts > SB_KEY_COMBINE_MAX_PARTS) return refuse(ctx, SB_ERR_INVALID, "n_parts is not in 2 .. SB_KEY_COMBINE_MAX_PARTS");
+        if (c.id_width != 1 && c.id_width != 2 && c.id_width != 4) return refuse(ctx, SB_ERR_INVALID, "id_width is not 1, 2 or 4");
+        const uint64_t limit = std::min<uint64_t>(SB_KEY_MAX_KEYS, (1ull << (8 * c.id_width)) - 1);
+        if (c.max_keys == 0 || c.max_keys > limit) return refuse(ctx, SB_ERR_INVALID, "max_keys is not in 1 .. min(SB_KEY_MAX_KEYS, 2^(8 * id_width) - 1)");
+        if (c.reserved) return refuse(ctx, SB_ERR_INVALID, "reserved is not 0");
+        if (!c.tuples) return refuse(ctx, SB_ERR_INVALID, "tuples is null");
+        if (c.rows > (1ull << 60)) return refuse(ctx, SB_ERR_INVALID, "rows * width overflows");
+        memset(&hc[i], 0, sizeof hc[i]);
+        for (uint32_t p = 0; p < c.n_parts; p++) {
+            const uint32_t w = c.part_width[p];
+            if (w != 1 && w != 2 && w != 4) return refuse(ctx, SB_ERR_INVALID, "part_width is not 1, 2 or 4");
+            if (c.part_keys[p] == 0 || c.part_keys[p] > SB_KEY_MAX_KEYS) return refuse(ctx, SB_ERR_INVALID, "part_keys is not in 1 .. SB_KEY_MAX_KEYS");
+            if (c.rows && !c.part_ids[p]) return refuse(ctx, SB_ERR_INVALID, "a part's ids are null");
+            if (c.part_ids[p] && (((uintptr_t)c.part_ids[p] & (w - 1)) || c.part_capacity[p] < c.rows * w))
+                return refuse(ctx, SB_ERR_INVALID, "a part's ids are not aligned to part_width or smaller than rows * part_width bytes");
+            hc[i].part[p] = (const uint8_t*)c.part_ids[p];
+            hc[i].width[p] = w;
+            hc[i].bound[p] = c.part_keys[p];
+        }
+        hc[i].n_parts = c.n_parts;
+        if (c.rows && !c.ids) return refuse(ctx, SB_ERR_INVALID, "ids is null");
+        if (c.ids && (((uintptr_t)c.ids & (c.id_width - 1)) || c.ids_capacity < c.rows * c.id_width))
+            return refuse(ctx, SB_ERR_INVALID, "ids not aligned to id_width or smaller than rows * id_width bytes");
+        memset(&hs[i], 0, sizeof hs[i]);
+        hs[i].rows = c.rows;
+        hs[i].kind = FK_UNSIGNED;   // (the codes order and come back as they are)
+        hs[i].ptype = SB_TYPE_UINT64;
+        hs[i].w = 8;
+        hk[i] = KeyCol{(uint8_t*)c.ids, slots, key_table_slots(c.max_keys) - 1, c.max_keys, c.id_width, 0};
+        slots += key_table_slots(c.max_keys);
+        kmax = std::max(kmax, c.max_keys);
+        max_rows = std::max(max_rows, c.rows);
+    }
+    for (uint64_t i = 0; i < n; i++) {   // (the bytes an item writes: rows * id_width; the inputs must survive until a replay)
+        const uintptr_t a0 = (uintptr_t)items[i].ids, a1 = a0 + items[i].rows * items[i].id_width;
+        if (a0 == a1) continue;   // (no byte is written)
+        for (uint64_t j = 0; j < n; j++) {
+            if (items[j].rows == 0) continue;
+            for (uint32_t p = 0; p < items[j].n_parts; p++) {
+                const uintptr_t b0 = (uintptr_t)items[j].part_ids[p], b1 = b0 + items[j].rows * items[j].part_width[p];
+                if (a0 < b1 && b0 < a1) return refuse(ctx, SB_ERR_INVALID, "ids overlaps a part of an item of the call");
+            }
+            if (j <= i) continue;
+            const uintptr_t b0 = (uintptr_t)items[j].ids, b1 = b0 + items[j].rows * items[j].id_width;
+            if (a0 < b1 && b0 < a1) return refuse(ctx, SB_ERR_INVALID, "ids of two items of one call overlap");
+        }
+    }
+    (void)hipSetDevice(ctx->device);
+    const size_t res_stride = key_result_words(kmax) * sizeof(uint64_t);
+    size_t off = align_up(n * sizeof(AggCol), 64);
+    const size_t o_kc = off;
+    off = align_up(off + n * sizeof(KeyCol), 64);
+    const size_t o_items = off;
+    off = align_up(off + n * sizeof(CombItem), 64);
+    const size_t upload = off, o_res = off;
+    off = align_up(off + n * res_stride, 64);
+    const size_t o_state = off;
+    off = align_up(off + n * sizeof(KeyState) + (size_t)slots * sizeof(uint64_t), 64);
+    const size_t o_sorted = off;
+    off += n * KEY_MAX_KEYS * sizeof(uint64_t);
+    if (!ensure(ctx, ctx->combine, off + 64)) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(key combine workspace) failed");
+    StageSlot* slot = acquire_slot(ctx, upload + n * res_stride);
+    if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
+    memset(slot->host, 0, upload);
+    memcpy(slot->host, hs.data(), n * sizeof(AggCol));
+    memcpy(slot->host + o_kc, hk.data(), n * sizeof(KeyCol));
+    memcpy(slot->host + o_items, hc.data(), n * sizeof(CombItem));
+    uint8_t* dev = ctx->combine.p;
+    hipError_t e = hipMemcpyAsync(dev, slot->host, upload, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) return check_hip(ctx, e, "key combine upload");
+    const CombLaunch cl{(const CombItem*)(dev + o_items), key_launch_at(dev, dev + o_kc, dev + o_state, dev + o_sorted, n, slots, kmax), max_rows};
+    launch_key_combine(ctx, cl, (uint64_t*)(dev + o_res));
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(slot->host + upload, dev + o_res, n * res_stride, hipMemcpyDeviceToHost, ctx->stream);
+    if (e != hipSuccess) return check_hip(ctx, e, "key combine");
+    (void)hipEventRecord(slot->done, ctx->stream);
+    slot->in_flight = true;
+    std::vector<void*> users(n);
+    for (uint64_t i = 0; i < n; i++) {
+        users[i] = &items[i];
+        items[i].live = items[i].n_keys = items[i].overflow = 0;
+    }
+    push_pending(ctx, Pending::COMB_ITEM, users.data(), slot->host + upload, res_stride, n);
+    if (!ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::KEY_COMBINE, items, n, sb_write_options{}, mem});
+    return SB_OK;
 }
 
 

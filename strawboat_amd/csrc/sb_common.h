@@ -381,6 +381,42 @@ struct KeyLaunch {   // what launch_decode needs to end a call with the collect 
     uint32_t kmax;
     uint32_t n_cols;
 };
+// ---- sb_key_combine (sb_key_combine.h): the key of a row is a tuple of 2 .. 4 part ids, each below KEY_MAX_KEYS.  Its
+// code is a 64-bit word with one COMB_FIELD_BITS field per part, part 0 highest, so that codes order as the tuples do
+// lexicographically.  The host's delivery, the kernels and tests/test_key_combine_host.py use these two functions.
+constexpr uint32_t COMB_MAX_PARTS = 4;             // SB_KEY_COMBINE_MAX_PARTS
+constexpr uint32_t COMB_FIELD_BITS = 10;           // 2^10 == KEY_MAX_KEYS: a valid part id fits a field
+static_assert((1u << COMB_FIELD_BITS) == KEY_MAX_KEYS && COMB_MAX_PARTS * COMB_FIELD_BITS <= 64, "a field per part id");
+__host__ __device__ inline uint64_t comb_pack(const uint32_t* part_id, uint32_t n_parts) {
+    uint64_t code = 0;
+    for (uint32_t p = 0; p < n_parts; p++) code = (code << COMB_FIELD_BITS) | (uint64_t)(part_id[p] & (KEY_MAX_KEYS - 1));
+    return code;
+}
+// the n_parts part ids of a code into out[0 .. n_parts), 0 into out[n_parts .. COMB_MAX_PARTS)
+__host__ __device__ inline void comb_unpack(uint64_t code, uint32_t n_parts, uint32_t* out) {
+    for (uint32_t p = COMB_MAX_PARTS; p-- > 0;) {
+        if (p >= n_parts) {
+            out[p] = 0;
+            continue;
+        }
+        out[p] = (uint32_t)(code & (KEY_MAX_KEYS - 1));
+        code >>= COMB_FIELD_BITS;
+    }
+}
+// one item of a key-combine call, next to its AggCol (rows; no selection; the codes are a FK_UNSIGNED column of 8-byte
+// values) and its KeyCol (ids, the table, max_keys), which k_key_finish and key_stage take as they are
+struct CombItem {
+    const uint8_t* part[COMB_MAX_PARTS];   // the part id arrays (input)
+    uint32_t width[COMB_MAX_PARTS];        // 1, 2 or 4 bytes per id
+    uint32_t bound[COMB_MAX_PARTS];        // an id at or above it: the row is not live
+    uint32_t n_parts;                      // 2 .. COMB_MAX_PARTS
+    uint32_t pad;
+};
+struct CombLaunch {
+    const CombItem* items;
+    KeyLaunch kl;          // acols / kcols / st / tabs / sorted of the call's items, as for sb_key_ids
+    uint64_t max_rows;     // of the call's items
+};
 // ---- sb_key_ids_var (sb_key_ids_bin.h): the keys are byte strings.  The order is sb_filter_columns_var's (bin_rel_prefix):
 // bytes unsigned, a proper prefix less than the longer string.  The helpers below are the host's and the device's alike
 // (tests/test_key_ids_var_host.py runs them against std::lexicographical_compare / std::lower_bound); a load never touches

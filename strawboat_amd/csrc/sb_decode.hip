@@ -3131,6 +3131,7 @@ static void launch_lzg(sb_ctx* ctx, const DecodeArgs& a, bool lzg_on, InflateJob
 #include "sb_topk.h"
 #include "sb_key_ids.h"
 #include "sb_key_ids_bin.h"
+#include "sb_key_combine.h"
 namespace sb {
 
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,

@@ -7,6 +7,10 @@ known before the synchronize, so every value column gets `max_keys` groups; the 
 empty, and `trim` cuts them off afterwards.  The selected rows whose key is null arrive in `out_of_range`.  More
 than `max_keys` distinct keys set the keys result's `overflow`, which is passed through, not raised: the groups
 mean nothing then.
+
+GROUP BY a, b: a list of 2 to 4 key columns.  Each goes through its key call with `max_keys`, `key_combine` turns
+the parts' ids into the ids of the distinct tuples, and the aggregate call takes those: still one interval.  A row
+with a null in any key column has no tuple and arrives in `out_of_range`.
 """
 from typing import List, Sequence, Tuple
 
@@ -15,6 +19,7 @@ import numpy as np
 from . import _native as N
 from .aggregate_grouped import MAX_GROUPS, Group, GroupedAggregate, aggregate_grouped
 from .aggregate_grouped_large import MAX_GROUPS_LARGE, aggregate_grouped_large
+from .key_combine import MAX_PARTS, key_combine
 from .key_ids import INTEGER_TYPES, key_ids
 from .key_ids_var import BINARY_TYPES, key_ids_var
 from .read import ColumnPages
@@ -28,11 +33,72 @@ def check_group_by(key_type, max_keys):
         raise ValueError("max_keys is %r, not an int in 1 .. %d" % (max_keys, MAX_GROUPS_LARGE))
 
 
-def group_by(ctx, key: ColumnPages, values: List[ColumnPages], selection=None,
+class GroupKeys:
+    """The keys of a GROUP BY over several columns: the parts' own key results and the combined tuples; the scalars
+    and `keys` are valid after Context.synchronize()."""
+
+    def __init__(self, parts, combined):
+        #: one KeyIds / KeyIdsVar per key column, in the order of the key list
+        self.parts = parts
+        #: the KeyCombine over their ids
+        self.combined = combined
+
+    ids = property(lambda self: self.combined.ids)
+    n_keys = property(lambda self: self.combined.n_keys)
+    max_keys = property(lambda self: self.combined.max_keys)
+
+    @property
+    def overflow(self):
+        """true if any part or the combine overflowed: the ids, and with them the groups, mean nothing then"""
+        return bool(self.combined.overflow) or any(bool(p.overflow) for p in self.parts)
+
+    @property
+    def keys(self):
+        """the distinct key tuples in ascending order, as tuples of the key columns' values (empty on an overflow)"""
+        return [] if self.overflow else self.combined.keys()
+
+    def __repr__(self):
+        return "GroupKeys(n_keys=%d, overflow=%r, parts=%r)" % (self.n_keys, self.overflow, self.parts)
+
+
+def _group_by_composite(ctx, keys, values, selection, ops, max_keys):
+    """group_by for a list of 2 .. 4 key columns: the integer parts in one key_ids call, the Binary / Utf8 parts in one
+    key_ids_var call, then key_combine and the aggregate call, all in the open interval"""
+    keys = list(keys)
+    if not 2 <= len(keys) <= MAX_PARTS:
+        raise ValueError("group_by takes one key column or a list of 2 .. %d, not %d" % (MAX_PARTS, len(keys)))
+    for k in keys:
+        if not isinstance(k, ColumnPages):
+            raise ValueError("a key is a ColumnPages, not %r" % type(k).__name__)
+        check_group_by(k.physical_type, max_keys)
+    max_keys = int(max_keys)
+    ints = [i for i, k in enumerate(keys) if k.physical_type in INTEGER_TYPES]
+    strs = [i for i, k in enumerate(keys) if k.physical_type not in INTEGER_TYPES]
+    parts = [None] * len(keys)
+    # (every part gets max_keys: a part with more distinct values than that cannot have fewer tuples)
+    if ints:
+        for i, r in zip(ints, key_ids(ctx, [keys[i] for i in ints], selection, max_keys=max_keys)):
+            parts[i] = r
+    if strs:
+        for i, r in zip(strs, key_ids_var(ctx, [keys[i] for i in strs], selection, max_keys=max_keys)):
+            parts[i] = r
+    kres = GroupKeys(parts, key_combine(ctx, parts, max_keys=max_keys))
+    if not values:
+        return kres, []
+    call = aggregate_grouped if max_keys <= MAX_GROUPS else aggregate_grouped_large
+    return kres, call(ctx, list(values), kres.ids, max_keys, selection, ops)
+
+
+def group_by(ctx, key, values: List[ColumnPages], selection=None,
              ops: Sequence[str] = ("count", "min", "max", "sum"), max_keys: int = N.SB_KEY_MAX_KEYS) -> Tuple[object, List[GroupedAggregate]]:
     """Enqueue the keys and ids of `key` and the per-key aggregates of every column of `values` under `selection`
     (one for all, or None: every row) on ctx's stream.  Returns (keys_result, [GroupedAggregate per value column]):
-    a KeyIds or KeyIdsVar, and results of max_keys groups each; all valid after ctx.synchronize()."""
+    a KeyIds or KeyIdsVar, and results of max_keys groups each; all valid after ctx.synchronize().
+
+    `key` may also be a list or tuple of 2 .. 4 ColumnPages, integer and Binary / Utf8 mixed (GROUP BY a, b): the
+    keys result is then a GroupKeys, whose `keys` are tuples of the columns' values in ascending order."""
+    if isinstance(key, (list, tuple)):
+        return _group_by_composite(ctx, key, values, selection, ops, max_keys)
     check_group_by(key.physical_type, max_keys)
     max_keys = int(max_keys)
     if key.physical_type in INTEGER_TYPES:
