@@ -453,7 +453,10 @@ int32_t sb_read_selected_var(sb_ctx* ctx, sb_column_read_selected_var* cols, uin
  *              zero-extended by type; sum_hi is the high word).  Float32 / Float64: the sum of ALL live rows, NaN and
  *              +-inf included, accumulated in double: its bits in sum_lo, sum_hi = 0.  No floating-point atomics: partial
  *              sums are combined in an order fixed by the launch shape, so the same call gives the same bits every time
- *              it is issued, a replayed interval included.
+ *              it is issued, a replayed interval included: the order of the double additions of a column's sum is a
+ *              function of the column's own page layout, data and selection alone, whatever other columns the call and
+ *              other calls the interval have.  Only a column that has a primitive Freq page itself is decoded in a
+ *              replayed interval, and such a column is decoded in every interval it is part of.
  *   nans       the live rows that are NaN (0 for integers, and 0 where `ops` has none of MIN / MAX / SUM: no value is
  *              looked at then).
  *

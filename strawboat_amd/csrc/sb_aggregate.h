@@ -13,7 +13,9 @@
 // its row to accumulators it keeps in registers for the whole tile (the whole page part in the RLE walk).  The workgroup
 // reduces ONCE per tile — shuffles across the wave, LDS across the four waves — and writes one partial record into the
 // tile's own slot.  Nothing is accumulated with atomics: the slots are combined in slot order, so the order of the double
-// additions of a float sum is fixed by the launch shape and the same call gives the same bits every time.
+// additions of a float sum is fixed by the launch shape and the same call gives the same bits every time.  That holds for
+// an interval that is issued again too: a column without a Freq page stays on the page route there, and a column with one
+// takes the decoded route in every interval it is part of (agg_tile marks it, the host goes by the mark).
 #pragma once
 
 namespace sb {
@@ -200,9 +202,17 @@ __device__ void agg_tile(const DecodeArgs& a, const AggLaunch& al, uint32_t ti, 
     const uint32_t rows = (uint32_t)min((uint64_t)TILE_ROWS, t.num_values - lo);
     const uint64_t hi = lo + rows;
     // A Freq page asks for the replay whatever the selection, as in filter_tile and rsel_tile: k_parse has logged the page
-    // for the second decode pass, and only the replay drops that record (see the head of sb_filter.h).
+    // for the second decode pass, and only the replay drops that record (see the head of sb_filter.h).  It marks its column
+    // (the slot of its first tile, which holds no record: k_agg_finish hands the mark to the host): the replay takes the
+    // decoded route for the marked columns alone, so the route of a column -- and with it the order of its float additions --
+    // is a matter of the column's own pages, not of what else the interval holds.  A marked column is not issued on this
+    // route again; if one is, the call fails instead of leaving the page out.
     if (d.codec == SB_CODEC_FREQ) {
-        if (threadIdx.x == 0 && tt.tile == 0) atomicOr(&a.status->kinds, KIND_REPLAY | KIND_FILTER_FREQ);
+        if (threadIdx.x == 0 && tt.tile == 0) {
+            gst64(&al.parts[al.tile_base + t.first_tile].live, AGG_PART_FREQ);
+            if (al.replayed) raise(a.status, SB_ERR_NYI, tt.page, 411);
+            else atomicOr(&a.status->kinds, KIND_REPLAY | KIND_FILTER_FREQ);
+        }
         return;
     }
     // a tile without a selected row: no value and no index is loaded, and its slot stays empty
@@ -379,8 +389,13 @@ __global__ void __launch_bounds__(WG) k_agg_finish(const AggCol* acols, const Ag
         nsel = g.rows;
     }
     AggAcc acc;
+    bool freq = false;   // a Freq page's mark among the tile slots (agg_tile)
     auto take = [&](const AggPart& p) {
         if (!p.live) return;
+        if (p.live == AGG_PART_FREQ) {
+            freq = true;
+            return;
+        }
         AggAcc b;
         b.cnt = p.cnt, b.nans = p.nans, b.kmin = p.kmin, b.kmax = p.kmax, b.s0 = p.s0, b.s1 = p.s1;
         acc = agg_merge(acc, b, flt);
@@ -388,6 +403,7 @@ __global__ void __launch_bounds__(WG) k_agg_finish(const AggCol* acols, const Ag
     for (uint64_t i = threadIdx.x; i < g.page_slots; i += WG) take(parts[g.page_slot0 + i]);
     for (uint64_t i = threadIdx.x; i < g.tile_slots; i += WG) take(parts[g.tile_slot0 + i]);
     acc = agg_wg_reduce(acc, flt, s_red);
+    freq = __syncthreads_or(freq) != 0;
     if (threadIdx.x == 0) {
         uint64_t* r = results + (uint64_t)blockIdx.x * AGG_RESULT_WORDS;
         const bool any = acc.cnt > acc.nans && (g.ops & AGG_VALUE_OPS);
@@ -398,7 +414,7 @@ __global__ void __launch_bounds__(WG) k_agg_finish(const AggCol* acols, const Ag
         r[4] = any && (g.ops & 4u) ? agg_unkey(g.kind, g.w, acc.kmax) : 0;
         r[5] = (g.ops & 8u) ? acc.s0 : 0;
         r[6] = (g.ops & 8u) ? acc.s1 : 0;
-        r[7] = 0;
+        r[7] = freq ? 1 : 0;   // for the host's replay (replay_interval)
     }
 }
 

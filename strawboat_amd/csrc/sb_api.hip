@@ -464,13 +464,19 @@ static int32_t replay_interval(sb_ctx* ctx) {
     // the grouped aggregate columns that met a Freq page say so in their result header (k_grp_finish): they alone take the
     // decoded route below, so that a column's route does not depend on what else the interval holds
     // (the two grouped calls keep their marks apart: one struct may be handed to both in one interval)
+    // (the columns of sb_aggregate_columns likewise, in the last word of their result record: k_agg_finish)
     ctx->grp_freq_users.clear();
     ctx->grpl_freq_users.clear();
+    ctx->agg_freq_users.clear();
     for (const auto& p : ctx->iv.pending)
         if (p.kind == Pending::AGG_GRP_COL || p.kind == Pending::AGG_GRPL_COL) {
             uint64_t met = 0;
             memcpy(&met, p.host + 2 * sizeof(uint64_t), sizeof met);
             if (met) (p.kind == Pending::AGG_GRP_COL ? ctx->grp_freq_users : ctx->grpl_freq_users).push_back(p.user);
+        } else if (p.kind == Pending::AGG_COL) {
+            uint64_t met = 0;
+            memcpy(&met, p.host + (AGG_RESULT_WORDS - 1) * sizeof(uint64_t), sizeof met);
+            if (met) ctx->agg_freq_users.push_back(p.user);
         }
     release_interval(ctx, sb_ctx::Interval::REPLAY);
     clear_freq_logs(ctx);
@@ -487,6 +493,7 @@ static int32_t replay_interval(sb_ctx* ctx) {
     ctx->filter_freq = false;
     ctx->grp_freq_users.clear();
     ctx->grpl_freq_users.clear();
+    ctx->agg_freq_users.clear();
     if (rc != SB_OK) ctx->iv.sticky = rc;
     rc = sb_ctx_synchronize(ctx);   // (in_replay: this one ends the interval whatever the device says)
     ctx->in_replay = false;
@@ -1365,7 +1372,7 @@ static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, 
         launch_keyv_finish(ctx, a, kl, d_vlen);
         if (sh.P) launch_keyv_assign(ctx, a, kl);
     } else if (mode.aggregate()) {
-        AggLaunch al{(const AggCol*)(ctx->tables.p + L.fcols), (AggPart*)(ctx->tables.p + L.aggp), sh.P * L.rle_parts, false, false};
+        AggLaunch al{(const AggCol*)(ctx->tables.p + L.fcols), (AggPart*)(ctx->tables.p + L.aggp), sh.P * L.rle_parts, false, false, ctx->in_replay};
         for (uint64_t i = 0; i < n; i++) ((mode.aggc[i].ops & AGG_VALUE_OPS) ? al.any_val : al.any_null) = true;
         // an empty slot is all zero: a page that failed or a tile without a selected row writes none
         const size_t slots = (size_t)(sh.P * L.rle_parts + sh.T);
@@ -2301,9 +2308,14 @@ int32_t sb_aggregate_columns(sb_ctx* ctx, sb_column_aggregate* cols, uint64_t n,
         users[i] = &cols[i];
     }
     if (ctx->in_replay && ctx->filter_freq) {
-        // the columns without a value op as ever (no page body is looked at); the others through a full decode
+        // The columns that met a Freq page in the first pass (and so asked for this replay, or would have) through a full
+        // decode; the others as ever, on the page route, whose slots -- and float bits -- are those of an interval that is
+        // not replayed (aggregate_grouped_impl has the same rule).
+        const std::vector<const void*>& freq_users = ctx->agg_freq_users;
         std::vector<bool> dec(n);
-        for (uint64_t i = 0; i < n; i++) dec[i] = (hs[i].ops & AGG_VALUE_OPS) != 0;
+        for (uint64_t i = 0; i < n; i++)
+            dec[i] = (hs[i].ops & AGG_VALUE_OPS) != 0 &&
+                     std::find(freq_users.begin(), freq_users.end(), (const void*)users[i]) != freq_users.end();
         std::vector<sb_column_read> r_val = take_if(rc_cols, dec);
         std::vector<AggCol> g_val = take_if(hs, dec);
         const std::vector<void*> u_val = take_if(users, dec);

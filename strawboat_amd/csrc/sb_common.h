@@ -590,7 +590,7 @@ struct SelLaunch {   // what launch_decode needs to end a call with the selected
 // records (AggPart) into slots of one array of the call: a slot per (page, part of a long RLE page) — the RLE walk and the
 // count-only route — and a slot per tile; k_agg_finish combines a column's slots, in slot order, into its result record.
 constexpr uint32_t AGG_VALUE_OPS = 2u | 4u | 8u;   // SB_AGG_MIN | SB_AGG_MAX | SB_AGG_SUM: the column's values are looked at
-constexpr uint32_t AGG_RESULT_WORDS = 8;           // { selected, count, nans, min, max, sum_lo, sum_hi, 0 }
+constexpr uint32_t AGG_RESULT_WORDS = 8;           // { selected, count, nans, min, max, sum_lo, sum_hi, the column met a Freq page }
 struct AggCol {
     const uint32_t* sel;   // the selection bitmap (input) or null: every row
     uint64_t rows;
@@ -602,17 +602,19 @@ struct AggCol {
     uint32_t w;            // bytes per value
 };
 struct AggPart {           // 64 bytes; all zero: the slot was not written (a page that failed, a tile without a selected row)
-    uint64_t live;         // 1: written
+    uint64_t live;         // 1: written; AGG_PART_FREQ: no record, the mark of a Freq page in the slot of its first tile
     uint64_t cnt, nans;    // live rows, NaNs among them
     uint64_t kmin, kmax;   // order keys (agg_key) of the live rows that are not NaN; ~0 / 0: none
     uint64_t s0, s1;       // integers: the 128-bit sum; floats: the bits of the double sum, 0
     uint64_t pad;
 };
+constexpr uint64_t AGG_PART_FREQ = 2;
 struct AggLaunch {   // what launch_decode needs to end a call with the aggregate kernels
     const AggCol* acols;
     AggPart* parts;
     uint64_t tile_base;    // the slot of the call's first tile (the page slots come first)
     bool any_val, any_null;
+    bool replayed;         // the call is issued again (a replay): the columns that met a Freq page are not on this route
 };
 // one column of a grouped aggregate call (sb_aggregate_grouped, sb_aggregate_grouped.h), next to its AggCol.  The slots are
 // the AggCol's; a slot holds `gmax` records (the call's largest n_groups), record g of slot s at index s * gmax + g, and a

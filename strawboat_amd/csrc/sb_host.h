@@ -28,7 +28,7 @@ struct StageSlot {
 //   FILTER_COL  the caller's `selected`       8 bytes: the bits set                       0               -
 //   RSEL_COL    sb_column_read_selected*      8 bytes: the bits set (values_len follows)  0               -
 //   RSEL_VAR_COL sb_column_read_selected_var* 16 bytes: the bits set, values_len          0               -
-//   AGG_COL     sb_column_aggregate*          64 bytes: the result record (AGG_RESULT_WORDS)  0           -
+//   AGG_COL     sb_column_aggregate*          64 bytes: the result record (AGG_RESULT_WORDS; word 7: the column met a Freq page)  0   -
 //   AGG_GRP_COL sb_column_aggregate_grouped*  64 bytes { selected, out_of_range }, then 64 per group  0       of header + groups
 //   AGG_GRPL_COL  the same, of an sb_aggregate_grouped_large call (a kind of its own: the Freq marks of the two calls are kept apart)
 //   TOPK_COL    sb_column_topk*               64 bytes { selected, count, nans, found }, then 16 per entry of `out`  0   of header + kmax entries
@@ -105,6 +105,7 @@ struct sb_ctx {
     sb::DevBuf staging;  // device staging for SB_MEM_HOST callers
     sb::DevBuf combine;  // sb_key_combine: the call's descriptors, results, states, tables and sorted codes
     sb::DevBuf filter_stage;   // sb_filter_columns: where the inflate queues put the values of LZ4 / Zstd / Snappy / Patas pages (no caller's buffer to inflate into)
+    std::vector<const void*> agg_freq_users;   // ... the same for the sb_column_aggregate structs of sb_aggregate_columns calls
     std::vector<const void*> grpl_freq_users;  // ... the same for the columns of sb_aggregate_grouped_large calls
     std::vector<const void*> grp_freq_users;   // during a replay: the sb_column_aggregate_grouped structs whose column met a Freq page in the first pass
     bool filter_freq = false;  // replay of an interval in which a filter or selected-read call met a Freq page: such calls decode into filter_stage first

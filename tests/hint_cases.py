@@ -12,7 +12,7 @@ What the model states beside the two functions:
     both passes feed the hint state (each ends in a synchronize).
   * the Freq second pass goes by no hint and changes no hint state, so a Freq page costs what its outer page costs: a
     replay when the tile kernel was left out, none otherwise -- whatever codec and size its exceptions block has.
-  * a sink call (filter, selected read, aggregates) consults no hint; a Freq page in one always asks for the decoded route
+  * a sink call (filter, IN list, selected read, aggregates, top-k, key ids) consults no hint; a Freq page in one always asks for the decoded route
     (KIND_FILTER_FREQ, sb_filter.h), hints or no hints, first call or second: always one replay.
   * sb_read_columns_sizes is recorded with the calls of the interval it closes and issued again with them.
   * kept as found, and followed: a sink call that meets a Zstd buffer or a giant LZ4 block still teaches the context
@@ -378,11 +378,15 @@ HISTORIES = {
     "giant_long2": ("giant", "long", "long"),
     "giant_long3": ("giant", "long", "long", "long"),
 }
-SINKS = ("filter", "read_selected", "aggregate", "aggregate_grouped")
+SINKS = ("filter", "read_selected", "aggregate", "aggregate_grouped", "filter_in", "topk", "key_ids", "aggregate_grouped_large")
 SINK_PROBES = ("zstd_1mib", "lz4_giant", "freq_zstd_1mib")
 SINK_HISTORIES = ("fresh", "long")
 HOST_HISTORIES = ("fresh", "idle2", "zstd_idle2", "long", "giant_long3")
 N_GROUPS = 16
+N_GROUPS_LARGE = 300       # aggregate_grouped_large: more groups than sb_aggregate_grouped takes, ids of two bytes
+IN_LITERALS = 8            # filter_in: literals drawn from the probe's column
+TOPK_K = 16
+KEY_MAX_KEYS = 256         # key_ids: every value of a U8 probe fits; the exceptions of the Int64 Freq probe overflow it
 
 
 class Expect:

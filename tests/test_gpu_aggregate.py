@@ -242,6 +242,42 @@ def test_float_sums_that_are_exact_in_no_order(gpu_ctx, ptype, codec):
         assert [(r._c.sum_lo, r.min_bytes, r.max_bytes) for r in again] == first
 
 
+@pytest.mark.parametrize("ptype", [S.T_F32, S.T_F64])
+def test_a_float_freq_column_gives_the_same_bits_in_every_interval(gpu_ctx, ptype):
+    """A column with a Freq page takes the decoded route whenever it is issued: alone, twice, next to another aggregate call
+    and next to a filter call.  (A column without one stays on the page route next to it: tests/test_gpu_replay_routes.py.)"""
+    import strawboat_amd as sb
+    from tests.test_gpu_freq import sparse
+    rows = 10_000
+    f = sparse(ptype, rows, 0.05, 2, null_density=0.1)
+    f["values"] = f["values"] * NP[ptype](0.1)   # (sums that are exact in no order: 0.7 on 95 % of the rows)
+    fp, fm = gen.oracle_write(f, max_page_size=2050, force_codec=S.FREQ)
+    if S.FREQ not in set(int(x) for x in S.stat_column(f["ptype"], f["nullable"], fp, fm)[0].tolist()):
+        pytest.fail("the oracle wrote no Freq page for type %d" % ptype)
+    fref = R.Ref(f, fp, fm)
+    fcp = upload(gpu_ctx, f, fp, fm)
+    b = gen.prim(S.T_F64, rows, uniq=100, null_density=0.2, runs=6, seed=2)
+    bp, bm = gen.oracle_write(b, max_page_size=4100, force_codec=S.RLE)
+    bcp = upload(gpu_ctx, b, bp, bm)
+    mask = np.random.default_rng(ptype).random(rows) < 0.4
+    bmp = bitmap(gpu_ctx, mask)
+    batch = sb.AggregateBatch(gpu_ctx, [fcp, fcp], [bmp, None])
+    seen = []
+    for others in (0, 0, 1, 2):
+        r0 = gpu_ctx.replays()
+        if others == 1:
+            sb.aggregate_columns(gpu_ctx, [bcp], bmp)
+        if others == 2:
+            sb.filter_columns(gpu_ctx, [fcp], [sb.Predicate("is_not_null")])
+        res = batch.enqueue()
+        gpu_ctx.synchronize()
+        assert gpu_ctx.replays() == r0 + 1
+        R.check(res[0], fref.want(mask), "Freq float column, selection")
+        R.check(res[1], fref.want(None), "Freq float column, every row")
+        seen.append([(r._c.sum_lo, r.min_bytes, r.max_bytes) for r in res])
+    assert seen[1:] == seen[:1] * 3
+
+
 # ---- 5: one long page (several workgroups share an RLE page)
 @pytest.mark.parametrize("codec", [S.RLE, S.DICT])
 def test_one_long_page(gpu_ctx, codec):

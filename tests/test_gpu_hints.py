@@ -12,7 +12,9 @@ on 90 % of its rows, so no comparison matches half of them: the predicate (<= 0,
 of the exceptions.
 
 Measured on an MI355X: a context costs 3.6 ms to create and destroy, so every case affords one; the module's 192 tests take
-8.5 s (9.9 s with SB_NO_HINTS=1), the slowest 0.2 s apart from the first, which loads the library (1.6 s)."""
+8.5 s (9.9 s with SB_NO_HINTS=1), the slowest 0.2 s apart from the first, which loads the library (1.6 s).  The 24 cases
+of the later sinks (filter_in, topk, key_ids, aggregate_grouped_large) add 6.2 s: their references run over the probes'
+millions of rows once per case (300 groups: 0.3 - 0.7 s a case)."""
 import ctypes as C
 import os
 import time
@@ -24,6 +26,8 @@ from oracle import sbo as S
 from tests import aggregate_grouped_ref as G
 from tests import aggregate_ref as R
 from tests import hint_cases as H
+from tests import key_ids_ref as K
+from tests import topk_ref as T
 
 pytestmark = pytest.mark.gpu
 POISON = 0xA5
@@ -151,12 +155,27 @@ def selection_tensor(ctx, mask):
     return up(ctx, bits)
 
 
+_wants = {}
+
+
+def _once(sink, seed, compute):
+    """the reference of a case's probe, computed for the first of its two runs and left unchanged (a case has a seed of its own)"""
+    if (sink, seed) not in _wants:
+        _wants[(sink, seed)] = compute()
+    return _wants[(sink, seed)]
+
+
 def run_sink(ctx, sink, cols, seed):
     import torch
     from strawboat_amd import filter as flt
     from strawboat_amd.aggregate import aggregate_columns
     from strawboat_amd.aggregate_grouped import aggregate_grouped
+    from strawboat_amd.aggregate_grouped_large import aggregate_grouped_large
+    from strawboat_amd.filter_in import InList, filter_in
+    from strawboat_amd.key_ids import key_ids
     from strawboat_amd.read_selected import read_selected
+    from strawboat_amd.topk import topk_columns
+    from tests.test_gpu_filter_in import want_in
     (col, pages, metas, want), = cols
     cp, = column_pages(ctx, cols)
     mask = matching(col, want)
@@ -167,6 +186,17 @@ def run_sink(ctx, sink, cols, seed):
         ctx.synchronize()
         assert sel.selected == int(mask.sum())
         assert np.array_equal(sel.numpy(), mask), "the selection bitmap differs"
+        return
+    if sink == "filter_in":
+        v = _typed(col, want)
+        lits = [v[int(i)].item() for i in np.random.default_rng(seed).integers(0, rows, H.IN_LITERALS)]
+        out = flt.Selection(torch.full(((rows + 31) // 32 * 4,), POISON, dtype=torch.uint8, device=ctx.torch_device), rows, None)
+        sel, = filter_in(ctx, [cp], [InList(lits)], out=[out])
+        ctx.synchronize()
+        hit = _once(sink, seed, lambda: want_in(col, v, np.ones(rows, bool), lits, False))
+        assert sel.selected == int(hit.sum()) > 0
+        assert np.array_equal(sel.numpy(), hit), "the selection bitmap differs"
+        assert not np.unpackbits(sel.bitmap.cpu().numpy(), bitorder="little")[rows:].any(), "bits behind the last row must be 0 after set"
         return
     sel = selection_tensor(ctx, mask)
     if sink == "read_selected":
@@ -181,6 +211,25 @@ def run_sink(ctx, sink, cols, seed):
         got, = aggregate_columns(ctx, [cp], sel, ops=AGG_OPS)
         ctx.synchronize()
         R.check(got, ref.want(mask, AGG_OPS), sink)
+        return
+    if sink == "topk":
+        got, = topk_columns(ctx, [cp], H.TOPK_K, False, sel)
+        ctx.synchronize()
+        T.check(got, _once(sink, seed, lambda: T.want(ref, mask, H.TOPK_K, False)), sink)
+        return
+    if sink == "key_ids":
+        ids_out = torch.full((rows * 2,), POISON, dtype=torch.uint8, device=ctx.torch_device).view(torch.uint16)   # (exactly rows ids)
+        got, = key_ids(ctx, [cp], sel, max_keys=H.KEY_MAX_KEYS, id_width=2, out=[ids_out])
+        ctx.synchronize()
+        want_keys = _once(sink, seed, lambda: K.want(ref, mask, H.KEY_MAX_KEYS, 2))
+        assert want_keys.overflow == (col["ptype"] != S.T_U8), "the Int64 Freq probe overflows max_keys, a U8 probe cannot"
+        K.check(got, want_keys, sink)   # (rows, selected, count, overflow; keys and ids where nothing overflowed)
+        return
+    if sink == "aggregate_grouped_large":
+        ids = np.random.default_rng(seed).integers(0, H.N_GROUPS_LARGE, rows).astype(np.uint16)
+        got, = aggregate_grouped_large(ctx, [cp], up(ctx, ids), H.N_GROUPS_LARGE, sel, ops=AGG_OPS)
+        ctx.synchronize()
+        G.check(got, _once(sink, seed, lambda: G.want(ref, ids, H.N_GROUPS_LARGE, mask, AGG_OPS)), sink)
         return
     ids = np.random.default_rng(seed).integers(0, H.N_GROUPS, rows).astype(np.uint8)
     got, = aggregate_grouped(ctx, [cp], up(ctx, ids), H.N_GROUPS, sel, ops=AGG_OPS)

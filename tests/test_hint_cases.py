@@ -147,8 +147,9 @@ def test_the_table_holds_every_case_it_is_meant_to():
             assert "%s-%s-host" % (p, h) in names
     for p in ("zstd_1mib", "lz4_giant", "freq_zstd_1mib"):
         for h in ("fresh", "long"):
-            for sink in ("filter", "read_selected", "aggregate", "aggregate_grouped"):
+            for sink in ("filter", "read_selected", "aggregate", "aggregate_grouped", "filter_in", "topk", "key_ids", "aggregate_grouped_large"):
                 assert "%s-%s-%s" % (p, h, sink) in names
+    assert len(H.SINKS) == 8 and len(set(H.SINKS)) == 8
 
 
 def _replays(name, **kw):
