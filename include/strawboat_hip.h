@@ -872,6 +872,86 @@ typedef struct sb_key_combine_item {
 
 int32_t sb_key_combine(sb_ctx* ctx, sb_key_combine_item* items, uint64_t n, int32_t mem);
 
+/* ------------------------------------------------------------------ ids of a key column's rows against a given list
+ * fact.fk = dim.pk with a small dimension; GROUP BY over a key set that is known (the dates of a month, status codes, the
+ * keys of the previous batch); ids that mean the same in every call, so that the grouped results of two row groups, two
+ * files or two ranks are index-aligned and can be added.  The pages of a key column, (optionally) a selection bitmap and a
+ * list of up to SB_KEY_MAX_KEYS values on the HOST go in; every row gets the id the list assigns to its value.  Nothing is
+ * discovered: one walk over the pages, no table, no sort.
+ *
+ *   live rows     a row is live if its selection bit is set and it is not null, exactly as for sb_key_ids; rows /
+ *                 selected / count mean what they mean there.
+ *   ids           one unsigned integer of id_width bytes per row of the column, all `rows` of them written.  A live row
+ *                 whose value equals values[i] gets value_ids[i], or i when value_ids is null.  Every other row gets all
+ *                 ones (SB_KEY_ID_NONE truncated to id_width): a row that is not selected, a null row (whatever bytes the
+ *                 page stores for it), and a live row whose value is not in the list.  Handed to sb_aggregate_grouped /
+ *                 sb_aggregate_grouped_large unchanged, the rows without an id end in out_of_range: inner-join semantics.
+ *   matched       the live rows that got an id; count - matched are the live rows the list does not know.
+ *   the list      in any order.  Numeric columns: n_values values of the column's width back to back in `values`,
+ *                 value_offsets null.  Binary columns: value i is values[value_offsets[i] .. value_offsets[i + 1]), exactly
+ *                 the fields of sb_column_filter_in.  A value that repeats takes the id of its first occurrence.  Several
+ *                 values may carry the same value_ids[i] (nation -> region: the ids are group ids directly).  Every id the
+ *                 list can hand out is below all ones of id_width: each value_ids[i], or n_values - 1 without value_ids.
+ *                 n_values == 0 is valid: every id is all ones and matched is 0.
+ *   comparison    integers by value with the type's signedness; binary values as byte strings, exactly as SB_PRED_EQ of
+ *                 sb_filter_columns_var: the empty string is a value, a trailing zero byte makes a different string.  A
+ *                 value between two entries of the list, below the first or above the last has no id.
+ *   determinism   the ids are a function of the pages, the selection and the list alone: the same bytes every time the
+ *                 call is issued, a replayed interval included; count and matched are sums of integers.
+ *   cost          one search per run of an RLE page and one per dictionary entry of a Dict / Freq page (strings too,
+ *                 through the page's id table), one per OneValue tile, one per row elsewhere.  A tile of 4096 rows without
+ *                 a selected row loads no value.
+ *
+ * Types: INT8..INT64, UINT8..UINT64, BINARY, LARGE_BINARY; the columns of a call may mix them, each with its own id_width.
+ *
+ * Refused at the call, nothing enqueued and no result field or byte of `ids` touched: Float32 / Float64, Boolean, Int128 /
+ * Int256, Null and SB_MEM_HOST (SB_ERR_NYI); id_width not 1 / 2 / 4, `ids` null with rows > 0, misaligned or smaller than
+ * rows * id_width, reserved0 or reserved != 0, two columns of one call whose `ids` overlap, n_values above
+ * SB_KEY_MAX_KEYS, an id that is all ones of id_width or does not fit it (SB_ERR_INVALID); the values / value_offsets
+ * refusals of sb_filter_columns_in and every argument refusal of sb_aggregate_columns, with their codes; for binary
+ * columns the page and row limits of sb_key_ids_var (SB_ERR_NYI).
+ *
+ * Enqueued like sb_key_ids and part of its synchronize interval in the same way, as a call of its own kind: on a replay it
+ * is issued again in its place, behind the filter calls that write its bitmap and in front of the sb_key_combine and
+ * aggregate calls that read its ids.  A numeric column with a Freq page asks for that replay itself and is then served
+ * from the decoded column; a binary Freq page is a virtual Dict page.  `selection`, `values`, `value_offsets` and
+ * `value_ids` are INPUTS: they stay valid and unmodified until the synchronize.  Page errors are the decoder's, with its
+ * codes, at the synchronize; `rows` and `selected` are delivered even when the interval failed, the other results and
+ * `ids` are unspecified then.  The call consults no launch hint of the read path and leaves its counters alone.
+ *
+ * Layout (pinned by tests/test_key_lookup_host.py): sb_column_key_lookup 168 bytes; physical_type 0, is_nullable 4,
+ * pages 8, pages_len 16, metas 24, n_pages 32, page_offsets 40, selection 48, selection_capacity 56, ids 64,
+ * ids_capacity 72, id_width 80, reserved0 84, values 88, value_offsets 96, value_ids 104, n_values 112,
+ * stage_capacity 120, reserved 128, rows 136, selected 144, count 152, matched 160. */
+typedef struct sb_column_key_lookup {
+    int32_t physical_type;   /* INT8..INT64, UINT8..UINT64, BINARY, LARGE_BINARY */
+    int32_t is_nullable;
+    const uint8_t* pages;    /* DEVICE, at any byte alignment */
+    uint64_t pages_len;
+    const sb_page_meta* metas; /* HOST */
+    uint64_t n_pages;
+    const uint64_t* page_offsets; /* optional (HOST), as in sb_column_read */
+    const uint8_t* selection;     /* DEVICE, input: as in sb_column_key_ids; NULL = every row */
+    uint64_t selection_capacity;
+    void* ids;               /* DEVICE, output: one id per row, aligned to id_width */
+    uint64_t ids_capacity;   /* >= rows * id_width bytes */
+    uint32_t id_width;       /* 1, 2 or 4 */
+    uint32_t reserved0;      /* must be 0 */
+    const uint8_t* values;         /* HOST: exactly sb_column_filter_in.values */
+    const uint64_t* value_offsets; /* HOST: binary columns only, exactly sb_column_filter_in.value_offsets */
+    const uint32_t* value_ids;     /* HOST, optional: n_values ids; NULL = the value's position in the list */
+    uint64_t n_values;       /* 0 .. SB_KEY_MAX_KEYS */
+    uint64_t stage_capacity; /* binary columns: as in sb_column_filter_var; 0 = 4 * pages_len */
+    uint64_t reserved;       /* must be 0 */
+    /* results (HOST, valid after sb_ctx_synchronize) */
+    uint64_t rows;           /* sum of num_values */
+    uint64_t selected;       /* bits set in `selection` below `rows` (== rows without a selection) */
+    uint64_t count;          /* selected rows that are not null */
+    uint64_t matched;        /* ... whose value is in the list */
+} sb_column_key_lookup;      /* 168 bytes */
+
+int32_t sb_key_lookup(sb_ctx* ctx, sb_column_key_lookup* cols, uint64_t n, int32_t mem);
+
 /* ------------------------------------------------------------------ encode
  * Replaces, per leaf column, the page loop of NativeWriter::encode_chunk
  * (src/write/common.rs:54-109): page slicing, then per page write::write -> write_simple

@@ -25,7 +25,7 @@ EXPORTS = ("sb_version", "sb_ctx_create", "sb_ctx_destroy", "sb_ctx_synchronize"
            "sb_schema_metadata_from_bytes", "sb_filter_columns", "sb_filter_columns_var", "sb_read_selected",
            "sb_read_selected_var", "sb_aggregate_columns", "sb_aggregate_grouped", "sb_filter_columns_in",
            "sb_topk_columns", "sb_key_ids", "sb_key_ids_var", "sb_aggregate_grouped_large",
-           "sb_key_combine")
+           "sb_key_combine", "sb_key_lookup")
 
 SB_PRED_EQ, SB_PRED_NE, SB_PRED_LT, SB_PRED_LE, SB_PRED_GT, SB_PRED_GE, SB_PRED_IS_NULL, SB_PRED_IS_NOT_NULL = range(8)
 SB_PRED_STARTS_WITH = 8   # binary types only (sb_filter_columns_var)
@@ -176,6 +176,16 @@ class KeyCombineItemC(C.Structure):
                 ("live", C.c_uint64), ("n_keys", C.c_uint64), ("overflow", C.c_uint64)]
 
 
+class ColumnKeyLookupC(C.Structure):
+    _fields_ = [("physical_type", C.c_int32), ("is_nullable", C.c_int32), ("pages", C.c_void_p),
+                ("pages_len", C.c_uint64), ("metas", C.POINTER(PageMetaC)), ("n_pages", C.c_uint64),
+                ("page_offsets", C.c_void_p), ("selection", C.c_void_p), ("selection_capacity", C.c_uint64),
+                ("ids", C.c_void_p), ("ids_capacity", C.c_uint64), ("id_width", C.c_uint32), ("reserved0", C.c_uint32),
+                ("values", C.c_void_p), ("value_offsets", C.c_void_p), ("value_ids", C.c_void_p),
+                ("n_values", C.c_uint64), ("stage_capacity", C.c_uint64), ("reserved", C.c_uint64),
+                ("rows", C.c_uint64), ("selected", C.c_uint64), ("count", C.c_uint64), ("matched", C.c_uint64)]
+
+
 class ColumnWriteC(C.Structure):
     _fields_ = [("physical_type", C.c_int32), ("is_nullable", C.c_int32), ("rows", C.c_uint64),
                 ("values", C.c_void_p), ("values_bit_offset", C.c_uint64), ("values_len", C.c_uint64),
@@ -287,6 +297,8 @@ def load():
     L.sb_key_ids_var.argtypes = [C.c_void_p, C.POINTER(ColumnKeyIdsVarC), C.c_uint64, C.c_int32]
     L.sb_key_combine.restype = C.c_int32
     L.sb_key_combine.argtypes = [C.c_void_p, C.POINTER(KeyCombineItemC), C.c_uint64, C.c_int32]
+    L.sb_key_lookup.restype = C.c_int32
+    L.sb_key_lookup.argtypes = [C.c_void_p, C.POINTER(ColumnKeyLookupC), C.c_uint64, C.c_int32]
     L.sb_read_columns_sizes.restype = C.c_int32
     L.sb_read_columns_sizes.argtypes = [C.c_void_p, C.POINTER(ColumnReadC), C.c_uint64, C.c_int32]
     L.sb_write_bound.restype = C.c_uint64

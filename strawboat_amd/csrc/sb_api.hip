@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "sb_host.h"
+#include "sb_key_lookup_prep.h"
 #include "sb_span.h"
 
 namespace sb {
@@ -13,7 +14,10 @@ namespace sb {
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
                    const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp = nullptr, const InCol* icols = nullptr,
                    const TopkLaunch* topk = nullptr, const KeyLaunch* keys = nullptr, const KeyVarLaunch* keyv = nullptr,
-                   const GrpLaunch* grpl = nullptr);
+                   const GrpLaunch* grpl = nullptr, const LookLaunch* look = nullptr);
+void launch_look_zero(sb_ctx* ctx, const LookLaunch& ll);
+void launch_look_finish(sb_ctx* ctx, const LookLaunch& ll, uint64_t* results);
+void launch_key_lookup_plain(sb_ctx* ctx, const LookLaunch& ll, const uint64_t* rows, const uint8_t* const* values, const uint8_t* const* validity);
 void launch_key_zero(sb_ctx* ctx, const KeyLaunch& kl);
 void launch_key_finish(sb_ctx* ctx, const KeyLaunch& kl, uint64_t* results);
 void launch_key_assign(sb_ctx* ctx, const DecodeArgs& a, const KeyLaunch& kl);
@@ -118,7 +122,7 @@ StageSlot* acquire_slot(sb_ctx* ctx, size_t need) {
     if (s.host)
         for (auto& p : ctx->iv.pending) {
             if (p.host < s.host || p.host >= s.host + s.cap) continue;
-            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::AGG_COL ? AGG_RESULT_WORDS * 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R || p.kind == Pending::AGG_GRP_COL || p.kind == Pending::AGG_GRPL_COL || p.kind == Pending::TOPK_COL || p.kind == Pending::KEY_COL || p.kind == Pending::KEY_VAR_COL || p.kind == Pending::COMB_ITEM) ? (size_t)p.bytes
+            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::AGG_COL ? AGG_RESULT_WORDS * 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R || p.kind == Pending::AGG_GRP_COL || p.kind == Pending::AGG_GRPL_COL || p.kind == Pending::TOPK_COL || p.kind == Pending::KEY_COL || p.kind == Pending::KEY_VAR_COL || p.kind == Pending::COMB_ITEM || p.kind == Pending::KEY_LOOK_COL) ? (size_t)p.bytes
                                                                                                    : (size_t)(2 * p.n + 1) * 8;
             ctx->iv.rescued.emplace_back(p.host, p.host + nb);
             p.host = ctx->iv.rescued.back().data();
@@ -257,7 +261,8 @@ struct ReadMode {
     // / sb_topk_columns, an aggregate call whose columns end in the top-k kernels
     // / sb_key_ids, an aggregate call whose columns end in the key kernels: two walks, the finish between them
     // / sb_key_ids_var, the same for binary columns, whose value blocks are staged as a filter call stages them
-    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR, AGGREGATE, AGG_GROUPED, AGG_GROUPED_LARGE, TOPK, KEY_IDS, KEY_IDS_VAR } kind;
+    // / sb_key_lookup, an aggregate call whose columns end in the lookup kernels: one walk, numeric and binary columns alike
+    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR, AGGREGATE, AGG_GROUPED, AGG_GROUPED_LARGE, TOPK, KEY_IDS, KEY_IDS_VAR, KEY_LOOKUP } kind;
     const FilterCol* filt = nullptr;             // FILTER: one per column
     const std::vector<uint8_t>* lits = nullptr;  // ... the literals of the FK_BYTES columns, FilterCol.lit being the offset of each
     bool in_list = false;                        // ... sb_filter_columns_in: `lits` begins with an InCol per column, whose pointers are offsets in `lits`
@@ -275,23 +280,26 @@ struct ReadMode {
     uint64_t key_slots = 0;                      // ... the slots of the columns' tables together
     const KeyVarCol* keyvc = nullptr;            // KEY_IDS_VAR: one per column beside aggc (key_kmax and key_slots as above)
     uint64_t key_kbytes = 0;                     // ... the largest keys_capacity of the call: bytes per result
+    const LookCol* lookc = nullptr;              // KEY_LOOKUP: one per column beside aggc, whose pointers are offsets in `lits` (the lists)
     // Where a column's result goes at the synchronize, as Pending has it (sb_host.h): users[i] beside pending_kind.  Set by
     // the entry points of the sinks: the callers' structs, for a filter call the caller's `selected` (results[i] + 1).
     // Null for the other kinds of call, whose results go to the sb_column_read structs of the call itself.
     void* const* users = nullptr;
     Pending::Kind pending_kind = Pending::READ_COL;
-    bool aggregate() const { return kind == AGGREGATE || kind == AGG_GROUPED || kind == AGG_GROUPED_LARGE || kind == TOPK || kind == KEY_IDS || kind == KEY_IDS_VAR; }   // an AggCol per column, slots per page part and tile
+    bool aggregate() const { return kind == AGGREGATE || kind == AGG_GROUPED || kind == AGG_GROUPED_LARGE || kind == TOPK || kind == KEY_IDS || kind == KEY_IDS_VAR || kind == KEY_LOOKUP; }   // an AggCol per column, slots per page part and tile
     bool grouped() const { return kind == AGG_GROUPED || kind == AGG_GROUPED_LARGE; }   // a GrpCol per column, flags and gmax records per slot
     bool grouped_large() const { return kind == AGG_GROUPED_LARGE; }                  // ... whose tile slots are a slot per chunk of GRPL_CHUNK_TILES tiles
     bool topk() const { return kind == TOPK; }
     bool key_ids() const { return kind == KEY_IDS; }
     bool key_var() const { return kind == KEY_IDS_VAR; }
+    bool key_lookup() const { return kind == KEY_LOOKUP; }
+    bool bin_id_tables() const { return kind == KEY_IDS_VAR || kind == KEY_LOOKUP; }   // a 16-bit id table and a bit table per binary Dict / Freq page
     bool filter() const { return kind == FILTER; }
     bool selected() const { return kind == SELECTED; }
     bool selected_var() const { return kind == SELECTED_VAR; }
     bool ranked() const { return kind == SELECTED || kind == SELECTED_VAR; }   // a SelCol and a rank table per column
     // binary columns whose value blocks are staged and compared or gathered: no offsets are written by the read's kernels
-    bool bin_staged() const { return kind == FILTER || kind == SELECTED_VAR || kind == KEY_IDS_VAR; }
+    bool bin_staged() const { return kind == FILTER || kind == SELECTED_VAR || kind == KEY_IDS_VAR || kind == KEY_LOOKUP; }
     // the columns end in a sink of their own: `values` is a share of the staging area, there is no validity buffer, and
     // the call neither consults nor feeds the launch hints of the read path
     bool sink() const { return kind == FILTER || kind == SELECTED || kind == SELECTED_VAR || aggregate(); }
@@ -299,7 +307,7 @@ struct ReadMode {
     // an AGGREGATE call, the header and the gmax group records of an AGG_GROUPED call, the header and the kmax entries of
     // a TOPK call, the header and the kmax key slots of a KEY_IDS call, the header, offsets and bytes of a KEY_IDS_VAR call
     uint64_t result_words() const {
-        return kind == SELECTED_VAR ? 2 : kind == AGGREGATE ? AGG_RESULT_WORDS : grouped() ? grp_result_words(grp_gmax) : kind == TOPK ? topk_result_words(topk_kmax) : kind == KEY_IDS ? key_result_words(key_kmax) : kind == KEY_IDS_VAR ? keyv_result_words(key_kmax, key_kbytes) : 1;
+        return kind == SELECTED_VAR ? 2 : kind == AGGREGATE ? AGG_RESULT_WORDS : grouped() ? grp_result_words(grp_gmax) : kind == TOPK ? topk_result_words(topk_kmax) : kind == KEY_IDS ? key_result_words(key_kmax) : kind == KEY_IDS_VAR ? keyv_result_words(key_kmax, key_kbytes) : kind == KEY_LOOKUP ? LOOK_RESULT_WORDS : 1;
     }
 };
 static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, const ReadMode& mode);
@@ -589,6 +597,16 @@ static void deliver_key_var_col(const Pending& p, bool ok) {
     if (len) memcpy(c->keys, p.host + sizeof head + (kmax + 1) * 8, len);
     if (cap > len) memset(c->keys + len, 0, cap - len);
 }
+// k_key_lookup_finish's record (sb_key_lookup.h); `ok` false: the interval failed, selected alone
+static void deliver_key_look_col(const Pending& p, bool ok) {
+    uint64_t v[LOOK_RESULT_WORDS];
+    memcpy(v, p.host, sizeof v);
+    sb_column_key_lookup* c = (sb_column_key_lookup*)p.user;
+    c->selected = v[0];
+    if (!ok) return;
+    c->count = v[1];
+    c->matched = v[2];
+}
 // k_key_finish's header and sorted codes of a key-combine item (sb_key_combine.h): { rows, live, n_keys, overflow, 0 .. },
 // then kmax codes, of which the first n_keys are unpacked into `tuples`; a failed interval delivers nothing
 static void deliver_comb_item(const Pending& p, bool ok) {
@@ -644,6 +662,7 @@ static void deliver_pending(sb_ctx* ctx, const Pending& p, int32_t rc) {
         case Pending::KEY_COL: deliver_key_col(p, rc == SB_OK); break;
         case Pending::KEY_VAR_COL: deliver_key_var_col(p, rc == SB_OK); break;
         case Pending::COMB_ITEM: deliver_comb_item(p, rc == SB_OK); break;
+        case Pending::KEY_LOOK_COL: deliver_key_look_col(p, rc == SB_OK); break;
         case Pending::WRITE_COL: deliver_write_col(p); break;
         case Pending::ENC_HINT:
             if (rc == SB_OK) apply_enc_hint(ctx, p);
@@ -922,6 +941,7 @@ static ReadLayout read_layout(uint64_t n, const ReadShape& sh, const ReadHints& 
     if (mode.topk()) off = align_up(off + n * sizeof(TopkCol), 64);     // (likewise)
     if (mode.key_ids()) off = align_up(off + n * sizeof(KeyCol), 64);   // (likewise)
     if (mode.key_var()) off = align_up(off + n * sizeof(KeyVarCol), 64);   // (likewise)
+    if (mode.key_lookup()) off = align_up(off + n * sizeof(LookCol), 64);  // (likewise)
     L.lits = off;
     if (mode.lits) off = align_up(off + mode.lits->size(), 64);
     L.upload = off;
@@ -956,6 +976,7 @@ static ReadLayout read_layout(uint64_t n, const ReadShape& sh, const ReadHints& 
     if (L.rle_parts > 1) off = align_up(off + P * sizeof(uint32_t), 64);
     L.aggp = off;   // an AGGREGATE call's partial records: a slot per (page, RLE part), then a slot per tile
     if (mode.kind == ReadMode::AGGREGATE) off = align_up(off + (P * L.rle_parts + sh.T) * sizeof(AggPart), 64);
+    if (mode.key_lookup()) off = align_up(off + n * sizeof(LookState), 64);   // a KEY_LOOKUP call: a state per column (zeroed)
     // an AGG_GROUPED call: a flag word per slot, a counter and a Freq mark per column (zeroed), then gmax records per slot (not zeroed)
     // (an AGG_GROUPED_LARGE call: the same with a slot per chunk in the tile slots' place)
     const uint64_t grp_tile_slots = mode.grouped_large() ? sh.C : sh.T;
@@ -1069,8 +1090,8 @@ static int32_t fill_read_tables(sb_ctx* ctx, uint8_t* host, const ReadLayout& L,
             t.first_tile = (uint32_t)tile_i;
             t.aux_off = scratch_off;
             scratch_off += align_up((len / 4 + N / 128 + 4 * ntiles + 16) * 4, 16);   // (4 * ntiles: tile_k0 / tile_base + tile_bytes, and the u64 tile totals of a long binary Dict page)
-            if (mode.key_var() && is_binary_t(c.physical_type)) scratch_off += keyv_id_table_words(len) * 4;    // (a 16-bit id per dictionary entry, in front of the bits: sb_key_ids_bin.h)
-            if ((mode.filter() || mode.key_var()) && is_binary_t(c.physical_type)) scratch_off += filter_bin_table_words(len) * 4;   // (a bit per dictionary entry: sb_filter_bin.h)
+            if (mode.bin_id_tables() && is_binary_t(c.physical_type)) scratch_off += keyv_id_table_words(len) * 4;    // (a 16-bit id per dictionary entry, in front of the bits: sb_key_ids_bin.h)
+            if ((mode.filter() || mode.bin_id_tables()) && is_binary_t(c.physical_type)) scratch_off += filter_bin_table_words(len) * 4;   // (a bit per dictionary entry: sb_filter_bin.h)
             t.infl_off = scratch_off;
             scratch_off += align_up((N + 1) * 8 + 16, 16);
             in_off += len;
@@ -1108,6 +1129,17 @@ static int32_t fill_read_tables(sb_ctx* ctx, uint8_t* host, const ReadLayout& L,
         if (mode.topk()) memcpy(host + L.bcols, mode.topkc, n * sizeof(TopkCol));
         if (mode.key_ids()) memcpy(host + L.bcols, mode.keyc, n * sizeof(KeyCol));
         if (mode.key_var()) memcpy(host + L.bcols, mode.keyvc, n * sizeof(KeyVarCol));
+        if (mode.key_lookup()) {   // the lists travel with the tables; the columns' pointers get their place
+            LookCol* hl = (LookCol*)(host + L.bcols);
+            memcpy(hl, mode.lookc, n * sizeof(LookCol));
+            if (mode.lits && !mode.lits->empty()) memcpy(host + L.lits, mode.lits->data(), mode.lits->size());
+            const uint8_t* base = ctx->tables.p + L.lits;
+            for (uint64_t i = 0; i < n; i++) {
+                hl[i].keys = (const uint64_t*)(base + (size_t)(uintptr_t)hl[i].keys);
+                hl[i].kid = (const uint32_t*)(base + (size_t)(uintptr_t)hl[i].kid);
+                hl[i].bytes = base + (size_t)(uintptr_t)hl[i].bytes;
+            }
+        }
     }
     SelCol* hsc = mode.ranked() ? (SelCol*)(host + L.fcols) : nullptr;
     for (uint64_t i = 0; hsc && i < n; i++) {   // the rank tables: behind the pages' areas, sized by the rows
@@ -1371,6 +1403,14 @@ static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, 
         // (a call without a page still has a result: selected, offsets of zero)
         launch_keyv_finish(ctx, a, kl, d_vlen);
         if (sh.P) launch_keyv_assign(ctx, a, kl);
+    } else if (mode.key_lookup()) {
+        LookLaunch ll{(const AggCol*)(ctx->tables.p + L.fcols), (const LookCol*)(ctx->tables.p + L.bcols), (LookState*)(ctx->tables.p + L.aggp), (uint32_t)n,
+                      sh.any_prim, sh.any_binary};
+        launch_look_zero(ctx, ll);
+        if (sh.P)
+            launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ll);
+        // (a call without a page still has a result: selected, and zeros)
+        launch_look_finish(ctx, ll, d_vlen);
     } else if (mode.aggregate()) {
         AggLaunch al{(const AggCol*)(ctx->tables.p + L.fcols), (AggPart*)(ctx->tables.p + L.aggp), sh.P * L.rle_parts, false, false, ctx->in_replay};
         for (uint64_t i = 0; i < n; i++) ((mode.aggc[i].ops & AGG_VALUE_OPS) ? al.any_val : al.any_null) = true;
@@ -1406,6 +1446,7 @@ static void push_pending(sb_ctx* ctx, Pending::Kind kind, void* const* users, co
         if (kind == Pending::TOPK_COL) pd.bytes = stride;   // (the header and kmax entries: the column's own k is in its struct)
         if (kind == Pending::KEY_COL || kind == Pending::COMB_ITEM) pd.bytes = stride;    // (likewise: the header and kmax key slots / codes)
         if (kind == Pending::KEY_VAR_COL) pd.bytes = stride, pd.n = kmax;   // (the header, kmax + 1 offsets, the bytes)
+        if (kind == Pending::KEY_LOOK_COL) pd.bytes = stride;
         ctx->iv.pending.push_back(pd);
     }
 }
@@ -1556,7 +1597,7 @@ constexpr bool has_pages_prefix() {
 static_assert(offsetof(sb_column_filter, page_offsets) == 40, "the pages of a sink column: 48 bytes");
 static_assert(has_pages_prefix<sb_column_filter_var>() && has_pages_prefix<sb_column_read_selected>() && has_pages_prefix<sb_column_read_selected_var>() &&
                   has_pages_prefix<sb_column_aggregate>() && has_pages_prefix<sb_column_aggregate_grouped>() && has_pages_prefix<sb_column_topk>() &&
-                  has_pages_prefix<sb_column_key_ids>() && has_pages_prefix<sb_column_key_ids_var>(),
+                  has_pages_prefix<sb_column_key_ids>() && has_pages_prefix<sb_column_key_ids_var>() && has_pages_prefix<sb_column_key_lookup>(),
               "every sink column begins with the seven fields of sb_column_filter, at its offsets");
 
 // The pages of a sink column as a read column (outputs: none yet)
@@ -2863,6 +2904,166 @@ int32_t sb_key_combine(sb_ctx* ctx, sb_key_combine_item* items, uint64_t n, int3
     push_pending(ctx, Pending::COMB_ITEM, users.data(), slot->host + upload, res_stride, n);
     if (!ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::KEY_COMBINE, items, n, sb_write_options{}, mem});
     return SB_OK;
+}
+
+// ------------------------------------------------------------------------------------ ids against a given list
+static_assert(sizeof(sb_column_key_lookup) == 168 && offsetof(sb_column_key_lookup, selection) == 48 && offsetof(sb_column_key_lookup, ids) == 64 &&
+                  offsetof(sb_column_key_lookup, id_width) == 80 && offsetof(sb_column_key_lookup, reserved0) == 84 &&
+                  offsetof(sb_column_key_lookup, values) == 88 && offsetof(sb_column_key_lookup, value_offsets) == 96 &&
+                  offsetof(sb_column_key_lookup, value_ids) == 104 && offsetof(sb_column_key_lookup, n_values) == 112 &&
+                  offsetof(sb_column_key_lookup, stage_capacity) == 120 && offsetof(sb_column_key_lookup, reserved) == 128 &&
+                  offsetof(sb_column_key_lookup, rows) == 136 && offsetof(sb_column_key_lookup, matched) == 160,
+              "sb_column_key_lookup: the offsets the header states");
+static_assert(sb_lookup::MAX_VALUES == SB_KEY_MAX_KEYS && SB_KEY_MAX_KEYS == KEY_MAX_KEYS, "the header's limit");
+
+// The prepared list of a column (sb_key_lookup_prep.h) appended to `blob` at a multiple of 8, as [words | ids | bytes]; lc's
+// pointers are offsets in `blob` until the lists have their place on the device.
+static void look_list_append(const sb_lookup::Prepared& pr, std::vector<uint8_t>& blob, LookCol* lc) {
+    blob.resize(align_up(blob.size(), 8));
+    lc->keys = (const uint64_t*)(uintptr_t)blob.size();
+    blob.insert(blob.end(), (const uint8_t*)pr.words.data(), (const uint8_t*)(pr.words.data() + pr.words.size()));
+    lc->kid = (const uint32_t*)(uintptr_t)blob.size();
+    blob.insert(blob.end(), (const uint8_t*)pr.ids.data(), (const uint8_t*)(pr.ids.data() + pr.ids.size()));
+    blob.resize(align_up(blob.size(), 8));
+    lc->bytes = (const uint8_t*)(uintptr_t)blob.size();
+    blob.insert(blob.end(), pr.bytes.begin(), pr.bytes.end());
+    lc->n = pr.n;
+    lc->steps = pr.steps;
+}
+
+// The sibling of key_ids_decoded for the numeric columns of a replayed call: searched from the staging area by
+// k_key_lookup_plain.  The lists go to the device in a buffer of the interval's, as filter_in_columns_decoded has it.
+static int32_t key_lookup_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pages, std::vector<AggCol>& hs, std::vector<LookCol>& hl,
+                                  const std::vector<uint8_t>& blob, void* const* users) {
+    const uint64_t n = pages.size();
+    std::vector<uint64_t> rows(n);
+    for (uint64_t i = 0; i < n; i++) rows[i] = hs[i].rows;
+    const sb_column_read* rr = nullptr;
+    int32_t rc = decode_for_replay(ctx, std::move(pages), rows.data(), "key lookup", &rr);
+    if (rc != SB_OK) return rc;
+    std::vector<const uint8_t*> vals(n), bits(n);
+    (void)replay_slots(rr, rows, hs, vals, bits);
+    // [AggCol per column][LookCol per column][the results][the columns' states][the lists]
+    const size_t res_stride = LOOK_RESULT_WORDS * sizeof(uint64_t);
+    size_t off = align_up(n * sizeof(AggCol), 64);
+    const size_t o_lc = off;
+    off = align_up(off + n * sizeof(LookCol), 64);
+    const size_t o_res = off;
+    off = align_up(off + n * res_stride, 64);
+    const size_t o_state = off;
+    off = align_up(off + n * sizeof(LookState), 64);
+    const size_t o_lists = off;
+    off += blob.size();
+    uint8_t* dev = nullptr;
+    if (hipMalloc((void**)&dev, off + 64) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(key lookup replay) failed");
+    ctx->iv.temp_dev.push_back(dev);
+    for (LookCol& lc : hl) {
+        lc.keys = (const uint64_t*)(dev + o_lists + (size_t)(uintptr_t)lc.keys);
+        lc.kid = (const uint32_t*)(dev + o_lists + (size_t)(uintptr_t)lc.kid);
+        lc.bytes = dev + o_lists + (size_t)(uintptr_t)lc.bytes;
+    }
+    // (copies that have ended when they return: the vectors do not outlive the call)
+    if (hipMemcpy(dev, hs.data(), n * sizeof(AggCol), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dev + o_lc, hl.data(), n * sizeof(LookCol), hipMemcpyHostToDevice) != hipSuccess ||
+        (!blob.empty() && hipMemcpy(dev + o_lists, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess))
+        return ctx->fail(SB_ERR_EXTERNAL, "key lookup replay: upload failed");
+    StageSlot* slot = acquire_slot(ctx, n * res_stride);
+    if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
+    uint64_t* d_res = (uint64_t*)(dev + o_res);
+    const LookLaunch ll{(const AggCol*)dev, (const LookCol*)(dev + o_lc), (LookState*)(dev + o_state), (uint32_t)n, true, false};
+    launch_look_zero(ctx, ll);
+    launch_key_lookup_plain(ctx, ll, rows.data(), vals.data(), bits.data());
+    launch_look_finish(ctx, ll, d_res);
+    return queue_sink_results(ctx, slot, d_res, res_stride, n, Pending::KEY_LOOK_COL, users, nullptr, "key lookup");
+}
+
+int32_t sb_key_lookup(sb_ctx* ctx, sb_column_key_lookup* cols, uint64_t n, int32_t mem) {
+    int32_t rc;
+    if (!sink_entry(ctx, cols, n, mem, "sb_key_lookup", &rc)) return rc;
+    std::vector<AggCol> hs(n);
+    std::vector<uint64_t> cap(n);
+    uint64_t pages = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_column_key_lookup& c = cols[i];
+        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(ctx, SB_ERR_INVALID, "bad physical_type");
+        const bool bin = is_binary_t(c.physical_type);
+        if (!bin && (c.physical_type < SB_TYPE_INT8 || c.physical_type > SB_TYPE_UINT64))
+            return refuse(ctx, SB_ERR_NYI, "key lookup is implemented for 8- to 64-bit integers and binary types");
+        if (c.id_width != 1 && c.id_width != 2 && c.id_width != 4) return refuse(ctx, SB_ERR_INVALID, "id_width is not 1, 2 or 4");
+        if (c.reserved0 || c.reserved) return refuse(ctx, SB_ERR_INVALID, "reserved is not 0");
+        const char* why = sb_lookup::check_list(bin, c.values, c.value_offsets, c.n_values);
+        if (!why) why = sb_lookup::check_ids(c.value_ids, c.n_values, c.id_width);
+        if (why) return refuse(ctx, SB_ERR_INVALID, why);
+        // (numbers: searched like a minimum is taken, every live value is looked at; strings: as sb_key_ids_var has them)
+        if ((rc = agg_check_fill(ctx, c, bin ? 0u : (uint32_t)SB_AGG_MIN, hs[i])) != SB_OK) return rc;
+        const uint64_t rows = hs[i].rows;
+        if (rows && !c.ids) return refuse(ctx, SB_ERR_INVALID, "ids is null");
+        if (c.ids && (((uintptr_t)c.ids & (c.id_width - 1)) || c.ids_capacity < rows * c.id_width))
+            return refuse(ctx, SB_ERR_INVALID, "ids not aligned to id_width or smaller than rows * id_width bytes");
+        for (uint64_t p = 0; bin && p < c.n_pages; p++)   // (the limits of sb_key_ids_var: its id tables and entry records)
+            if (c.metas[p].num_values > (1ull << KEYV_INDEX_BITS) || c.metas[p].length / 8 >= (1ull << KEYV_INDEX_BITS))
+                return refuse(ctx, SB_ERR_NYI, "sb_key_lookup: a binary page of more than 2^26 rows or of 2^29 bytes or more");
+        if (bin) pages += c.n_pages;
+        // the share of the staging area a filter column has (the caller's stage_capacity stays as given: a replay reads it again)
+        cap[i] = bin ? (c.stage_capacity ? c.stage_capacity : 4 * c.pages_len) : rows * type_width(c.physical_type);
+    }
+    if (pages >= (1ull << KEYV_PAGE_BITS)) return refuse(ctx, SB_ERR_NYI, "sb_key_lookup: 2^28 binary pages or more in one call");
+    for (uint64_t i = 0; i < n; i++)   // (the bytes a column writes: rows * id_width)
+        for (uint64_t j = i + 1; j < n; j++) {
+            const uintptr_t a0 = (uintptr_t)cols[i].ids, a1 = a0 + hs[i].rows * cols[i].id_width;
+            const uintptr_t b0 = (uintptr_t)cols[j].ids, b1 = b0 + hs[j].rows * cols[j].id_width;
+            if (a0 < b1 && b0 < a1) return refuse(ctx, SB_ERR_INVALID, "ids of two columns of one call overlap");
+        }
+    // the lists as the kernels search them, one blob for the call
+    std::vector<LookCol> hl(n);
+    std::vector<uint8_t> blob;
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_column_key_lookup& c = cols[i];
+        memset(&hl[i], 0, sizeof hl[i]);
+        hl[i].ids = (uint8_t*)c.ids;
+        hl[i].idw = c.id_width;
+        const sb_lookup::Prepared pr = is_binary_t(c.physical_type)
+                                           ? sb_lookup::prepare_binary(c.values, c.value_offsets, c.value_ids, c.n_values)
+                                           : sb_lookup::prepare_numeric(c.values, hs[i].w, hs[i].kind == FK_SIGNED, c.value_ids, c.n_values);
+        look_list_append(pr, blob, &hl[i]);
+    }
+    (void)hipSetDevice(ctx->device);
+    std::vector<sb_column_read> rc_cols(n);
+    std::vector<void*> users(n);
+    for (uint64_t i = 0; i < n; i++) {
+        rc_cols[i] = read_col_of(cols[i]);
+        users[i] = &cols[i];
+    }
+    if (ctx->in_replay && ctx->filter_freq) {
+        // The numeric columns through a full decode, as sb_key_ids has it; the binary columns as ever (a binary Freq page is
+        // a virtual Dict page).  The ids are a function of the data and the list alone, so the route does not show in them.
+        std::vector<bool> dec(n);
+        for (uint64_t i = 0; i < n; i++) dec[i] = !is_binary_t(rc_cols[i].physical_type);
+        std::vector<sb_column_read> r_num = take_if(rc_cols, dec);
+        std::vector<AggCol> g_num = take_if(hs, dec);
+        std::vector<LookCol> l_num = take_if(hl, dec);
+        const std::vector<void*> u_num = take_if(users, dec);
+        take_if(cap, dec);
+        if (!r_num.empty()) rc = key_lookup_decoded(ctx, std::move(r_num), g_num, l_num, blob, u_num.data());
+    }
+    if (rc == SB_OK && !rc_cols.empty()) {
+        if ((rc = stage_shares(ctx, rc_cols.data(), cap.data(), rc_cols.size())) != SB_OK) return rc;
+        ReadMode mode{ReadMode::KEY_LOOKUP};
+        mode.aggc = hs.data();
+        mode.lookc = hl.data();
+        mode.lits = &blob;
+        mode.users = users.data();
+        mode.pending_kind = Pending::KEY_LOOK_COL;
+        rc = read_columns_impl(ctx, rc_cols.data(), rc_cols.size(), SB_MEM_DEVICE, mode);
+    }
+    if (rc != SB_OK) return rc;
+    for (uint64_t i = 0; i < n; i++) {   // (after the last thing that can refuse the call: a page outside pages_len)
+        sb_column_key_lookup& c = cols[i];
+        column_rows(c, &c.rows);
+        c.selected = c.count = c.matched = 0;
+    }
+    if (!ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::KEY_LOOKUP, cols, n, sb_write_options{}, mem});
+    return rc;
 }
 
 

@@ -381,6 +381,32 @@ struct KeyLaunch {   // what launch_decode needs to end a call with the collect 
     uint32_t kmax;
     uint32_t n_cols;
 };
+// one column of a key-lookup call (sb_key_lookup, sb_key_lookup.h), next to its AggCol (of which sel, rows, kind and w are
+// used).  The caller's list as the kernels search it: InCol's two forms -- numeric: n order keys (in_key), ascending;
+// binary: n + 1 ascending offsets into `bytes`, the literals back to back in byte-string order with 8 zero bytes behind
+// them -- without duplicates, and beside it the id the list gives each sorted position.
+struct LookCol {
+    uint8_t* ids;           // the caller's ids: one unsigned integer of `idw` bytes per row of the column (output)
+    const uint64_t* keys;
+    const uint32_t* kid;    // n ids, each below all ones of `idw`: kid[i] belongs to keys[i]
+    const uint8_t* bytes;   // binary columns
+    uint32_t n;             // 0 .. KEY_MAX_KEYS
+    uint32_t steps;         // key_steps(n)
+    uint32_t idw;           // 1, 2 or 4
+    uint32_t pad;
+};
+struct LookState {          // 16 bytes per column, zeroed before the walk; one integer add per tile / page part into each
+    uint64_t count;         // live rows
+    uint64_t matched;       // ... whose value is in the list
+};
+constexpr uint32_t LOOK_RESULT_WORDS = 4;   // { selected, count, matched, 0 }
+struct LookLaunch {   // what launch_decode needs to end a call with the lookup kernels
+    const AggCol* acols;
+    const LookCol* lcols;
+    LookState* st;         // [n_cols]
+    uint32_t n_cols;
+    bool any_num, any_bin;
+};
 // ---- sb_key_combine (sb_key_combine.h): the key of a row is a tuple of 2 .. 4 part ids, each below KEY_MAX_KEYS.  Its
 // code is a 64-bit word with one COMB_FIELD_BITS field per part, part 0 highest, so that codes order as the tuples do
 // lexicographically.  The host's delivery, the kernels and tests/test_key_combine_host.py use these two functions.

@@ -3131,12 +3131,13 @@ static void launch_lzg(sb_ctx* ctx, const DecodeArgs& a, bool lzg_on, InflateJob
 #include "sb_topk.h"
 #include "sb_key_ids.h"
 #include "sb_key_ids_bin.h"
+#include "sb_key_lookup.h"
 #include "sb_key_combine.h"
 namespace sb {
 
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
                    const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp, const InCol* icols, const TopkLaunch* topk,
-                   const KeyLaunch* keys, const KeyVarLaunch* keyv, const GrpLaunch* grpl) {
+                   const KeyLaunch* keys, const KeyVarLaunch* keyv, const GrpLaunch* grpl, const LookLaunch* look) {
     hipStream_t s = ctx->stream;
     (void)hipMemsetAsync(a.job_counts, 0, 16 * sizeof(uint32_t), s);
     const bool qa = !(a.read_skips & RSKIP_QUEUE_A);
@@ -3177,16 +3178,16 @@ void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_p
         launch_rsel_bin_base(ctx, a);
         launch_zstd_split(a, a.jobs_b, a.job_counts + 1, a.job_counts + 9, a.job_cap_b, s);
     }
-    if (any_binary && keyv) {   // sb_key_ids_var: likewise (sb_key_ids_bin.h)
+    if (any_binary && (keyv || look)) {   // sb_key_ids_var, sb_key_lookup: likewise (sb_key_ids_bin.h)
         launch_keyv_base(ctx, a);
         launch_zstd_split(a, a.jobs_b, a.job_counts + 1, a.job_counts + 9, a.job_cap_b, s);
     }
-    if (any_binary && !flt && !rsel_bin && !keyv && a.n_tiles >= BIN_DEFER_TILES) {   // long binary Dict pages: the tiles' value bytes by a workgroup per tile
+    if (any_binary && !flt && !rsel_bin && !keyv && !look && a.n_tiles >= BIN_DEFER_TILES) {   // long binary Dict pages: the tiles' value bytes by a workgroup per tile
         KScope k(ctx, "k_bin_tile_sums");
         k_bin_tile_sums<<<min(a.n_tiles, TILE_GRID), WG, 0, s>>>(a);
         k_bin_tile_scan<<<min((a.n_pages + WG / 64 - 1) / (WG / 64), 1024u), WG, 0, s>>>(a);
     }
-    if (any_binary && !flt && !rsel_bin && !keyv) {  // (without binary columns the host knows every values_len itself)
+    if (any_binary && !flt && !rsel_bin && !keyv && !look) {  // (without binary columns the host knows every values_len itself)
         KScope k(ctx, K_COLSCAN);
         k_colscan<<<a.n_cols, 64, 0, s>>>(a, col_values_len);
         launch_zstd_split(a, a.jobs_b, a.job_counts + 1, a.job_counts + 9, a.job_cap_b, s);
@@ -3245,6 +3246,10 @@ void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_p
     }
     if (keyv) {   // sb_key_ids_var: ... of distinct byte strings
         launch_keyv_collect(ctx, a, *keyv);
+        return;
+    }
+    if (look) {   // sb_key_lookup: ... searched in the columns' lists, an id per row (sb_key_lookup.h)
+        launch_key_lookup(ctx, a, *look);
         return;
     }
     // the three expand kernels work on disjoint pages (page-level RLE, tiles of primitives, tiles of binary columns): side

@@ -111,6 +111,35 @@ def group_by(ctx, key, values: List[ColumnPages], selection=None,
     return kres, call(ctx, list(values), kres.ids, max_keys, selection, ops)
 
 
+def group_by_keys(ctx, key: ColumnPages, key_values, values: List[ColumnPages], selection=None,
+                  ops: Sequence[str] = ("count", "min", "max", "sum"), value_ids=None, n_groups=None):
+    """GROUP BY over a key set that is given: `key_lookup` of `key` against `key_values` (with `value_ids`, several
+    values may share a group), then the per-group aggregates of every column of `values`, in the open interval.
+    Returns (KeyLookup, [GroupedAggregate per value column]); group g belongs to key_values[g], or to the values whose
+    value id is g.  n_groups: None = the largest id + 1.  The ids are the list's own, so the groups of two calls with one
+    list are index-aligned: the count and sum records of two row groups, files or ranks add, group by group.  Selected
+    rows whose key is null or not in the list arrive in `out_of_range`."""
+    from .key_lookup import key_lookup, list_values
+    n_values = len(list_values(key.physical_type, key_values))
+    if value_ids is None:
+        largest = n_values - 1
+    else:
+        ids = [int(v) for v in (value_ids.tolist() if isinstance(value_ids, np.ndarray) else value_ids)]
+        largest = max(ids) if ids else -1
+    if n_groups is None:
+        n_groups = max(1, largest + 1)
+    if isinstance(n_groups, bool) or not isinstance(n_groups, (int, np.integer)) or not 1 <= n_groups <= MAX_GROUPS_LARGE:
+        raise ValueError("n_groups is %r, not an int in 1 .. %d" % (n_groups, MAX_GROUPS_LARGE))
+    if largest >= n_groups:
+        raise ValueError("the list hands out the id %d, n_groups is %d" % (largest, n_groups))
+    n_groups = int(n_groups)
+    kres = key_lookup(ctx, [key], [key_values], None if value_ids is None else [value_ids], selection)[0]
+    if not values:
+        return kres, []
+    call = aggregate_grouped if n_groups <= MAX_GROUPS else aggregate_grouped_large
+    return kres, call(ctx, list(values), kres.ids, n_groups, selection, ops)
+
+
 def trim(keys_result, aggregates: List[GroupedAggregate]) -> List[List[Group]]:
     """After the synchronize: the groups of every value column that have a key, groups[i][g] belonging to key g of
     keys_result.  Raises on an overflow of the keys: the ids, and with them the groups, mean nothing then."""
