@@ -596,6 +596,78 @@ int32_t sb_aggregate_grouped(sb_ctx* ctx, sb_column_aggregate_grouped* cols, uin
 
 int32_t sb_aggregate_grouped_large(sb_ctx* ctx, sb_column_aggregate_grouped* cols, uint64_t n, int32_t mem);
 
+/* ------------------------------------------------------------------ aggregate, weighted: sum(y * w) per group
+ * SELECT k, count(y), sum(y * w) ... WHERE x < 5 GROUP BY k.  sb_aggregate_grouped_large with one more dense per-row
+ * input beside `group_ids`: `weights` (DEVICE), one value of `weight_type` per row of the column -- a column that
+ * sb_read_columns decoded earlier in the interval, or any per-row expression the caller computed.  With SB_WGT_SQUARE the
+ * weight of a row is its own y: the sum of squares.  The results are sb_agg_group records, index-aligned with those of the
+ * grouped calls: min / max are written as zero bytes, sum_lo / sum_hi hold the sum of products, nans counts NaN products.
+ *
+ *   operands      y from the pages and w from `weights`, each of INT8..INT64, UINT8..UINT64, FLOAT32, FLOAT64,
+ *                 independently chosen.  `weights`: aligned to the type's width, weights_capacity >= rows * width.
+ *                 `weights_validity` (optional, DEVICE): an LSB-first bitmap as sb_read_columns writes it, 4-byte aligned,
+ *                 >= 4*ceil(rows/32) bytes; NULL: every weight is valid.  Bits behind `rows` are ignored.
+ *   SB_WGT_SQUARE weights, weights_validity and their capacities must be NULL / 0 and weight_type 0.
+ *   groups        group_ids / group_id_width / n_groups as for sb_aggregate_grouped_large, n_groups 1 .. 1024.  group_ids
+ *                 NULL is allowed only with n_groups == 1, group_id_width == 0 and group_ids_capacity == 0: every selected
+ *                 row is in group 0 (the ungrouped case).
+ *   live rows     selected, id < n_groups, y not null, weight valid.  Weights, validity bits and ids of unselected rows
+ *                 are never loaded.  groups[g].selected: the group's selected rows; groups[g].count: its live rows; the
+ *                 sum of groups[g].selected over g, plus out_of_range, is `selected`.
+ *   ops           SB_AGG_COUNT and SB_AGG_SUM; MIN / MAX are refused (SB_ERR_INVALID).  Without SUM only def levels, ids
+ *                 and weight validity are read, sum / nans are 0, every physical type is accepted.
+ *   int x int     both operands extended by their own signedness, multiplied exactly; the group's sum is the true sum
+ *                 modulo 2^128 (two's complement in sum_lo / sum_hi), the same in any order.  nans 0.
+ *   otherwise     the product is (double)y * (double)w (integer to double: round to nearest), summed in double over all
+ *                 live rows, NaN and +-inf included; the bits in sum_lo, sum_hi 0; nans: live rows whose product is NaN.
+ *                 No floating-point atomics: the order of a group's additions is a function of the column's own page
+ *                 layout, data, ids and selection alone, a replayed interval included.  The bits are this call's own.
+ *
+ * Refused at the call, nothing enqueued, no result field and no byte of `groups` touched: SB_ERR_NYI for SUM on Boolean /
+ * Int128 / Int256 / Binary / LargeBinary / Null and for SB_MEM_HOST; SB_ERR_INVALID for a bad weight_type, null,
+ * misaligned or short weights, misaligned or short weights_validity, an inconsistent SB_WGT_SQUARE or ungrouped form,
+ * unknown flags, reserved != 0, n_groups 0 or above 1024, and every argument refusal of sb_aggregate_grouped; SB_ERR_IO for
+ * a page outside [0, pages_len).
+ *
+ * Enqueued like sb_aggregate_grouped; `selection`, `group_ids`, `weights` and `weights_validity` are INPUTS that stay
+ * unmodified until the synchronize.  `rows` and `selected` are delivered even when the interval failed.
+ *
+ * Layout (pinned by tests/test_aggregate_weighted_host.py): 168 bytes; the first 92 bytes are sb_column_aggregate_grouped's,
+ * then flags 92, weights 96, weights_capacity 104, weights_validity 112, weights_validity_capacity 120, weight_type 128,
+ * reserved 132, groups 136, rows 144, selected 152, out_of_range 160. */
+#define SB_WGT_SQUARE 1u   /* flags bit 0: the weight of a row is its own y */
+
+typedef struct sb_column_aggregate_weighted {
+    int32_t physical_type;   /* SB_TYPE_* */
+    int32_t is_nullable;
+    const uint8_t* pages;    /* DEVICE, at any byte alignment */
+    uint64_t pages_len;
+    const sb_page_meta* metas; /* HOST */
+    uint64_t n_pages;
+    const uint64_t* page_offsets; /* optional (HOST), as in sb_column_read */
+    const uint8_t* selection;     /* DEVICE, input; NULL = every row */
+    uint64_t selection_capacity;
+    const void* group_ids;        /* DEVICE, input; NULL: the ungrouped form (n_groups 1, width and capacity 0) */
+    uint64_t group_ids_capacity;
+    uint32_t group_id_width;      /* 1, 2 or 4 (0 in the ungrouped form) */
+    uint32_t n_groups;            /* 1 .. SB_AGG_LARGE_MAX_GROUPS */
+    uint32_t ops;                 /* SB_AGG_COUNT | SB_AGG_SUM */
+    uint32_t flags;               /* SB_WGT_* bits */
+    const void* weights;          /* DEVICE, input: one value of weight_type per row, aligned to its width */
+    uint64_t weights_capacity;    /* >= rows * width bytes */
+    const uint8_t* weights_validity;     /* DEVICE, input, optional: LSB-first bitmap, 4-byte aligned */
+    uint64_t weights_validity_capacity;  /* >= 4*ceil(rows/32) bytes */
+    int32_t weight_type;          /* SB_TYPE_* of `weights` (0 with SB_WGT_SQUARE) */
+    uint32_t reserved;            /* must be 0 */
+    sb_agg_group* groups;         /* HOST, n_groups entries, filled at the synchronize; must live until then */
+    /* results (HOST, valid after sb_ctx_synchronize) */
+    uint64_t rows;
+    uint64_t selected;
+    uint64_t out_of_range;
+} sb_column_aggregate_weighted;   /* 168 bytes */
+
+int32_t sb_aggregate_weighted(sb_ctx* ctx, sb_column_aggregate_weighted* cols, uint64_t n, int32_t mem);
+
 /* ------------------------------------------------------------------ top-k
  * SELECT ... WHERE x < 5 ORDER BY y [DESC] LIMIT k.  The pages of a column and (optionally) a selection bitmap go in; the
  * k best of the selected rows come back in `out` (HOST) with their row numbers, with which sb_read_selected fetches the

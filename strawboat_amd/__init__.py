@@ -15,14 +15,15 @@ from .read_selected_var import ReadSelectedVarBatch, SelectedBinaryArray, read_s
 from .aggregate import Aggregate, AggregateBatch, aggregate_columns  # noqa: F401
 from .aggregate_grouped import GroupedAggregate, GroupedAggregateBatch, aggregate_grouped  # noqa: F401
 from .aggregate_grouped_large import GroupedAggregateLargeBatch, aggregate_grouped_large  # noqa: F401
+from .aggregate_weighted import WeightedAggregateBatch, aggregate_weighted  # noqa: F401
 from .topk import TopK, TopKBatch, selection_of_rows, topk_columns  # noqa: F401
 from .key_ids import KeyIds, KeyIdsBatch, key_ids  # noqa: F401
 from .key_ids_var import KeyIdsVar, KeyIdsVarBatch, key_ids_var  # noqa: F401
 from .key_lookup import KeyLookup, KeyLookupBatch, key_lookup  # noqa: F401
 from .key_combine import KeyCombine, KeyCombineBatch, key_combine  # noqa: F401
-from .group_by import GroupKeys, group_by, group_by_keys  # noqa: F401
+from .group_by import GroupKeys, group_by, group_by_keys, group_by_weighted  # noqa: F401
 
 __all__ = ["Context", "read", "write", "filter", "Predicate", "Selection", "filter_columns", "like_predicate", "InList", "FilterInBatch", "filter_in", "read_selected", "ReadSelectedBatch", "SelectedArray",
            "read_selected_var", "ReadSelectedVarBatch", "SelectedBinaryArray", "aggregate_columns", "AggregateBatch", "Aggregate",
-           "aggregate_grouped", "GroupedAggregateBatch", "GroupedAggregate", "aggregate_grouped_large", "GroupedAggregateLargeBatch", "group_by", "topk_columns", "TopKBatch", "TopK", "selection_of_rows", "key_ids", "KeyIdsBatch", "KeyIds", "key_ids_var", "KeyIdsVarBatch", "KeyIdsVar", "key_combine", "KeyCombineBatch", "KeyCombine", "GroupKeys", "key_lookup", "KeyLookupBatch", "KeyLookup", "group_by_keys", "WriteOptions", "PageMeta", "ColumnMeta", "Compression",
+           "aggregate_grouped", "GroupedAggregateBatch", "GroupedAggregate", "aggregate_grouped_large", "GroupedAggregateLargeBatch", "aggregate_weighted", "WeightedAggregateBatch", "group_by", "group_by_weighted", "topk_columns", "TopKBatch", "TopK", "selection_of_rows", "key_ids", "KeyIdsBatch", "KeyIds", "key_ids_var", "KeyIdsVarBatch", "KeyIdsVar", "key_combine", "KeyCombineBatch", "KeyCombine", "GroupKeys", "key_lookup", "KeyLookupBatch", "KeyLookup", "group_by_keys", "WriteOptions", "PageMeta", "ColumnMeta", "Compression",
            "CommonCompression", "PhysicalType"]

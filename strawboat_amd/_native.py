@@ -25,7 +25,7 @@ EXPORTS = ("sb_version", "sb_ctx_create", "sb_ctx_destroy", "sb_ctx_synchronize"
            "sb_schema_metadata_from_bytes", "sb_filter_columns", "sb_filter_columns_var", "sb_read_selected",
            "sb_read_selected_var", "sb_aggregate_columns", "sb_aggregate_grouped", "sb_filter_columns_in",
            "sb_topk_columns", "sb_key_ids", "sb_key_ids_var", "sb_aggregate_grouped_large",
-           "sb_key_combine", "sb_key_lookup")
+           "sb_key_combine", "sb_key_lookup", "sb_aggregate_weighted")
 
 SB_PRED_EQ, SB_PRED_NE, SB_PRED_LT, SB_PRED_LE, SB_PRED_GT, SB_PRED_GE, SB_PRED_IS_NULL, SB_PRED_IS_NOT_NULL = range(8)
 SB_PRED_STARTS_WITH = 8   # binary types only (sb_filter_columns_var)
@@ -37,6 +37,7 @@ SB_SEL_SET, SB_SEL_AND, SB_SEL_OR = range(3)
 SB_AGG_COUNT, SB_AGG_MIN, SB_AGG_MAX, SB_AGG_SUM = 1, 2, 4, 8
 SB_AGG_MAX_GROUPS = 256
 SB_AGG_LARGE_MAX_GROUPS = 1024   # == SB_KEY_MAX_KEYS
+SB_WGT_SQUARE = 1                # sb_aggregate_weighted: flags bit 0, the weight of a row is its own y
 SB_TOPK_MAX_K = 256
 SB_TOPK_SMALLEST, SB_TOPK_LARGEST = 0, 1
 SB_KEY_MAX_KEYS = 1024
@@ -130,6 +131,18 @@ class ColumnAggregateGroupedC(C.Structure):
                 ("page_offsets", C.c_void_p), ("selection", C.c_void_p), ("selection_capacity", C.c_uint64),
                 ("group_ids", C.c_void_p), ("group_ids_capacity", C.c_uint64), ("group_id_width", C.c_uint32),
                 ("n_groups", C.c_uint32), ("ops", C.c_uint32), ("reserved", C.c_uint32),
+                ("groups", C.POINTER(AggGroupC)), ("rows", C.c_uint64), ("selected", C.c_uint64),
+                ("out_of_range", C.c_uint64)]
+
+
+class ColumnAggregateWeightedC(C.Structure):
+    _fields_ = [("physical_type", C.c_int32), ("is_nullable", C.c_int32), ("pages", C.c_void_p),
+                ("pages_len", C.c_uint64), ("metas", C.POINTER(PageMetaC)), ("n_pages", C.c_uint64),
+                ("page_offsets", C.c_void_p), ("selection", C.c_void_p), ("selection_capacity", C.c_uint64),
+                ("group_ids", C.c_void_p), ("group_ids_capacity", C.c_uint64), ("group_id_width", C.c_uint32),
+                ("n_groups", C.c_uint32), ("ops", C.c_uint32), ("flags", C.c_uint32),
+                ("weights", C.c_void_p), ("weights_capacity", C.c_uint64), ("weights_validity", C.c_void_p),
+                ("weights_validity_capacity", C.c_uint64), ("weight_type", C.c_int32), ("reserved", C.c_uint32),
                 ("groups", C.POINTER(AggGroupC)), ("rows", C.c_uint64), ("selected", C.c_uint64),
                 ("out_of_range", C.c_uint64)]
 
@@ -289,6 +302,8 @@ def load():
     L.sb_aggregate_grouped.argtypes = [C.c_void_p, C.POINTER(ColumnAggregateGroupedC), C.c_uint64, C.c_int32]
     L.sb_aggregate_grouped_large.restype = C.c_int32
     L.sb_aggregate_grouped_large.argtypes = [C.c_void_p, C.POINTER(ColumnAggregateGroupedC), C.c_uint64, C.c_int32]
+    L.sb_aggregate_weighted.restype = C.c_int32
+    L.sb_aggregate_weighted.argtypes = [C.c_void_p, C.POINTER(ColumnAggregateWeightedC), C.c_uint64, C.c_int32]
     L.sb_topk_columns.restype = C.c_int32
     L.sb_topk_columns.argtypes = [C.c_void_p, C.POINTER(ColumnTopKC), C.c_uint64, C.c_int32]
     L.sb_key_ids.restype = C.c_int32

@@ -14,7 +14,7 @@ namespace sb {
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
                    const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp = nullptr, const InCol* icols = nullptr,
                    const TopkLaunch* topk = nullptr, const KeyLaunch* keys = nullptr, const KeyVarLaunch* keyv = nullptr,
-                   const GrpLaunch* grpl = nullptr, const LookLaunch* look = nullptr);
+                   const GrpLaunch* grpl = nullptr, const LookLaunch* look = nullptr, const WgtLaunch* wgt = nullptr);
 void launch_look_zero(sb_ctx* ctx, const LookLaunch& ll);
 void launch_look_finish(sb_ctx* ctx, const LookLaunch& ll, uint64_t* results);
 void launch_key_lookup_plain(sb_ctx* ctx, const LookLaunch& ll, const uint64_t* rows, const uint8_t* const* values, const uint8_t* const* validity);
@@ -39,6 +39,10 @@ void launch_grpl_zero(sb_ctx* ctx, const GrpLaunch& gl, uint32_t n_cols);
 void launch_grpl_finish(sb_ctx* ctx, const GrpLaunch& gl, uint64_t* results, uint32_t n_cols);
 void launch_grpl_plain(sb_ctx* ctx, const GrpLaunch& gl, uint32_t n_cols, const uint64_t* rows, const uint8_t* const* values,
                        const uint8_t* const* validity);
+void launch_wgt_zero(sb_ctx* ctx, const WgtLaunch& wl, uint32_t n_cols);
+void launch_wgt_finish(sb_ctx* ctx, const WgtLaunch& wl, uint64_t* results, uint32_t n_cols);
+void launch_wgt_plain(sb_ctx* ctx, const WgtLaunch& wl, uint32_t n_cols, const uint64_t* rows, const uint8_t* const* values,
+                      const uint8_t* const* validity);
 void launch_agg_finish(sb_ctx* ctx, const AggCol* acols, const AggPart* parts, uint64_t* results, uint32_t n_cols);
 void launch_agg_plain(sb_ctx* ctx, const AggCol* acols, uint32_t n_cols, AggPart* parts, const uint64_t* rows, const uint8_t* const* values,
                       const uint8_t* const* validity);
@@ -122,7 +126,7 @@ StageSlot* acquire_slot(sb_ctx* ctx, size_t need) {
     if (s.host)
         for (auto& p : ctx->iv.pending) {
             if (p.host < s.host || p.host >= s.host + s.cap) continue;
-            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::AGG_COL ? AGG_RESULT_WORDS * 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R || p.kind == Pending::AGG_GRP_COL || p.kind == Pending::AGG_GRPL_COL || p.kind == Pending::TOPK_COL || p.kind == Pending::KEY_COL || p.kind == Pending::KEY_VAR_COL || p.kind == Pending::COMB_ITEM || p.kind == Pending::KEY_LOOK_COL) ? (size_t)p.bytes
+            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::AGG_COL ? AGG_RESULT_WORDS * 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R || p.kind == Pending::AGG_GRP_COL || p.kind == Pending::AGG_GRPL_COL || p.kind == Pending::AGG_WGT_COL || p.kind == Pending::TOPK_COL || p.kind == Pending::KEY_COL || p.kind == Pending::KEY_VAR_COL || p.kind == Pending::COMB_ITEM || p.kind == Pending::KEY_LOOK_COL) ? (size_t)p.bytes
                                                                                                    : (size_t)(2 * p.n + 1) * 8;
             ctx->iv.rescued.emplace_back(p.host, p.host + nb);
             p.host = ctx->iv.rescued.back().data();
@@ -258,11 +262,12 @@ struct ReadMode {
     // sb_aggregate_columns, whose columns end in the aggregate kernels
     // / sb_aggregate_grouped, an aggregate call whose columns end in the grouped aggregate kernels
     // / sb_aggregate_grouped_large, the same with up to 1024 groups: a slot per chunk of 16 tiles instead of a slot per tile
+    // / sb_aggregate_weighted, the same slots and chunks, a WgtCol per column beside its GrpCol, the weighted kernels
     // / sb_topk_columns, an aggregate call whose columns end in the top-k kernels
     // / sb_key_ids, an aggregate call whose columns end in the key kernels: two walks, the finish between them
     // / sb_key_ids_var, the same for binary columns, whose value blocks are staged as a filter call stages them
     // / sb_key_lookup, an aggregate call whose columns end in the lookup kernels: one walk, numeric and binary columns alike
-    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR, AGGREGATE, AGG_GROUPED, AGG_GROUPED_LARGE, TOPK, KEY_IDS, KEY_IDS_VAR, KEY_LOOKUP } kind;
+    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR, AGGREGATE, AGG_GROUPED, AGG_GROUPED_LARGE, TOPK, KEY_IDS, KEY_IDS_VAR, KEY_LOOKUP, AGG_WEIGHTED } kind;
     const FilterCol* filt = nullptr;             // FILTER: one per column
     const std::vector<uint8_t>* lits = nullptr;  // ... the literals of the FK_BYTES columns, FilterCol.lit being the offset of each
     bool in_list = false;                        // ... sb_filter_columns_in: `lits` begins with an InCol per column, whose pointers are offsets in `lits`
@@ -273,6 +278,7 @@ struct ReadMode {
     const AggCol* aggc = nullptr;                // AGGREGATE: one per column (the slots: filled in with the call's tables)
     const GrpCol* grpc = nullptr;                // AGG_GROUPED, AGG_GROUPED_LARGE: one per column beside aggc
     uint32_t grp_gmax = 0;                       // ... the largest n_groups of the call: records per slot
+    const WgtCol* wgtc = nullptr;                // AGG_WEIGHTED: one per column beside aggc and grpc
     const TopkCol* topkc = nullptr;              // TOPK: one per column beside aggc
     uint32_t topk_kmax = 0;                      // ... the largest k of the call: records per slot
     const KeyCol* keyc = nullptr;                // KEY_IDS: one per column beside aggc
@@ -286,9 +292,10 @@ struct ReadMode {
     // Null for the other kinds of call, whose results go to the sb_column_read structs of the call itself.
     void* const* users = nullptr;
     Pending::Kind pending_kind = Pending::READ_COL;
-    bool aggregate() const { return kind == AGGREGATE || kind == AGG_GROUPED || kind == AGG_GROUPED_LARGE || kind == TOPK || kind == KEY_IDS || kind == KEY_IDS_VAR || kind == KEY_LOOKUP; }   // an AggCol per column, slots per page part and tile
-    bool grouped() const { return kind == AGG_GROUPED || kind == AGG_GROUPED_LARGE; }   // a GrpCol per column, flags and gmax records per slot
-    bool grouped_large() const { return kind == AGG_GROUPED_LARGE; }                  // ... whose tile slots are a slot per chunk of GRPL_CHUNK_TILES tiles
+    bool aggregate() const { return kind == AGGREGATE || kind == AGG_GROUPED || kind == AGG_GROUPED_LARGE || kind == AGG_WEIGHTED || kind == TOPK || kind == KEY_IDS || kind == KEY_IDS_VAR || kind == KEY_LOOKUP; }   // an AggCol per column, slots per page part and tile
+    bool grouped() const { return kind == AGG_GROUPED || kind == AGG_GROUPED_LARGE || kind == AGG_WEIGHTED; }   // a GrpCol per column, flags and gmax records per slot
+    bool grouped_large() const { return kind == AGG_GROUPED_LARGE || kind == AGG_WEIGHTED; }   // ... whose tile slots are a slot per chunk of GRPL_CHUNK_TILES tiles
+    bool weighted() const { return kind == AGG_WEIGHTED; }                            // ... and a WgtCol per column behind the GrpCols
     bool topk() const { return kind == TOPK; }
     bool key_ids() const { return kind == KEY_IDS; }
     bool key_var() const { return kind == KEY_IDS_VAR; }
@@ -475,12 +482,13 @@ static int32_t replay_interval(sb_ctx* ctx) {
     // (the columns of sb_aggregate_columns likewise, in the last word of their result record: k_agg_finish)
     ctx->grp_freq_users.clear();
     ctx->grpl_freq_users.clear();
+    ctx->wgt_freq_users.clear();
     ctx->agg_freq_users.clear();
     for (const auto& p : ctx->iv.pending)
-        if (p.kind == Pending::AGG_GRP_COL || p.kind == Pending::AGG_GRPL_COL) {
+        if (p.kind == Pending::AGG_GRP_COL || p.kind == Pending::AGG_GRPL_COL || p.kind == Pending::AGG_WGT_COL) {
             uint64_t met = 0;
             memcpy(&met, p.host + 2 * sizeof(uint64_t), sizeof met);
-            if (met) (p.kind == Pending::AGG_GRP_COL ? ctx->grp_freq_users : ctx->grpl_freq_users).push_back(p.user);
+            if (met) (p.kind == Pending::AGG_GRP_COL ? ctx->grp_freq_users : p.kind == Pending::AGG_GRPL_COL ? ctx->grpl_freq_users : ctx->wgt_freq_users).push_back(p.user);
         } else if (p.kind == Pending::AGG_COL) {
             uint64_t met = 0;
             memcpy(&met, p.host + (AGG_RESULT_WORDS - 1) * sizeof(uint64_t), sizeof met);
@@ -501,6 +509,7 @@ static int32_t replay_interval(sb_ctx* ctx) {
     ctx->filter_freq = false;
     ctx->grp_freq_users.clear();
     ctx->grpl_freq_users.clear();
+    ctx->wgt_freq_users.clear();
     ctx->agg_freq_users.clear();
     if (rc != SB_OK) ctx->iv.sticky = rc;
     rc = sb_ctx_synchronize(ctx);   // (in_replay: this one ends the interval whatever the device says)
@@ -546,6 +555,16 @@ static void deliver_agg_grp_col(const Pending& p, bool ok) {
     uint64_t head[8];
     memcpy(head, p.host, sizeof head);
     sb_column_aggregate_grouped* c = (sb_column_aggregate_grouped*)p.user;
+    c->selected = head[0];
+    if (!ok) return;
+    c->out_of_range = head[1];
+    memcpy(c->groups, p.host + sizeof head, (size_t)p.bytes - sizeof head);
+}
+// k_wgt_finish's header and group records (sb_aggregate_weighted.h); `ok` false: the interval failed, selected alone
+static void deliver_agg_wgt_col(const Pending& p, bool ok) {
+    uint64_t head[8];
+    memcpy(head, p.host, sizeof head);
+    sb_column_aggregate_weighted* c = (sb_column_aggregate_weighted*)p.user;
     c->selected = head[0];
     if (!ok) return;
     c->out_of_range = head[1];
@@ -658,6 +677,7 @@ static void deliver_pending(sb_ctx* ctx, const Pending& p, int32_t rc) {
         case Pending::AGG_COL: deliver_agg_col(p); break;
         case Pending::AGG_GRP_COL:
         case Pending::AGG_GRPL_COL: deliver_agg_grp_col(p, rc == SB_OK); break;
+        case Pending::AGG_WGT_COL: deliver_agg_wgt_col(p, rc == SB_OK); break;
         case Pending::TOPK_COL: deliver_topk_col(p, rc == SB_OK); break;
         case Pending::KEY_COL: deliver_key_col(p, rc == SB_OK); break;
         case Pending::KEY_VAR_COL: deliver_key_var_col(p, rc == SB_OK); break;
@@ -916,7 +936,7 @@ static ReadHints read_hints(sb_ctx* ctx, const ReadMode& mode, const ReadShape& 
 // Where the call's tables sit, on the device (ctx->tables) and — up to `upload` — in the staging slot, whose next n words
 // receive the results.  A pure function of shape, hints and mode.
 struct ReadLayout {
-    size_t cols, tasks, fcols, bcols, lits, upload, descs, tiles, jobs_a, jobs_b, jobs_z, counts, vlen, zb_counts, zb_frames, zs, rle, bpg, aggp, grp_recs, topk_recs, key_sorted, total;
+    size_t cols, tasks, fcols, bcols, wcols, lits, upload, descs, tiles, jobs_a, jobs_b, jobs_z, counts, vlen, zb_counts, zb_frames, zs, rle, bpg, aggp, grp_recs, topk_recs, key_sorted, total;
     size_t job_cap;        // queue entries: 2 per page + room for the frames of Zstd buffers that are several frames (one entry per frame)
     bool want_z;           // queue Z (calls with binary columns that produce values): Zstd payloads known to k_parse, entropy stages with queue A's
     uint64_t zs_seg_cap;
@@ -938,6 +958,8 @@ static ReadLayout read_layout(uint64_t n, const ReadShape& sh, const ReadHints& 
     L.bcols = off;
     if (mode.selected_var()) off = align_up(off + n * sizeof(SelBin), 64);
     if (mode.grouped()) off = align_up(off + n * sizeof(GrpCol), 64);   // (in the SelBins' place)
+    L.wcols = off;
+    if (mode.weighted()) off = align_up(off + n * sizeof(WgtCol), 64);   // (behind the GrpCols)
     if (mode.topk()) off = align_up(off + n * sizeof(TopkCol), 64);     // (likewise)
     if (mode.key_ids()) off = align_up(off + n * sizeof(KeyCol), 64);   // (likewise)
     if (mode.key_var()) off = align_up(off + n * sizeof(KeyVarCol), 64);   // (likewise)
@@ -1126,6 +1148,7 @@ static int32_t fill_read_tables(sb_ctx* ctx, uint8_t* host, const ReadLayout& L,
             tile0 += ntiles;
         }
         if (mode.grouped()) memcpy(host + L.bcols, mode.grpc, n * sizeof(GrpCol));
+        if (mode.weighted()) memcpy(host + L.wcols, mode.wgtc, n * sizeof(WgtCol));
         if (mode.topk()) memcpy(host + L.bcols, mode.topkc, n * sizeof(TopkCol));
         if (mode.key_ids()) memcpy(host + L.bcols, mode.keyc, n * sizeof(KeyCol));
         if (mode.key_var()) memcpy(host + L.bcols, mode.keyvc, n * sizeof(KeyVarCol));
@@ -1370,6 +1393,15 @@ static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, 
         GrpLaunch gl{(const AggCol*)(ctx->tables.p + L.fcols), (const GrpCol*)(ctx->tables.p + L.bcols), (uint64_t*)(ctx->tables.p + L.aggp),
                      (GrpPart*)(ctx->tables.p + L.grp_recs), slots, sh.P * L.rle_parts, mode.grp_gmax, false, false, (uint32_t)n, ctx->in_replay};
         for (uint64_t i = 0; i < n; i++) ((mode.aggc[i].ops & AGG_VALUE_OPS) ? gl.any_val : gl.any_null) = true;
+        if (mode.weighted()) {
+            const WgtLaunch wl{gl, (const WgtCol*)(ctx->tables.p + L.wcols)};
+            launch_wgt_zero(ctx, wl, (uint32_t)n);
+            if (sh.P)
+                launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &wl);
+            // (a call without a page still has a result: selected, and empty groups)
+            launch_wgt_finish(ctx, wl, d_vlen, (uint32_t)n);
+            return;
+        }
         if (large) launch_grpl_zero(ctx, gl, (uint32_t)n);
         else launch_grp_zero(ctx, gl, (uint32_t)n);
         if (sh.P && large)
@@ -2509,6 +2541,147 @@ int32_t sb_aggregate_grouped(sb_ctx* ctx, sb_column_aggregate_grouped* cols, uin
 }
 int32_t sb_aggregate_grouped_large(sb_ctx* ctx, sb_column_aggregate_grouped* cols, uint64_t n, int32_t mem) {
     return aggregate_grouped_impl(ctx, cols, n, mem, true);
+}
+
+// ------------------------------------------------------------------------------------ aggregate, weighted
+static_assert(sizeof(sb_column_aggregate_weighted) == 168 && offsetof(sb_column_aggregate_weighted, ops) == offsetof(sb_column_aggregate_grouped, ops) &&
+                  offsetof(sb_column_aggregate_weighted, group_ids) == offsetof(sb_column_aggregate_grouped, group_ids) &&
+                  has_pages_prefix<sb_column_aggregate_weighted>(),
+              "sb_column_aggregate_weighted begins with the first 92 bytes of sb_column_aggregate_grouped");
+
+// The sibling of grp_columns_decoded: reduced from the staging area by k_wgt_plain into a slot per GRPL_CHUNK_TILES *
+// TILE_ROWS rows, combined by k_wgt_finish.
+static int32_t wgt_columns_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pages, std::vector<AggCol>& hs, const std::vector<GrpCol>& hg,
+                                   const std::vector<WgtCol>& hw, void* const* users) {
+    const uint64_t n = pages.size();
+    std::vector<uint64_t> rows(n);
+    for (uint64_t i = 0; i < n; i++) rows[i] = hs[i].rows;
+    const sb_column_read* rr = nullptr;
+    int32_t rc = decode_for_replay(ctx, std::move(pages), rows.data(), "weighted aggregate", &rr);
+    if (rc != SB_OK) return rc;
+    uint32_t gmax = 1;
+    for (const GrpCol& g : hg) gmax = std::max(gmax, g.n_groups);
+    std::vector<const uint8_t*> vals(n), bits(n);
+    (void)replay_slots(rr, rows, hs, vals, bits);
+    uint64_t slots = 0;   // the columns' chunks back to back, in the tile slots' place
+    for (AggCol& g : hs) {
+        g.tile_slot0 = slots;
+        g.tile_slots = grpl_chunks(g.tile_slots);
+        slots += g.tile_slots;
+    }
+    // [AggCol per column][GrpCol per column][WgtCol per column][the results][the slots' flags, the columns' counters and Freq marks][the slots' records]
+    const size_t res_stride = grp_result_words(gmax) * sizeof(uint64_t);
+    size_t off = align_up(n * sizeof(AggCol), 64);
+    const size_t o_gc = off;
+    off = align_up(off + n * sizeof(GrpCol), 64);
+    const size_t o_wc = off;
+    off = align_up(off + n * sizeof(WgtCol), 64);
+    const size_t o_res = off;
+    off = align_up(off + n * res_stride, 64);
+    const size_t o_flags = off;
+    off = align_up(off + (size_t)(slots + 2 * n) * sizeof(uint64_t), 64);
+    const size_t o_recs = off;
+    off += (size_t)slots * gmax * sizeof(GrpPart);
+    uint8_t* dev = nullptr;
+    if (hipMalloc((void**)&dev, off + 64) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(weighted aggregate replay) failed");
+    ctx->iv.temp_dev.push_back(dev);
+    if (hipMemcpy(dev, hs.data(), n * sizeof(AggCol), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dev + o_gc, hg.data(), n * sizeof(GrpCol), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dev + o_wc, hw.data(), n * sizeof(WgtCol), hipMemcpyHostToDevice) != hipSuccess)
+        return ctx->fail(SB_ERR_EXTERNAL, "weighted aggregate replay: upload failed");
+    StageSlot* slot = acquire_slot(ctx, n * res_stride);
+    if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
+    uint64_t* d_res = (uint64_t*)(dev + o_res);
+    const WgtLaunch wl{GrpLaunch{(const AggCol*)dev, (const GrpCol*)(dev + o_gc), (uint64_t*)(dev + o_flags), (GrpPart*)(dev + o_recs), slots, 0, gmax, true, false,
+                                 (uint32_t)n, true},
+                       (const WgtCol*)(dev + o_wc)};
+    launch_wgt_zero(ctx, wl, (uint32_t)n);
+    launch_wgt_plain(ctx, wl, (uint32_t)n, rows.data(), vals.data(), bits.data());
+    launch_wgt_finish(ctx, wl, d_res, (uint32_t)n);
+    return queue_sink_results(ctx, slot, d_res, res_stride, n, Pending::AGG_WGT_COL, users, hg.data(), "weighted aggregate");
+}
+
+int32_t sb_aggregate_weighted(sb_ctx* ctx, sb_column_aggregate_weighted* cols, uint64_t n, int32_t mem) {
+    int32_t rc;
+    if (!sink_entry(ctx, cols, n, mem, "sb_aggregate_weighted", &rc)) return rc;
+    std::vector<AggCol> hs(n);
+    std::vector<GrpCol> hg(n);
+    std::vector<WgtCol> hw(n);
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_column_aggregate_weighted& c = cols[i];
+        if ((rc = agg_check_ops(ctx, c)) != SB_OK) return rc;
+        if (c.ops & (SB_AGG_MIN | SB_AGG_MAX)) return refuse(ctx, SB_ERR_INVALID, "min / max of a product are not offered: ops is SB_AGG_COUNT | SB_AGG_SUM");
+        if (c.flags & ~SB_WGT_SQUARE) return refuse(ctx, SB_ERR_INVALID, "unknown flags bits");
+        if (c.n_groups == 0 || c.n_groups > SB_AGG_LARGE_MAX_GROUPS) return refuse(ctx, SB_ERR_INVALID, "n_groups is not in 1 .. SB_AGG_LARGE_MAX_GROUPS");
+        if (!c.group_ids) {   // the ungrouped form
+            if (c.n_groups != 1 || c.group_id_width != 0 || c.group_ids_capacity != 0)
+                return refuse(ctx, SB_ERR_INVALID, "group_ids is null: n_groups must be 1, group_id_width and group_ids_capacity 0");
+        } else if (c.group_id_width != 1 && c.group_id_width != 2 && c.group_id_width != 4) {
+            return refuse(ctx, SB_ERR_INVALID, "group_id_width is not 1, 2 or 4");
+        }
+        if (!c.groups) return refuse(ctx, SB_ERR_INVALID, "groups is null");
+        const bool square = (c.flags & SB_WGT_SQUARE) != 0;
+        if (square && (c.weights || c.weights_capacity || c.weights_validity || c.weights_validity_capacity || c.weight_type != 0))
+            return refuse(ctx, SB_ERR_INVALID, "SB_WGT_SQUARE: weights, weights_validity and their capacities must be null / 0 and weight_type 0");
+        if (!square && !filter_comparable(c.weight_type)) return refuse(ctx, SB_ERR_INVALID, "weight_type is not an 8- to 64-bit integer or a float");
+        if ((rc = agg_check_fill(ctx, c, c.ops, hs[i], "sum(y * w) is implemented for 8- to 64-bit integers and floats")) != SB_OK) return rc;
+        const uint64_t rows = hs[i].rows;
+        if (c.group_ids && (((uintptr_t)c.group_ids & (c.group_id_width - 1)) || c.group_ids_capacity < rows * c.group_id_width))
+            return refuse(ctx, SB_ERR_INVALID, "group_ids not aligned to group_id_width or smaller than rows * group_id_width bytes");
+        const uint32_t ww = square ? hs[i].w : type_width(c.weight_type);
+        if (!square) {
+            if (!c.weights) return refuse(ctx, SB_ERR_INVALID, "weights is null");
+            if (((uintptr_t)c.weights & (ww - 1)) || c.weights_capacity < rows * ww)
+                return refuse(ctx, SB_ERR_INVALID, "weights not aligned to the width of weight_type or smaller than rows * width bytes");
+            if (c.weights_validity && (((uintptr_t)c.weights_validity & 3) || c.weights_validity_capacity < (rows + 31) / 32 * 4))
+                return refuse(ctx, SB_ERR_INVALID, "weights_validity not 4-byte aligned or smaller than 4*ceil(rows/32) bytes");
+        }
+        hg[i] = GrpCol{(const uint8_t*)c.group_ids, c.group_id_width, c.n_groups};
+        const uint32_t wkind = square ? hs[i].kind : value_kind(c.weight_type);
+        const bool flt = hs[i].kind == FK_F32 || hs[i].kind == FK_F64 || wkind == FK_F32 || wkind == FK_F64;
+        hw[i] = WgtCol{square ? nullptr : (const uint8_t*)c.weights, square ? nullptr : c.weights_validity, wkind, ww, flt ? 1u : 0u, 0u};
+    }
+    (void)hipSetDevice(ctx->device);
+    std::vector<sb_column_read> rc_cols(n);
+    std::vector<void*> users(n);
+    for (uint64_t i = 0; i < n; i++) {
+        rc_cols[i] = read_col_of(cols[i]);
+        users[i] = &cols[i];
+    }
+    if (ctx->in_replay && ctx->filter_freq) {
+        // the columns that met a Freq page in the first pass through a full decode, the others on the page route
+        // (aggregate_grouped_impl has the same rule); the marks are this call's own
+        const std::vector<const void*>& freq_users = ctx->wgt_freq_users;
+        std::vector<bool> dec(n);
+        for (uint64_t i = 0; i < n; i++)
+            dec[i] = (hs[i].ops & AGG_VALUE_OPS) != 0 &&
+                     std::find(freq_users.begin(), freq_users.end(), (const void*)users[i]) != freq_users.end();
+        std::vector<sb_column_read> r_val = take_if(rc_cols, dec);
+        std::vector<AggCol> g_val = take_if(hs, dec);
+        const std::vector<GrpCol> c_val = take_if(hg, dec);
+        const std::vector<WgtCol> w_val = take_if(hw, dec);
+        const std::vector<void*> u_val = take_if(users, dec);
+        if (!r_val.empty()) rc = wgt_columns_decoded(ctx, std::move(r_val), g_val, c_val, w_val, u_val.data());
+    }
+    if (rc == SB_OK && !rc_cols.empty()) {
+        if ((rc = stage_shares(ctx, rc_cols.data(), agg_stage_caps(hs).data(), rc_cols.size())) != SB_OK) return rc;
+        ReadMode mode{ReadMode::AGG_WEIGHTED};
+        for (const GrpCol& g : hg) mode.grp_gmax = std::max(mode.grp_gmax, g.n_groups);
+        mode.aggc = hs.data();
+        mode.grpc = hg.data();
+        mode.wgtc = hw.data();
+        mode.users = users.data();
+        mode.pending_kind = Pending::AGG_WGT_COL;
+        rc = read_columns_impl(ctx, rc_cols.data(), rc_cols.size(), SB_MEM_DEVICE, mode);
+    }
+    if (rc != SB_OK) return rc;
+    for (uint64_t i = 0; i < n; i++) {   // (after the last thing that can refuse the call: a page outside pages_len)
+        sb_column_aggregate_weighted& c = cols[i];
+        column_rows(c, &c.rows);
+        c.selected = c.out_of_range = 0;
+    }
+    if (!ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::AGG_WEIGHTED, cols, n, sb_write_options{}, mem});
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------ top-k

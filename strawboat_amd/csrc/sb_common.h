@@ -693,6 +693,39 @@ __host__ __device__ inline uint32_t grpl_page_of(const PageTask* tasks, uint32_t
     }
     return p0 + lo;
 }
+// sb_aggregate_weighted (sb_aggregate_weighted.h): sum(y * w) per group.  The structs, slots and chunks of
+// sb_aggregate_grouped_large, and beside a column's AggCol and GrpCol (whose ids are null in the ungrouped form: every
+// selected row is in group 0) its weights:
+struct WgtCol {
+    const uint8_t* w;      // one value of `ww` bytes per row of the column (input); null: the row's own y (SB_WGT_SQUARE)
+    const uint8_t* wv;     // the weights' validity, LSB first, or null: every weight is valid
+    uint32_t wkind;        // FK_* of the weights
+    uint32_t ww;           // bytes per weight
+    uint32_t flt;          // 1: either operand is a float, the products are added in double; 0: exact 128-bit products
+    uint32_t pad;
+};
+struct WgtLaunch {   // what launch_decode needs to end a call with the weighted aggregate kernels
+    GrpLaunch gl;
+    const WgtCol* wcols;
+};
+// The low 128 bits of x * y, each a 64-bit word that stands for a signed (x_signed: two's complement) or unsigned integer.
+// With xu, yu the words read as unsigned: x = xu - 2^64 [x < 0], so x * y = xu * yu - 2^64 ([x < 0] yu + [y < 0] xu) mod 2^128.
+__host__ __device__ inline uint64_t wgt_umulhi(uint64_t x, uint64_t y) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umul64hi(x, y);
+#else
+    const uint64_t x0 = x & 0xFFFFFFFFull, x1 = x >> 32, y0 = y & 0xFFFFFFFFull, y1 = y >> 32;
+    const uint64_t p00 = x0 * y0, p01 = x0 * y1, p10 = x1 * y0, p11 = x1 * y1;
+    const uint64_t mid = (p00 >> 32) + (p01 & 0xFFFFFFFFull) + (p10 & 0xFFFFFFFFull);   // (< 3 * 2^32: no overflow)
+    return p11 + (p01 >> 32) + (p10 >> 32) + (mid >> 32);
+#endif
+}
+__host__ __device__ inline void wgt_mul128(uint64_t x, bool x_signed, uint64_t y, bool y_signed, uint64_t& lo, uint64_t& hi) {
+    lo = x * y;
+    hi = wgt_umulhi(x, y);
+    if (x_signed && (x >> 63)) hi -= y;
+    if (y_signed && (y >> 63)) hi -= x;
+}
 // one column of a top-k call (sb_topk_columns, sb_topk.h), next to its AggCol, whose slots it uses.  A slot is a header and
 // `kmax` records (the call's largest k), record i of slot s at index s * kmax + i; the headers are zeroed, the records
 // are not, and a record is read only below its header's n.

@@ -3128,6 +3128,7 @@ static void launch_lzg(sb_ctx* ctx, const DecodeArgs& a, bool lzg_on, InflateJob
 #include "sb_aggregate.h"
 #include "sb_aggregate_grouped.h"
 #include "sb_aggregate_grouped_large.h"
+#include "sb_aggregate_weighted.h"
 #include "sb_topk.h"
 #include "sb_key_ids.h"
 #include "sb_key_ids_bin.h"
@@ -3137,7 +3138,7 @@ namespace sb {
 
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
                    const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp, const InCol* icols, const TopkLaunch* topk,
-                   const KeyLaunch* keys, const KeyVarLaunch* keyv, const GrpLaunch* grpl, const LookLaunch* look) {
+                   const KeyLaunch* keys, const KeyVarLaunch* keyv, const GrpLaunch* grpl, const LookLaunch* look, const WgtLaunch* wgt) {
     hipStream_t s = ctx->stream;
     (void)hipMemsetAsync(a.job_counts, 0, 16 * sizeof(uint32_t), s);
     const bool qa = !(a.read_skips & RSKIP_QUEUE_A);
@@ -3234,6 +3235,10 @@ void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_p
     }
     if (grpl) {   // sb_aggregate_grouped_large: ... with a table per chunk of 16 tiles
         launch_grpl(ctx, a, *grpl);
+        return;
+    }
+    if (wgt) {   // sb_aggregate_weighted: ... of the sums of y * w
+        launch_wgt(ctx, a, *wgt);
         return;
     }
     if (topk) {   // sb_topk_columns: ... to the k best rows per column

@@ -31,6 +31,7 @@ struct StageSlot {
 //   AGG_COL     sb_column_aggregate*          64 bytes: the result record (AGG_RESULT_WORDS; word 7: the column met a Freq page)  0   -
 //   AGG_GRP_COL sb_column_aggregate_grouped*  64 bytes { selected, out_of_range }, then 64 per group  0       of header + groups
 //   AGG_GRPL_COL  the same, of an sb_aggregate_grouped_large call (a kind of its own: the Freq marks of the two calls are kept apart)
+//   AGG_WGT_COL sb_column_aggregate_weighted*  the same record, of an sb_aggregate_weighted call (its own struct, its own Freq marks)
 //   TOPK_COL    sb_column_topk*               64 bytes { selected, count, nans, found }, then 16 per entry of `out`  0   of header + kmax entries
 //   KEY_COL     sb_column_key_ids*            64 bytes { selected, count, n_keys, overflow }, then 8 per slot of `keys`  0   of header + kmax slots
 //   KEY_VAR_COL sb_column_key_ids_var*        64 bytes { selected, count, n_keys, overflow, keys_len }, then kmax + 1 offsets, then the keys' bytes  0   of the record
@@ -42,7 +43,7 @@ struct StageSlot {
 //   NESTED_R    sb_nested_levels_read[n]      the page records of an enqueued level call  items           of the records
 // (acquire_slot sizes what it moves out of a recycled slot by this table)
 struct Pending {
-    enum Kind { READ_COL, WRITE_COL, ENC_HINT, NESTED_W, NESTED_R, FILTER_COL, RSEL_COL, RSEL_VAR_COL, AGG_COL, AGG_GRP_COL, AGG_GRPL_COL, TOPK_COL, KEY_COL, KEY_VAR_COL, COMB_ITEM, KEY_LOOK_COL } kind;
+    enum Kind { READ_COL, WRITE_COL, ENC_HINT, NESTED_W, NESTED_R, FILTER_COL, RSEL_COL, RSEL_VAR_COL, AGG_COL, AGG_GRP_COL, AGG_GRPL_COL, TOPK_COL, KEY_COL, KEY_VAR_COL, COMB_ITEM, KEY_LOOK_COL, AGG_WGT_COL } kind;
     void* user;
     const uint8_t* host;
     uint64_t n;
@@ -107,6 +108,7 @@ struct sb_ctx {
     sb::DevBuf combine;  // sb_key_combine: the call's descriptors, results, states, tables and sorted codes
     sb::DevBuf filter_stage;   // sb_filter_columns: where the inflate queues put the values of LZ4 / Zstd / Snappy / Patas pages (no caller's buffer to inflate into)
     std::vector<const void*> agg_freq_users;   // ... the same for the sb_column_aggregate structs of sb_aggregate_columns calls
+    std::vector<const void*> wgt_freq_users;   // ... the same for the columns of sb_aggregate_weighted calls
     std::vector<const void*> grpl_freq_users;  // ... the same for the columns of sb_aggregate_grouped_large calls
     std::vector<const void*> grp_freq_users;   // during a replay: the sb_column_aggregate_grouped structs whose column met a Freq page in the first pass
     bool filter_freq = false;  // replay of an interval in which a filter or selected-read call met a Freq page: such calls decode into filter_stage first
@@ -244,7 +246,7 @@ struct sb_ctx {
     // never a one-workgroup walk over a million-row page.  (The callers' column arrays and buffers live until the
     // synchronize anyway: the results are written into them there.)
     struct Call {
-        enum Kind { READ, WRITE, FILTER, FILTER_VAR, FILTER_IN, READ_SEL, READ_SEL_VAR, AGGREGATE, AGG_GROUPED, AGG_GROUPED_LARGE, TOPK, KEY_IDS, KEY_IDS_VAR, KEY_COMBINE, SIZES, KEY_LOOKUP } kind;   // sb_read_columns, sb_write_columns, sb_filter_columns, sb_filter_columns_var, sb_filter_columns_in, sb_read_selected, sb_read_selected_var, sb_aggregate_columns, sb_aggregate_grouped, sb_aggregate_grouped_large, sb_topk_columns, sb_key_ids, sb_key_ids_var, sb_key_combine, sb_read_columns_sizes (its enqueue: the call's own synchronize may be the one that replays), sb_key_lookup
+        enum Kind { READ, WRITE, FILTER, FILTER_VAR, FILTER_IN, READ_SEL, READ_SEL_VAR, AGGREGATE, AGG_GROUPED, AGG_GROUPED_LARGE, TOPK, KEY_IDS, KEY_IDS_VAR, KEY_COMBINE, SIZES, KEY_LOOKUP, AGG_WEIGHTED } kind;   // sb_read_columns, sb_write_columns, sb_filter_columns, sb_filter_columns_var, sb_filter_columns_in, sb_read_selected, sb_read_selected_var, sb_aggregate_columns, sb_aggregate_grouped, sb_aggregate_grouped_large, sb_topk_columns, sb_key_ids, sb_key_ids_var, sb_key_combine, sb_read_columns_sizes (its enqueue: the call's own synchronize may be the one that replays), sb_key_lookup, sb_aggregate_weighted
         void* cols;
         uint64_t n;
         sb_write_options opts;
@@ -357,6 +359,7 @@ inline int32_t reissue(sb_ctx* ctx, sb_ctx::Call& cl) {
         case sb_ctx::Call::AGGREGATE: return sb_aggregate_columns(ctx, (sb_column_aggregate*)cl.cols, cl.n, cl.mem);
         case sb_ctx::Call::AGG_GROUPED: return sb_aggregate_grouped(ctx, (sb_column_aggregate_grouped*)cl.cols, cl.n, cl.mem);
         case sb_ctx::Call::AGG_GROUPED_LARGE: return sb_aggregate_grouped_large(ctx, (sb_column_aggregate_grouped*)cl.cols, cl.n, cl.mem);
+        case sb_ctx::Call::AGG_WEIGHTED: return sb_aggregate_weighted(ctx, (sb_column_aggregate_weighted*)cl.cols, cl.n, cl.mem);
         case sb_ctx::Call::TOPK: return sb_topk_columns(ctx, (sb_column_topk*)cl.cols, cl.n, cl.mem);
         case sb_ctx::Call::KEY_IDS: return sb_key_ids(ctx, (sb_column_key_ids*)cl.cols, cl.n, cl.mem);
         case sb_ctx::Call::KEY_IDS_VAR: return sb_key_ids_var(ctx, (sb_column_key_ids_var*)cl.cols, cl.n, cl.mem);

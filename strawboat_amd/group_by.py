@@ -61,9 +61,9 @@ class GroupKeys:
         return "GroupKeys(n_keys=%d, overflow=%r, parts=%r)" % (self.n_keys, self.overflow, self.parts)
 
 
-def _group_by_composite(ctx, keys, values, selection, ops, max_keys):
-    """group_by for a list of 2 .. 4 key columns: the integer parts in one key_ids call, the Binary / Utf8 parts in one
-    key_ids_var call, then key_combine and the aggregate call, all in the open interval"""
+def _composite_keys(ctx, keys, selection, max_keys):
+    """the keys of a list of 2 .. 4 key columns: the integer parts in one key_ids call, the Binary / Utf8 parts in one
+    key_ids_var call, then key_combine, all in the open interval"""
     keys = list(keys)
     if not 2 <= len(keys) <= MAX_PARTS:
         raise ValueError("group_by takes one key column or a list of 2 .. %d, not %d" % (MAX_PARTS, len(keys)))
@@ -82,11 +82,17 @@ def _group_by_composite(ctx, keys, values, selection, ops, max_keys):
     if strs:
         for i, r in zip(strs, key_ids_var(ctx, [keys[i] for i in strs], selection, max_keys=max_keys)):
             parts[i] = r
-    kres = GroupKeys(parts, key_combine(ctx, parts, max_keys=max_keys))
-    if not values:
-        return kres, []
-    call = aggregate_grouped if max_keys <= MAX_GROUPS else aggregate_grouped_large
-    return kres, call(ctx, list(values), kres.ids, max_keys, selection, ops)
+    return GroupKeys(parts, key_combine(ctx, parts, max_keys=max_keys))
+
+
+def _keys_of(ctx, key, selection, max_keys):
+    """the key call(s) of group_by / group_by_weighted, enqueued: a KeyIds, a KeyIdsVar or (a key list) a GroupKeys"""
+    if isinstance(key, (list, tuple)):
+        return _composite_keys(ctx, key, selection, max_keys)
+    check_group_by(key.physical_type, max_keys)
+    if key.physical_type in INTEGER_TYPES:
+        return key_ids(ctx, [key], selection, max_keys=int(max_keys))[0]
+    return key_ids_var(ctx, [key], selection, max_keys=int(max_keys))[0]
 
 
 def group_by(ctx, key, values: List[ColumnPages], selection=None,
@@ -97,18 +103,27 @@ def group_by(ctx, key, values: List[ColumnPages], selection=None,
 
     `key` may also be a list or tuple of 2 .. 4 ColumnPages, integer and Binary / Utf8 mixed (GROUP BY a, b): the
     keys result is then a GroupKeys, whose `keys` are tuples of the columns' values in ascending order."""
-    if isinstance(key, (list, tuple)):
-        return _group_by_composite(ctx, key, values, selection, ops, max_keys)
-    check_group_by(key.physical_type, max_keys)
+    kres = _keys_of(ctx, key, selection, max_keys)
     max_keys = int(max_keys)
-    if key.physical_type in INTEGER_TYPES:
-        kres = key_ids(ctx, [key], selection, max_keys=max_keys)[0]
-    else:
-        kres = key_ids_var(ctx, [key], selection, max_keys=max_keys)[0]
     if not values:
         return kres, []
     call = aggregate_grouped if max_keys <= MAX_GROUPS else aggregate_grouped_large
     return kres, call(ctx, list(values), kres.ids, max_keys, selection, ops)
+
+
+def group_by_weighted(ctx, key, values: List[ColumnPages], weights, selection=None, max_keys: int = N.SB_KEY_MAX_KEYS,
+                      square: bool = False) -> Tuple[object, List[GroupedAggregate]]:
+    """SELECT k, count(y), sum(y * w) ... WHERE ... GROUP BY k: group_by's key chain (`key` one column or a list of
+    2 .. 4), then `aggregate_weighted` of every column of `values` with its entry of `weights` (None with
+    square=True: sum(y * y)), in the open interval.  Returns what group_by returns; `trim` cuts the groups behind
+    n_keys off."""
+    from .aggregate_weighted import WeightedAggregateBatch, check_weights
+    values = list(values)
+    check_weights(ctx, values, weights, square)   # (before a key call is made)
+    kres = _keys_of(ctx, key, selection, max_keys)
+    if not values:
+        return kres, []
+    return kres, WeightedAggregateBatch(ctx, values, weights, kres.ids, int(max_keys), selection, ("count", "sum"), square).enqueue()
 
 
 def group_by_keys(ctx, key: ColumnPages, key_values, values: List[ColumnPages], selection=None,
