@@ -1024,6 +1024,90 @@ typedef struct sb_column_key_lookup {
 
 int32_t sb_key_lookup(sb_ctx* ctx, sb_column_key_lookup* cols, uint64_t n, int32_t mem);
 
+/* ------------------------------------------------------------------ range-bucket ids of a numeric key column
+ * GROUP BY date_trunc('month', d) over a Date32 or timestamp column; price, age or latency bands (CASE WHEN x < 10 ..,
+ * width_bucket); histograms; any GROUP BY over a Float32 / Float64 column.  The key calls above are equality; here a row's
+ * id says WHERE its value falls.  The pages of a numeric key column, (optionally) a selection bitmap and up to
+ * SB_BUCKET_MAX_BOUNDS bounds on the HOST go in; every row gets the id of its bucket.  One walk over the pages, the walk of
+ * sb_key_lookup with the lower bound kept.
+ *
+ *   live rows     a row is live if its selection bit is set and it is not null, exactly as for sb_key_lookup; rows /
+ *                 selected / count mean what they mean there.  All `rows` ids are written.
+ *   bounds        n_bounds (0 .. SB_BUCKET_MAX_BOUNDS) values of the column's width back to back, strictly increasing under
+ *                 the column's comparison: integers by value with the type's signedness, floats by IEEE value with
+ *                 -0.0 == +0.0 (so { -0.0, +0.0 } is not increasing).  -inf and +inf are bounds like any other; a NaN
+ *                 bound is refused.
+ *   bucket of x   b(x) = the number of bounds <= x: bucket 0 is below bounds[0], bucket i is [bounds[i - 1], bounds[i]),
+ *                 bucket n_bounds is [bounds[n_bounds - 1], ..).  With SB_BUCKET_RIGHT_CLOSED in `flags`, b(x) = the number
+ *                 of bounds < x: bucket i is (bounds[i - 1], bounds[i]].  n_bounds == 0: every value is in bucket 0.
+ *   ids           a live row that is not a NaN gets bucket_ids[b(x)], or b(x) when bucket_ids is null.  bucket_ids has
+ *                 n_bounds + 1 entries; several buckets may share an id; an entry equal to SB_KEY_ID_NONE means "no id"
+ *                 (to drop the open-ended buckets, for instance); every other entry is below all ones of id_width, and so
+ *                 is n_bounds when bucket_ids is null.
+ *   NaN           a live NaN of either sign and any payload gets nan_id truncated to id_width; nan_id == SB_KEY_ID_NONE
+ *                 means all ones, any other nan_id is below all ones of id_width.  For integer columns nan_id must be
+ *                 SB_KEY_ID_NONE.  Every live NaN is counted in `nans`.
+ *   other rows    a row that is not selected, a null row (whatever bytes the page stores for it) and a live row whose
+ *                 bucket is mapped to "no id" get all ones of id_width.
+ *   matched       the live rows whose id is not all ones; a NaN row with a real nan_id counts.
+ *   determinism   the ids are a function of the pages, the selection and the struct alone: the same bytes every time the
+ *                 call is issued, a replayed interval included; count, matched and nans are sums of integers.
+ *   cost          one search per run of an RLE page, one per dictionary entry of a Dict page, one per OneValue tile, one
+ *                 per row elsewhere.  A tile of 4096 rows without a selected row loads no value.
+ *
+ * Types: INT8..INT64, UINT8..UINT64, FLOAT32, FLOAT64; the columns of a call may mix them, each with its own id_width.
+ *
+ * Refused at the call, nothing enqueued and no result field or byte of `ids` touched: Binary, Boolean, Int128 / Int256,
+ * Null and SB_MEM_HOST (SB_ERR_NYI); id_width not 1 / 2 / 4, `ids` null with rows > 0, misaligned or smaller than
+ * rows * id_width, reserved0 or reserved != 0, two columns of one call whose `ids` overlap, an unknown flags bit, n_bounds
+ * above SB_BUCKET_MAX_BOUNDS, bounds null with n_bounds > 0, bounds that are not strictly increasing or hold a NaN, an id
+ * that does not fit id_width, nan_id set on an integer column (SB_ERR_INVALID); every argument refusal of
+ * sb_aggregate_columns, with its code.
+ *
+ * Enqueued like sb_key_lookup and part of its synchronize interval in the same way, as a call of its own kind: on a replay
+ * it is issued again in its place.  A column with a Freq page asks for that replay itself and is then served from the
+ * decoded column.  `selection`, `bounds` and `bucket_ids` are INPUTS: they stay valid and unmodified until the
+ * synchronize.  Page errors are the decoder's, with its codes, at the synchronize (a Float32 Patas page among them, as for
+ * sb_read_columns); `rows` and `selected` are delivered even when the interval failed, the other results and `ids` are
+ * unspecified then.  The call consults no launch hint of the read path and leaves its counters alone.
+ *
+ * Layout (pinned by tests/test_key_buckets_host.py): sb_column_key_buckets 168 bytes; physical_type 0, is_nullable 4,
+ * pages 8, pages_len 16, metas 24, n_pages 32, page_offsets 40, selection 48, selection_capacity 56, ids 64,
+ * ids_capacity 72, id_width 80, flags 84, bounds 88, bucket_ids 96, n_bounds 104, nan_id 112, reserved0 116,
+ * reserved 120, rows 128, selected 136, count 144, matched 152, nans 160. */
+#define SB_BUCKET_MAX_BOUNDS 1023u    /* 1024 buckets == SB_AGG_LARGE_MAX_GROUPS */
+#define SB_BUCKET_RIGHT_CLOSED 1u     /* flags bit 0 */
+
+typedef struct sb_column_key_buckets {
+    int32_t physical_type;   /* INT8..INT64, UINT8..UINT64, FLOAT32, FLOAT64 */
+    int32_t is_nullable;
+    const uint8_t* pages;    /* DEVICE, at any byte alignment */
+    uint64_t pages_len;
+    const sb_page_meta* metas; /* HOST */
+    uint64_t n_pages;
+    const uint64_t* page_offsets; /* optional (HOST), as in sb_column_read */
+    const uint8_t* selection;     /* DEVICE, input: as in sb_column_key_ids; NULL = every row */
+    uint64_t selection_capacity;
+    void* ids;               /* DEVICE, output: one id per row, aligned to id_width */
+    uint64_t ids_capacity;   /* >= rows * id_width bytes */
+    uint32_t id_width;       /* 1, 2 or 4 */
+    uint32_t flags;          /* SB_BUCKET_RIGHT_CLOSED or 0 */
+    const uint8_t* bounds;         /* HOST: n_bounds values of the column's width, strictly increasing */
+    const uint32_t* bucket_ids;    /* HOST, optional: n_bounds + 1 ids; NULL = the bucket's number */
+    uint64_t n_bounds;       /* 0 .. SB_BUCKET_MAX_BOUNDS */
+    uint32_t nan_id;         /* the id of a live NaN; SB_KEY_ID_NONE = all ones (required for integer columns) */
+    uint32_t reserved0;      /* must be 0 */
+    uint64_t reserved;       /* must be 0 */
+    /* results (HOST, valid after sb_ctx_synchronize) */
+    uint64_t rows;           /* sum of num_values */
+    uint64_t selected;       /* bits set in `selection` below `rows` (== rows without a selection) */
+    uint64_t count;          /* selected rows that are not null */
+    uint64_t matched;        /* ... whose id is not all ones */
+    uint64_t nans;           /* ... that are NaN */
+} sb_column_key_buckets;     /* 168 bytes */
+
+int32_t sb_key_buckets(sb_ctx* ctx, sb_column_key_buckets* cols, uint64_t n, int32_t mem);
+
 /* ------------------------------------------------------------------ encode
  * Replaces, per leaf column, the page loop of NativeWriter::encode_chunk
  * (src/write/common.rs:54-109): page slicing, then per page write::write -> write_simple

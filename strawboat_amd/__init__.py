@@ -20,10 +20,11 @@ from .topk import TopK, TopKBatch, selection_of_rows, topk_columns  # noqa: F401
 from .key_ids import KeyIds, KeyIdsBatch, key_ids  # noqa: F401
 from .key_ids_var import KeyIdsVar, KeyIdsVarBatch, key_ids_var  # noqa: F401
 from .key_lookup import KeyLookup, KeyLookupBatch, key_lookup  # noqa: F401
+from .key_buckets import KeyBuckets, KeyBucketsBatch, key_buckets  # noqa: F401
 from .key_combine import KeyCombine, KeyCombineBatch, key_combine  # noqa: F401
-from .group_by import GroupKeys, group_by, group_by_keys, group_by_weighted  # noqa: F401
+from .group_by import GroupKeys, Histogram, group_by, group_by_buckets, group_by_keys, histogram, group_by_weighted  # noqa: F401
 
 __all__ = ["Context", "read", "write", "filter", "Predicate", "Selection", "filter_columns", "like_predicate", "InList", "FilterInBatch", "filter_in", "read_selected", "ReadSelectedBatch", "SelectedArray",
            "read_selected_var", "ReadSelectedVarBatch", "SelectedBinaryArray", "aggregate_columns", "AggregateBatch", "Aggregate",
-           "aggregate_grouped", "GroupedAggregateBatch", "GroupedAggregate", "aggregate_grouped_large", "GroupedAggregateLargeBatch", "aggregate_weighted", "WeightedAggregateBatch", "group_by", "group_by_weighted", "topk_columns", "TopKBatch", "TopK", "selection_of_rows", "key_ids", "KeyIdsBatch", "KeyIds", "key_ids_var", "KeyIdsVarBatch", "KeyIdsVar", "key_combine", "KeyCombineBatch", "KeyCombine", "GroupKeys", "key_lookup", "KeyLookupBatch", "KeyLookup", "group_by_keys", "WriteOptions", "PageMeta", "ColumnMeta", "Compression",
+           "aggregate_grouped", "GroupedAggregateBatch", "GroupedAggregate", "aggregate_grouped_large", "GroupedAggregateLargeBatch", "aggregate_weighted", "WeightedAggregateBatch", "group_by", "group_by_weighted", "topk_columns", "TopKBatch", "TopK", "selection_of_rows", "key_ids", "KeyIdsBatch", "KeyIds", "key_ids_var", "KeyIdsVarBatch", "KeyIdsVar", "key_combine", "KeyCombineBatch", "KeyCombine", "GroupKeys", "key_lookup", "KeyLookupBatch", "KeyLookup", "group_by_keys", "key_buckets", "KeyBucketsBatch", "KeyBuckets", "group_by_buckets", "histogram", "Histogram", "WriteOptions", "PageMeta", "ColumnMeta", "Compression",
            "CommonCompression", "PhysicalType"]

@@ -25,7 +25,7 @@ EXPORTS = ("sb_version", "sb_ctx_create", "sb_ctx_destroy", "sb_ctx_synchronize"
            "sb_schema_metadata_from_bytes", "sb_filter_columns", "sb_filter_columns_var", "sb_read_selected",
            "sb_read_selected_var", "sb_aggregate_columns", "sb_aggregate_grouped", "sb_filter_columns_in",
            "sb_topk_columns", "sb_key_ids", "sb_key_ids_var", "sb_aggregate_grouped_large",
-           "sb_key_combine", "sb_key_lookup", "sb_aggregate_weighted")
+           "sb_key_combine", "sb_key_lookup", "sb_aggregate_weighted", "sb_key_buckets")
 
 SB_PRED_EQ, SB_PRED_NE, SB_PRED_LT, SB_PRED_LE, SB_PRED_GT, SB_PRED_GE, SB_PRED_IS_NULL, SB_PRED_IS_NOT_NULL = range(8)
 SB_PRED_STARTS_WITH = 8   # binary types only (sb_filter_columns_var)
@@ -42,6 +42,8 @@ SB_TOPK_MAX_K = 256
 SB_TOPK_SMALLEST, SB_TOPK_LARGEST = 0, 1
 SB_KEY_MAX_KEYS = 1024
 SB_KEY_ID_NONE = 0xFFFFFFFF
+SB_BUCKET_MAX_BOUNDS = 1023       # sb_key_buckets: 1024 buckets == SB_AGG_LARGE_MAX_GROUPS
+SB_BUCKET_RIGHT_CLOSED = 1        # ... flags bit 0: bucket i is (bounds[i - 1], bounds[i]]
 SB_KEY_VAR_MAX_BYTES = 1 << 20
 SB_KEY_OVERFLOW_KEYS, SB_KEY_OVERFLOW_BYTES = 1, 2
 SB_KEY_COMBINE_MAX_PARTS = 4
@@ -199,6 +201,17 @@ class ColumnKeyLookupC(C.Structure):
                 ("rows", C.c_uint64), ("selected", C.c_uint64), ("count", C.c_uint64), ("matched", C.c_uint64)]
 
 
+class ColumnKeyBucketsC(C.Structure):
+    _fields_ = [("physical_type", C.c_int32), ("is_nullable", C.c_int32), ("pages", C.c_void_p),
+                ("pages_len", C.c_uint64), ("metas", C.POINTER(PageMetaC)), ("n_pages", C.c_uint64),
+                ("page_offsets", C.c_void_p), ("selection", C.c_void_p), ("selection_capacity", C.c_uint64),
+                ("ids", C.c_void_p), ("ids_capacity", C.c_uint64), ("id_width", C.c_uint32), ("flags", C.c_uint32),
+                ("bounds", C.c_void_p), ("bucket_ids", C.c_void_p), ("n_bounds", C.c_uint64),
+                ("nan_id", C.c_uint32), ("reserved0", C.c_uint32), ("reserved", C.c_uint64),
+                ("rows", C.c_uint64), ("selected", C.c_uint64), ("count", C.c_uint64), ("matched", C.c_uint64),
+                ("nans", C.c_uint64)]
+
+
 class ColumnWriteC(C.Structure):
     _fields_ = [("physical_type", C.c_int32), ("is_nullable", C.c_int32), ("rows", C.c_uint64),
                 ("values", C.c_void_p), ("values_bit_offset", C.c_uint64), ("values_len", C.c_uint64),
@@ -302,6 +315,8 @@ def load():
     L.sb_aggregate_grouped.argtypes = [C.c_void_p, C.POINTER(ColumnAggregateGroupedC), C.c_uint64, C.c_int32]
     L.sb_aggregate_grouped_large.restype = C.c_int32
     L.sb_aggregate_grouped_large.argtypes = [C.c_void_p, C.POINTER(ColumnAggregateGroupedC), C.c_uint64, C.c_int32]
+    L.sb_key_buckets.restype = C.c_int32
+    L.sb_key_buckets.argtypes = [C.c_void_p, C.POINTER(ColumnKeyBucketsC), C.c_uint64, C.c_int32]
     L.sb_aggregate_weighted.restype = C.c_int32
     L.sb_aggregate_weighted.argtypes = [C.c_void_p, C.POINTER(ColumnAggregateWeightedC), C.c_uint64, C.c_int32]
     L.sb_topk_columns.restype = C.c_int32

@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "sb_host.h"
+#include "sb_key_buckets_prep.h"
 #include "sb_key_lookup_prep.h"
 #include "sb_span.h"
 
@@ -14,7 +15,11 @@ namespace sb {
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
                    const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp = nullptr, const InCol* icols = nullptr,
                    const TopkLaunch* topk = nullptr, const KeyLaunch* keys = nullptr, const KeyVarLaunch* keyv = nullptr,
-                   const GrpLaunch* grpl = nullptr, const LookLaunch* look = nullptr, const WgtLaunch* wgt = nullptr);
+                   const GrpLaunch* grpl = nullptr, const LookLaunch* look = nullptr, const WgtLaunch* wgt = nullptr,
+                   const BuckLaunch* buck = nullptr);
+void launch_buck_zero(sb_ctx* ctx, const BuckLaunch& bl);
+void launch_buck_finish(sb_ctx* ctx, const BuckLaunch& bl, uint64_t* results);
+void launch_key_buckets_plain(sb_ctx* ctx, const BuckLaunch& bl, const uint64_t* rows, const uint8_t* const* values, const uint8_t* const* validity);
 void launch_look_zero(sb_ctx* ctx, const LookLaunch& ll);
 void launch_look_finish(sb_ctx* ctx, const LookLaunch& ll, uint64_t* results);
 void launch_key_lookup_plain(sb_ctx* ctx, const LookLaunch& ll, const uint64_t* rows, const uint8_t* const* values, const uint8_t* const* validity);
@@ -126,7 +131,7 @@ StageSlot* acquire_slot(sb_ctx* ctx, size_t need) {
     if (s.host)
         for (auto& p : ctx->iv.pending) {
             if (p.host < s.host || p.host >= s.host + s.cap) continue;
-            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::AGG_COL ? AGG_RESULT_WORDS * 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R || p.kind == Pending::AGG_GRP_COL || p.kind == Pending::AGG_GRPL_COL || p.kind == Pending::AGG_WGT_COL || p.kind == Pending::TOPK_COL || p.kind == Pending::KEY_COL || p.kind == Pending::KEY_VAR_COL || p.kind == Pending::COMB_ITEM || p.kind == Pending::KEY_LOOK_COL) ? (size_t)p.bytes
+            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::AGG_COL ? AGG_RESULT_WORDS * 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R || p.kind == Pending::AGG_GRP_COL || p.kind == Pending::AGG_GRPL_COL || p.kind == Pending::AGG_WGT_COL || p.kind == Pending::TOPK_COL || p.kind == Pending::KEY_COL || p.kind == Pending::KEY_VAR_COL || p.kind == Pending::COMB_ITEM || p.kind == Pending::KEY_LOOK_COL || p.kind == Pending::KEY_BUCKET_COL) ? (size_t)p.bytes
                                                                                                    : (size_t)(2 * p.n + 1) * 8;
             ctx->iv.rescued.emplace_back(p.host, p.host + nb);
             p.host = ctx->iv.rescued.back().data();
@@ -267,7 +272,8 @@ struct ReadMode {
     // / sb_key_ids, an aggregate call whose columns end in the key kernels: two walks, the finish between them
     // / sb_key_ids_var, the same for binary columns, whose value blocks are staged as a filter call stages them
     // / sb_key_lookup, an aggregate call whose columns end in the lookup kernels: one walk, numeric and binary columns alike
-    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR, AGGREGATE, AGG_GROUPED, AGG_GROUPED_LARGE, TOPK, KEY_IDS, KEY_IDS_VAR, KEY_LOOKUP, AGG_WEIGHTED } kind;
+    // / sb_key_buckets, an aggregate call whose columns end in the bucket kernels: the same walk over numeric columns
+    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR, AGGREGATE, AGG_GROUPED, AGG_GROUPED_LARGE, TOPK, KEY_IDS, KEY_IDS_VAR, KEY_LOOKUP, AGG_WEIGHTED, KEY_BUCKETS } kind;
     const FilterCol* filt = nullptr;             // FILTER: one per column
     const std::vector<uint8_t>* lits = nullptr;  // ... the literals of the FK_BYTES columns, FilterCol.lit being the offset of each
     bool in_list = false;                        // ... sb_filter_columns_in: `lits` begins with an InCol per column, whose pointers are offsets in `lits`
@@ -287,12 +293,13 @@ struct ReadMode {
     const KeyVarCol* keyvc = nullptr;            // KEY_IDS_VAR: one per column beside aggc (key_kmax and key_slots as above)
     uint64_t key_kbytes = 0;                     // ... the largest keys_capacity of the call: bytes per result
     const LookCol* lookc = nullptr;              // KEY_LOOKUP: one per column beside aggc, whose pointers are offsets in `lits` (the lists)
+    const BuckCol* buckc = nullptr;              // KEY_BUCKETS: one per column beside aggc, whose pointers are offsets in `lits` (the bounds and ids)
     // Where a column's result goes at the synchronize, as Pending has it (sb_host.h): users[i] beside pending_kind.  Set by
     // the entry points of the sinks: the callers' structs, for a filter call the caller's `selected` (results[i] + 1).
     // Null for the other kinds of call, whose results go to the sb_column_read structs of the call itself.
     void* const* users = nullptr;
     Pending::Kind pending_kind = Pending::READ_COL;
-    bool aggregate() const { return kind == AGGREGATE || kind == AGG_GROUPED || kind == AGG_GROUPED_LARGE || kind == AGG_WEIGHTED || kind == TOPK || kind == KEY_IDS || kind == KEY_IDS_VAR || kind == KEY_LOOKUP; }   // an AggCol per column, slots per page part and tile
+    bool aggregate() const { return kind == AGGREGATE || kind == AGG_GROUPED || kind == AGG_GROUPED_LARGE || kind == AGG_WEIGHTED || kind == TOPK || kind == KEY_IDS || kind == KEY_IDS_VAR || kind == KEY_LOOKUP || kind == KEY_BUCKETS; }   // an AggCol per column, slots per page part and tile
     bool grouped() const { return kind == AGG_GROUPED || kind == AGG_GROUPED_LARGE || kind == AGG_WEIGHTED; }   // a GrpCol per column, flags and gmax records per slot
     bool grouped_large() const { return kind == AGG_GROUPED_LARGE || kind == AGG_WEIGHTED; }   // ... whose tile slots are a slot per chunk of GRPL_CHUNK_TILES tiles
     bool weighted() const { return kind == AGG_WEIGHTED; }                            // ... and a WgtCol per column behind the GrpCols
@@ -300,6 +307,7 @@ struct ReadMode {
     bool key_ids() const { return kind == KEY_IDS; }
     bool key_var() const { return kind == KEY_IDS_VAR; }
     bool key_lookup() const { return kind == KEY_LOOKUP; }
+    bool key_buckets() const { return kind == KEY_BUCKETS; }
     bool bin_id_tables() const { return kind == KEY_IDS_VAR || kind == KEY_LOOKUP; }   // a 16-bit id table and a bit table per binary Dict / Freq page
     bool filter() const { return kind == FILTER; }
     bool selected() const { return kind == SELECTED; }
@@ -314,7 +322,7 @@ struct ReadMode {
     // an AGGREGATE call, the header and the gmax group records of an AGG_GROUPED call, the header and the kmax entries of
     // a TOPK call, the header and the kmax key slots of a KEY_IDS call, the header, offsets and bytes of a KEY_IDS_VAR call
     uint64_t result_words() const {
-        return kind == SELECTED_VAR ? 2 : kind == AGGREGATE ? AGG_RESULT_WORDS : grouped() ? grp_result_words(grp_gmax) : kind == TOPK ? topk_result_words(topk_kmax) : kind == KEY_IDS ? key_result_words(key_kmax) : kind == KEY_IDS_VAR ? keyv_result_words(key_kmax, key_kbytes) : kind == KEY_LOOKUP ? LOOK_RESULT_WORDS : 1;
+        return kind == SELECTED_VAR ? 2 : kind == AGGREGATE ? AGG_RESULT_WORDS : grouped() ? grp_result_words(grp_gmax) : kind == TOPK ? topk_result_words(topk_kmax) : kind == KEY_IDS ? key_result_words(key_kmax) : kind == KEY_IDS_VAR ? keyv_result_words(key_kmax, key_kbytes) : kind == KEY_LOOKUP ? LOOK_RESULT_WORDS : kind == KEY_BUCKETS ? BUCK_RESULT_WORDS : 1;
     }
 };
 static int32_t read_columns_impl(sb_ctx* ctx, sb_column_read* cols, uint64_t n, int32_t mem, const ReadMode& mode);
@@ -626,6 +634,17 @@ static void deliver_key_look_col(const Pending& p, bool ok) {
     c->count = v[1];
     c->matched = v[2];
 }
+// k_key_buckets_finish's record (sb_key_buckets.h); `ok` false: the interval failed, selected alone
+static void deliver_key_bucket_col(const Pending& p, bool ok) {
+    uint64_t v[BUCK_RESULT_WORDS];
+    memcpy(v, p.host, sizeof v);
+    sb_column_key_buckets* c = (sb_column_key_buckets*)p.user;
+    c->selected = v[0];
+    if (!ok) return;
+    c->count = v[1];
+    c->matched = v[2];
+    c->nans = v[3];
+}
 // k_key_finish's header and sorted codes of a key-combine item (sb_key_combine.h): { rows, live, n_keys, overflow, 0 .. },
 // then kmax codes, of which the first n_keys are unpacked into `tuples`; a failed interval delivers nothing
 static void deliver_comb_item(const Pending& p, bool ok) {
@@ -683,6 +702,7 @@ static void deliver_pending(sb_ctx* ctx, const Pending& p, int32_t rc) {
         case Pending::KEY_VAR_COL: deliver_key_var_col(p, rc == SB_OK); break;
         case Pending::COMB_ITEM: deliver_comb_item(p, rc == SB_OK); break;
         case Pending::KEY_LOOK_COL: deliver_key_look_col(p, rc == SB_OK); break;
+        case Pending::KEY_BUCKET_COL: deliver_key_bucket_col(p, rc == SB_OK); break;
         case Pending::WRITE_COL: deliver_write_col(p); break;
         case Pending::ENC_HINT:
             if (rc == SB_OK) apply_enc_hint(ctx, p);
@@ -964,6 +984,7 @@ static ReadLayout read_layout(uint64_t n, const ReadShape& sh, const ReadHints& 
     if (mode.key_ids()) off = align_up(off + n * sizeof(KeyCol), 64);   // (likewise)
     if (mode.key_var()) off = align_up(off + n * sizeof(KeyVarCol), 64);   // (likewise)
     if (mode.key_lookup()) off = align_up(off + n * sizeof(LookCol), 64);  // (likewise)
+    if (mode.key_buckets()) off = align_up(off + n * sizeof(BuckCol), 64);  // (likewise)
     L.lits = off;
     if (mode.lits) off = align_up(off + mode.lits->size(), 64);
     L.upload = off;
@@ -999,6 +1020,7 @@ static ReadLayout read_layout(uint64_t n, const ReadShape& sh, const ReadHints& 
     L.aggp = off;   // an AGGREGATE call's partial records: a slot per (page, RLE part), then a slot per tile
     if (mode.kind == ReadMode::AGGREGATE) off = align_up(off + (P * L.rle_parts + sh.T) * sizeof(AggPart), 64);
     if (mode.key_lookup()) off = align_up(off + n * sizeof(LookState), 64);   // a KEY_LOOKUP call: a state per column (zeroed)
+    if (mode.key_buckets()) off = align_up(off + n * sizeof(BuckState), 64);  // a KEY_BUCKETS call: likewise
     // an AGG_GROUPED call: a flag word per slot, a counter and a Freq mark per column (zeroed), then gmax records per slot (not zeroed)
     // (an AGG_GROUPED_LARGE call: the same with a slot per chunk in the tile slots' place)
     const uint64_t grp_tile_slots = mode.grouped_large() ? sh.C : sh.T;
@@ -1161,6 +1183,16 @@ static int32_t fill_read_tables(sb_ctx* ctx, uint8_t* host, const ReadLayout& L,
                 hl[i].keys = (const uint64_t*)(base + (size_t)(uintptr_t)hl[i].keys);
                 hl[i].kid = (const uint32_t*)(base + (size_t)(uintptr_t)hl[i].kid);
                 hl[i].bytes = base + (size_t)(uintptr_t)hl[i].bytes;
+            }
+        }
+        if (mode.key_buckets()) {   // likewise: the bounds and ids travel with the tables
+            BuckCol* hb = (BuckCol*)(host + L.bcols);
+            memcpy(hb, mode.buckc, n * sizeof(BuckCol));
+            if (mode.lits && !mode.lits->empty()) memcpy(host + L.lits, mode.lits->data(), mode.lits->size());
+            const uint8_t* base = ctx->tables.p + L.lits;
+            for (uint64_t i = 0; i < n; i++) {
+                hb[i].keys = (const uint64_t*)(base + (size_t)(uintptr_t)hb[i].keys);
+                hb[i].bid = (const uint32_t*)(base + (size_t)(uintptr_t)hb[i].bid);
             }
         }
     }
@@ -1443,6 +1475,14 @@ static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, 
             launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ll);
         // (a call without a page still has a result: selected, and zeros)
         launch_look_finish(ctx, ll, d_vlen);
+    } else if (mode.key_buckets()) {
+        BuckLaunch bl{(const AggCol*)(ctx->tables.p + L.fcols), (const BuckCol*)(ctx->tables.p + L.bcols), (BuckState*)(ctx->tables.p + L.aggp), (uint32_t)n};
+        launch_buck_zero(ctx, bl);
+        if (sh.P)
+            launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                          nullptr, &bl);
+        // (a call without a page still has a result: selected, and zeros)
+        launch_buck_finish(ctx, bl, d_vlen);
     } else if (mode.aggregate()) {
         AggLaunch al{(const AggCol*)(ctx->tables.p + L.fcols), (AggPart*)(ctx->tables.p + L.aggp), sh.P * L.rle_parts, false, false, ctx->in_replay};
         for (uint64_t i = 0; i < n; i++) ((mode.aggc[i].ops & AGG_VALUE_OPS) ? al.any_val : al.any_null) = true;
@@ -1478,7 +1518,7 @@ static void push_pending(sb_ctx* ctx, Pending::Kind kind, void* const* users, co
         if (kind == Pending::TOPK_COL) pd.bytes = stride;   // (the header and kmax entries: the column's own k is in its struct)
         if (kind == Pending::KEY_COL || kind == Pending::COMB_ITEM) pd.bytes = stride;    // (likewise: the header and kmax key slots / codes)
         if (kind == Pending::KEY_VAR_COL) pd.bytes = stride, pd.n = kmax;   // (the header, kmax + 1 offsets, the bytes)
-        if (kind == Pending::KEY_LOOK_COL) pd.bytes = stride;
+        if (kind == Pending::KEY_LOOK_COL || kind == Pending::KEY_BUCKET_COL) pd.bytes = stride;
         ctx->iv.pending.push_back(pd);
     }
 }
@@ -1629,7 +1669,8 @@ constexpr bool has_pages_prefix() {
 static_assert(offsetof(sb_column_filter, page_offsets) == 40, "the pages of a sink column: 48 bytes");
 static_assert(has_pages_prefix<sb_column_filter_var>() && has_pages_prefix<sb_column_read_selected>() && has_pages_prefix<sb_column_read_selected_var>() &&
                   has_pages_prefix<sb_column_aggregate>() && has_pages_prefix<sb_column_aggregate_grouped>() && has_pages_prefix<sb_column_topk>() &&
-                  has_pages_prefix<sb_column_key_ids>() && has_pages_prefix<sb_column_key_ids_var>() && has_pages_prefix<sb_column_key_lookup>(),
+                  has_pages_prefix<sb_column_key_ids>() && has_pages_prefix<sb_column_key_ids_var>() && has_pages_prefix<sb_column_key_lookup>() &&
+                  has_pages_prefix<sb_column_key_buckets>(),
               "every sink column begins with the seven fields of sb_column_filter, at its offsets");
 
 // The pages of a sink column as a read column (outputs: none yet)
@@ -3236,6 +3277,158 @@ int32_t sb_key_lookup(sb_ctx* ctx, sb_column_key_lookup* cols, uint64_t n, int32
         c.selected = c.count = c.matched = 0;
     }
     if (!ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::KEY_LOOKUP, cols, n, sb_write_options{}, mem});
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------ range-bucket ids
+static_assert(sizeof(sb_column_key_buckets) == 168 && offsetof(sb_column_key_buckets, selection) == 48 &&
+                  offsetof(sb_column_key_buckets, selection_capacity) == 56 && offsetof(sb_column_key_buckets, ids) == 64 &&
+                  offsetof(sb_column_key_buckets, ids_capacity) == 72 && offsetof(sb_column_key_buckets, id_width) == 80 &&
+                  offsetof(sb_column_key_buckets, flags) == 84 && offsetof(sb_column_key_buckets, bounds) == 88 &&
+                  offsetof(sb_column_key_buckets, bucket_ids) == 96 && offsetof(sb_column_key_buckets, n_bounds) == 104 &&
+                  offsetof(sb_column_key_buckets, nan_id) == 112 && offsetof(sb_column_key_buckets, reserved0) == 116 &&
+                  offsetof(sb_column_key_buckets, reserved) == 120 && offsetof(sb_column_key_buckets, rows) == 128 &&
+                  offsetof(sb_column_key_buckets, selected) == 136 && offsetof(sb_column_key_buckets, count) == 144 &&
+                  offsetof(sb_column_key_buckets, matched) == 152 && offsetof(sb_column_key_buckets, nans) == 160,
+              "sb_column_key_buckets: the offsets the header states");
+static_assert(offsetof(sb_column_key_buckets, id_width) == offsetof(sb_column_key_lookup, id_width) &&
+                  offsetof(sb_column_key_buckets, ids_capacity) == offsetof(sb_column_key_lookup, ids_capacity),
+              "the first 84 bytes are sb_column_key_lookup's");
+static_assert(sb_buckets::MAX_BOUNDS == SB_BUCKET_MAX_BOUNDS && SB_BUCKET_MAX_BOUNDS == BUCK_MAX_BOUNDS && SB_BUCKET_MAX_BOUNDS + 1 == SB_AGG_LARGE_MAX_GROUPS &&
+                  sb_buckets::RIGHT_CLOSED == SB_BUCKET_RIGHT_CLOSED && sb_buckets::ID_NONE == SB_KEY_ID_NONE,
+              "the header's limits");
+static_assert(sb_buckets::UNSIGNED == FK_UNSIGNED && sb_buckets::SIGNED == FK_SIGNED && sb_buckets::F32 == FK_F32 && sb_buckets::F64 == FK_F64,
+              "the preparation's kinds are the kernels'");
+
+// The prepared bounds of a column (sb_key_buckets_prep.h) appended to `blob` at a multiple of 8, as [keys | ids]; bc's
+// pointers are offsets in `blob` until the lists have their place on the device.
+static void buck_list_append(const sb_buckets::Prepared& pr, std::vector<uint8_t>& blob, BuckCol* bc) {
+    blob.resize(align_up(blob.size(), 8));
+    bc->keys = (const uint64_t*)(uintptr_t)blob.size();
+    blob.insert(blob.end(), (const uint8_t*)pr.keys.data(), (const uint8_t*)(pr.keys.data() + pr.keys.size()));
+    bc->bid = (const uint32_t*)(uintptr_t)blob.size();
+    blob.insert(blob.end(), (const uint8_t*)pr.ids.data(), (const uint8_t*)(pr.ids.data() + pr.ids.size()));
+    bc->nan_lo = pr.nan_lo;
+    bc->nan_hi = pr.nan_hi;
+    bc->n = pr.n;
+    bc->steps = pr.steps;
+}
+
+// key_lookup_decoded's sibling: the columns of a replayed call searched from the staging area by k_key_buckets_plain
+static int32_t key_buckets_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pages, std::vector<AggCol>& hs, std::vector<BuckCol>& hb,
+                                   const std::vector<uint8_t>& blob, void* const* users) {
+    const uint64_t n = pages.size();
+    std::vector<uint64_t> rows(n);
+    for (uint64_t i = 0; i < n; i++) rows[i] = hs[i].rows;
+    const sb_column_read* rr = nullptr;
+    int32_t rc = decode_for_replay(ctx, std::move(pages), rows.data(), "key buckets", &rr);
+    if (rc != SB_OK) return rc;
+    std::vector<const uint8_t*> vals(n), bits(n);
+    (void)replay_slots(rr, rows, hs, vals, bits);
+    // [AggCol per column][BuckCol per column][the results][the columns' states][the lists]
+    const size_t res_stride = BUCK_RESULT_WORDS * sizeof(uint64_t);
+    size_t off = align_up(n * sizeof(AggCol), 64);
+    const size_t o_bc = off;
+    off = align_up(off + n * sizeof(BuckCol), 64);
+    const size_t o_res = off;
+    off = align_up(off + n * res_stride, 64);
+    const size_t o_state = off;
+    off = align_up(off + n * sizeof(BuckState), 64);
+    const size_t o_lists = off;
+    off += blob.size();
+    uint8_t* dev = nullptr;
+    if (hipMalloc((void**)&dev, off + 64) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(key buckets replay) failed");
+    ctx->iv.temp_dev.push_back(dev);
+    for (BuckCol& bc : hb) {
+        bc.keys = (const uint64_t*)(dev + o_lists + (size_t)(uintptr_t)bc.keys);
+        bc.bid = (const uint32_t*)(dev + o_lists + (size_t)(uintptr_t)bc.bid);
+    }
+    // (copies that have ended when they return: the vectors do not outlive the call)
+    if (hipMemcpy(dev, hs.data(), n * sizeof(AggCol), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dev + o_bc, hb.data(), n * sizeof(BuckCol), hipMemcpyHostToDevice) != hipSuccess ||
+        (!blob.empty() && hipMemcpy(dev + o_lists, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess))
+        return ctx->fail(SB_ERR_EXTERNAL, "key buckets replay: upload failed");
+    StageSlot* slot = acquire_slot(ctx, n * res_stride);
+    if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
+    uint64_t* d_res = (uint64_t*)(dev + o_res);
+    const BuckLaunch bl{(const AggCol*)dev, (const BuckCol*)(dev + o_bc), (BuckState*)(dev + o_state), (uint32_t)n};
+    launch_buck_zero(ctx, bl);
+    launch_key_buckets_plain(ctx, bl, rows.data(), vals.data(), bits.data());
+    launch_buck_finish(ctx, bl, d_res);
+    return queue_sink_results(ctx, slot, d_res, res_stride, n, Pending::KEY_BUCKET_COL, users, nullptr, "key buckets");
+}
+
+int32_t sb_key_buckets(sb_ctx* ctx, sb_column_key_buckets* cols, uint64_t n, int32_t mem) {
+    int32_t rc;
+    if (!sink_entry(ctx, cols, n, mem, "sb_key_buckets", &rc)) return rc;
+    std::vector<AggCol> hs(n);
+    std::vector<uint64_t> cap(n);
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_column_key_buckets& c = cols[i];
+        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(ctx, SB_ERR_INVALID, "bad physical_type");
+        const bool is_int = c.physical_type >= SB_TYPE_INT8 && c.physical_type <= SB_TYPE_UINT64;
+        if (!is_int && c.physical_type != SB_TYPE_FLOAT32 && c.physical_type != SB_TYPE_FLOAT64)
+            return refuse(ctx, SB_ERR_NYI, "key buckets are implemented for 8- to 64-bit integers and floats");
+        if (c.id_width != 1 && c.id_width != 2 && c.id_width != 4) return refuse(ctx, SB_ERR_INVALID, "id_width is not 1, 2 or 4");
+        if (c.reserved0 || c.reserved) return refuse(ctx, SB_ERR_INVALID, "reserved is not 0");
+        const uint32_t kind = value_kind(c.physical_type), w = type_width(c.physical_type);
+        const char* why = sb_buckets::check_bounds(kind, w, c.flags, c.bounds, c.n_bounds);
+        if (!why) why = sb_buckets::check_ids(kind, c.bucket_ids, c.n_bounds, c.id_width, c.nan_id);
+        if (why) return refuse(ctx, SB_ERR_INVALID, why);
+        // (searched like a minimum is taken: every live value is looked at)
+        if ((rc = agg_check_fill(ctx, c, (uint32_t)SB_AGG_MIN, hs[i])) != SB_OK) return rc;
+        const uint64_t rows = hs[i].rows;
+        if (rows && !c.ids) return refuse(ctx, SB_ERR_INVALID, "ids is null");
+        if (c.ids && (((uintptr_t)c.ids & (c.id_width - 1)) || c.ids_capacity < rows * c.id_width))
+            return refuse(ctx, SB_ERR_INVALID, "ids not aligned to id_width or smaller than rows * id_width bytes");
+        cap[i] = rows * w;   // the share of the staging area a filter column has
+    }
+    for (uint64_t i = 0; i < n; i++)   // (the bytes a column writes: rows * id_width)
+        for (uint64_t j = i + 1; j < n; j++) {
+            const uintptr_t a0 = (uintptr_t)cols[i].ids, a1 = a0 + hs[i].rows * cols[i].id_width;
+            const uintptr_t b0 = (uintptr_t)cols[j].ids, b1 = b0 + hs[j].rows * cols[j].id_width;
+            if (a0 < b1 && b0 < a1) return refuse(ctx, SB_ERR_INVALID, "ids of two columns of one call overlap");
+        }
+    // the bounds as the kernels search them, one blob for the call
+    std::vector<BuckCol> hb(n);
+    std::vector<uint8_t> blob;
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_column_key_buckets& c = cols[i];
+        memset(&hb[i], 0, sizeof hb[i]);
+        hb[i].ids = (uint8_t*)c.ids;
+        hb[i].idw = c.id_width;
+        hb[i].right_closed = c.flags & SB_BUCKET_RIGHT_CLOSED;
+        hb[i].nan_id = c.nan_id;
+        buck_list_append(sb_buckets::prepare(hs[i].kind, hs[i].w, c.bounds, c.bucket_ids, c.n_bounds), blob, &hb[i]);
+    }
+    (void)hipSetDevice(ctx->device);
+    std::vector<sb_column_read> rc_cols(n);
+    std::vector<void*> users(n);
+    for (uint64_t i = 0; i < n; i++) {
+        rc_cols[i] = read_col_of(cols[i]);
+        users[i] = &cols[i];
+    }
+    if (ctx->in_replay && ctx->filter_freq) {
+        // Every column through a full decode, as sb_key_lookup has its numeric columns.  The ids are a function of the data
+        // and the struct alone, so the route does not show in them.
+        rc = key_buckets_decoded(ctx, std::move(rc_cols), hs, hb, blob, users.data());
+    } else {
+        if ((rc = stage_shares(ctx, rc_cols.data(), cap.data(), rc_cols.size())) != SB_OK) return rc;
+        ReadMode mode{ReadMode::KEY_BUCKETS};
+        mode.aggc = hs.data();
+        mode.buckc = hb.data();
+        mode.lits = &blob;
+        mode.users = users.data();
+        mode.pending_kind = Pending::KEY_BUCKET_COL;
+        rc = read_columns_impl(ctx, rc_cols.data(), rc_cols.size(), SB_MEM_DEVICE, mode);
+    }
+    if (rc != SB_OK) return rc;
+    for (uint64_t i = 0; i < n; i++) {   // (after the last thing that can refuse the call: a page outside pages_len)
+        sb_column_key_buckets& c = cols[i];
+        column_rows(c, &c.rows);
+        c.selected = c.count = c.matched = c.nans = 0;
+    }
+    if (!ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::KEY_BUCKETS, cols, n, sb_write_options{}, mem});
     return rc;
 }
 

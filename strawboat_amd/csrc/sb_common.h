@@ -407,6 +407,36 @@ struct LookLaunch {   // what launch_decode needs to end a call with the lookup 
     uint32_t n_cols;
     bool any_num, any_bin;
 };
+// one column of a key-buckets call (sb_key_buckets, sb_key_buckets.h), next to its AggCol (of which sel, rows, kind and w are
+// used).  The caller's bounds as order keys (in_key), strictly ascending, and the id of each of the n + 1 buckets: bucket 0
+// below keys[0], bucket i from keys[i - 1] to keys[i].  A float whose order key is below nan_lo or above nan_hi is a NaN
+// (the keys of -inf and +inf); an integer column has 0 and all ones there, which no key is outside of.
+constexpr uint32_t BUCK_MAX_BOUNDS = 1023;   // SB_BUCKET_MAX_BOUNDS: n + 1 <= KEY_MAX_KEYS ids, 4 KiB of LDS
+struct BuckCol {
+    uint8_t* ids;           // the caller's ids: one unsigned integer of `idw` bytes per row of the column (output)
+    const uint64_t* keys;   // n order keys
+    const uint32_t* bid;    // n + 1 ids, each below all ones of `idw` or 0xFFFFFFFF ("no id")
+    uint64_t nan_lo, nan_hi;
+    uint32_t n;             // 0 .. BUCK_MAX_BOUNDS
+    uint32_t steps;         // key_steps(n)
+    uint32_t idw;           // 1, 2 or 4
+    uint32_t right_closed;  // SB_BUCKET_RIGHT_CLOSED: a value equal to a bound stays below it
+    uint32_t nan_id;        // the id of a live NaN; 0xFFFFFFFF: all ones
+    uint32_t pad;
+};
+struct BuckState {          // 32 bytes per column, zeroed before the walk; one integer add per tile / page part into each
+    uint64_t count;         // live rows
+    uint64_t matched;       // ... whose id is not all ones
+    uint64_t nans;          // ... that are NaN
+    uint64_t pad;
+};
+constexpr uint32_t BUCK_RESULT_WORDS = 4;   // { selected, count, matched, nans }
+struct BuckLaunch {   // what launch_decode needs to end a call with the bucket kernels
+    const AggCol* acols;
+    const BuckCol* bcols;
+    BuckState* st;         // [n_cols]
+    uint32_t n_cols;
+};
 // ---- sb_key_combine (sb_key_combine.h): the key of a row is a tuple of 2 .. 4 part ids, each below KEY_MAX_KEYS.  Its
 // code is a 64-bit word with one COMB_FIELD_BITS field per part, part 0 highest, so that codes order as the tuples do
 // lexicographically.  The host's delivery, the kernels and tests/test_key_combine_host.py use these two functions.

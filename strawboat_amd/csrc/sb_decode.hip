@@ -3133,12 +3133,14 @@ static void launch_lzg(sb_ctx* ctx, const DecodeArgs& a, bool lzg_on, InflateJob
 #include "sb_key_ids.h"
 #include "sb_key_ids_bin.h"
 #include "sb_key_lookup.h"
+#include "sb_key_buckets.h"
 #include "sb_key_combine.h"
 namespace sb {
 
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
                    const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp, const InCol* icols, const TopkLaunch* topk,
-                   const KeyLaunch* keys, const KeyVarLaunch* keyv, const GrpLaunch* grpl, const LookLaunch* look, const WgtLaunch* wgt) {
+                   const KeyLaunch* keys, const KeyVarLaunch* keyv, const GrpLaunch* grpl, const LookLaunch* look, const WgtLaunch* wgt,
+                   const BuckLaunch* buck) {
     hipStream_t s = ctx->stream;
     (void)hipMemsetAsync(a.job_counts, 0, 16 * sizeof(uint32_t), s);
     const bool qa = !(a.read_skips & RSKIP_QUEUE_A);
@@ -3255,6 +3257,10 @@ void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_p
     }
     if (look) {   // sb_key_lookup: ... searched in the columns' lists, an id per row (sb_key_lookup.h)
         launch_key_lookup(ctx, a, *look);
+        return;
+    }
+    if (buck) {   // sb_key_buckets: ... searched among the columns' bounds, a bucket id per row (sb_key_buckets.h)
+        launch_key_buckets(ctx, a, *buck);
         return;
     }
     // the three expand kernels work on disjoint pages (page-level RLE, tiles of primitives, tiles of binary columns): side

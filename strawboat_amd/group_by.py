@@ -155,6 +155,80 @@ def group_by_keys(ctx, key: ColumnPages, key_values, values: List[ColumnPages], 
     return kres, call(ctx, list(values), kres.ids, n_groups, selection, ops)
 
 
+def _bucket_groups(key, bounds, bucket_ids, n_groups, nan_id):
+    """What group_by_buckets checks before anything is enqueued: the bounds, and that every id has a group.
+    Returns (the bounds as an array, n_groups)."""
+    from .key_buckets import NONE, bounds_values
+    if not isinstance(key, ColumnPages):
+        raise ValueError("a column is a ColumnPages, not %r" % type(key).__name__)
+    arr = bounds_values(key.physical_type, bounds)
+    if bucket_ids is None:
+        handed = [int(arr.size)]
+    else:
+        raw = bucket_ids.tolist() if isinstance(bucket_ids, np.ndarray) else list(bucket_ids)
+        handed = [int(v) for v in raw if isinstance(v, (int, np.integer)) and not isinstance(v, bool) and int(v) != NONE]
+    if isinstance(nan_id, (int, np.integer)) and not isinstance(nan_id, bool) and int(nan_id) != NONE:
+        handed.append(int(nan_id))
+    largest = max(handed) if handed else -1
+    if n_groups is None:
+        n_groups = max(1, largest + 1)
+    if isinstance(n_groups, bool) or not isinstance(n_groups, (int, np.integer)) or not 1 <= n_groups <= MAX_GROUPS_LARGE:
+        raise ValueError("n_groups is %r, not an int in 1 .. %d" % (n_groups, MAX_GROUPS_LARGE))
+    if largest >= n_groups:
+        raise ValueError("the buckets hand out the id %d, n_groups is %d" % (largest, n_groups))
+    return arr, int(n_groups)
+
+
+def group_by_buckets(ctx, key: ColumnPages, bounds, values: List[ColumnPages], selection=None,
+                     ops: Sequence[str] = ("count", "min", "max", "sum"), bucket_ids=None, n_groups=None,
+                     right_closed=False, nan_id=None):
+    """GROUP BY where the key falls: `key_buckets` of `key` among `bounds`, then the per-group aggregates of every
+    column of `values` (`aggregate_grouped` up to 256 groups, `aggregate_grouped_large` beyond), in the open interval.
+    Returns (KeyBuckets, [GroupedAggregate per value column]); group g is bucket g, or the buckets whose bucket id is
+    g.  n_groups: None = the largest id + 1.  The ids are the bounds' own, so the groups of two calls with one list of
+    bounds are index-aligned: the count and sum records of two row groups, files or ranks add, group by group.
+    Selected rows whose key is null, a NaN without a `nan_id`, or in a bucket without an id arrive in `out_of_range`."""
+    from .key_buckets import KeyBucketsBatch
+    arr, n_groups = _bucket_groups(key, bounds, bucket_ids, n_groups, nan_id)
+    batch = KeyBucketsBatch(ctx, [key], [arr], None if bucket_ids is None else [bucket_ids], selection, right_closed, nan_id)
+    agg = None
+    if values:   # (both calls are prepared, and with that checked, before either is enqueued)
+        from .aggregate_grouped import GroupedAggregateBatch
+        from .aggregate_grouped_large import GroupedAggregateLargeBatch
+        prepared = GroupedAggregateBatch if n_groups <= MAX_GROUPS else GroupedAggregateLargeBatch
+        agg = prepared(ctx, list(values), batch.results[0].ids, n_groups, selection, ops)
+    kres = batch.enqueue()[0]
+    return kres, agg.enqueue() if agg is not None else []
+
+
+class Histogram:
+    """The count-only chain of `histogram`; every property is valid after Context.synchronize()."""
+
+    def __init__(self, buckets, aggregate):
+        #: the KeyBuckets of the column
+        self.buckets = buckets
+        #: the GroupedAggregate ("count") of the column under its own bucket ids
+        self.aggregate = aggregate
+
+    @property
+    def counts(self):
+        """the n_bounds + 1 counts of the selected, non-null rows that are not NaN, as an int64 array"""
+        return np.array([g.count for g in self.aggregate.groups], dtype=np.int64)
+
+    nans = property(lambda self: self.buckets.nans)
+
+    def __repr__(self):
+        return "Histogram(buckets=%d, %r)" % (self.buckets.n_bounds + 1, self.buckets)
+
+
+def histogram(ctx, column: ColumnPages, bounds, selection=None, right_closed=False) -> Histogram:
+    """The histogram of a numeric column over `bounds`: `key_buckets` of the column, then the count of the column
+    itself per bucket, in the open interval.  After the synchronize `counts` has the n_bounds + 1 counts; nulls and
+    NaNs are in none of them (`nans` counts the latter)."""
+    kres, aggs = group_by_buckets(ctx, column, bounds, [column], selection, ("count",), None, None, right_closed, None)
+    return Histogram(kres, aggs[0])
+
+
 def trim(keys_result, aggregates: List[GroupedAggregate]) -> List[List[Group]]:
     """After the synchronize: the groups of every value column that have a key, groups[i][g] belonging to key g of
     keys_result.  Raises on an overflow of the keys: the ids, and with them the groups, mean nothing then."""
