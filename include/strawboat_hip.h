@@ -325,6 +325,76 @@ typedef struct sb_column_filter_in {
 
 int32_t sb_filter_columns_in(sb_ctx* ctx, sb_column_filter_in* cols, uint64_t n, int32_t mem);
 
+/* Column against column: `WHERE a < b`, `l_commitdate < l_receiptdate`, `end_ts >= start_ts`, `price > cost`.  The pages
+ * of a primitive column y go in with a dense DEVICE array `other`: one value of `other_type` per row of the column (a
+ * column decoded earlier in the interval by sb_read_columns, or any per-row expression of the engine's), optionally with
+ * a validity bitmap.  Bit `row` of the result is  y[row] op other[row] ; it is combined into `selection` exactly as
+ * sb_filter_columns combines its result.  Nothing of y is written, nothing of `other` is modified.
+ *
+ * Ops: SB_PRED_EQ .. SB_PRED_GE.  Types: y and `other` are each one of INT8..INT64, UINT8..UINT64, FLOAT32, FLOAT64,
+ * chosen independently (the pairing rule of sb_aggregate_weighted):
+ *   integer vs integer   both are extended by their own signedness and compared EXACTLY as mathematical integers,
+ *                        whatever the widths: a negative signed value is below every unsigned value, UINT64 2^63 is
+ *                        above INT64's maximum.
+ *   a float on a side    both are converted to double (integers round to nearest, ties to even) and compared as IEEE
+ *                        754: a NaN on either side satisfies only NE, -0.0 == +0.0, -inf and +inf are ordered like any
+ *                        value.  An INT64 / UINT64 above 2^53 in magnitude is compared AFTER that rounding: 2^53 + 1
+ *                        equals the double 2^53.
+ * Nulls: a row satisfies nothing, NE included, when y is null at that row or bit `row` of `other_validity` is 0.
+ * other_validity == NULL: every operand is valid.  Bits behind `rows` are ignored, and so is whatever the slot of an
+ * invalid operand holds.
+ *
+ * `other`: aligned to the width of other_type, other_capacity >= rows * width bytes.  `other_validity`: 4-byte aligned,
+ * LSB first as sb_read_columns writes it, other_validity_capacity >= 4*ceil(rows/32) bytes.  Both are INPUTS that must
+ * stay valid and unmodified until sb_ctx_synchronize: a replay reads them again.
+ *
+ * `selection`, combine, `rows` / `selected`, the zero bits behind `rows` after SET, page errors (the decoder's codes, at
+ * the synchronize), page_offsets and the place in the synchronize interval are those of sb_filter_columns bit for bit:
+ * on a replay the call is issued again in its place and gives the same bits in all three modes; a column with a
+ * primitive Freq page asks for the replay itself and is then compared from the decoded staging area.  No launch hint of
+ * the read path is consulted or fed.  Per codec: plain and inflated pages load y and the operand once per row; a OneValue
+ * page keeps y in a register; an RLE page hands every row its run's value; a Dict page gathers the row's entry (an index
+ * beyond the dictionary raises what a read raises); bit-packed pages are unpacked in LDS.  No run and no dictionary entry
+ * can be decided once any more: the cost follows the rows.
+ *
+ * Refused at the call (nothing enqueued, no result field and no selection byte touched): y or `other` of Boolean /
+ * Int128 / Int256 / Binary / LargeBinary / Null, SB_MEM_HOST (SB_ERR_NYI); an op outside EQ .. GE, a bad combine, a
+ * physical_type or other_type outside the enum, `other` null, not aligned to its width or shorter than rows * width,
+ * `other_validity` misaligned or short, a validity capacity without a pointer, flags != 0, reserved != 0, a `selection`
+ * that overlaps `other` or `other_validity` of its own column, two columns of one call whose selections overlap, and
+ * every argument refusal of sb_filter_columns (SB_ERR_INVALID); a page outside [0, pages_len) (SB_ERR_IO; like its
+ * siblings' this one refusal is also what the next sb_ctx_synchronize returns).
+ *
+ * Layout (pinned by tests/test_filter_cmp_host.py): sb_column_filter_cmp 136 bytes; physical_type 0, is_nullable 4,
+ * pages 8, pages_len 16, metas 24, n_pages 32, page_offsets 40, op 48, combine 52, other 56, other_capacity 64,
+ * other_validity 72, other_validity_capacity 80, other_type 88, flags 92, reserved 96, selection 104,
+ * selection_capacity 112, rows 120, selected 128.  The first 56 bytes are sb_column_filter's. */
+typedef struct sb_column_filter_cmp {
+    int32_t physical_type;   /* SB_TYPE_* of y */
+    int32_t is_nullable;
+    const uint8_t* pages;    /* DEVICE, at any byte alignment */
+    uint64_t pages_len;
+    const sb_page_meta* metas; /* HOST */
+    uint64_t n_pages;
+    const uint64_t* page_offsets; /* optional (HOST) */
+    int32_t op;              /* SB_PRED_EQ .. SB_PRED_GE */
+    int32_t combine;         /* SB_SEL_* */
+    const uint8_t* other;    /* DEVICE (input): one value of other_type per row, aligned to its width */
+    uint64_t other_capacity; /* >= rows * width bytes */
+    const uint8_t* other_validity; /* DEVICE (input), optional: LSB-first bitmap, 4-byte aligned */
+    uint64_t other_validity_capacity; /* >= 4*ceil(rows/32) bytes when other_validity is given, else 0 */
+    int32_t other_type;      /* SB_TYPE_* of `other` */
+    uint32_t flags;          /* 0 */
+    uint64_t reserved;       /* 0 */
+    uint8_t* selection;      /* DEVICE: LSB-first bitmap, 4-byte aligned */
+    uint64_t selection_capacity; /* >= 4*ceil(rows/32) bytes */
+    /* results (HOST, valid after sb_ctx_synchronize) */
+    uint64_t rows;
+    uint64_t selected;
+} sb_column_filter_cmp;      /* 136 bytes */
+
+int32_t sb_filter_columns_cmp(sb_ctx* ctx, sb_column_filter_cmp* cols, uint64_t n, int32_t mem);
+
 /* ------------------------------------------------------------------ selected read
  * The second half of the filter: the pages of a payload column and a selection bitmap go in, the selected rows come
  * out packed.  Output row k is the column's row at the k-th set bit of `selection` below `rows`: its `values` are the

@@ -25,7 +25,8 @@ EXPORTS = ("sb_version", "sb_ctx_create", "sb_ctx_destroy", "sb_ctx_synchronize"
            "sb_schema_metadata_from_bytes", "sb_filter_columns", "sb_filter_columns_var", "sb_read_selected",
            "sb_read_selected_var", "sb_aggregate_columns", "sb_aggregate_grouped", "sb_filter_columns_in",
            "sb_topk_columns", "sb_key_ids", "sb_key_ids_var", "sb_aggregate_grouped_large",
-           "sb_key_combine", "sb_key_lookup", "sb_aggregate_weighted", "sb_key_buckets")
+           "sb_key_combine", "sb_key_lookup", "sb_aggregate_weighted", "sb_key_buckets",
+           "sb_filter_columns_cmp")
 
 SB_PRED_EQ, SB_PRED_NE, SB_PRED_LT, SB_PRED_LE, SB_PRED_GT, SB_PRED_GE, SB_PRED_IS_NULL, SB_PRED_IS_NOT_NULL = range(8)
 SB_PRED_STARTS_WITH = 8   # binary types only (sb_filter_columns_var)
@@ -212,6 +213,16 @@ class ColumnKeyBucketsC(C.Structure):
                 ("nans", C.c_uint64)]
 
 
+class ColumnFilterCmpC(C.Structure):
+    _fields_ = [("physical_type", C.c_int32), ("is_nullable", C.c_int32), ("pages", C.c_void_p),
+                ("pages_len", C.c_uint64), ("metas", C.POINTER(PageMetaC)), ("n_pages", C.c_uint64),
+                ("page_offsets", C.c_void_p), ("op", C.c_int32), ("combine", C.c_int32),
+                ("other", C.c_void_p), ("other_capacity", C.c_uint64), ("other_validity", C.c_void_p),
+                ("other_validity_capacity", C.c_uint64), ("other_type", C.c_int32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint64), ("selection", C.c_void_p), ("selection_capacity", C.c_uint64),
+                ("rows", C.c_uint64), ("selected", C.c_uint64)]
+
+
 class ColumnWriteC(C.Structure):
     _fields_ = [("physical_type", C.c_int32), ("is_nullable", C.c_int32), ("rows", C.c_uint64),
                 ("values", C.c_void_p), ("values_bit_offset", C.c_uint64), ("values_len", C.c_uint64),
@@ -317,6 +328,8 @@ def load():
     L.sb_aggregate_grouped_large.argtypes = [C.c_void_p, C.POINTER(ColumnAggregateGroupedC), C.c_uint64, C.c_int32]
     L.sb_key_buckets.restype = C.c_int32
     L.sb_key_buckets.argtypes = [C.c_void_p, C.POINTER(ColumnKeyBucketsC), C.c_uint64, C.c_int32]
+    L.sb_filter_columns_cmp.restype = C.c_int32
+    L.sb_filter_columns_cmp.argtypes = [C.c_void_p, C.POINTER(ColumnFilterCmpC), C.c_uint64, C.c_int32]
     L.sb_aggregate_weighted.restype = C.c_int32
     L.sb_aggregate_weighted.argtypes = [C.c_void_p, C.POINTER(ColumnAggregateWeightedC), C.c_uint64, C.c_int32]
     L.sb_topk_columns.restype = C.c_int32

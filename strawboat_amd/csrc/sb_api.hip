@@ -16,7 +16,9 @@ void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_p
                    const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp = nullptr, const InCol* icols = nullptr,
                    const TopkLaunch* topk = nullptr, const KeyLaunch* keys = nullptr, const KeyVarLaunch* keyv = nullptr,
                    const GrpLaunch* grpl = nullptr, const LookLaunch* look = nullptr, const WgtLaunch* wgt = nullptr,
-                   const BuckLaunch* buck = nullptr);
+                   const BuckLaunch* buck = nullptr, const CmpCol* ccols = nullptr);
+void launch_filter_cmp_plain(sb_ctx* ctx, const FilterCol& f, const CmpCol& cc, const uint8_t* values, const uint8_t* validity, uint64_t rows, uint32_t w,
+                             uint64_t* count);
 void launch_buck_zero(sb_ctx* ctx, const BuckLaunch& bl);
 void launch_buck_finish(sb_ctx* ctx, const BuckLaunch& bl, uint64_t* results);
 void launch_key_buckets_plain(sb_ctx* ctx, const BuckLaunch& bl, const uint64_t* rows, const uint8_t* const* values, const uint8_t* const* validity);
@@ -131,7 +133,7 @@ StageSlot* acquire_slot(sb_ctx* ctx, size_t need) {
     if (s.host)
         for (auto& p : ctx->iv.pending) {
             if (p.host < s.host || p.host >= s.host + s.cap) continue;
-            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::AGG_COL ? AGG_RESULT_WORDS * 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R || p.kind == Pending::AGG_GRP_COL || p.kind == Pending::AGG_GRPL_COL || p.kind == Pending::AGG_WGT_COL || p.kind == Pending::TOPK_COL || p.kind == Pending::KEY_COL || p.kind == Pending::KEY_VAR_COL || p.kind == Pending::COMB_ITEM || p.kind == Pending::KEY_LOOK_COL || p.kind == Pending::KEY_BUCKET_COL) ? (size_t)p.bytes
+            const size_t nb = (p.kind == Pending::READ_COL || p.kind == Pending::FILTER_COL || p.kind == Pending::FILTER_CMP_COL || p.kind == Pending::RSEL_COL) ? 8 : p.kind == Pending::RSEL_VAR_COL ? 16 : p.kind == Pending::AGG_COL ? AGG_RESULT_WORDS * 8 : p.kind == Pending::ENC_HINT ? 128 : (p.kind == Pending::NESTED_W || p.kind == Pending::NESTED_R || p.kind == Pending::AGG_GRP_COL || p.kind == Pending::AGG_GRPL_COL || p.kind == Pending::AGG_WGT_COL || p.kind == Pending::TOPK_COL || p.kind == Pending::KEY_COL || p.kind == Pending::KEY_VAR_COL || p.kind == Pending::COMB_ITEM || p.kind == Pending::KEY_LOOK_COL || p.kind == Pending::KEY_BUCKET_COL) ? (size_t)p.bytes
                                                                                                    : (size_t)(2 * p.n + 1) * 8;
             ctx->iv.rescued.emplace_back(p.host, p.host + nb);
             p.host = ctx->iv.rescued.back().data();
@@ -273,10 +275,12 @@ struct ReadMode {
     // / sb_key_ids_var, the same for binary columns, whose value blocks are staged as a filter call stages them
     // / sb_key_lookup, an aggregate call whose columns end in the lookup kernels: one walk, numeric and binary columns alike
     // / sb_key_buckets, an aggregate call whose columns end in the bucket kernels: the same walk over numeric columns
-    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR, AGGREGATE, AGG_GROUPED, AGG_GROUPED_LARGE, TOPK, KEY_IDS, KEY_IDS_VAR, KEY_LOOKUP, AGG_WEIGHTED, KEY_BUCKETS } kind;
+    // / sb_filter_columns_cmp, a filter call whose columns end in the kernels of sb_filter_cmp.h: a CmpCol beside every FilterCol
+    enum Kind { READ, SIZES, FREQ_PASS, FILTER, SELECTED, SELECTED_VAR, AGGREGATE, AGG_GROUPED, AGG_GROUPED_LARGE, TOPK, KEY_IDS, KEY_IDS_VAR, KEY_LOOKUP, AGG_WEIGHTED, KEY_BUCKETS, FILTER_CMP } kind;
     const FilterCol* filt = nullptr;             // FILTER: one per column
     const std::vector<uint8_t>* lits = nullptr;  // ... the literals of the FK_BYTES columns, FilterCol.lit being the offset of each
     bool in_list = false;                        // ... sb_filter_columns_in: `lits` begins with an InCol per column, whose pointers are offsets in `lits`
+                                                 // FILTER_CMP: `filt` as for FILTER, and `lits` is a CmpCol per column
     bool sizes() const { return kind == SIZES; }
     bool freq_pass() const { return kind == FREQ_PASS; }
     const SelCol* selc = nullptr;                // SELECTED: one per column (rank: filled in with the call's tables)
@@ -309,15 +313,16 @@ struct ReadMode {
     bool key_lookup() const { return kind == KEY_LOOKUP; }
     bool key_buckets() const { return kind == KEY_BUCKETS; }
     bool bin_id_tables() const { return kind == KEY_IDS_VAR || kind == KEY_LOOKUP; }   // a 16-bit id table and a bit table per binary Dict / Freq page
-    bool filter() const { return kind == FILTER; }
+    bool filter() const { return kind == FILTER || kind == FILTER_CMP; }
+    bool filter_cmp() const { return kind == FILTER_CMP; }
     bool selected() const { return kind == SELECTED; }
     bool selected_var() const { return kind == SELECTED_VAR; }
     bool ranked() const { return kind == SELECTED || kind == SELECTED_VAR; }   // a SelCol and a rank table per column
     // binary columns whose value blocks are staged and compared or gathered: no offsets are written by the read's kernels
-    bool bin_staged() const { return kind == FILTER || kind == SELECTED_VAR || kind == KEY_IDS_VAR || kind == KEY_LOOKUP; }
+    bool bin_staged() const { return filter() || kind == SELECTED_VAR || kind == KEY_IDS_VAR || kind == KEY_LOOKUP; }
     // the columns end in a sink of their own: `values` is a share of the staging area, there is no validity buffer, and
     // the call neither consults nor feeds the launch hints of the read path
-    bool sink() const { return kind == FILTER || kind == SELECTED || kind == SELECTED_VAR || aggregate(); }
+    bool sink() const { return filter() || kind == SELECTED || kind == SELECTED_VAR || aggregate(); }
     // words of 8 bytes that come back per column: { selected, values_len } for a SELECTED_VAR call, the result record of
     // an AGGREGATE call, the header and the gmax group records of an AGG_GROUPED call, the header and the kmax entries of
     // a TOPK call, the header and the kmax key slots of a KEY_IDS call, the header, offsets and bytes of a KEY_IDS_VAR call
@@ -690,7 +695,8 @@ static void apply_enc_hint(sb_ctx* ctx, const Pending& p) {
 static void deliver_pending(sb_ctx* ctx, const Pending& p, int32_t rc) {
     switch (p.kind) {
         case Pending::READ_COL: deliver_read_col(p); break;
-        case Pending::FILTER_COL: deliver_filter_col(p); break;
+        case Pending::FILTER_COL:
+        case Pending::FILTER_CMP_COL: deliver_filter_col(p); break;
         case Pending::RSEL_COL: deliver_rsel_col(p); break;
         case Pending::RSEL_VAR_COL: deliver_rsel_var_col(p); break;
         case Pending::AGG_COL: deliver_agg_col(p); break;
@@ -1404,7 +1410,10 @@ static void launch_read(sb_ctx* ctx, const ReadMode& mode, const ReadShape& sh, 
             if (mode.filt[i].combine == SB_SEL_SET) fl.any_set = true;
         }
         const InCol* icols = mode.in_list ? (const InCol*)(ctx->tables.p + L.lits) : nullptr;
-        if (sh.P) launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, &fl, nullptr, nullptr, nullptr, icols);
+        const CmpCol* ccols = mode.filter_cmp() ? (const CmpCol*)(ctx->tables.p + L.lits) : nullptr;
+        if (sh.P)
+            launch_decode(ctx, a, sh.any_binary, sh.any_prim, h.lzg_launch, d_vlen, &fl, nullptr, nullptr, nullptr, icols, nullptr, nullptr, nullptr, nullptr, nullptr,
+                          nullptr, nullptr, ccols);
     } else if (mode.selected()) {
         SelLaunch sl{(const SelCol*)(ctx->tables.p + L.fcols), d_vlen, false};
         for (uint64_t i = 0; i < n; i++)
@@ -1670,7 +1679,7 @@ static_assert(offsetof(sb_column_filter, page_offsets) == 40, "the pages of a si
 static_assert(has_pages_prefix<sb_column_filter_var>() && has_pages_prefix<sb_column_read_selected>() && has_pages_prefix<sb_column_read_selected_var>() &&
                   has_pages_prefix<sb_column_aggregate>() && has_pages_prefix<sb_column_aggregate_grouped>() && has_pages_prefix<sb_column_topk>() &&
                   has_pages_prefix<sb_column_key_ids>() && has_pages_prefix<sb_column_key_ids_var>() && has_pages_prefix<sb_column_key_lookup>() &&
-                  has_pages_prefix<sb_column_key_buckets>(),
+                  has_pages_prefix<sb_column_key_buckets>() && has_pages_prefix<sb_column_filter_cmp>(),
               "every sink column begins with the seven fields of sb_column_filter, at its offsets");
 
 // The pages of a sink column as a read column (outputs: none yet)
@@ -2135,6 +2144,119 @@ int32_t sb_filter_columns_in(sb_ctx* ctx, sb_column_filter_in* cols, uint64_t n,
     mode.pending_kind = Pending::FILTER_COL;
     rc = read_columns_impl(ctx, rc_cols.data(), m, SB_MEM_DEVICE, mode);
     if (rc == SB_OK && first_issue) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::FILTER_IN, cols, n, sb_write_options{}, mem});
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------ column against column
+static_assert(sizeof(sb_column_filter_cmp) == 136 && offsetof(sb_column_filter_cmp, op) == 48 && offsetof(sb_column_filter_cmp, combine) == 52 &&
+                  offsetof(sb_column_filter_cmp, other) == 56 && offsetof(sb_column_filter_cmp, other_capacity) == 64 &&
+                  offsetof(sb_column_filter_cmp, other_validity) == 72 && offsetof(sb_column_filter_cmp, other_validity_capacity) == 80 &&
+                  offsetof(sb_column_filter_cmp, other_type) == 88 && offsetof(sb_column_filter_cmp, flags) == 92 &&
+                  offsetof(sb_column_filter_cmp, reserved) == 96 && offsetof(sb_column_filter_cmp, selection) == 104 &&
+                  offsetof(sb_column_filter_cmp, selection_capacity) == 112 && offsetof(sb_column_filter_cmp, rows) == 120 &&
+                  offsetof(sb_column_filter_cmp, selected) == 128,
+              "sb_column_filter_cmp: the offsets the header states");
+static_assert(offsetof(sb_column_filter_cmp, op) == offsetof(sb_column_filter, op) && offsetof(sb_column_filter_cmp, combine) == offsetof(sb_column_filter, combine) &&
+                  offsetof(sb_column_filter, literal) == 56,
+              "the first 56 bytes are sb_column_filter's");
+
+// The columns of a replayed call: decoded, and compared from the staging area (filter_columns_decoded with the operands,
+// which are the callers' own device buffers)
+static int32_t filter_cmp_columns_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pages, const uint64_t* rows, const FilterCol* hf, const CmpCol* hcc,
+                                          void* const* sel_out) {
+    hipStream_t s = ctx->stream;
+    const uint64_t m = pages.size();
+    const sb_column_read* rr = nullptr;
+    int32_t rc = decode_for_replay(ctx, std::move(pages), rows, "filter", &rr);
+    if (rc != SB_OK) return rc;
+    uint64_t* d_counts = nullptr;
+    if (hipMalloc((void**)&d_counts, m * sizeof(uint64_t)) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter counts) failed");
+    ctx->iv.temp_dev.push_back(d_counts);
+    StageSlot* slot = acquire_slot(ctx, m * sizeof(uint64_t));
+    if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
+    for (uint64_t i = 0; i < m; i++) {
+        if (hf[i].combine == SB_SEL_SET && rows[i]) (void)hipMemsetAsync(hf[i].sel, 0, (rows[i] + 31) / 32 * 4, s);
+        launch_filter_cmp_plain(ctx, hf[i], hcc[i], (const uint8_t*)rr[i].values, rr[i].is_nullable ? rr[i].validity : nullptr, rows[i],
+                                type_width(rr[i].physical_type), d_counts + i);
+    }
+    return queue_sink_results(ctx, slot, d_counts, sizeof(uint64_t), m, Pending::FILTER_CMP_COL, sel_out, nullptr, "filter");
+}
+
+int32_t sb_filter_columns_cmp(sb_ctx* ctx, sb_column_filter_cmp* cols, uint64_t n, int32_t mem) {
+    int32_t rc;
+    if (!sink_entry(ctx, cols, n, mem, "sb_filter_columns_cmp", &rc)) return rc;
+    std::vector<uint64_t> rows(n), cap(n);
+    auto overlap = [](const uint8_t* a, uint64_t an, const uint8_t* b, uint64_t bn) { return an && bn && a < b + bn && b < a + an; };
+    for (uint64_t i = 0; i < n; i++) {
+        const sb_column_filter_cmp& c = cols[i];
+        if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(ctx, SB_ERR_INVALID, "bad physical_type");
+        if (c.other_type < 0 || c.other_type > SB_TYPE_NULL) return refuse(ctx, SB_ERR_INVALID, "bad other_type");
+        if (c.op < SB_PRED_EQ || c.op > SB_PRED_GE) return refuse(ctx, SB_ERR_INVALID, "bad op: SB_PRED_EQ .. SB_PRED_GE");
+        if (c.combine < SB_SEL_SET || c.combine > SB_SEL_OR) return refuse(ctx, SB_ERR_INVALID, "bad combine");
+        if (c.flags) return refuse(ctx, SB_ERR_INVALID, "flags is not 0");
+        if (c.reserved) return refuse(ctx, SB_ERR_INVALID, "reserved is not 0");
+        if (!filter_comparable(c.physical_type) || !filter_comparable(c.other_type))
+            return refuse(ctx, SB_ERR_NYI, "column comparisons are implemented for 8- to 64-bit integers and floats on both sides");
+        if (!column_rows(c, &rows[i])) return refuse(ctx, SB_ERR_INVALID, "metas is null");
+        const uint64_t r = rows[i], sel_bytes = (r + 31) / 32 * 4, ow = type_width(c.other_type);
+        if (r && (!c.selection || ((uintptr_t)c.selection & 3) || c.selection_capacity < sel_bytes))
+            return refuse(ctx, SB_ERR_INVALID, "selection missing, not 4-byte aligned or smaller than 4*ceil(rows/32) bytes");
+        if (r && !c.other) return refuse(ctx, SB_ERR_INVALID, "other is null");
+        if (c.other && (((uintptr_t)c.other & (ow - 1)) || c.other_capacity < r * ow))
+            return refuse(ctx, SB_ERR_INVALID, "other not aligned to its width or smaller than rows * width bytes");
+        if (!c.other_validity && c.other_validity_capacity) return refuse(ctx, SB_ERR_INVALID, "other_validity_capacity without other_validity");
+        if (c.other_validity && (((uintptr_t)c.other_validity & 3) || c.other_validity_capacity < sel_bytes))
+            return refuse(ctx, SB_ERR_INVALID, "other_validity not 4-byte aligned or smaller than 4*ceil(rows/32) bytes");
+        if (overlap(c.selection, sel_bytes, c.other, r * ow) || (c.other_validity && overlap(c.selection, sel_bytes, c.other_validity, sel_bytes)))
+            return refuse(ctx, SB_ERR_INVALID, "selection overlaps other or other_validity");
+        for (uint64_t j = 0; j < i; j++)
+            if (overlap(c.selection, sel_bytes, cols[j].selection, (rows[j] + 31) / 32 * 4))
+                return refuse(ctx, SB_ERR_INVALID, "two columns of one call share a selection buffer: chain them with two calls");
+        cap[i] = r * type_width(c.physical_type);   // the share of the staging area a comparison column has
+    }
+    // [CmpCol per column] in the literals' place, FilterCol per column beside
+    std::vector<uint8_t> blob(n * sizeof(CmpCol));
+    std::vector<CmpCol> hcc(n);
+    std::vector<FilterCol> hf(n);
+    std::vector<sb_column_read> rc_cols(n);
+    std::vector<void*> sel_out(n);
+    for (uint64_t i = 0; i < n; i++) {
+        sb_column_filter_cmp& c = cols[i];
+        static_assert(offsetof(sb_column_filter_cmp, selected) == offsetof(sb_column_filter_cmp, rows) + 8, "{ rows, selected }");
+        sel_out[i] = &c.selected;
+        rc_cols[i] = read_col_of(c);
+        FilterCol& f = hf[i];
+        memset(&f, 0, sizeof f);
+        static const uint32_t MASKS[6] = {2u, 13u, 1u, 3u, 4u, 6u};   // EQ NE LT LE GT GE over (less, equal, greater, unordered)
+        f.sel = (uint32_t*)c.selection;
+        f.kind = value_kind(c.physical_type);
+        f.mask = MASKS[c.op];
+        f.op = (uint32_t)c.op;
+        f.combine = (uint32_t)c.combine;
+        f.ptype = c.physical_type;
+        hcc[i] = CmpCol{c.other, (const uint32_t*)c.other_validity, value_kind(c.other_type), type_width(c.other_type)};
+    }
+    if (n) memcpy(blob.data(), hcc.data(), n * sizeof(CmpCol));
+    (void)hipSetDevice(ctx->device);
+    if (ctx->in_replay && ctx->filter_freq) {
+        // every column through a full decode, as sb_filter_columns has its comparison columns.  The bits are a function of
+        // the data and the struct alone, so the route does not show in them.
+        rc = filter_cmp_columns_decoded(ctx, std::move(rc_cols), rows.data(), hf.data(), hcc.data(), sel_out.data());
+    } else {
+        if ((rc = stage_shares(ctx, rc_cols.data(), cap.data(), n)) != SB_OK) return rc;
+        ReadMode mode{ReadMode::FILTER_CMP};
+        mode.filt = hf.data();
+        mode.lits = &blob;
+        mode.users = sel_out.data();
+        mode.pending_kind = Pending::FILTER_CMP_COL;
+        rc = read_columns_impl(ctx, rc_cols.data(), n, SB_MEM_DEVICE, mode);
+    }
+    if (rc != SB_OK) return rc;
+    for (uint64_t i = 0; i < n; i++) {   // (after the last thing that can refuse the call: a page outside pages_len)
+        cols[i].rows = rows[i];
+        cols[i].selected = 0;
+    }
+    if (!ctx->in_replay) ctx->iv.calls.push_back(sb_ctx::Call{sb_ctx::Call::FILTER_CMP, cols, n, sb_write_options{}, mem});
     return rc;
 }
 

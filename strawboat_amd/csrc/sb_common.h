@@ -32,6 +32,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/strawboat_hip.h"
 
 namespace sb {
@@ -793,6 +795,61 @@ constexpr uint32_t FILTER_MASK_SUB = FILTER_MASK_SUFFIX | FILTER_MASK_SUBSTR | F
 // words of the bit table (a bit per dictionary entry) that a filter call reserves at the END of the aux area of every page
 // of a binary comparison column: an entry is a u64 length and its bytes, so a page of L bytes has at most L / 8 of them
 __host__ __device__ inline uint64_t filter_bin_table_words(uint64_t page_len) { return (page_len / 256 + 4) & ~3ull; }
+// one column of a column-against-column call (sb_filter_columns_cmp, sb_filter_cmp.h), next to its FilterCol (sel, kind =
+// how y compares, mask, combine).  Nothing of it is written.
+struct CmpCol {
+    const uint8_t* other;   // one value of `ow` bytes per row of the column (input)
+    const uint32_t* ov;     // the operands' validity, LSB first in 32-bit words, or null: every operand is valid
+    uint32_t okind;         // FK_* of the operands
+    uint32_t ow;            // bytes per operand
+};
+// The relation of y to o (0 less, 1 equal, 2 greater, 3 unordered), whose bit of FilterCol.mask is the row's result.  The
+// host's and the device's alike (tests/test_filter_cmp_host.py runs them on the edge values of every type pair).
+// Integers: each word extended by its own signedness; where the signs differ the negative one is below, where they agree
+// the words order as unsigned ones do (two's complement keeps the order of two negatives).
+__host__ __device__ inline uint64_t cmp_ext(bool is_signed, uint32_t w, uint64_t raw) {
+    const uint32_t sh = 64 - 8 * w;
+    return is_signed ? (uint64_t)((int64_t)(raw << sh) >> sh) : raw;
+}
+__host__ __device__ inline uint32_t cmp_rel_int(uint64_t y, bool y_signed, uint64_t o, bool o_signed) {
+    const bool yn = y_signed && (y >> 63), on = o_signed && (o >> 63);
+    const uint32_t r = y < o ? 0u : y == o ? 1u : 2u;
+    return yn != on ? (yn ? 0u : 2u) : r;
+}
+// a value of kind K (FK_*) as a double: integers round to nearest even
+template <uint32_t K>
+__host__ __device__ inline double cmp_dbl(uint32_t w, uint64_t raw) {
+    if (K == FK_F32) return (double)__builtin_bit_cast(float, (uint32_t)raw);
+    if (K == FK_F64) return __builtin_bit_cast(double, raw);
+    if (K == FK_SIGNED) return (double)(int64_t)cmp_ext(true, w, raw);
+    return (double)raw;
+}
+__host__ __device__ inline uint32_t cmp_rel_dbl(double y, double o) { return y < o ? 0u : y == o ? 1u : y > o ? 2u : 3u; }
+// y (kind YK, yw bytes) against o (kind OK, ow bytes): a pair of integers exactly, any pair with a float as doubles
+template <uint32_t YK, uint32_t OK>
+__host__ __device__ inline uint32_t cmp_rel(uint32_t yw, uint64_t y, uint32_t ow, uint64_t o) {
+    if (YK <= FK_SIGNED && OK <= FK_SIGNED) return cmp_rel_int(cmp_ext(YK == FK_SIGNED, yw, y), YK == FK_SIGNED, cmp_ext(OK == FK_SIGNED, ow, o), OK == FK_SIGNED);
+    return cmp_rel_dbl(cmp_dbl<YK>(yw, y), cmp_dbl<OK>(ow, o));
+}
+// the type pair resolved once, outside the loops over rows: f(integral_constant yk, integral_constant ok)
+template <uint32_t YK, class F>
+__host__ __device__ __forceinline__ void cmp_pair_o(uint32_t okind, F&& f) {
+    switch (okind) {
+        case FK_UNSIGNED: f(std::integral_constant<uint32_t, YK>{}, std::integral_constant<uint32_t, FK_UNSIGNED>{}); break;
+        case FK_SIGNED: f(std::integral_constant<uint32_t, YK>{}, std::integral_constant<uint32_t, FK_SIGNED>{}); break;
+        case FK_F32: f(std::integral_constant<uint32_t, YK>{}, std::integral_constant<uint32_t, FK_F32>{}); break;
+        default: f(std::integral_constant<uint32_t, YK>{}, std::integral_constant<uint32_t, FK_F64>{}); break;
+    }
+}
+template <class F>
+__host__ __device__ __forceinline__ void cmp_pair(uint32_t ykind, uint32_t okind, F&& f) {
+    switch (ykind) {
+        case FK_UNSIGNED: cmp_pair_o<FK_UNSIGNED>(okind, f); break;
+        case FK_SIGNED: cmp_pair_o<FK_SIGNED>(okind, f); break;
+        case FK_F32: cmp_pair_o<FK_F32>(okind, f); break;
+        default: cmp_pair_o<FK_F64>(okind, f); break;
+    }
+}
 constexpr uint32_t LZ4_BIG_MIN = 64u << 10;
 constexpr uint32_t RSKIP_QUEUE_A = 1u, RSKIP_TILES = 2u;   // k_zstd_split + k_inflate + k_inflate_lz4 of queue A / k_expand
 

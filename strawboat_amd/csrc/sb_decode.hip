@@ -3123,6 +3123,7 @@ static void launch_lzg(sb_ctx* ctx, const DecodeArgs& a, bool lzg_on, InflateJob
 #include "sb_filter_bin.h"
 #include "sb_filter_sub.h"
 #include "sb_filter_in.h"
+#include "sb_filter_cmp.h"
 #include "sb_read_sel.h"
 #include "sb_read_sel_bin.h"
 #include "sb_aggregate.h"
@@ -3140,7 +3141,7 @@ namespace sb {
 void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_prim, bool lzg_on, uint64_t* col_values_len, const FilterLaunch* flt,
                    const SelLaunch* rsel, const AggLaunch* agg, const GrpLaunch* grp, const InCol* icols, const TopkLaunch* topk,
                    const KeyLaunch* keys, const KeyVarLaunch* keyv, const GrpLaunch* grpl, const LookLaunch* look, const WgtLaunch* wgt,
-                   const BuckLaunch* buck) {
+                   const BuckLaunch* buck, const CmpCol* ccols) {
     hipStream_t s = ctx->stream;
     (void)hipMemsetAsync(a.job_counts, 0, 16 * sizeof(uint32_t), s);
     const bool qa = !(a.read_skips & RSKIP_QUEUE_A);
@@ -3210,6 +3211,10 @@ void launch_decode(sb_ctx* ctx, const DecodeArgs& a, bool any_binary, bool any_p
     if (any_binary && a.lz4_big_min != 0xFFFFFFFFu) {
         KScope k(ctx, "k_inflate_lz4_big(values)");
         k_inflate_lz4_big<<<min(a.zs_segs ? a.job_cap_a : 2 * a.n_pages, LZ4_BIG_POOL), LB_T, 0, s>>>(a.jobs_b, a.job_counts + 1, a.status, a.lz4_big_min, a.job_cap_a, a.lzg_skipped);
+    }
+    if (flt && ccols) {   // sb_filter_columns_cmp: ... compared with the columns' dense operands (sb_filter_cmp.h)
+        launch_filter_cmp(ctx, a, *flt, ccols);
+        return;
     }
     if (flt && icols) {   // sb_filter_columns_in: ... searched in the columns' lists (sb_filter_in.h)
         launch_filter_in(ctx, a, *flt, icols);

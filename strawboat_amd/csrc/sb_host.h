@@ -37,6 +37,7 @@ struct StageSlot {
 //   KEY_VAR_COL sb_column_key_ids_var*        64 bytes { selected, count, n_keys, overflow, keys_len }, then kmax + 1 offsets, then the keys' bytes  0   of the record
 //   KEY_LOOK_COL sb_column_key_lookup*        32 bytes { selected, count, matched, 0 }    0               -
 //   KEY_BUCKET_COL sb_column_key_buckets*     32 bytes { selected, count, matched, nans } 0               -
+//   FILTER_CMP_COL the caller's `selected`    8 bytes: the bits set (sb_filter_columns_cmp) 0             -
 //   COMB_ITEM   sb_key_combine_item*          64 bytes { rows, live, n_keys, overflow }, then 8 per sorted code (unpacked into `tuples`)  0   of header + kmax codes
 //   WRITE_COL   sb_column_write*              u64 [n lengths][n num_values][out_len]      pages           -
 //   ENC_HINT    null                          32 words: pages per codec of a write call   the plan's key  -
@@ -44,7 +45,7 @@ struct StageSlot {
 //   NESTED_R    sb_nested_levels_read[n]      the page records of an enqueued level call  items           of the records
 // (acquire_slot sizes what it moves out of a recycled slot by this table)
 struct Pending {
-    enum Kind { READ_COL, WRITE_COL, ENC_HINT, NESTED_W, NESTED_R, FILTER_COL, RSEL_COL, RSEL_VAR_COL, AGG_COL, AGG_GRP_COL, AGG_GRPL_COL, TOPK_COL, KEY_COL, KEY_VAR_COL, COMB_ITEM, KEY_LOOK_COL, AGG_WGT_COL, KEY_BUCKET_COL } kind;
+    enum Kind { READ_COL, WRITE_COL, ENC_HINT, NESTED_W, NESTED_R, FILTER_COL, RSEL_COL, RSEL_VAR_COL, AGG_COL, AGG_GRP_COL, AGG_GRPL_COL, TOPK_COL, KEY_COL, KEY_VAR_COL, COMB_ITEM, KEY_LOOK_COL, AGG_WGT_COL, KEY_BUCKET_COL, FILTER_CMP_COL } kind;
     void* user;
     const uint8_t* host;
     uint64_t n;
@@ -247,7 +248,7 @@ struct sb_ctx {
     // never a one-workgroup walk over a million-row page.  (The callers' column arrays and buffers live until the
     // synchronize anyway: the results are written into them there.)
     struct Call {
-        enum Kind { READ, WRITE, FILTER, FILTER_VAR, FILTER_IN, READ_SEL, READ_SEL_VAR, AGGREGATE, AGG_GROUPED, AGG_GROUPED_LARGE, TOPK, KEY_IDS, KEY_IDS_VAR, KEY_COMBINE, SIZES, KEY_LOOKUP, AGG_WEIGHTED, KEY_BUCKETS } kind;   // sb_read_columns, sb_write_columns, sb_filter_columns, sb_filter_columns_var, sb_filter_columns_in, sb_read_selected, sb_read_selected_var, sb_aggregate_columns, sb_aggregate_grouped, sb_aggregate_grouped_large, sb_topk_columns, sb_key_ids, sb_key_ids_var, sb_key_combine, sb_read_columns_sizes (its enqueue: the call's own synchronize may be the one that replays), sb_key_lookup, sb_aggregate_weighted, sb_key_buckets
+        enum Kind { READ, WRITE, FILTER, FILTER_VAR, FILTER_IN, READ_SEL, READ_SEL_VAR, AGGREGATE, AGG_GROUPED, AGG_GROUPED_LARGE, TOPK, KEY_IDS, KEY_IDS_VAR, KEY_COMBINE, SIZES, KEY_LOOKUP, AGG_WEIGHTED, KEY_BUCKETS, FILTER_CMP } kind;   // sb_read_columns, sb_write_columns, sb_filter_columns, sb_filter_columns_var, sb_filter_columns_in, sb_read_selected, sb_read_selected_var, sb_aggregate_columns, sb_aggregate_grouped, sb_aggregate_grouped_large, sb_topk_columns, sb_key_ids, sb_key_ids_var, sb_key_combine, sb_read_columns_sizes (its enqueue: the call's own synchronize may be the one that replays), sb_key_lookup, sb_aggregate_weighted, sb_key_buckets, sb_filter_columns_cmp
         void* cols;
         uint64_t n;
         sb_write_options opts;
@@ -367,6 +368,7 @@ inline int32_t reissue(sb_ctx* ctx, sb_ctx::Call& cl) {
         case sb_ctx::Call::KEY_COMBINE: return sb_key_combine(ctx, (sb_key_combine_item*)cl.cols, cl.n, cl.mem);
         case sb_ctx::Call::KEY_LOOKUP: return sb_key_lookup(ctx, (sb_column_key_lookup*)cl.cols, cl.n, cl.mem);
         case sb_ctx::Call::KEY_BUCKETS: return sb_key_buckets(ctx, (sb_column_key_buckets*)cl.cols, cl.n, cl.mem);
+        case sb_ctx::Call::FILTER_CMP: return sb_filter_columns_cmp(ctx, (sb_column_filter_cmp*)cl.cols, cl.n, cl.mem);
     }
     return SB_ERR_INVALID;
 }
