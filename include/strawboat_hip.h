@@ -1185,17 +1185,35 @@ int32_t sb_key_buckets(sb_ctx* ctx, sb_column_key_buckets* cols, uint64_t n, int
  * boolean|binary (src/compression/integer/mod.rs:35-70, double/mod.rs:32-67,
  * boolean/mod.rs:23-61, binary/mod.rs:26-93), and the PageMeta bookkeeping (:102-107).
  * Output: the column's pages back to back (the bytes NativeWriter would write_all) and
- * one sb_page_meta per page. */
+ * one sb_page_meta per page.
+ *
+ * Slices.  A column may be a slice of a longer Arrow array, presented without copying:
+ *  - validity: row i is bit validity_bit_offset + i of `validity`.  The offset may be 8 or more (a Bitmap whose pointer
+ *    was not advanced).  The library reads at most ceil((validity_bit_offset + rows) / 8) bytes from `validity`, and
+ *    nothing outside bits [validity_bit_offset, validity_bit_offset + rows) reaches the pages.
+ *  - Boolean values: row i is bit values_bit_offset + i of `values`, chosen independently of the validity offset; at most
+ *    ceil((values_bit_offset + rows) / 8) bytes are read.  A page of a Basic codec (None / LZ4 / Zstd / Snappy) whose first
+ *    value bit is byte aligned holds the bitmap's bytes as they stand (boolean/mod.rs:44-54): the spare bits of its last
+ *    byte are whatever follows the page in the buffer (the next page's rows, or for the last page the bits behind the
+ *    slice inside that byte).  At an unaligned first bit the page is re-packed from bit 0 and padded with zeros.  RLE and
+ *    OneValue pages never depend on bits outside the slice.
+ *  - Binary / LargeBinary: `offsets` holds rows + 1 entries and offsets[0] may be non-zero: entries [start, start + rows]
+ *    of the parent array.  `values` is then the parent's whole values buffer and `values_len` its whole length
+ *    (array.values().len(), which enters the selector and the hdr9 of Dict / Freq / OneValue pages); only bytes
+ *    [offsets[0], offsets[rows]) are page content.
+ *  - primitives: `values` points at row 0 of the slice, start * width bytes into its buffer; it needs the alignment of
+ *    the type at most (none is required), rows * width bytes are read.
+ * With SB_MEM_HOST exactly these byte counts are staged: (offset + rows + 7) / 8, values_len, (rows + 1) * width. */
 typedef struct sb_column_write {
     int32_t physical_type;
     int32_t is_nullable;
     uint64_t rows;
     const void* values;          /* DEVICE: values buffer / boolean bitmap / binary value bytes */
-    uint64_t values_bit_offset;  /* boolean: bit offset of row 0 in `values` */
+    uint64_t values_bit_offset;  /* boolean: bit offset of row 0 in `values` (any value; see Slices above) */
     uint64_t values_len;         /* binary: byte length of the whole values buffer (array.values().len()) */
     const uint8_t* validity;     /* DEVICE or NULL (no validity bitmap) */
-    uint64_t validity_bit_offset;
-    const void* offsets;         /* DEVICE: binary offsets, rows+1 entries */
+    uint64_t validity_bit_offset; /* bit of row 0 in `validity`; may be >= 8 */
+    const void* offsets;         /* DEVICE: binary offsets, rows+1 entries; offsets[0] may be non-zero */
     /* outputs */
     uint8_t* out_pages;          /* DEVICE, capacity >= sb_write_bound() */
     uint64_t out_capacity;
