@@ -1096,6 +1096,24 @@ static void queue_copybacks(sb_ctx* ctx, sb_column_read* cols, uint64_t n, const
     }
 }
 
+// The list structs of the sinks carry offsets into the call's blob (in_set_append, look_list_append, buck_list_append)
+// until the blob has a device address: `base`, in the call's tables on the page route, in a ReplayArena on the decoded one.
+extern "C++" {   // (overloads: not inside the C linkage of the entry points)
+static void rebase(InCol& c, const uint8_t* base) {
+    c.keys = (const uint64_t*)(base + (size_t)(uintptr_t)c.keys);
+    c.bytes = base + (size_t)(uintptr_t)c.bytes;
+}
+static void rebase(LookCol& c, const uint8_t* base) {
+    c.keys = (const uint64_t*)(base + (size_t)(uintptr_t)c.keys);
+    c.kid = (const uint32_t*)(base + (size_t)(uintptr_t)c.kid);
+    c.bytes = base + (size_t)(uintptr_t)c.bytes;
+}
+static void rebase(BuckCol& c, const uint8_t* base) {
+    c.keys = (const uint64_t*)(base + (size_t)(uintptr_t)c.keys);
+    c.bid = (const uint32_t*)(base + (size_t)(uintptr_t)c.bid);
+}
+}   // extern "C++"
+
 // The call's tables in the staging slot: ColDesc per column, PageTask per page (with the page's share of the scratch
 // buffer, which is grown to fit), and for a filter call its FilterCol per column and the literals
 static int32_t fill_read_tables(sb_ctx* ctx, uint8_t* host, const ReadLayout& L, const sb_column_read* cols, uint64_t n,
@@ -1156,10 +1174,7 @@ static int32_t fill_read_tables(sb_ctx* ctx, uint8_t* host, const ReadLayout& L,
         for (uint64_t i = 0; i < n; i++)
             if (hfc[i].kind == FK_BYTES) hfc[i].lit += (uint64_t)(uintptr_t)(ctx->tables.p + L.lits);
         InCol* hic = mode.in_list ? (InCol*)(host + L.lits) : nullptr;
-        for (uint64_t i = 0; hic && i < n; i++) {
-            hic[i].keys = (const uint64_t*)(ctx->tables.p + L.lits + (size_t)(uintptr_t)hic[i].keys);
-            hic[i].bytes = ctx->tables.p + L.lits + (size_t)(uintptr_t)hic[i].bytes;
-        }
+        for (uint64_t i = 0; hic && i < n; i++) rebase(hic[i], ctx->tables.p + L.lits);
     }
     if (mode.aggregate()) {   // the columns' slots among the call's partial records (read_layout: L.aggp)
         AggCol* hac = (AggCol*)(host + L.fcols);
@@ -1184,22 +1199,13 @@ static int32_t fill_read_tables(sb_ctx* ctx, uint8_t* host, const ReadLayout& L,
             LookCol* hl = (LookCol*)(host + L.bcols);
             memcpy(hl, mode.lookc, n * sizeof(LookCol));
             if (mode.lits && !mode.lits->empty()) memcpy(host + L.lits, mode.lits->data(), mode.lits->size());
-            const uint8_t* base = ctx->tables.p + L.lits;
-            for (uint64_t i = 0; i < n; i++) {
-                hl[i].keys = (const uint64_t*)(base + (size_t)(uintptr_t)hl[i].keys);
-                hl[i].kid = (const uint32_t*)(base + (size_t)(uintptr_t)hl[i].kid);
-                hl[i].bytes = base + (size_t)(uintptr_t)hl[i].bytes;
-            }
+            for (uint64_t i = 0; i < n; i++) rebase(hl[i], ctx->tables.p + L.lits);
         }
         if (mode.key_buckets()) {   // likewise: the bounds and ids travel with the tables
             BuckCol* hb = (BuckCol*)(host + L.bcols);
             memcpy(hb, mode.buckc, n * sizeof(BuckCol));
             if (mode.lits && !mode.lits->empty()) memcpy(host + L.lits, mode.lits->data(), mode.lits->size());
-            const uint8_t* base = ctx->tables.p + L.lits;
-            for (uint64_t i = 0; i < n; i++) {
-                hb[i].keys = (const uint64_t*)(base + (size_t)(uintptr_t)hb[i].keys);
-                hb[i].bid = (const uint32_t*)(base + (size_t)(uintptr_t)hb[i].bid);
-            }
+            for (uint64_t i = 0; i < n; i++) rebase(hb[i], ctx->tables.p + L.lits);
         }
     }
     SelCol* hsc = mode.ranked() ? (SelCol*)(host + L.fcols) : nullptr;
@@ -1716,6 +1722,44 @@ static std::vector<T> take_if(std::vector<T>& v, const std::vector<bool>& dec) {
     v.swap(rest);
     return taken;
 }
+
+// The last part of an entry point begins with the call's columns as read columns, and the callers' structs as the users of
+// their results
+template <class Col>
+static void read_cols_of(Col* cols, uint64_t n, std::vector<sb_column_read>& rc_cols, std::vector<void*>& users) {
+    rc_cols.resize(n);
+    users.resize(n);
+    for (uint64_t i = 0; i < n; i++) {
+        rc_cols[i] = read_col_of(cols[i]);
+        users[i] = &cols[i];
+    }
+}
+
+// The `ids` output of a key sink (id_width, ids, ids_capacity), in two steps as the aggregate check has them: the width,
+// which the limits an entry point checks next go by, and -- once the rows are known -- the buffer.  The message of the
+// refusal (SB_ERR_INVALID) or null.
+template <class Col>
+static const char* ids_check_width(const Col& c) {
+    return c.id_width != 1 && c.id_width != 2 && c.id_width != 4 ? "id_width is not 1, 2 or 4" : nullptr;
+}
+template <class Col>
+static const char* ids_check_buffer(const Col& c, uint64_t rows) {
+    if (rows && !c.ids) return "ids is null";
+    if (c.ids && (((uintptr_t)c.ids & (c.id_width - 1)) || c.ids_capacity < rows * c.id_width))
+        return "ids not aligned to id_width or smaller than rows * id_width bytes";
+    return nullptr;
+}
+// ... and of the columns of one call together: the bytes a column writes are rows * id_width (hs[i].rows: agg_check_fill's)
+template <class Col>
+static const char* ids_check_overlaps(const Col* cols, const std::vector<AggCol>& hs) {
+    for (size_t i = 0; i < hs.size(); i++)
+        for (size_t j = i + 1; j < hs.size(); j++) {
+            const uintptr_t a0 = (uintptr_t)cols[i].ids, a1 = a0 + hs[i].rows * cols[i].id_width;
+            const uintptr_t b0 = (uintptr_t)cols[j].ids, b1 = b0 + hs[j].rows * cols[j].id_width;
+            if (a0 < b1 && b0 < a1) return "ids of two columns of one call overlap";
+        }
+    return nullptr;
+}
 }   // extern "C++"
 
 // The normal route: column i's share of the staging area, cap[i] bytes at a multiple of 64, as the `values` of its read
@@ -1770,6 +1814,92 @@ static int32_t decode_for_replay(sb_ctx* ctx, std::vector<sb_column_read>&& page
     return freq_second_pass(ctx);
 }
 
+// ... as the aggregate and key sinks begin their replay: the rows from the columns' AggCols, the decode, and the decoded
+// columns as the plain kernels take them -- values and validity of each, and its slots in its AggCol: one per TILE_ROWS
+// rows, the columns' back to back.
+struct ReplayCols {
+    std::vector<uint64_t> rows;
+    std::vector<const uint8_t*> vals, bits;
+    uint64_t slots = 0;
+};
+static int32_t open_replay(sb_ctx* ctx, std::vector<sb_column_read>&& pages, std::vector<AggCol>& hs, const char* what, ReplayCols& rp) {
+    const size_t n = hs.size();
+    rp.rows.resize(n);
+    for (size_t i = 0; i < n; i++) rp.rows[i] = hs[i].rows;
+    const sb_column_read* rr = nullptr;
+    int32_t rc = decode_for_replay(ctx, std::move(pages), rp.rows.data(), what, &rr);
+    if (rc != SB_OK) return rc;
+    rp.vals.resize(n);
+    rp.bits.resize(n);
+    for (size_t i = 0; i < n; i++) {
+        rp.vals[i] = (const uint8_t*)rr[i].values;
+        rp.bits[i] = rr[i].is_nullable ? rr[i].validity : nullptr;
+        hs[i].page_slot0 = hs[i].page_slots = 0;
+        hs[i].tile_slot0 = rp.slots;
+        hs[i].tile_slots = (rp.rows[i] + TILE_ROWS - 1) / TILE_ROWS;
+        rp.slots += hs[i].tile_slots;
+    }
+    return SB_OK;
+}
+// ... the large grouped and the weighted sink: the columns' chunks back to back, in the tile slots' place.  Returns the slots.
+static uint64_t chunk_slots(std::vector<AggCol>& hs) {
+    uint64_t slots = 0;
+    for (AggCol& g : hs) {
+        g.tile_slot0 = slots;
+        g.tile_slots = grpl_chunks(g.tile_slots);
+        slots += g.tile_slots;
+    }
+    return slots;
+}
+
+// The temporary device buffer of one decoded call: sections at multiples of 64 in the order they are added, those with a
+// host source uploaded once the buffer exists.  It belongs to the interval (iv.temp_dev) and is freed when that ends.
+// what: the buffer, for the error texts.
+extern "C++" {   // (a member template: not inside the C linkage of the entry points)
+struct ReplayArena {
+    struct Upload {
+        size_t off;
+        const void* host;
+        size_t bytes;
+    };
+    uint8_t* dev = nullptr;
+    size_t total = 0;
+    std::vector<Upload> uploads;
+    size_t add(size_t bytes) {
+        const size_t off = align_up(total, 64);
+        total = off + bytes;
+        return off;
+    }
+    // (the source is read at the upload, not here.  A section of no bytes is not uploaded: the routes' struct arrays never
+    // are one, a decoded call having a column at least, so only an empty blob of lists meets this)
+    size_t add(const void* host, size_t bytes) {
+        const size_t off = add(bytes);
+        if (bytes) uploads.push_back(Upload{off, host, bytes});
+        return off;
+    }
+    int32_t alloc(sb_ctx* ctx, const char* what) {
+        if (hipMalloc((void**)&dev, total + 64) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, std::string("hipMalloc(") + what + ") failed");
+        ctx->iv.temp_dev.push_back(dev);
+        return SB_OK;
+    }
+    // (copies that have ended when they return: their sources do not outlive the call)
+    int32_t upload(sb_ctx* ctx, const std::string& failed) {
+        for (const Upload& u : uploads)
+            if (hipMemcpy(dev + u.off, u.host, u.bytes, hipMemcpyHostToDevice) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, failed);
+        return SB_OK;
+    }
+    // both; a call whose sections hold addresses of the buffer itself takes the two steps apart
+    int32_t commit(sb_ctx* ctx, const char* what) {
+        const int32_t rc = alloc(ctx, what);
+        return rc != SB_OK ? rc : upload(ctx, std::string(what) + ": upload failed");
+    }
+    template <class T>
+    T* at(size_t off) const {
+        return (T*)(dev + off);
+    }
+};
+}   // extern "C++"
+
 // ... second half: the plain kernels are launched, and their results -- `stride` bytes per column at d_res -- travel to
 // the slot, which was acquired before the launches, and from there to the callers at the synchronize.
 static int32_t queue_sink_results(sb_ctx* ctx, StageSlot* slot, const void* d_res, size_t stride, uint64_t n, Pending::Kind kind, void* const* users,
@@ -1791,11 +1921,13 @@ static int32_t filter_columns_decoded(sb_ctx* ctx, std::vector<sb_column_read>&&
     const sb_column_read* rr = nullptr;
     int32_t rc = decode_for_replay(ctx, std::move(pages), rows, "filter", &rr);
     if (rc != SB_OK) return rc;
-    uint64_t* d_counts = nullptr;
-    if (hipMalloc((void**)&d_counts, m * sizeof(uint64_t)) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter counts) failed");
-    ctx->iv.temp_dev.push_back(d_counts);
+    // [bits set per column]
+    ReplayArena a;
+    const size_t o_counts = a.add(m * sizeof(uint64_t));
+    if ((rc = a.commit(ctx, "filter counts")) != SB_OK) return rc;
     StageSlot* slot = acquire_slot(ctx, m * sizeof(uint64_t));
     if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
+    uint64_t* d_counts = a.at<uint64_t>(o_counts);
     for (uint64_t i = 0; i < m; i++) {
         if (hf[i].combine == SB_SEL_SET && rows[i]) (void)hipMemsetAsync(hf[i].sel, 0, (rows[i] + 31) / 32 * 4, s);
         launch_filter_plain(ctx, hf[i], (const uint8_t*)rr[i].values, rr[i].is_nullable ? rr[i].validity : nullptr, rows[i],
@@ -2034,21 +2166,18 @@ static int32_t filter_in_columns_decoded(sb_ctx* ctx, std::vector<sb_column_read
     const sb_column_read* rr = nullptr;
     int32_t rc = decode_for_replay(ctx, std::move(pages), rows, "filter", &rr);
     if (rc != SB_OK) return rc;
-    uint8_t* d_buf = nullptr;
-    const size_t o_sets = align_up(m * sizeof(uint64_t), 64);
-    if (hipMalloc((void**)&d_buf, o_sets + blob.size() + 8) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter counts) failed");
-    ctx->iv.temp_dev.push_back(d_buf);
-    // (a copy that has ended when it returns: `blob` does not outlive the call)
-    if (!blob.empty() && hipMemcpy(d_buf + o_sets, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess)
-        return ctx->fail(SB_ERR_EXTERNAL, "H2D of the lists failed");
-    uint64_t* d_counts = (uint64_t*)d_buf;
+    // [bits set per column][the sets]
+    ReplayArena a;
+    const size_t o_counts = a.add(m * sizeof(uint64_t));
+    const size_t o_sets = a.add(blob.data(), blob.size());
+    if ((rc = a.alloc(ctx, "filter counts")) != SB_OK || (rc = a.upload(ctx, "H2D of the lists failed")) != SB_OK) return rc;
     StageSlot* slot = acquire_slot(ctx, m * sizeof(uint64_t));
     if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
+    uint64_t* d_counts = a.at<uint64_t>(o_counts);
     for (uint64_t i = 0; i < m; i++) {
         if (hf[i].combine == SB_SEL_SET && rows[i]) (void)hipMemsetAsync(hf[i].sel, 0, (rows[i] + 31) / 32 * 4, s);
         InCol ic = hic[i];
-        ic.keys = (const uint64_t*)(d_buf + o_sets + (size_t)(uintptr_t)ic.keys);
-        ic.bytes = d_buf + o_sets + (size_t)(uintptr_t)ic.bytes;
+        rebase(ic, a.at<uint8_t>(o_sets));
         launch_filter_in_plain(ctx, hf[i], ic, (const uint8_t*)rr[i].values, rr[i].is_nullable ? rr[i].validity : nullptr, rows[i],
                                type_width(rr[i].physical_type), d_counts + i);
     }
@@ -2169,11 +2298,13 @@ static int32_t filter_cmp_columns_decoded(sb_ctx* ctx, std::vector<sb_column_rea
     const sb_column_read* rr = nullptr;
     int32_t rc = decode_for_replay(ctx, std::move(pages), rows, "filter", &rr);
     if (rc != SB_OK) return rc;
-    uint64_t* d_counts = nullptr;
-    if (hipMalloc((void**)&d_counts, m * sizeof(uint64_t)) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(filter counts) failed");
-    ctx->iv.temp_dev.push_back(d_counts);
+    // [bits set per column]
+    ReplayArena a;
+    const size_t o_counts = a.add(m * sizeof(uint64_t));
+    if ((rc = a.commit(ctx, "filter counts")) != SB_OK) return rc;
     StageSlot* slot = acquire_slot(ctx, m * sizeof(uint64_t));
     if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
+    uint64_t* d_counts = a.at<uint64_t>(o_counts);
     for (uint64_t i = 0; i < m; i++) {
         if (hf[i].combine == SB_SEL_SET && rows[i]) (void)hipMemsetAsync(hf[i].sel, 0, (rows[i] + 31) / 32 * 4, s);
         launch_filter_cmp_plain(ctx, hf[i], hcc[i], (const uint8_t*)rr[i].values, rr[i].is_nullable ? rr[i].validity : nullptr, rows[i],
@@ -2267,32 +2398,31 @@ static int32_t rsel_columns_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& p
     const sb_column_read* rr = nullptr;
     int32_t rc = decode_for_replay(ctx, std::move(pages), rows, "selected-read", &rr);
     if (rc != SB_OK) return rc;
-    // [SelCol per column][bits set per column][the rank tables]
-    size_t off = align_up(n * sizeof(SelCol), 64);
-    const size_t o_counts = off;
-    off = align_up(off + n * sizeof(uint64_t), 64);
-    std::vector<size_t> o_rank(n);
+    // [SelCol per column][bits set per column][the rank tables, each at a multiple of 16]
+    std::vector<size_t> rank_off(n);
+    size_t rank_bytes = 0;
     for (uint64_t i = 0; i < n; i++) {
-        o_rank[i] = off;
-        off += align_up(rsel_rank_words(rows[i]) * 8, 16);
+        rank_off[i] = rank_bytes;
+        rank_bytes += align_up(rsel_rank_words(rows[i]) * 8, 16);
     }
-    uint8_t* dev = nullptr;
-    if (hipMalloc((void**)&dev, off) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(selected-read replay) failed");
-    ctx->iv.temp_dev.push_back(dev);
+    ReplayArena a;
+    const size_t o_sc = a.add(hs.data(), n * sizeof(SelCol));
+    const size_t o_counts = a.add(n * sizeof(uint64_t));
+    const size_t o_rank = a.add(rank_bytes);
+    if ((rc = a.alloc(ctx, "selected-read replay")) != SB_OK) return rc;
     std::vector<const uint8_t*> vals(n), bits(n);
     bool any_nullable = false;
     for (uint64_t i = 0; i < n; i++) {
-        hs[i].rank = (uint64_t*)(dev + o_rank[i]);
+        hs[i].rank = a.at<uint64_t>(o_rank + rank_off[i]);
         vals[i] = (const uint8_t*)rr[i].values;
         bits[i] = rr[i].is_nullable ? rr[i].validity : nullptr;
         if (hs[i].validity) any_nullable = true;
     }
-    if (hipMemcpy(dev, hs.data(), n * sizeof(SelCol), hipMemcpyHostToDevice) != hipSuccess)
-        return ctx->fail(SB_ERR_EXTERNAL, "selected-read replay: upload failed");
+    if ((rc = a.upload(ctx, "selected-read replay: upload failed")) != SB_OK) return rc;
     StageSlot* slot = acquire_slot(ctx, n * sizeof(uint64_t));
     if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
-    uint64_t* d_counts = (uint64_t*)(dev + o_counts);
-    launch_rsel_plain(ctx, (const SelCol*)dev, (uint32_t)n, d_counts, any_nullable, rows, vals.data(), bits.data());
+    uint64_t* d_counts = a.at<uint64_t>(o_counts);
+    launch_rsel_plain(ctx, a.at<const SelCol>(o_sc), (uint32_t)n, d_counts, any_nullable, rows, vals.data(), bits.data());
     return queue_sink_results(ctx, slot, d_counts, sizeof(uint64_t), n, Pending::RSEL_COL, users, nullptr, "selected-read");
 }
 
@@ -2484,50 +2614,26 @@ static std::vector<uint64_t> agg_stage_caps(const std::vector<AggCol>& hs) {
     return cap;
 }
 
-// The decoded columns of a replay as the plain kernels of the aggregate, grouped and top-k sinks take them: values and
-// validity of each, and its slots in its AggCol -- one per TILE_ROWS rows, the columns' back to back.  Returns the slots.
-static uint64_t replay_slots(const sb_column_read* rr, const std::vector<uint64_t>& rows, std::vector<AggCol>& hs, std::vector<const uint8_t*>& vals,
-                             std::vector<const uint8_t*>& bits) {
-    uint64_t slots = 0;
-    for (size_t i = 0; i < hs.size(); i++) {
-        vals[i] = (const uint8_t*)rr[i].values;
-        bits[i] = rr[i].is_nullable ? rr[i].validity : nullptr;
-        hs[i].page_slot0 = hs[i].page_slots = 0;
-        hs[i].tile_slot0 = slots;
-        hs[i].tile_slots = (rows[i] + TILE_ROWS - 1) / TILE_ROWS;
-        slots += hs[i].tile_slots;
-    }
-    return slots;
-}
-
 // The columns with a value op of a replayed call: decoded, and reduced from the staging area by k_agg_plain with the same
 // sink: a slot per TILE_ROWS rows.
 static int32_t agg_columns_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pages, std::vector<AggCol>& hs, void* const* users) {
     const uint64_t n = pages.size();
-    std::vector<uint64_t> rows(n);
-    for (uint64_t i = 0; i < n; i++) rows[i] = hs[i].rows;
-    const sb_column_read* rr = nullptr;
-    int32_t rc = decode_for_replay(ctx, std::move(pages), rows.data(), "aggregate", &rr);
+    ReplayCols rp;
+    int32_t rc = open_replay(ctx, std::move(pages), hs, "aggregate", rp);
     if (rc != SB_OK) return rc;
     // [AggCol per column][the result records][the partial records: a slot per TILE_ROWS rows]
-    size_t off = align_up(n * sizeof(AggCol), 64);
-    const size_t o_res = off;
-    off = align_up(off + n * AGG_RESULT_WORDS * sizeof(uint64_t), 64);
-    const size_t o_parts = off;
-    std::vector<const uint8_t*> vals(n), bits(n);
-    const uint64_t slots = replay_slots(rr, rows, hs, vals, bits);
-    off += (size_t)slots * sizeof(AggPart);
-    uint8_t* dev = nullptr;
-    if (hipMalloc((void**)&dev, off + 64) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(aggregate replay) failed");
-    ctx->iv.temp_dev.push_back(dev);
-    if (hipMemcpy(dev, hs.data(), n * sizeof(AggCol), hipMemcpyHostToDevice) != hipSuccess)
-        return ctx->fail(SB_ERR_EXTERNAL, "aggregate replay: upload failed");
-    StageSlot* slot = acquire_slot(ctx, n * AGG_RESULT_WORDS * sizeof(uint64_t));
+    const size_t res_stride = AGG_RESULT_WORDS * sizeof(uint64_t);
+    ReplayArena a;
+    const size_t o_ac = a.add(hs.data(), n * sizeof(AggCol));
+    const size_t o_res = a.add(n * res_stride);
+    const size_t o_parts = a.add((size_t)rp.slots * sizeof(AggPart));
+    if ((rc = a.commit(ctx, "aggregate replay")) != SB_OK) return rc;
+    StageSlot* slot = acquire_slot(ctx, n * res_stride);
     if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
-    uint64_t* d_res = (uint64_t*)(dev + o_res);
-    launch_agg_plain(ctx, (const AggCol*)dev, (uint32_t)n, (AggPart*)(dev + o_parts), rows.data(), vals.data(), bits.data());
-    launch_agg_finish(ctx, (const AggCol*)dev, (const AggPart*)(dev + o_parts), d_res, (uint32_t)n);
-    return queue_sink_results(ctx, slot, d_res, AGG_RESULT_WORDS * sizeof(uint64_t), n, Pending::AGG_COL, users, nullptr, "aggregate");
+    uint64_t* d_res = a.at<uint64_t>(o_res);
+    launch_agg_plain(ctx, a.at<const AggCol>(o_ac), (uint32_t)n, a.at<AggPart>(o_parts), rp.rows.data(), rp.vals.data(), rp.bits.data());
+    launch_agg_finish(ctx, a.at<const AggCol>(o_ac), a.at<const AggPart>(o_parts), d_res, (uint32_t)n);
+    return queue_sink_results(ctx, slot, d_res, res_stride, n, Pending::AGG_COL, users, nullptr, "aggregate");
 }
 
 int32_t sb_aggregate_columns(sb_ctx* ctx, sb_column_aggregate* cols, uint64_t n, int32_t mem) {
@@ -2537,12 +2643,9 @@ int32_t sb_aggregate_columns(sb_ctx* ctx, sb_column_aggregate* cols, uint64_t n,
     for (uint64_t i = 0; i < n; i++)
         if ((rc = agg_check_ops(ctx, cols[i])) != SB_OK || (rc = agg_check_fill(ctx, cols[i], cols[i].ops, hs[i])) != SB_OK) return rc;
     (void)hipSetDevice(ctx->device);
-    std::vector<sb_column_read> rc_cols(n);
-    std::vector<void*> users(n);
-    for (uint64_t i = 0; i < n; i++) {
-        rc_cols[i] = read_col_of(cols[i]);
-        users[i] = &cols[i];
-    }
+    std::vector<sb_column_read> rc_cols;
+    std::vector<void*> users;
+    read_cols_of(cols, n, rc_cols, users);
     if (ctx->in_replay && ctx->filter_freq) {
         // The columns that met a Freq page in the first pass (and so asked for this replay, or would have) through a full
         // decode; the others as ever, on the page route, whose slots -- and float bits -- are those of an interval that is
@@ -2584,51 +2687,32 @@ int32_t sb_aggregate_columns(sb_ctx* ctx, sb_column_aggregate* cols, uint64_t n,
 static int32_t grp_columns_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pages, std::vector<AggCol>& hs, const std::vector<GrpCol>& hg,
                                    void* const* users, bool large) {
     const uint64_t n = pages.size();
-    std::vector<uint64_t> rows(n);
-    for (uint64_t i = 0; i < n; i++) rows[i] = hs[i].rows;
-    const sb_column_read* rr = nullptr;
-    int32_t rc = decode_for_replay(ctx, std::move(pages), rows.data(), "grouped aggregate", &rr);
+    ReplayCols rp;
+    int32_t rc = open_replay(ctx, std::move(pages), hs, "grouped aggregate", rp);
     if (rc != SB_OK) return rc;
     uint32_t gmax = 1;
     for (const GrpCol& g : hg) gmax = std::max(gmax, g.n_groups);
-    std::vector<const uint8_t*> vals(n), bits(n);
-    uint64_t slots = replay_slots(rr, rows, hs, vals, bits);
-    if (large) {   // the columns' chunks back to back, in the tile slots' place
-        slots = 0;
-        for (AggCol& g : hs) {
-            g.tile_slot0 = slots;
-            g.tile_slots = grpl_chunks(g.tile_slots);
-            slots += g.tile_slots;
-        }
-    }
+    const uint64_t slots = large ? chunk_slots(hs) : rp.slots;
     // [AggCol per column][GrpCol per column][the results][the slots' flags, the columns' counters and Freq marks][the slots' records]
     const size_t res_stride = grp_result_words(gmax) * sizeof(uint64_t);
-    size_t off = align_up(n * sizeof(AggCol), 64);
-    const size_t o_gc = off;
-    off = align_up(off + n * sizeof(GrpCol), 64);
-    const size_t o_res = off;
-    off = align_up(off + n * res_stride, 64);
-    const size_t o_flags = off;
-    off = align_up(off + (size_t)(slots + 2 * n) * sizeof(uint64_t), 64);
-    const size_t o_recs = off;
-    off += (size_t)slots * gmax * sizeof(GrpPart);
-    uint8_t* dev = nullptr;
-    if (hipMalloc((void**)&dev, off + 64) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(grouped aggregate replay) failed");
-    ctx->iv.temp_dev.push_back(dev);
-    if (hipMemcpy(dev, hs.data(), n * sizeof(AggCol), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dev + o_gc, hg.data(), n * sizeof(GrpCol), hipMemcpyHostToDevice) != hipSuccess)
-        return ctx->fail(SB_ERR_EXTERNAL, "grouped aggregate replay: upload failed");
+    ReplayArena a;
+    const size_t o_ac = a.add(hs.data(), n * sizeof(AggCol));
+    const size_t o_gc = a.add(hg.data(), n * sizeof(GrpCol));
+    const size_t o_res = a.add(n * res_stride);
+    const size_t o_flags = a.add((size_t)(slots + 2 * n) * sizeof(uint64_t));
+    const size_t o_recs = a.add((size_t)slots * gmax * sizeof(GrpPart));
+    if ((rc = a.commit(ctx, "grouped aggregate replay")) != SB_OK) return rc;
     StageSlot* slot = acquire_slot(ctx, n * res_stride);
     if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
-    uint64_t* d_res = (uint64_t*)(dev + o_res);
-    GrpLaunch gl{(const AggCol*)dev, (const GrpCol*)(dev + o_gc), (uint64_t*)(dev + o_flags), (GrpPart*)(dev + o_recs), slots, 0, gmax, true, false, (uint32_t)n, true};
+    uint64_t* d_res = a.at<uint64_t>(o_res);
+    GrpLaunch gl{a.at<const AggCol>(o_ac), a.at<const GrpCol>(o_gc), a.at<uint64_t>(o_flags), a.at<GrpPart>(o_recs), slots, 0, gmax, true, false, (uint32_t)n, true};
     if (large) {
         launch_grpl_zero(ctx, gl, (uint32_t)n);
-        launch_grpl_plain(ctx, gl, (uint32_t)n, rows.data(), vals.data(), bits.data());
+        launch_grpl_plain(ctx, gl, (uint32_t)n, rp.rows.data(), rp.vals.data(), rp.bits.data());
         launch_grpl_finish(ctx, gl, d_res, (uint32_t)n);
     } else {
         launch_grp_zero(ctx, gl, (uint32_t)n);
-        launch_grp_plain(ctx, gl, (uint32_t)n, rows.data(), vals.data(), bits.data());
+        launch_grp_plain(ctx, gl, (uint32_t)n, rp.rows.data(), rp.vals.data(), rp.bits.data());
         launch_grp_finish(ctx, gl, d_res, (uint32_t)n);
     }
     return queue_sink_results(ctx, slot, d_res, res_stride, n, large ? Pending::AGG_GRPL_COL : Pending::AGG_GRP_COL, users, hg.data(), "grouped aggregate");
@@ -2658,12 +2742,9 @@ static int32_t aggregate_grouped_impl(sb_ctx* ctx, sb_column_aggregate_grouped* 
         hg[i] = GrpCol{(const uint8_t*)c.group_ids, c.group_id_width, c.n_groups};
     }
     (void)hipSetDevice(ctx->device);
-    std::vector<sb_column_read> rc_cols(n);
-    std::vector<void*> users(n);
-    for (uint64_t i = 0; i < n; i++) {
-        rc_cols[i] = read_col_of(cols[i]);
-        users[i] = &cols[i];
-    }
+    std::vector<sb_column_read> rc_cols;
+    std::vector<void*> users;
+    read_cols_of(cols, n, rc_cols, users);
     if (ctx->in_replay && ctx->filter_freq) {
         // The columns that met a Freq page in the first pass (and so asked for this replay, or would have) through a full
         // decode; the others as ever, on the page route, whose slots -- and float bits -- are those of an interval that is
@@ -2717,49 +2798,30 @@ static_assert(sizeof(sb_column_aggregate_weighted) == 168 && offsetof(sb_column_
 static int32_t wgt_columns_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pages, std::vector<AggCol>& hs, const std::vector<GrpCol>& hg,
                                    const std::vector<WgtCol>& hw, void* const* users) {
     const uint64_t n = pages.size();
-    std::vector<uint64_t> rows(n);
-    for (uint64_t i = 0; i < n; i++) rows[i] = hs[i].rows;
-    const sb_column_read* rr = nullptr;
-    int32_t rc = decode_for_replay(ctx, std::move(pages), rows.data(), "weighted aggregate", &rr);
+    ReplayCols rp;
+    int32_t rc = open_replay(ctx, std::move(pages), hs, "weighted aggregate", rp);
     if (rc != SB_OK) return rc;
     uint32_t gmax = 1;
     for (const GrpCol& g : hg) gmax = std::max(gmax, g.n_groups);
-    std::vector<const uint8_t*> vals(n), bits(n);
-    (void)replay_slots(rr, rows, hs, vals, bits);
-    uint64_t slots = 0;   // the columns' chunks back to back, in the tile slots' place
-    for (AggCol& g : hs) {
-        g.tile_slot0 = slots;
-        g.tile_slots = grpl_chunks(g.tile_slots);
-        slots += g.tile_slots;
-    }
+    const uint64_t slots = chunk_slots(hs);
     // [AggCol per column][GrpCol per column][WgtCol per column][the results][the slots' flags, the columns' counters and Freq marks][the slots' records]
     const size_t res_stride = grp_result_words(gmax) * sizeof(uint64_t);
-    size_t off = align_up(n * sizeof(AggCol), 64);
-    const size_t o_gc = off;
-    off = align_up(off + n * sizeof(GrpCol), 64);
-    const size_t o_wc = off;
-    off = align_up(off + n * sizeof(WgtCol), 64);
-    const size_t o_res = off;
-    off = align_up(off + n * res_stride, 64);
-    const size_t o_flags = off;
-    off = align_up(off + (size_t)(slots + 2 * n) * sizeof(uint64_t), 64);
-    const size_t o_recs = off;
-    off += (size_t)slots * gmax * sizeof(GrpPart);
-    uint8_t* dev = nullptr;
-    if (hipMalloc((void**)&dev, off + 64) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(weighted aggregate replay) failed");
-    ctx->iv.temp_dev.push_back(dev);
-    if (hipMemcpy(dev, hs.data(), n * sizeof(AggCol), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dev + o_gc, hg.data(), n * sizeof(GrpCol), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dev + o_wc, hw.data(), n * sizeof(WgtCol), hipMemcpyHostToDevice) != hipSuccess)
-        return ctx->fail(SB_ERR_EXTERNAL, "weighted aggregate replay: upload failed");
+    ReplayArena a;
+    const size_t o_ac = a.add(hs.data(), n * sizeof(AggCol));
+    const size_t o_gc = a.add(hg.data(), n * sizeof(GrpCol));
+    const size_t o_wc = a.add(hw.data(), n * sizeof(WgtCol));
+    const size_t o_res = a.add(n * res_stride);
+    const size_t o_flags = a.add((size_t)(slots + 2 * n) * sizeof(uint64_t));
+    const size_t o_recs = a.add((size_t)slots * gmax * sizeof(GrpPart));
+    if ((rc = a.commit(ctx, "weighted aggregate replay")) != SB_OK) return rc;
     StageSlot* slot = acquire_slot(ctx, n * res_stride);
     if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
-    uint64_t* d_res = (uint64_t*)(dev + o_res);
-    const WgtLaunch wl{GrpLaunch{(const AggCol*)dev, (const GrpCol*)(dev + o_gc), (uint64_t*)(dev + o_flags), (GrpPart*)(dev + o_recs), slots, 0, gmax, true, false,
+    uint64_t* d_res = a.at<uint64_t>(o_res);
+    const WgtLaunch wl{GrpLaunch{a.at<const AggCol>(o_ac), a.at<const GrpCol>(o_gc), a.at<uint64_t>(o_flags), a.at<GrpPart>(o_recs), slots, 0, gmax, true, false,
                                  (uint32_t)n, true},
-                       (const WgtCol*)(dev + o_wc)};
+                       a.at<const WgtCol>(o_wc)};
     launch_wgt_zero(ctx, wl, (uint32_t)n);
-    launch_wgt_plain(ctx, wl, (uint32_t)n, rows.data(), vals.data(), bits.data());
+    launch_wgt_plain(ctx, wl, (uint32_t)n, rp.rows.data(), rp.vals.data(), rp.bits.data());
     launch_wgt_finish(ctx, wl, d_res, (uint32_t)n);
     return queue_sink_results(ctx, slot, d_res, res_stride, n, Pending::AGG_WGT_COL, users, hg.data(), "weighted aggregate");
 }
@@ -2805,12 +2867,9 @@ int32_t sb_aggregate_weighted(sb_ctx* ctx, sb_column_aggregate_weighted* cols, u
         hw[i] = WgtCol{square ? nullptr : (const uint8_t*)c.weights, square ? nullptr : c.weights_validity, wkind, ww, flt ? 1u : 0u, 0u};
     }
     (void)hipSetDevice(ctx->device);
-    std::vector<sb_column_read> rc_cols(n);
-    std::vector<void*> users(n);
-    for (uint64_t i = 0; i < n; i++) {
-        rc_cols[i] = read_col_of(cols[i]);
-        users[i] = &cols[i];
-    }
+    std::vector<sb_column_read> rc_cols;
+    std::vector<void*> users;
+    read_cols_of(cols, n, rc_cols, users);
     if (ctx->in_replay && ctx->filter_freq) {
         // the columns that met a Freq page in the first pass through a full decode, the others on the page route
         // (aggregate_grouped_impl has the same rule); the marks are this call's own
@@ -2853,38 +2912,26 @@ int32_t sb_aggregate_weighted(sb_ctx* ctx, sb_column_aggregate_weighted* cols, u
 static int32_t topk_columns_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pages, std::vector<AggCol>& hs, const std::vector<TopkCol>& ht,
                                     void* const* users) {
     const uint64_t n = pages.size();
-    std::vector<uint64_t> rows(n);
-    for (uint64_t i = 0; i < n; i++) rows[i] = hs[i].rows;
-    const sb_column_read* rr = nullptr;
-    int32_t rc = decode_for_replay(ctx, std::move(pages), rows.data(), "top-k", &rr);
+    ReplayCols rp;
+    int32_t rc = open_replay(ctx, std::move(pages), hs, "top-k", rp);
     if (rc != SB_OK) return rc;
     uint32_t kmax = 1;
     for (const TopkCol& t : ht) kmax = std::max(kmax, t.k);
-    std::vector<const uint8_t*> vals(n), bits(n);
-    const uint64_t slots = replay_slots(rr, rows, hs, vals, bits);
     // [AggCol per column][TopkCol per column][the results][the slots' headers][the slots' records]
     const size_t res_stride = topk_result_words(kmax) * sizeof(uint64_t);
-    size_t off = align_up(n * sizeof(AggCol), 64);
-    const size_t o_tc = off;
-    off = align_up(off + n * sizeof(TopkCol), 64);
-    const size_t o_res = off;
-    off = align_up(off + n * res_stride, 64);
-    const size_t o_heads = off;
-    off = align_up(off + (size_t)slots * sizeof(TopkHead), 64);
-    const size_t o_recs = off;
-    off += (size_t)slots * kmax * sizeof(TopkRec);
-    uint8_t* dev = nullptr;
-    if (hipMalloc((void**)&dev, off + 64) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(top-k replay) failed");
-    ctx->iv.temp_dev.push_back(dev);
-    if (hipMemcpy(dev, hs.data(), n * sizeof(AggCol), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dev + o_tc, ht.data(), n * sizeof(TopkCol), hipMemcpyHostToDevice) != hipSuccess)
-        return ctx->fail(SB_ERR_EXTERNAL, "top-k replay: upload failed");
+    ReplayArena a;
+    const size_t o_ac = a.add(hs.data(), n * sizeof(AggCol));
+    const size_t o_tc = a.add(ht.data(), n * sizeof(TopkCol));
+    const size_t o_res = a.add(n * res_stride);
+    const size_t o_heads = a.add((size_t)rp.slots * sizeof(TopkHead));
+    const size_t o_recs = a.add((size_t)rp.slots * kmax * sizeof(TopkRec));
+    if ((rc = a.commit(ctx, "top-k replay")) != SB_OK) return rc;
     StageSlot* slot = acquire_slot(ctx, n * res_stride);
     if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
-    uint64_t* d_res = (uint64_t*)(dev + o_res);
-    TopkLaunch tl{(const AggCol*)dev, (const TopkCol*)(dev + o_tc), (TopkHead*)(dev + o_heads), (TopkRec*)(dev + o_recs), slots, 0, kmax};
+    uint64_t* d_res = a.at<uint64_t>(o_res);
+    TopkLaunch tl{a.at<const AggCol>(o_ac), a.at<const TopkCol>(o_tc), a.at<TopkHead>(o_heads), a.at<TopkRec>(o_recs), rp.slots, 0, kmax};
     launch_topk_zero(ctx, tl);
-    launch_topk_plain(ctx, tl, (uint32_t)n, rows.data(), vals.data(), bits.data());
+    launch_topk_plain(ctx, tl, (uint32_t)n, rp.rows.data(), rp.vals.data(), rp.bits.data());
     launch_topk_finish(ctx, tl, d_res, (uint32_t)n);
     return queue_sink_results(ctx, slot, d_res, res_stride, n, Pending::TOPK_COL, users, nullptr, "top-k");
 }
@@ -2906,12 +2953,9 @@ int32_t sb_topk_columns(sb_ctx* ctx, sb_column_topk* cols, uint64_t n, int32_t m
         ht[i] = TopkCol{c.k, c.order == SB_TOPK_LARGEST ? 1u : 0u};
     }
     (void)hipSetDevice(ctx->device);
-    std::vector<sb_column_read> rc_cols(n);
-    std::vector<void*> users(n);
-    for (uint64_t i = 0; i < n; i++) {
-        rc_cols[i] = read_col_of(cols[i]);
-        users[i] = &cols[i];
-    }
+    std::vector<sb_column_read> rc_cols;
+    std::vector<void*> users;
+    read_cols_of(cols, n, rc_cols, users);
     if (ctx->in_replay && ctx->filter_freq) {
         // Every column through a full decode, as sb_aggregate_columns has it.  The result is one set in one sequence on
         // either route, so which interval a column is decoded in does not show in its bytes.
@@ -2947,38 +2991,26 @@ static KeyLaunch key_launch_at(uint8_t* acols, uint8_t* kcols, uint8_t* state, u
 static int32_t key_ids_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pages, std::vector<AggCol>& hs, const std::vector<KeyCol>& hk, uint64_t slots,
                                uint32_t kmax, void* const* users) {
     const uint64_t n = pages.size();
-    std::vector<uint64_t> rows(n);
-    for (uint64_t i = 0; i < n; i++) rows[i] = hs[i].rows;
-    const sb_column_read* rr = nullptr;
-    int32_t rc = decode_for_replay(ctx, std::move(pages), rows.data(), "key ids", &rr);
+    ReplayCols rp;
+    int32_t rc = open_replay(ctx, std::move(pages), hs, "key ids", rp);
     if (rc != SB_OK) return rc;
-    std::vector<const uint8_t*> vals(n), bits(n);
-    (void)replay_slots(rr, rows, hs, vals, bits);
     // [AggCol per column][KeyCol per column][the results][the columns' states, their tables][the sorted keys]
     const size_t res_stride = key_result_words(kmax) * sizeof(uint64_t);
-    size_t off = align_up(n * sizeof(AggCol), 64);
-    const size_t o_kc = off;
-    off = align_up(off + n * sizeof(KeyCol), 64);
-    const size_t o_res = off;
-    off = align_up(off + n * res_stride, 64);
-    const size_t o_state = off;
-    off = align_up(off + n * sizeof(KeyState) + (size_t)slots * sizeof(uint64_t), 64);
-    const size_t o_sorted = off;
-    off += n * KEY_MAX_KEYS * sizeof(uint64_t);
-    uint8_t* dev = nullptr;
-    if (hipMalloc((void**)&dev, off + 64) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(key ids replay) failed");
-    ctx->iv.temp_dev.push_back(dev);
-    if (hipMemcpy(dev, hs.data(), n * sizeof(AggCol), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dev + o_kc, hk.data(), n * sizeof(KeyCol), hipMemcpyHostToDevice) != hipSuccess)
-        return ctx->fail(SB_ERR_EXTERNAL, "key ids replay: upload failed");
+    ReplayArena a;
+    const size_t o_ac = a.add(hs.data(), n * sizeof(AggCol));
+    const size_t o_kc = a.add(hk.data(), n * sizeof(KeyCol));
+    const size_t o_res = a.add(n * res_stride);
+    const size_t o_state = a.add(n * sizeof(KeyState) + (size_t)slots * sizeof(uint64_t));
+    const size_t o_sorted = a.add(n * KEY_MAX_KEYS * sizeof(uint64_t));
+    if ((rc = a.commit(ctx, "key ids replay")) != SB_OK) return rc;
     StageSlot* slot = acquire_slot(ctx, n * res_stride);
     if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
-    uint64_t* d_res = (uint64_t*)(dev + o_res);
-    const KeyLaunch kl = key_launch_at(dev, dev + o_kc, dev + o_state, dev + o_sorted, n, slots, kmax);
+    uint64_t* d_res = a.at<uint64_t>(o_res);
+    const KeyLaunch kl = key_launch_at(a.at<uint8_t>(o_ac), a.at<uint8_t>(o_kc), a.at<uint8_t>(o_state), a.at<uint8_t>(o_sorted), n, slots, kmax);
     launch_key_zero(ctx, kl);
-    launch_key_collect_plain(ctx, kl, rows.data(), vals.data(), bits.data());
+    launch_key_collect_plain(ctx, kl, rp.rows.data(), rp.vals.data(), rp.bits.data());
     launch_key_finish(ctx, kl, d_res);
-    launch_key_assign_plain(ctx, kl, rows.data(), vals.data(), bits.data());
+    launch_key_assign_plain(ctx, kl, rp.rows.data(), rp.vals.data(), rp.bits.data());
     return queue_sink_results(ctx, slot, d_res, res_stride, n, Pending::KEY_COL, users, nullptr, "key ids");
 }
 
@@ -2994,34 +3026,23 @@ int32_t sb_key_ids(sb_ctx* ctx, sb_column_key_ids* cols, uint64_t n, int32_t mem
         if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(ctx, SB_ERR_INVALID, "bad physical_type");
         if (c.physical_type < SB_TYPE_INT8 || c.physical_type > SB_TYPE_UINT64)
             return refuse(ctx, SB_ERR_NYI, "key ids are implemented for 8- to 64-bit integers");
-        if (c.id_width != 1 && c.id_width != 2 && c.id_width != 4) return refuse(ctx, SB_ERR_INVALID, "id_width is not 1, 2 or 4");
+        if (const char* why = ids_check_width(c)) return refuse(ctx, SB_ERR_INVALID, why);
         const uint64_t limit = std::min<uint64_t>(SB_KEY_MAX_KEYS, (1ull << (8 * c.id_width)) - 1);
         if (c.max_keys == 0 || c.max_keys > limit) return refuse(ctx, SB_ERR_INVALID, "max_keys is not in 1 .. min(SB_KEY_MAX_KEYS, 2^(8 * id_width) - 1)");
         if (c.reserved) return refuse(ctx, SB_ERR_INVALID, "reserved is not 0");
         if (!c.keys) return refuse(ctx, SB_ERR_INVALID, "keys is null");
         // (collected like a minimum: every live value is looked at)
         if ((rc = agg_check_fill(ctx, c, SB_AGG_MIN, hs[i], "key ids are implemented for 8- to 64-bit integers")) != SB_OK) return rc;
-        const uint64_t rows = hs[i].rows;
-        if (rows && !c.ids) return refuse(ctx, SB_ERR_INVALID, "ids is null");
-        if (c.ids && (((uintptr_t)c.ids & (c.id_width - 1)) || c.ids_capacity < rows * c.id_width))
-            return refuse(ctx, SB_ERR_INVALID, "ids not aligned to id_width or smaller than rows * id_width bytes");
+        if (const char* why = ids_check_buffer(c, hs[i].rows)) return refuse(ctx, SB_ERR_INVALID, why);
         hk[i] = KeyCol{(uint8_t*)c.ids, slots, key_table_slots(c.max_keys) - 1, c.max_keys, c.id_width, 0};
         slots += key_table_slots(c.max_keys);
         kmax = std::max(kmax, c.max_keys);
     }
-    for (uint64_t i = 0; i < n; i++)   // (the bytes a column writes: rows * id_width)
-        for (uint64_t j = i + 1; j < n; j++) {
-            const uintptr_t a0 = (uintptr_t)cols[i].ids, a1 = a0 + hs[i].rows * cols[i].id_width;
-            const uintptr_t b0 = (uintptr_t)cols[j].ids, b1 = b0 + hs[j].rows * cols[j].id_width;
-            if (a0 < b1 && b0 < a1) return refuse(ctx, SB_ERR_INVALID, "ids of two columns of one call overlap");
-        }
+    if (const char* why = ids_check_overlaps(cols, hs)) return refuse(ctx, SB_ERR_INVALID, why);
     (void)hipSetDevice(ctx->device);
-    std::vector<sb_column_read> rc_cols(n);
-    std::vector<void*> users(n);
-    for (uint64_t i = 0; i < n; i++) {
-        rc_cols[i] = read_col_of(cols[i]);
-        users[i] = &cols[i];
-    }
+    std::vector<sb_column_read> rc_cols;
+    std::vector<void*> users;
+    read_cols_of(cols, n, rc_cols, users);
     if (ctx->in_replay && ctx->filter_freq) {
         // Every column through a full decode, as sb_aggregate_columns has it.  Keys and ids are functions of the data alone,
         // so which interval a column is decoded in does not show in its bytes.
@@ -3070,7 +3091,7 @@ int32_t sb_key_ids_var(sb_ctx* ctx, sb_column_key_ids_var* cols, uint64_t n, int
         const sb_column_key_ids_var& c = cols[i];
         if (c.physical_type < 0 || c.physical_type > SB_TYPE_NULL) return refuse(ctx, SB_ERR_INVALID, "bad physical_type");
         if (!is_binary_t(c.physical_type)) return refuse(ctx, SB_ERR_NYI, "sb_key_ids_var takes Binary / LargeBinary columns (integers: sb_key_ids)");
-        if (c.id_width != 1 && c.id_width != 2 && c.id_width != 4) return refuse(ctx, SB_ERR_INVALID, "id_width is not 1, 2 or 4");
+        if (const char* why = ids_check_width(c)) return refuse(ctx, SB_ERR_INVALID, why);
         const uint64_t limit = std::min<uint64_t>(SB_KEY_MAX_KEYS, (1ull << (8 * c.id_width)) - 1);
         if (c.max_keys == 0 || c.max_keys > limit) return refuse(ctx, SB_ERR_INVALID, "max_keys is not in 1 .. min(SB_KEY_MAX_KEYS, 2^(8 * id_width) - 1)");
         if (c.reserved) return refuse(ctx, SB_ERR_INVALID, "reserved is not 0");
@@ -3078,10 +3099,7 @@ int32_t sb_key_ids_var(sb_ctx* ctx, sb_column_key_ids_var* cols, uint64_t n, int
         if (c.keys_capacity > SB_KEY_VAR_MAX_BYTES) return refuse(ctx, SB_ERR_INVALID, "keys_capacity exceeds SB_KEY_VAR_MAX_BYTES");
         if (!c.keys && c.keys_capacity) return refuse(ctx, SB_ERR_INVALID, "keys is null");
         if ((rc = agg_check_fill(ctx, c, 0u, hs[i])) != SB_OK) return rc;
-        const uint64_t rows = hs[i].rows;
-        if (rows && !c.ids) return refuse(ctx, SB_ERR_INVALID, "ids is null");
-        if (c.ids && (((uintptr_t)c.ids & (c.id_width - 1)) || c.ids_capacity < rows * c.id_width))
-            return refuse(ctx, SB_ERR_INVALID, "ids not aligned to id_width or smaller than rows * id_width bytes");
+        if (const char* why = ids_check_buffer(c, hs[i].rows)) return refuse(ctx, SB_ERR_INVALID, why);
         // page and row / entry number are fields of the word a slot holds (kv_word, sb_common.h)
         for (uint64_t p = 0; p < c.n_pages; p++)
             if (c.metas[p].num_values > (1ull << KEYV_INDEX_BITS) || c.metas[p].length / 8 >= (1ull << KEYV_INDEX_BITS))
@@ -3094,19 +3112,11 @@ int32_t sb_key_ids_var(sb_ctx* ctx, sb_column_key_ids_var* cols, uint64_t n, int
         cap[i] = c.stage_capacity ? c.stage_capacity : 4 * c.pages_len;   // (the caller's field stays as given: a replay reads it again)
     }
     if (pages >= (1ull << KEYV_PAGE_BITS)) return refuse(ctx, SB_ERR_NYI, "sb_key_ids_var: 2^28 pages or more in one call");
-    for (uint64_t i = 0; i < n; i++)   // (the bytes a column writes: rows * id_width)
-        for (uint64_t j = i + 1; j < n; j++) {
-            const uintptr_t a0 = (uintptr_t)cols[i].ids, a1 = a0 + hs[i].rows * cols[i].id_width;
-            const uintptr_t b0 = (uintptr_t)cols[j].ids, b1 = b0 + hs[j].rows * cols[j].id_width;
-            if (a0 < b1 && b0 < a1) return refuse(ctx, SB_ERR_INVALID, "ids of two columns of one call overlap");
-        }
+    if (const char* why = ids_check_overlaps(cols, hs)) return refuse(ctx, SB_ERR_INVALID, why);
     (void)hipSetDevice(ctx->device);
-    std::vector<sb_column_read> rc_cols(n);
-    std::vector<void*> users(n);
-    for (uint64_t i = 0; i < n; i++) {
-        rc_cols[i] = read_col_of(cols[i]);
-        users[i] = &cols[i];
-    }
+    std::vector<sb_column_read> rc_cols;
+    std::vector<void*> users;
+    read_cols_of(cols, n, rc_cols, users);
     if ((rc = stage_shares(ctx, rc_cols.data(), cap.data(), n)) != SB_OK) return rc;
     ReadMode mode{ReadMode::KEY_IDS_VAR};
     mode.aggc = hs.data();
@@ -3156,7 +3166,7 @@ int32_t sb_key_combine(sb_ctx* ctx, sb_key_combine_item* items, uint64_t n, int3
     for (uint64_t i = 0; i < n; i++) {
         const sb_key_combine_item& c = items[i];
         if (c.n_parts < 2 || c.n_parts > SB_KEY_COMBINE_MAX_PARTS) return refuse(ctx, SB_ERR_INVALID, "n_parts is not in 2 .. SB_KEY_COMBINE_MAX_PARTS");
-        if (c.id_width != 1 && c.id_width != 2 && c.id_width != 4) return refuse(ctx, SB_ERR_INVALID, "id_width is not 1, 2 or 4");
+        if (const char* why = ids_check_width(c)) return refuse(ctx, SB_ERR_INVALID, why);
         const uint64_t limit = std::min<uint64_t>(SB_KEY_MAX_KEYS, (1ull << (8 * c.id_width)) - 1);
         if (c.max_keys == 0 || c.max_keys > limit) return refuse(ctx, SB_ERR_INVALID, "max_keys is not in 1 .. min(SB_KEY_MAX_KEYS, 2^(8 * id_width) - 1)");
         if (c.reserved) return refuse(ctx, SB_ERR_INVALID, "reserved is not 0");
@@ -3175,9 +3185,7 @@ int32_t sb_key_combine(sb_ctx* ctx, sb_key_combine_item* items, uint64_t n, int3
             hc[i].bound[p] = c.part_keys[p];
         }
         hc[i].n_parts = c.n_parts;
-        if (c.rows && !c.ids) return refuse(ctx, SB_ERR_INVALID, "ids is null");
-        if (c.ids && (((uintptr_t)c.ids & (c.id_width - 1)) || c.ids_capacity < c.rows * c.id_width))
-            return refuse(ctx, SB_ERR_INVALID, "ids not aligned to id_width or smaller than rows * id_width bytes");
+        if (const char* why = ids_check_buffer(c, c.rows)) return refuse(ctx, SB_ERR_INVALID, why);
         memset(&hs[i], 0, sizeof hs[i]);
         hs[i].rows = c.rows;
         hs[i].kind = FK_UNSIGNED;   // (the codes order and come back as they are)
@@ -3272,43 +3280,26 @@ static void look_list_append(const sb_lookup::Prepared& pr, std::vector<uint8_t>
 static int32_t key_lookup_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pages, std::vector<AggCol>& hs, std::vector<LookCol>& hl,
                                   const std::vector<uint8_t>& blob, void* const* users) {
     const uint64_t n = pages.size();
-    std::vector<uint64_t> rows(n);
-    for (uint64_t i = 0; i < n; i++) rows[i] = hs[i].rows;
-    const sb_column_read* rr = nullptr;
-    int32_t rc = decode_for_replay(ctx, std::move(pages), rows.data(), "key lookup", &rr);
+    ReplayCols rp;
+    int32_t rc = open_replay(ctx, std::move(pages), hs, "key lookup", rp);
     if (rc != SB_OK) return rc;
-    std::vector<const uint8_t*> vals(n), bits(n);
-    (void)replay_slots(rr, rows, hs, vals, bits);
     // [AggCol per column][LookCol per column][the results][the columns' states][the lists]
     const size_t res_stride = LOOK_RESULT_WORDS * sizeof(uint64_t);
-    size_t off = align_up(n * sizeof(AggCol), 64);
-    const size_t o_lc = off;
-    off = align_up(off + n * sizeof(LookCol), 64);
-    const size_t o_res = off;
-    off = align_up(off + n * res_stride, 64);
-    const size_t o_state = off;
-    off = align_up(off + n * sizeof(LookState), 64);
-    const size_t o_lists = off;
-    off += blob.size();
-    uint8_t* dev = nullptr;
-    if (hipMalloc((void**)&dev, off + 64) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(key lookup replay) failed");
-    ctx->iv.temp_dev.push_back(dev);
-    for (LookCol& lc : hl) {
-        lc.keys = (const uint64_t*)(dev + o_lists + (size_t)(uintptr_t)lc.keys);
-        lc.kid = (const uint32_t*)(dev + o_lists + (size_t)(uintptr_t)lc.kid);
-        lc.bytes = dev + o_lists + (size_t)(uintptr_t)lc.bytes;
-    }
-    // (copies that have ended when they return: the vectors do not outlive the call)
-    if (hipMemcpy(dev, hs.data(), n * sizeof(AggCol), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dev + o_lc, hl.data(), n * sizeof(LookCol), hipMemcpyHostToDevice) != hipSuccess ||
-        (!blob.empty() && hipMemcpy(dev + o_lists, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess))
-        return ctx->fail(SB_ERR_EXTERNAL, "key lookup replay: upload failed");
+    ReplayArena a;
+    const size_t o_ac = a.add(hs.data(), n * sizeof(AggCol));
+    const size_t o_lc = a.add(hl.data(), n * sizeof(LookCol));
+    const size_t o_res = a.add(n * res_stride);
+    const size_t o_state = a.add(n * sizeof(LookState));
+    const size_t o_lists = a.add(blob.data(), blob.size());
+    if ((rc = a.alloc(ctx, "key lookup replay")) != SB_OK) return rc;
+    for (LookCol& lc : hl) rebase(lc, a.at<uint8_t>(o_lists));
+    if ((rc = a.upload(ctx, "key lookup replay: upload failed")) != SB_OK) return rc;
     StageSlot* slot = acquire_slot(ctx, n * res_stride);
     if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
-    uint64_t* d_res = (uint64_t*)(dev + o_res);
-    const LookLaunch ll{(const AggCol*)dev, (const LookCol*)(dev + o_lc), (LookState*)(dev + o_state), (uint32_t)n, true, false};
+    uint64_t* d_res = a.at<uint64_t>(o_res);
+    const LookLaunch ll{a.at<const AggCol>(o_ac), a.at<const LookCol>(o_lc), a.at<LookState>(o_state), (uint32_t)n, true, false};
     launch_look_zero(ctx, ll);
-    launch_key_lookup_plain(ctx, ll, rows.data(), vals.data(), bits.data());
+    launch_key_lookup_plain(ctx, ll, rp.rows.data(), rp.vals.data(), rp.bits.data());
     launch_look_finish(ctx, ll, d_res);
     return queue_sink_results(ctx, slot, d_res, res_stride, n, Pending::KEY_LOOK_COL, users, nullptr, "key lookup");
 }
@@ -3325,7 +3316,7 @@ int32_t sb_key_lookup(sb_ctx* ctx, sb_column_key_lookup* cols, uint64_t n, int32
         const bool bin = is_binary_t(c.physical_type);
         if (!bin && (c.physical_type < SB_TYPE_INT8 || c.physical_type > SB_TYPE_UINT64))
             return refuse(ctx, SB_ERR_NYI, "key lookup is implemented for 8- to 64-bit integers and binary types");
-        if (c.id_width != 1 && c.id_width != 2 && c.id_width != 4) return refuse(ctx, SB_ERR_INVALID, "id_width is not 1, 2 or 4");
+        if (const char* why = ids_check_width(c)) return refuse(ctx, SB_ERR_INVALID, why);
         if (c.reserved0 || c.reserved) return refuse(ctx, SB_ERR_INVALID, "reserved is not 0");
         const char* why = sb_lookup::check_list(bin, c.values, c.value_offsets, c.n_values);
         if (!why) why = sb_lookup::check_ids(c.value_ids, c.n_values, c.id_width);
@@ -3333,9 +3324,7 @@ int32_t sb_key_lookup(sb_ctx* ctx, sb_column_key_lookup* cols, uint64_t n, int32
         // (numbers: searched like a minimum is taken, every live value is looked at; strings: as sb_key_ids_var has them)
         if ((rc = agg_check_fill(ctx, c, bin ? 0u : (uint32_t)SB_AGG_MIN, hs[i])) != SB_OK) return rc;
         const uint64_t rows = hs[i].rows;
-        if (rows && !c.ids) return refuse(ctx, SB_ERR_INVALID, "ids is null");
-        if (c.ids && (((uintptr_t)c.ids & (c.id_width - 1)) || c.ids_capacity < rows * c.id_width))
-            return refuse(ctx, SB_ERR_INVALID, "ids not aligned to id_width or smaller than rows * id_width bytes");
+        if ((why = ids_check_buffer(c, rows))) return refuse(ctx, SB_ERR_INVALID, why);
         for (uint64_t p = 0; bin && p < c.n_pages; p++)   // (the limits of sb_key_ids_var: its id tables and entry records)
             if (c.metas[p].num_values > (1ull << KEYV_INDEX_BITS) || c.metas[p].length / 8 >= (1ull << KEYV_INDEX_BITS))
                 return refuse(ctx, SB_ERR_NYI, "sb_key_lookup: a binary page of more than 2^26 rows or of 2^29 bytes or more");
@@ -3344,12 +3333,7 @@ int32_t sb_key_lookup(sb_ctx* ctx, sb_column_key_lookup* cols, uint64_t n, int32
         cap[i] = bin ? (c.stage_capacity ? c.stage_capacity : 4 * c.pages_len) : rows * type_width(c.physical_type);
     }
     if (pages >= (1ull << KEYV_PAGE_BITS)) return refuse(ctx, SB_ERR_NYI, "sb_key_lookup: 2^28 binary pages or more in one call");
-    for (uint64_t i = 0; i < n; i++)   // (the bytes a column writes: rows * id_width)
-        for (uint64_t j = i + 1; j < n; j++) {
-            const uintptr_t a0 = (uintptr_t)cols[i].ids, a1 = a0 + hs[i].rows * cols[i].id_width;
-            const uintptr_t b0 = (uintptr_t)cols[j].ids, b1 = b0 + hs[j].rows * cols[j].id_width;
-            if (a0 < b1 && b0 < a1) return refuse(ctx, SB_ERR_INVALID, "ids of two columns of one call overlap");
-        }
+    if (const char* why = ids_check_overlaps(cols, hs)) return refuse(ctx, SB_ERR_INVALID, why);
     // the lists as the kernels search them, one blob for the call
     std::vector<LookCol> hl(n);
     std::vector<uint8_t> blob;
@@ -3364,12 +3348,9 @@ int32_t sb_key_lookup(sb_ctx* ctx, sb_column_key_lookup* cols, uint64_t n, int32
         look_list_append(pr, blob, &hl[i]);
     }
     (void)hipSetDevice(ctx->device);
-    std::vector<sb_column_read> rc_cols(n);
-    std::vector<void*> users(n);
-    for (uint64_t i = 0; i < n; i++) {
-        rc_cols[i] = read_col_of(cols[i]);
-        users[i] = &cols[i];
-    }
+    std::vector<sb_column_read> rc_cols;
+    std::vector<void*> users;
+    read_cols_of(cols, n, rc_cols, users);
     if (ctx->in_replay && ctx->filter_freq) {
         // The numeric columns through a full decode, as sb_key_ids has it; the binary columns as ever (a binary Freq page is
         // a virtual Dict page).  The ids are a function of the data and the list alone, so the route does not show in them.
@@ -3440,42 +3421,26 @@ static void buck_list_append(const sb_buckets::Prepared& pr, std::vector<uint8_t
 static int32_t key_buckets_decoded(sb_ctx* ctx, std::vector<sb_column_read>&& pages, std::vector<AggCol>& hs, std::vector<BuckCol>& hb,
                                    const std::vector<uint8_t>& blob, void* const* users) {
     const uint64_t n = pages.size();
-    std::vector<uint64_t> rows(n);
-    for (uint64_t i = 0; i < n; i++) rows[i] = hs[i].rows;
-    const sb_column_read* rr = nullptr;
-    int32_t rc = decode_for_replay(ctx, std::move(pages), rows.data(), "key buckets", &rr);
+    ReplayCols rp;
+    int32_t rc = open_replay(ctx, std::move(pages), hs, "key buckets", rp);
     if (rc != SB_OK) return rc;
-    std::vector<const uint8_t*> vals(n), bits(n);
-    (void)replay_slots(rr, rows, hs, vals, bits);
     // [AggCol per column][BuckCol per column][the results][the columns' states][the lists]
     const size_t res_stride = BUCK_RESULT_WORDS * sizeof(uint64_t);
-    size_t off = align_up(n * sizeof(AggCol), 64);
-    const size_t o_bc = off;
-    off = align_up(off + n * sizeof(BuckCol), 64);
-    const size_t o_res = off;
-    off = align_up(off + n * res_stride, 64);
-    const size_t o_state = off;
-    off = align_up(off + n * sizeof(BuckState), 64);
-    const size_t o_lists = off;
-    off += blob.size();
-    uint8_t* dev = nullptr;
-    if (hipMalloc((void**)&dev, off + 64) != hipSuccess) return ctx->fail(SB_ERR_EXTERNAL, "hipMalloc(key buckets replay) failed");
-    ctx->iv.temp_dev.push_back(dev);
-    for (BuckCol& bc : hb) {
-        bc.keys = (const uint64_t*)(dev + o_lists + (size_t)(uintptr_t)bc.keys);
-        bc.bid = (const uint32_t*)(dev + o_lists + (size_t)(uintptr_t)bc.bid);
-    }
-    // (copies that have ended when they return: the vectors do not outlive the call)
-    if (hipMemcpy(dev, hs.data(), n * sizeof(AggCol), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dev + o_bc, hb.data(), n * sizeof(BuckCol), hipMemcpyHostToDevice) != hipSuccess ||
-        (!blob.empty() && hipMemcpy(dev + o_lists, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess))
-        return ctx->fail(SB_ERR_EXTERNAL, "key buckets replay: upload failed");
+    ReplayArena a;
+    const size_t o_ac = a.add(hs.data(), n * sizeof(AggCol));
+    const size_t o_bc = a.add(hb.data(), n * sizeof(BuckCol));
+    const size_t o_res = a.add(n * res_stride);
+    const size_t o_state = a.add(n * sizeof(BuckState));
+    const size_t o_lists = a.add(blob.data(), blob.size());
+    if ((rc = a.alloc(ctx, "key buckets replay")) != SB_OK) return rc;
+    for (BuckCol& bc : hb) rebase(bc, a.at<uint8_t>(o_lists));
+    if ((rc = a.upload(ctx, "key buckets replay: upload failed")) != SB_OK) return rc;
     StageSlot* slot = acquire_slot(ctx, n * res_stride);
     if (!slot) return ctx->fail(SB_ERR_EXTERNAL, "hipHostMalloc(staging) failed");
-    uint64_t* d_res = (uint64_t*)(dev + o_res);
-    const BuckLaunch bl{(const AggCol*)dev, (const BuckCol*)(dev + o_bc), (BuckState*)(dev + o_state), (uint32_t)n};
+    uint64_t* d_res = a.at<uint64_t>(o_res);
+    const BuckLaunch bl{a.at<const AggCol>(o_ac), a.at<const BuckCol>(o_bc), a.at<BuckState>(o_state), (uint32_t)n};
     launch_buck_zero(ctx, bl);
-    launch_key_buckets_plain(ctx, bl, rows.data(), vals.data(), bits.data());
+    launch_key_buckets_plain(ctx, bl, rp.rows.data(), rp.vals.data(), rp.bits.data());
     launch_buck_finish(ctx, bl, d_res);
     return queue_sink_results(ctx, slot, d_res, res_stride, n, Pending::KEY_BUCKET_COL, users, nullptr, "key buckets");
 }
@@ -3491,7 +3456,7 @@ int32_t sb_key_buckets(sb_ctx* ctx, sb_column_key_buckets* cols, uint64_t n, int
         const bool is_int = c.physical_type >= SB_TYPE_INT8 && c.physical_type <= SB_TYPE_UINT64;
         if (!is_int && c.physical_type != SB_TYPE_FLOAT32 && c.physical_type != SB_TYPE_FLOAT64)
             return refuse(ctx, SB_ERR_NYI, "key buckets are implemented for 8- to 64-bit integers and floats");
-        if (c.id_width != 1 && c.id_width != 2 && c.id_width != 4) return refuse(ctx, SB_ERR_INVALID, "id_width is not 1, 2 or 4");
+        if (const char* why = ids_check_width(c)) return refuse(ctx, SB_ERR_INVALID, why);
         if (c.reserved0 || c.reserved) return refuse(ctx, SB_ERR_INVALID, "reserved is not 0");
         const uint32_t kind = value_kind(c.physical_type), w = type_width(c.physical_type);
         const char* why = sb_buckets::check_bounds(kind, w, c.flags, c.bounds, c.n_bounds);
@@ -3500,17 +3465,10 @@ int32_t sb_key_buckets(sb_ctx* ctx, sb_column_key_buckets* cols, uint64_t n, int
         // (searched like a minimum is taken: every live value is looked at)
         if ((rc = agg_check_fill(ctx, c, (uint32_t)SB_AGG_MIN, hs[i])) != SB_OK) return rc;
         const uint64_t rows = hs[i].rows;
-        if (rows && !c.ids) return refuse(ctx, SB_ERR_INVALID, "ids is null");
-        if (c.ids && (((uintptr_t)c.ids & (c.id_width - 1)) || c.ids_capacity < rows * c.id_width))
-            return refuse(ctx, SB_ERR_INVALID, "ids not aligned to id_width or smaller than rows * id_width bytes");
+        if ((why = ids_check_buffer(c, rows))) return refuse(ctx, SB_ERR_INVALID, why);
         cap[i] = rows * w;   // the share of the staging area a filter column has
     }
-    for (uint64_t i = 0; i < n; i++)   // (the bytes a column writes: rows * id_width)
-        for (uint64_t j = i + 1; j < n; j++) {
-            const uintptr_t a0 = (uintptr_t)cols[i].ids, a1 = a0 + hs[i].rows * cols[i].id_width;
-            const uintptr_t b0 = (uintptr_t)cols[j].ids, b1 = b0 + hs[j].rows * cols[j].id_width;
-            if (a0 < b1 && b0 < a1) return refuse(ctx, SB_ERR_INVALID, "ids of two columns of one call overlap");
-        }
+    if (const char* why = ids_check_overlaps(cols, hs)) return refuse(ctx, SB_ERR_INVALID, why);
     // the bounds as the kernels search them, one blob for the call
     std::vector<BuckCol> hb(n);
     std::vector<uint8_t> blob;
@@ -3524,12 +3482,9 @@ int32_t sb_key_buckets(sb_ctx* ctx, sb_column_key_buckets* cols, uint64_t n, int
         buck_list_append(sb_buckets::prepare(hs[i].kind, hs[i].w, c.bounds, c.bucket_ids, c.n_bounds), blob, &hb[i]);
     }
     (void)hipSetDevice(ctx->device);
-    std::vector<sb_column_read> rc_cols(n);
-    std::vector<void*> users(n);
-    for (uint64_t i = 0; i < n; i++) {
-        rc_cols[i] = read_col_of(cols[i]);
-        users[i] = &cols[i];
-    }
+    std::vector<sb_column_read> rc_cols;
+    std::vector<void*> users;
+    read_cols_of(cols, n, rc_cols, users);
     if (ctx->in_replay && ctx->filter_freq) {
         // Every column through a full decode, as sb_key_lookup has its numeric columns.  The ids are a function of the data
         // and the struct alone, so the route does not show in them.
